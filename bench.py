@@ -8,7 +8,7 @@ BH, then the conditional HITON-PC stage (level-synchronous test_subsets batches)
 CI tests counted = p(p-1)/2 level-0 tests + the reference-equivalent number of conditional tests (the count the
 sequential reference order would execute; identical to the CPU oracle's by construction).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: this script starts N ranks ITSELF (re-executes under `python -m torch.distributed.run --nproc-per-node N`,
 rendezvous on 127.0.0.1), one rank per GPU, backend nccl (= RCCL over xGMI); when it is already running under
@@ -17,9 +17,14 @@ Targets of every feed-forward round are dealt over the ranks by estimated work (
 all-gathered (flashweave.jl_amd/dist.py).  Total work is fixed as N grows -> "strong".  It fails loudly if fewer
 than N GPUs are visible.
 
-Two schedules are measured in every run (both in the ONE JSON line rank 0 prints):
-  * headline (`value`, `ms_per_step`): --feed-forward / --round-size as given (defaults below);
-  * `other_schedule`: the other one of {feed_forward = 1 in rounds of R targets, feed_forward = 0}.
+A plain run sets up, warms up, times the K headline steps (`value`, `ms_per_step`: --feed-forward / --round-size as given,
+defaults below) and prints the ONE JSON line rank 0 prints.  --full adds the measurements that take runs of their own:
+  * `other_schedule`: the other one of {feed_forward = 1 in rounds of R targets, feed_forward = 0};
+  * the one-chain pass `roofline` is measured on (without it, `roofline` comes from the headline pass's counters);
+  * `cpu_baseline`: the CPU oracle on a bounded sample of the workload.
+--dump-outputs DIR: after the timed steps, the network the last one returned (the arrays Engine.lgl hands its caller) is
+written as DIR/<name>.npy in float64, untested whitelist entries marked in pc_tested instead of by NaN; the inputs are
+seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -35,6 +40,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+DUMP_KEYS = ("edge_src", "edge_dst", "edge_weight", "pc_off", "pc_idx", "pc_weight", "pc_pval", "pc_tested")
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files together, .npy headers included
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s (spec)
 DEFAULT_ROUND = 1024    # granularity of the default feed-forward round size: R = 1024 * ceil(p / 10240), i.e. ~10 rounds per pass
                         # (cfg3: R = 1024; cfg4: R = 5120); results do not depend on the number of GPUs, only on R
@@ -112,14 +119,20 @@ def parse_args(argv=None):
     ap.add_argument("--no-cor-matrix", action="store_true",
                     help="fz: dense_cor = false (fw_params.no_cor_mat) on top of --stream-columns: no p x p matrix at any time, level 0 "
                          "multiplies and screens the centred columns tile by tile (learning.jl:42, tests.jl:118-147)")
-    ap.add_argument("--no-other-schedule", action="store_true", help="skip the second (other_schedule) measurement")
-    ap.add_argument("--no-one-chain", action="store_true", help="skip the one-chain pass the per-kernel roofline figures come from")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: other_schedule, the one-chain roofline pass, the CPU baseline "
+                         "(a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the network of the last one (the arrays Engine.lgl returns) as DIR/<name>.npy, "
+                         "float64, at most 64 MB in all")
+    ap.add_argument("--no-other-schedule", action="store_true", help="--full: skip the second (other_schedule) measurement")
+    ap.add_argument("--no-one-chain", action="store_true", help="--full: skip the one-chain pass the per-kernel roofline figures come from")
     ap.add_argument("--host-seam", action="store_true",
                     help="also time the pass with FW_HOST_HITON=1: the host job pool over fw_test_subsets_batch-style "
                          "launches, the seam a Julia host would call (hiton.jl:100)")
     ap.add_argument("--check-determinism", action="store_true", help="compare every timed pass with the first (network bytes, reference-order test count) and report on stderr; not for a measured line")
     ap.add_argument("--host-normalize", action="store_true", help="normalise the count table with the host front-end (preprocess.py) instead of the device one")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-workers", type=int, default=-1,
                     help="threads of the multi-core CPU leg (-1: all hardware threads; 0: skip it)")
@@ -159,6 +172,29 @@ def launch(args, argv):
     env.setdefault("OMP_NUM_THREADS", "8")
     sys.stderr.write("bench.py: starting %d ranks: %s\n" % (n, " ".join(cmd)))
     sys.exit(subprocess.call(cmd, env=env))
+
+
+def dump_outputs(net, out_dir):
+    """--dump-outputs: one float64 .npy per array of the network (int32 / int64 indices are exact in float64), all of them finite.
+    A neighbour that a feed-forward whitelist admitted without a test carries (NaN, NaN) in pc_weight / pc_pval (hiton.jl:20-30);
+    the dump writes 0 there and marks the entries in pc_tested (1 = a test's weight and p-value, 0 = admitted untested).  An array
+    larger than an equal share of DUMP_MAX_BYTES is replaced by a fixed, seeded sample of its entries, in index order (the same
+    indices for pc_weight, pc_pval and pc_tested)."""
+    arrays = {k: np.ascontiguousarray(net[k], dtype=np.float64).ravel() for k in DUMP_KEYS if k != "pc_tested"}
+    untested = np.isnan(arrays["pc_weight"]) & np.isnan(arrays["pc_pval"])
+    arrays["pc_tested"] = (~untested).astype(np.float64)
+    for k in ("pc_weight", "pc_pval"):
+        arrays[k] = np.where(untested, 0.0, arrays[k])
+    bad = [k for k, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise SystemExit("bench.py --dump-outputs: non-finite values in %s" % ", ".join(bad))
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_MAX_BYTES - 256 * len(DUMP_KEYS)) // (8 * len(DUMP_KEYS))  # elements per array; 256 B per .npy header
+    for k in DUMP_KEYS:
+        a = arrays[k]
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def cpu_baseline(args, cfg, data, n, p, eng, level0_per_step):
@@ -560,8 +596,10 @@ def main():
     simulating = args.simulate_world > 1 and world == 1
     meas = measure_sim if simulating else measure
     main_m = meas(ff, R if ff else 0, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(main_m["net"], args.dump_outputs)
     other_m = None
-    if not args.no_other_schedule:
+    if args.full and not args.no_other_schedule:
         off, oR = (0, 0) if ff else (1, auto_R)
         other_m = meas(off, oR, max(1, min(args.steps, 3)), 1)
     # per-kernel figures: with the default two concurrent chains the launches of the two streams overlap, and per-launch
@@ -569,7 +607,7 @@ def main():
     # comes from one extra pass with ONE chain -- the segment kernel alone on the GPU -- so that its kernel seconds are
     # a lower bound of that pass and comparable with the headline step.
     one_m = None
-    if world == 1 and not simulating and not args.no_one_chain and not args.stream_columns and cfg["test_name"] in ("fz", "fz_nz"):
+    if args.full and world == 1 and not simulating and not args.no_one_chain and not args.stream_columns and cfg["test_name"] in ("fz", "fz_nz"):
         knobs_were = os.environ.get("FW_KNOBS")
         os.environ["FW_KNOBS"], os.environ["FW_DH_CHAINS"] = "1", "1"  # (the library reads FW_* knobs only under FW_KNOBS=1)
         one_m = measure(ff, R if ff else 0, max(1, min(args.steps, 3)), 1)
@@ -703,6 +741,8 @@ def main():
         cpu, cpu_skipped = None, None
         if world > 1:
             cpu_skipped = "the CPU baseline is timed at N = 1 only"
+        elif not args.full:
+            cpu_skipped = "the CPU baseline runs with --full"
         elif not args.no_cpu_baseline:
             cpu = cpu_baseline(args, cfg, data, n, p, eng, main_m["level0"])
 
@@ -715,7 +755,7 @@ def main():
                     "exchange": m["exchange"], "simulated_world": m.get("simulated_world")}
 
         out = {"metric": "ci_tests_per_sec", "value": main_m["value"], "unit": "tests/s", "n_gpus": world, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": main_m["ms_per_step"], "higher_is_better": True, "scaling": "strong",
+               "warmup": args.warmup, "full": bool(args.full), "ms_per_step": main_m["ms_per_step"], "higher_is_better": True, "scaling": "strong",
                "vs_baseline": None, "dtype": "f64" if cfg["test_name"] in ("fz", "fz_nz") else "i32",
                "data": "bundled table of the reference's tests" if cfg.get("label") else "synthetic",
                "config": {"workload": cfg.get("label") or "%s: fwsynth-v1 %d OTUs x %d samples, %s, max_k=%d, alpha=0.01" %

@@ -10,7 +10,7 @@ CFG=${1:-cfg3}
 shift
 for N in 1 2 4 8; do
   if [ $N = 1 ]; then SW=""; else SW="--simulate-world $N --simulate-rank -1"; fi
-  timeout 900 python bench.py --config $CFG $SW --steps 3 --warmup 1 --no-cpu-baseline "$@" > $O/${CFG}_n$N.json 2> $O/${CFG}_n$N.err
+  timeout 900 python bench.py --config $CFG $SW --steps 3 --warmup 1 --full --no-cpu-baseline "$@" > $O/${CFG}_n$N.json 2> $O/${CFG}_n$N.err
   python - $O/${CFG}_n$N.json $N <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
