@@ -43,7 +43,8 @@ def _integral(a):
 
 def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
-                  meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, **unsupported):
+                  meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
+                  no_red_tests=True, **unsupported):
     """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False).
     meta_data: optional samples x meta-variables table (numbers and / or string factors), handled like the reference's
     meta_data_path input: one-hot encoding, discretisation for the discrete tests, +1 shift for fz_nz (preprocess.py).
@@ -59,7 +60,10 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     conditional tests can only come from the data, so dense_cor=False implies recursive_pcor=False (a warning says so when the
     caller left recursive_pcor at its default).
     device_normalize: normalise integer count tables on the device (fw_normalize_counts; all four modes); False, or a table of
-    non-integral abundances, takes the host front-end (preprocess.py)."""
+    non-integral abundances, takes the host front-end (preprocess.py).
+    fast_elim (learning.jl:430,469): False runs HITON-PC's exact elimination phase -- a member that fails its test stays in the
+    conditioning pool of the later members (hiton.jl:67-70).  no_red_tests (an LGL keyword, learning.jl:207): with fast_elim=False,
+    no_red_tests=False keeps the elimination-phase statistics in PC (hiton.jl:388-390); with fast_elim=True it has no effect."""
     if unsupported:
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
     import time
@@ -102,7 +106,7 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
         eng.set_data(mat)
         if test_name == "fz" and dense_cor:
             eng.compute_cor()
-        net = eng.lgl(feed_forward=feed_forward, round_size=round_size)
+        net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests)
         counters = eng.counters()
     finally:
         eng.close()
@@ -111,7 +115,8 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header),
                     parameters=dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha,
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,
-                                    recursive_pcor=recursive_pcor, dense_cor=dense_cor,
+                                    recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
+                                    no_red_tests=bool(no_red_tests),
                                     schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
                                               else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
                                               else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),

@@ -112,6 +112,7 @@ struct DhParams {
     int spec0_depth_light;          // ... and this many candidates while the last launch held fewer than spec0_light_below ranks
     unsigned long long spec0_light_below;
     int spec1_depth;          // interleaving-phase look-ahead behind a candidate that is about to be accepted (same two conditions)
+    int elim_mode;            // fw_learn_opts.elim_mode: 0 fast_elim; 1 fast_elim = false (dh_commit); 2 ... and no update_PC_dict! (dh_advance)
 };
 
 // Is v one of the target's whitelisted neighbours?  Called by the whole wavefront with a uniform v: the lanes read 64 entries of
@@ -182,7 +183,9 @@ __device__ __forceinline__ double dh_alg_bytes_disc32(int a, unsigned long long 
 // (stores of one lane are made visible to the others by workgroup-scope fences: one L1 per CU, no cache maintenance);
 // the loops over the target's arrays (removing the candidate from the pool, the phase switch, update_PC_dict!) are
 // spread over the lanes -- a single lane walking 250 dependent global loads per candidate was 100 us per round.
-__device__ bool dh_advance(DhTgt &x, const DhArrays &A, int lane, int d1)
+// keep_elim_stats (elim_mode 2: fast_elim = no_red_tests = false): update_PC_dict! is skipped (hiton.jl:388-390), PC keeps the
+// elimination-phase statistics.
+__device__ bool dh_advance(DhTgt &x, const DhArrays &A, int lane, int d1, bool keep_elim_stats = false)
 {
     for (;;) {
         int32_t *acc = A.acc + DH_ACC_OFF(x, x.cur, d1);
@@ -263,8 +266,8 @@ __device__ bool dh_advance(DhTgt &x, const DhArrays &A, int lane, int d1)
             for (int q = lane; q < x.ntpc; q += 64) acc[q] = A.tpc_key[x.co + q];
             x.na = x.ntpc;
             x.pos = 0;
-        } else {  // hiton.jl:249-256 update_PC_dict!
-            for (int i = lane; i < x.npc; i += 64) {
+        } else {  // hiton.jl:249-256 update_PC_dict! (skipped when fast_elim = no_red_tests = false, hiton.jl:388-390)
+            for (int i = keep_elim_stats ? x.npc : lane; i < x.npc; i += 64) {
                 const int32_t k = A.pc_key[x.co + i];
                 for (int q = 0; q < x.ntpc; ++q)
                     if (A.tpc_key[x.co + q] == k) {
@@ -297,6 +300,7 @@ __device__ __forceinline__ unsigned int dh_ceil_div(unsigned long long w, unsign
 // first stop (smallest segment index) ends the job; otherwise the lexicographic maximum of (p, segment index), i.e.
 // "later wins ties" (tests.jl:338).  Every lane returns the same values.
 #define DH_MAX_SPEC 8  // look-ahead jobs per target (register arrays in dh_step_kernel)
+#define DH_SPEC_EXACT 4  // default look-ahead depth of the exact elimination mode (fw_learn_opts.elim_mode != 0)
 
 struct DhMerge {
     bool stop;
@@ -373,14 +377,21 @@ __device__ __forceinline__ DhMerge dh_merge(const FwSegOut *__restrict__ so, lon
 }
 
 // issig (tests.jl:1-3) -> hiton.jl:61-63: the candidate at x.pos joins the accepted list (buffer x.cur) and TPC / PC,
-// or is dropped.  Every lane computes the same state; lane 0 writes.
+// or is dropped.  Every lane computes the same state; lane 0 writes.  Returns whether the candidate joined the accepted list.
+// exact (fast_elim = false, hiton.jl:67-70): a rejected elimination-phase member re-enters the pool all the same, without
+// entering PC -- the pool of the next member no longer depends on this verdict.
 __device__ __forceinline__ bool dh_commit(DhTgt &x, const DhArrays &A, int lane, int d1, double r_stat, double r_p, int r_pow,
-                                          double alpha)
+                                          double alpha, bool exact = false)
 {
     const int32_t *cands = x.phase == 0 ? A.cand0 + x.cand_off : A.tpc_key + x.co;
     const int32_t cand = cands[x.pos];
     ++x.pos;
-    if (!(r_p < alpha && r_pow)) return false;
+    if (!(r_p < alpha && r_pow)) {
+        if (!(exact && x.phase == 1)) return false;
+        if (lane == 0) A.acc[DH_ACC_OFF(x, x.cur, d1) + x.na] = cand;
+        ++x.na;
+        return true;
+    }
     if (lane == 0) {
         A.acc[DH_ACC_OFF(x, x.cur, d1) + x.na] = cand;
         if (x.phase == 0) {
@@ -1217,7 +1228,7 @@ __device__ __forceinline__ bool mi_publish(MiQueue *__restrict__ Q, MiBoard *__r
 // the persistent kernel's own clock reads (per job: phase times for FW_TRACE_HOST): a wall_clock64() is a scalar memory round trip,
 // four of them per job were ~5 % of a light job -- taken only when the host asks for the trace (DhParams::mi_trace)
 #define MI_CLK() (P.mi_trace ? wall_clock64() : 0ull)
-template <int L, int NXY, int PRE, bool R4>
+template <int L, int NXY, int PRE, bool R4, bool EX>
 __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, MiQueue *__restrict__ Q,
                                         MiBoard *__restrict__ boards, FwSegOut *__restrict__ res, int32_t *__restrict__ bacc)
 {
@@ -1235,7 +1246,7 @@ __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, 
     const unsigned long long per = R4 ? 4ull : 1ull;  // ranks per wavefront and lock-step round
     for (;;) {
         if (wave == 0) {
-            const bool more = dh_advance(x, A, lane, 1);
+            const bool more = dh_advance(x, A, lane, 1, EX && P.elim_mode == 2);
             if (lane == 0) {
                 J.go = more ? 1 : 0;
                 if (more) {
@@ -1506,7 +1517,7 @@ __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, 
             x.c_eval += ev;
             x.c_alg += (P.max_k <= 3 && a <= FW_UNRANK32_A) ? dh_alg_bytes_disc32(a, ev, P.max_k, P.disc_bytes_per_col)
                                                             : dh_alg_bytes(a, ev, P.max_k, P.disc_bytes_per_col);
-            dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha);
+            dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, EX);
         }
     }
     if (wave == 0 && lane == 0) {
@@ -1525,7 +1536,9 @@ __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, 
 #ifndef DH_MI_OCC
 #define DH_MI_OCC 1  // workgroups per CU the register budget is sized for
 #endif
-template <int L, int NXY, int PRE, bool R4>
+// EX: exact elimination (fw_learn_opts.elim_mode 1 / 2) -- a compile-time instantiation, so that the default one keeps its
+// register allocation
+template <int L, int NXY, int PRE, bool R4, bool EX>
 __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__restrict__ tg, int ntg, const int32_t *__restrict__ order,
                                                            DhArrays A, MiDev M, DhParams P, MiQueue *__restrict__ Q,
                                                            MiBoard *__restrict__ boards, FwSegOut *__restrict__ res,
@@ -1556,7 +1569,7 @@ __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__r
         const unsigned int ts = (unsigned int)dh_mi_tj.go;
         __syncthreads();  // (dh_mi_team rewrites the descriptor)
         if (ts >= P.mi_team) break;
-        dh_mi_team<L, NXY, PRE, R4>(tg, ntg, order[ts], Q, boards, res, bacc);
+        dh_mi_team<L, NXY, PRE, R4, EX>(tg, ntg, order[ts], Q, boards, res, bacc);
     }
     unsigned int jobctr = 0u;
     bool tail_seen = false;
@@ -1576,7 +1589,7 @@ __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__r
         __builtin_amdgcn_wave_barrier();
         for (;;) {
             const unsigned long long tka0 = MI_CLK();
-            const bool more_jobs = dh_advance(x, A, lane, 1);
+            const bool more_jobs = dh_advance(x, A, lane, 1, EX && P.elim_mode == 2);
             MI_TICK(6, tka0);
             if (!more_jobs) break;
             // other targets' big enumerations first: they are the critical path of the pass
@@ -1766,7 +1779,7 @@ __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__r
             x.c_eval += ev;
             x.c_alg += (P.max_k <= 3 && a <= FW_UNRANK32_A) ? dh_alg_bytes_disc32(a, ev, P.max_k, P.disc_bytes_per_col)
                                                             : dh_alg_bytes(a, ev, P.max_k, P.disc_bytes_per_col);
-            dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha);
+            dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, EX);
             MI_TICK(8, tkc0);
         }
         if (lane == 0) {
@@ -1885,7 +1898,7 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
                 x.c_eval_short += x.na <= FW_HK_A ? x.jevaluated : 0ull;
                 x.na_max = x.na > x.na_max ? x.na : x.na_max;
                 x.c_alg += dh_alg_bytes(x.na, x.jevaluated, P.max_k, P.disc_bytes_per_col);
-                kept = dh_commit(x, A, lane, d1, r_stat, r_p, r_pow, P.alpha);
+                kept = dh_commit(x, A, lane, d1, r_stat, r_p, r_pow, P.alpha, P.elim_mode != 0);
             }
         }
         if (nsp_done > 0) {
@@ -1929,11 +1942,11 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
                 x.c_eval += M.ev;
                 x.c_eval_short += n <= FW_HK_A ? M.ev : 0ull;
                 x.c_alg += dh_alg_bytes(n, M.ev, P.max_k, P.disc_bytes_per_col);
-                const bool k = dh_commit(x, A, lane, d1, r_stat, r_p, M.stop ? M.pow : 1, P.alpha);
+                const bool k = dh_commit(x, A, lane, d1, r_stat, r_p, M.stop ? M.pow : 1, P.alpha, P.elim_mode != 0);
                 valid = ph1 ? k : !k;
             }
         }
-        if (!x.jactive && x.phase != 2 && dh_advance(x, A, lane, d1)) {
+        if (!x.jactive && x.phase != 2 && dh_advance(x, A, lane, d1, P.elim_mode == 2)) {
             const unsigned long long N = dh_enum_size(x.na, P.max_k, P.max_tests);  // (32-bit binomials where every term fits)
             x.jN = N;
             x.jnext = 0ull;
@@ -1946,7 +1959,8 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
             x.jevaluated = 0ull;
             x.jactive = 1;
             if (lane == 0 && (unsigned int)x.na > g->max_a) atomicMax(&g->max_a, (unsigned int)x.na);  // rare: only on a new maximum
-            {   // phase 0: the list can still take every whitelisted neighbour it has not met; phase 1: pools never exceed TPC
+            {   // phase 0: the list can still take every whitelisted neighbour it has not met; phase 1: pools never exceed TPC (plus the
+                // second entries of whitelisted members) -- in exact mode as well: its pools are those of fast mode when every member is kept
                 const int abi = x.phase == 0 ? x.na + x.wl_n - x.wl_used : (x.na > x.ntpc ? x.na : x.ntpc);
                 if (lane == 0 && (unsigned int)abi > g->max_ab) atomicMax(&g->max_ab, (unsigned int)abi);
             }
@@ -2508,6 +2522,7 @@ static DhParams dh_make_params(fw_ctx *c, int ntg, int spec_depth, int spec0_dep
     P.seg_q = fz ? 256u : 4u;
     P.seg_min = fz ? 256u : 8u;
     P.disc_bytes_per_col = fz ? 0.0 : (double)c->P.n * (c->P.kind == FW_MI ? 1.0 : 2.0) / 8.0;
+    P.elim_mode = c->elim_mode;
     return P;
 }
 
@@ -2538,8 +2553,14 @@ static unsigned dh_mi_launch(fw_ctx *c, hipStream_t st, DhTgt *d_tg, int ntg, co
     P.mi_trace = trace_host ? 1u : 0u;
 #endif
 #define DH_MI_LAUNCH(LL, NN, PP, RR)                                                                                                  \
-    hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order, A, M, P, \
-                       d_mq, d_boards, d_mres, d_bacc)
+    do {                                                                                                                              \
+        if (P.elim_mode != 0)                                                                                                         \
+            hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR, true>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order, A, M, \
+                               P, d_mq, d_boards, d_mres, d_bacc);                                                                    \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR, false>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order, A, M, \
+                               P, d_mq, d_boards, d_mres, d_bacc);                                                                    \
+    } while (0)
     const bool pre = c->P.n <= MI_PRE_N && c->P.max_k <= MI_PRE_K;
     // four subsets per wavefront step (mi_test_core4): n <= 5120, max_k <= 3, 2 x 2 cells per stratum.  FW_MI_ROW4=0: one per step
     static const bool row4_env = [] { const char *e = fw_knob("FW_MI_ROW4"); return !(e && atoi(e) == 0); }();
@@ -2649,7 +2670,10 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
     // GPU / one rank of 8): off 326.7 / 112.0; depth 4 always 338 / 103; depth 4 below 4M 318.5 / 104.4, below 8M
     // 317.3 / 104.6, below 12M 314.8 / 103.6, below 16M 341 -- a launch that already fills the GPU only pays for the
     // jobs wasted behind every dropped member (3.7 % of the members at cfg3)
-    static const int spec_env = [] { const char *e = fw_knob("FW_DH_SPEC"); return e ? atoi(e) : 4; }();
+    // Exact elimination (elim_mode 1 / 2): no look-ahead job is ever discarded (a rejected member re-enters the pool as well), so
+    // the chain of a target with m members takes about m / (depth + 1) rounds; default DH_SPEC_EXACT
+    static const int spec_env = [] { const char *e = fw_knob("FW_DH_SPEC"); return e ? atoi(e) : -1; }();
+    const int spec_dflt = c->elim_mode != 0 ? DH_SPEC_EXACT : 4;
     // discrete kinds: persistent wavefronts + boards (dh_mi_target_kernel); FW_MI_ROUNDS=1 keeps the level-synchronous rounds over
     // the segment kernels (the path of the ABI's fw_test_subsets_batch) for comparison.  Fisher-z always runs as rounds (a
     // persistent-workgroup variant was built in r02, lost 140 vs 58 ms on the heavy rounds, and was removed in r03).
@@ -2657,7 +2681,7 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
     // (more than 65 535 samples: 32-bit cell counts -- only the segment kernels have that form, so such data takes the rounds)
     const bool nzk = c->P.kind == FW_FZ_NZ;  // fz_nz (r05): rounds like fz, with the sub-matrix kernel in front of the segment kernel
     const bool per_target = c->P.kind != FW_FZ && !nzk && !mi_rounds;  // (r04: the persistent kernel has a 32-bit-count form too, PRE = 2)
-    const int spec_depth = c->P.kind == FW_FZ ? std::min(std::max(spec_env, 0), DH_MAX_SPEC) : 0;
+    const int spec_depth = c->P.kind == FW_FZ ? std::min(std::max(spec_env >= 0 ? spec_env : spec_dflt, 0), DH_MAX_SPEC) : 0;
     const int d1 = spec_depth + 1;
     // interleaving-phase look-ahead (first windows of the next candidates, same accepted list): FW_DH_SPEC0 candidates,
     // only while the last launch held fewer than FW_DH_SPEC0_BELOW ranks and fewer than FW_DH_SPEC0_JOBS jobs -- it

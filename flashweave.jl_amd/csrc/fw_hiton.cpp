@@ -50,6 +50,11 @@ struct Target {
     // speculative posting (interleaving phase): candidates [pos, posted_end) have a job in the pool or a buffered result
     size_t posted_end = 0;
     std::vector<std::pair<int32_t, FwJobOut>> ready;  // finished but not yet committed (candidate index, result)
+    // exact elimination (fw_learn_opts.elim_mode 1 / 2, fast_elim = false): every member re-enters the pool whatever its verdict
+    // (hiton.jl:67-70), so the pool of member j + 1 is (pool of j without c_{j+1}) + [c_j] -- known before any result.  post_acc:
+    // the pool as it will stand before candidate posted_end (elimination phase only)
+    int elim_mode = 0;
+    std::vector<int32_t> post_acc;
     bool in_wl(int32_t v) const { return wl_n > 0 && std::binary_search(wl, wl + wl_n, v); }
 };
 
@@ -104,8 +109,9 @@ static bool advance(const fw_ctx *c, Target &t)
             t.pos = 0;
             t.posted_end = 0;  // every interleaving candidate has been committed at this point
             t.ready.clear();
-        } else {  // hiton.jl:249-256 update_PC_dict!
-            for (size_t i = 0; i < t.PC.key.size(); ++i) {
+            if (t.elim_mode != 0) t.post_acc = t.acc;
+        } else {  // hiton.jl:249-256 update_PC_dict!, skipped when fast_elim = no_red_tests = false (:388-390)
+            for (size_t i = 0; t.elim_mode != 2 && i < t.PC.key.size(); ++i) {
                 const int ti = t.TPC.find(t.PC.key[i]);
                 if (ti >= 0 && (t.TPC.pval[ti] > t.PC.pval[i] || std::isnan(t.PC.pval[i]))) {
                     t.PC.stat[i] = t.TPC.stat[ti];
@@ -315,6 +321,7 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
     if (opt.world_size < 1) opt.world_size = 1;
     if (opt.rank < 0 || opt.rank >= opt.world_size) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: rank %d outside world of %d", opt.rank, opt.world_size);
     if (opt.world_size > 1 && !allgather) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: world_size > 1 needs an allgather callback");
+    if (opt.elim_mode < 0 || opt.elim_mode > 2) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: elim_mode %d is not 0, 1 or 2", opt.elim_mode);
     if (!c->have_level0) {
         int rc = fw_level0(c, nullptr);
         if (rc) return rc;
@@ -327,6 +334,11 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
         ~ViewGuard() { c->mi_view = old; }
     } view_guard{c, c->mi_view};
     c->mi_view = 1;
+    struct ElimGuard {  // the device rounds read the mode from the context (fw_devhiton.hip)
+        fw_ctx *c;
+        ~ElimGuard() { c->elim_mode = 0; }
+    } elim_guard{c};
+    c->elim_mode = opt.elim_mode;
     const int p = c->P.p;
     const bool discrete = c->P.kind == FW_MI || c->P.kind == FW_MI_NZ;
     const double t0 = now_s();
@@ -432,6 +444,7 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                 if (owner[i - r0] != opt.rank) continue;
                 Target t;
                 t.T = order[i];
+                t.elim_mode = opt.elim_mode;
                 if (discrete && c->levels[t.T] < 2) {  // hiton.jl:182-184
                     t.phase = 2;
                     tg.push_back(std::move(t));
@@ -602,12 +615,17 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                         c->cnt.subsets_calls += 1;
                         const int32_t cand = t.cands[t.pos];
                         ++t.pos;
+                        const bool exact = t.elim_mode != 0 && t.phase == 1;  // the pool grows either way: nothing posted is void
                         if (o.pval < c->P.alpha && o.suff_power) {  // issig, tests.jl:1-3; hiton.jl:61-63
                             t.acc.push_back(cand);
                             (t.phase == 0 ? t.TPC : t.PC).set(cand, o.stat, o.pval);
-                            ++epoch[ti];  // accepted set changed: later speculative jobs / results are void
-                            t.ready.clear();
-                            t.posted_end = t.pos;
+                            if (!exact) {
+                                ++epoch[ti];  // accepted set changed: later speculative jobs / results are void
+                                t.ready.clear();
+                                t.posted_end = t.pos;
+                            }
+                        } else if (exact) {  // hiton.jl:67-70
+                            t.acc.push_back(cand);
                         }
                     }
                     if (t.phase == 2) {
@@ -617,6 +635,29 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                     // post: the current candidate, plus speculative ones while interleaving.  Speculation is only used
                     // once few targets are left (the latency-bound tail); with thousands of active targets the launches
                     // are full anyway and the extra host bookkeeping would cost more than the saved rounds.
+                    if (t.elim_mode != 0 && t.phase == 1) {
+                        // exact elimination: every member's job at once, each against its own pool (they are independent)
+                        if (t.posted_end < t.pos) {  // (members advance() settled without a test: t.acc is the pool before t.pos)
+                            t.posted_end = t.pos;
+                            t.post_acc = t.acc;
+                        }
+                        for (; t.posted_end < t.cands.size(); ++t.posted_end) {
+                            const size_t ci = t.posted_end;
+                            const int32_t cand = t.cands[ci];
+                            if (t.in_wl(cand)) {  // hiton.jl:20-30: pushed once more, no test (advance() records it)
+                                t.post_acc.push_back(cand);
+                                continue;
+                            }
+                            t.post_acc.erase(std::remove(t.post_acc.begin(), t.post_acc.end(), cand), t.post_acc.end());
+                            if (!t.post_acc.empty()) {  // (an empty pool is the sentinel of advance(): no test)
+                                fwi_pool_add(c, pool, t.T, cand, t.post_acc.data(), (int)t.post_acc.size(), ti);
+                                pool.live.back().aux = (int32_t)ci;
+                                pool.live.back().epoch = epoch[ti];
+                            }
+                            t.post_acc.push_back(cand);
+                        }
+                        continue;
+                    }
                     if (t.posted_end < t.pos) t.posted_end = t.pos;
                     const size_t depth = n_unfinished <= FW_SPEC_TARGETS ? (size_t)FW_SPEC_DEPTH : 1;
                     const size_t limit = t.phase == 0 ? std::min(t.cands.size(), t.pos + depth) : t.pos + 1;
@@ -632,7 +673,11 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                 touched.clear();
                 // a speculative job (not the head candidate of its target) only ever runs its first window: most
                 // rejections happen within the first few tests, and a voided long job would be pure waste
-                for (FwPoolJob &j : pool.live) j.hold = (size_t)j.aux != tg[(size_t)j.tag].pos && j.next > 0;
+                // (exact elimination: no job is speculative)
+                for (FwPoolJob &j : pool.live) {
+                    const Target &t = tg[(size_t)j.tag];
+                    j.hold = (size_t)j.aux != t.pos && j.next > 0 && !(t.elim_mode != 0 && t.phase == 1);
+                }
                 c->cnt.t_host_advance_s += now_s() - ta0;
                 if (pool.live.empty()) break;
                 fin.clear();

@@ -47,9 +47,15 @@ class _Counters(C.Structure):
                 ("l0_mfma_flops", C.c_double), ("t_l0_mfma_s", C.c_double)]
 
 
+def elim_mode(fast_elim=True, no_red_tests=True):
+    """fw_learn_opts.elim_mode of the reference's keywords: 0 fast_elim; 1 fast_elim = false; 2 fast_elim = no_red_tests = false
+    (no_red_tests has no effect with fast_elim = true, hiton.jl:388-390)."""
+    return 0 if fast_elim else (1 if no_red_tests else 2)
+
+
 class _LearnOpts(C.Structure):
     _fields_ = [("feed_forward", C.c_int32), ("round_size", C.c_int32), ("rank", C.c_int32),
-                ("world_size", C.c_int32), ("max_targets", C.c_int32), ("reserved0", C.c_int32)]
+                ("world_size", C.c_int32), ("max_targets", C.c_int32), ("elim_mode", C.c_int32)]
 
 
 PREPARE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
@@ -315,10 +321,10 @@ class Engine:
     def cor_allgather_comm(self, rows_per_rank):
         self._ck(self.L.fw_cor_mat_allgather_comm(self.h, int(rows_per_rank)))
 
-    def lgl_comm(self, feed_forward=True, round_size=1, max_targets=0, edge_dict=True):
+    def lgl_comm(self, feed_forward=True, round_size=1, max_targets=0, edge_dict=True, fast_elim=True, no_red_tests=True):
         """fw_learn_network_comm: LGL of a target-sharded run, the per-round exchange issued by the library (rank / world_size are the
-        communicator's)."""
-        opts = _LearnOpts(int(feed_forward), int(round_size), 0, 1, int(max_targets), 0)
+        communicator's).  fast_elim / no_red_tests: as in lgl."""
+        opts = _LearnOpts(int(feed_forward), int(round_size), 0, 1, int(max_targets), elim_mode(fast_elim, no_red_tests))
         ne = C.c_int64(0)
         self._ck(self.L.fw_learn_network_comm(self.h, C.byref(opts), C.byref(ne)))
         return self._network(ne.value, edge_dict)
@@ -392,11 +398,14 @@ class Engine:
         return int(bad.value)
 
     # -- LGL -----------------------------------------------------------------------------------------
-    def lgl(self, feed_forward=True, round_size=1, rank=0, world_size=1, max_targets=0, allgather=None, edge_dict=True, dev_exchange=None):
+    def lgl(self, feed_forward=True, round_size=1, rank=0, world_size=1, max_targets=0, allgather=None, edge_dict=True, dev_exchange=None,
+            fast_elim=True, no_red_tests=True):
         """LGL minus normalisation (src/learning.jl:203-279).  Returns dict(edges={(i,j): w}, directed=CSR);
         edge_dict=False leaves the edges as the three arrays fw_network_get fills (edge_src, edge_dst, edge_weight) and
-        skips the Python dictionary (48 000 tuples cost ~8 ms at cfg3)."""
-        opts = _LearnOpts(int(feed_forward), int(round_size), int(rank), int(world_size), int(max_targets), 0)
+        skips the Python dictionary (48 000 tuples cost ~8 ms at cfg3).
+        fast_elim=False: exact HITON-PC elimination (hiton.jl:67-70: a rejected member stays in the conditioning pool);
+        no_red_tests=False (with fast_elim=False only): PC keeps the elimination-phase statistics (hiton.jl:388-390)."""
+        opts = _LearnOpts(int(feed_forward), int(round_size), int(rank), int(world_size), int(max_targets), elim_mode(fast_elim, no_red_tests))
         ne = C.c_int64(0)
         cb = None
         if allgather is not None:

@@ -260,7 +260,10 @@ typedef struct fw_learn_opts {
     int32_t rank;          /* this process' rank in a target-sharded run (0 for single GPU) */
     int32_t world_size;    /* number of ranks; the targets of a round are dealt by estimated work (heaviest first to the least loaded rank) */
     int32_t max_targets;   /* > 0: stop after this many targets of the schedule (sampling; 0 = all) */
-    int32_t reserved0;
+    int32_t elim_mode;     /* HITON-PC elimination phase (src/hiton.jl:53-78,388-390; was reserved0, zero keeps its meaning):
+                              0 = fast_elim = true (default); 1 = fast_elim = false: a rejected member re-enters the conditioning
+                              pool but not PC; 2 = fast_elim = false, no_red_tests = false: as 1, and PC keeps the elimination-phase
+                              statistics (update_PC_dict! skipped).  Anything else: FW_ERR_ARG */
 } fw_learn_opts;
 
 /* replaces: LGL minus normalisation (src/learning.jl:203-279): level 0 (if not yet run), target ordering,
