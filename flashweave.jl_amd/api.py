@@ -15,6 +15,10 @@ class FWResult(dict):
         """save_network (src/io.jl:300-336): .edgelist or .gml by extension."""
         fio.save_network(path, self["edges"], self["variable_ids"], self["meta_variable_mask"])
 
+    def save_rejections(self, path, digits=5):
+        """save_rejections (src/io.jl:296-318)."""
+        fio.save_rejections(path, self, digits=digits)
+
 
 def default_round_size(p):
     """Targets per feed-forward round when the caller does not choose.
@@ -44,7 +48,7 @@ def _integral(a):
 def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
                   meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
-                  no_red_tests=True, **unsupported):
+                  no_red_tests=True, track_rejections=False, **unsupported):
     """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False).
     meta_data: optional samples x meta-variables table (numbers and / or string factors), handled like the reference's
     meta_data_path input: one-hot encoding, discretisation for the discrete tests, +1 shift for fz_nz (preprocess.py).
@@ -63,7 +67,11 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     non-integral abundances, takes the host front-end (preprocess.py).
     fast_elim (learning.jl:430,469): False runs HITON-PC's exact elimination phase -- a member that fails its test stays in the
     conditioning pool of the later members (hiton.jl:67-70).  no_red_tests (an LGL keyword, learning.jl:207): with fast_elim=False,
-    no_red_tests=False keeps the elimination-phase statistics in PC (hiton.jl:388-390); with fast_elim=True it has no effect."""
+    no_red_tests=False keeps the elimination-phase statistics in PC (hiton.jl:388-390); with fast_elim=True it has no effect.
+    track_rejections (learning.jl:446,469): True also returns, for every candidate a conditional test removed from a target's
+    neighbourhood, the conditioning set that did it: result["rejections"] = {target: {candidate: (Zs, (stat, pval, df, suff_power),
+    (num_tests, frac))}} with 0-based variable ids (the reference's rejections(net_result)); {} when off.  io.save_rejections writes
+    them in the reference's file format."""
     if unsupported:
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
     import time
@@ -106,7 +114,8 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
         eng.set_data(mat)
         if test_name == "fz" and dense_cor:
             eng.compute_cor()
-        net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests)
+        net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests,
+                      track_rejections=track_rejections)
         counters = eng.counters()
     finally:
         eng.close()
@@ -116,8 +125,8 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
                     parameters=dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha,
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,
                                     recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
-                                    no_red_tests=bool(no_red_tests),
+                                    no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections),
                                     schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
                                               else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
                                               else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),
-                    counters=counters)
+                    counters=counters, rejections=net["rejections"])

@@ -179,6 +179,7 @@ int fw_ctx_destroy(fw_ctx *c)
     free_dev(c->d_nzrecs);
     free_dev(c->d_arena);
     free_dev(c->d_bh);
+    free_dev(c->d_rej);
     free_dev(c->d_l0m_i);
     free_dev(c->d_l0m_d);
     for (FwDevBuf &b : c->d_mig_tab) free_dev(b);
@@ -347,6 +348,32 @@ int fw_set_row_views(fw_ctx *c, int32_t on)
 {
     CHECK_CTX(c);
     c->mi_view = on ? 1 : 0;
+    return FW_OK;
+}
+
+int fw_set_track_rejections(fw_ctx *c, int32_t on)
+{
+    CHECK_CTX(c);
+    c->track_rej = on ? 1 : 0;
+    return FW_OK;
+}
+
+int fw_rejections_count(const fw_ctx *c, int64_t *n)
+{
+    CHECK_CTX(c);
+    if (!n) return fw_fail(c, FW_ERR_ARG, "fw_rejections_count: NULL output");
+    if (!c->have_rej) return fw_fail(c, FW_ERR_STATE, "fw_rejections_count: no fw_learn_network has run with fw_set_track_rejections(1)");
+    *n = (int64_t)c->rej.size();
+    return FW_OK;
+}
+
+int fw_rejections_get(const fw_ctx *c, fw_rejection *out)
+{
+    CHECK_CTX(c);
+    if (!c->have_rej) return fw_fail(c, FW_ERR_STATE, "fw_rejections_get: no fw_learn_network has run with fw_set_track_rejections(1)");
+    if (c->rej.empty()) return FW_OK;
+    if (!out) return fw_fail(c, FW_ERR_ARG, "fw_rejections_get: NULL output");
+    memcpy(out, c->rej.data(), sizeof(fw_rejection) * c->rej.size());
     return FW_OK;
 }
 

@@ -81,6 +81,7 @@ struct DhArrays {
     const int32_t *nb_idx;
     const double *nb_stat, *nb_p;
     const float *tmat;  // fz rounds (r06): the targets' local correlation matrices (DhTgt::tm_off), else null
+    fw_rejection *rej;  // rejection log (fw_set_track_rejections): one slot per directed level-0 entry (dh_rej_write), else null
 };
 
 struct DhParams {
@@ -162,6 +163,57 @@ __device__ __forceinline__ unsigned long long dh_enum_size(int a, int max_k, lon
     }
     if (max_tests > 0 && (unsigned long long)max_tests < N) N = (unsigned long long)max_tests;
     return N;
+}
+
+// Rejection log (update_sig_result!, hiton.jl:71-76): the job of (x.T, cand) over acc[0..a) ended with test number nt of its enumeration
+// (tests.jl:281-346 order: sizes max_k .. 1, lexicographic positions), and that test is not significant.  ONE lane unranks nt - 1 against
+// the list the job ran on and writes the record to the candidate's slot of the target's level-0 list: a fixed address per (target,
+// candidate), so neither atomics nor an order between wavefronts are involved.  nt = 0: the job ended without a test (tests.jl:293-296).
+// frac is filled in on the host (from n_acc).
+__device__ __noinline__ void dh_rej_write(const DhTgt &x, const DhArrays &A, int max_k, int32_t cand, const int32_t *acc, int a,
+                                          unsigned long long nt, double stat, double p, int df, int pow)
+{
+    const int32_t *b = A.nb_idx + x.nb_off;
+    int lo = 0, hi = x.nb_n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (b[mid] < cand)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    if (lo >= x.nb_n || b[lo] != cand) return;  // (every candidate is a level-0 neighbour: never taken)
+    fw_rejection r;
+    r.target = x.T;
+    r.candidate = cand;
+    r.n_zs = 0;
+#pragma unroll
+    for (int q = 0; q < FW_MAX_K; ++q) r.zs[q] = 0;
+    if (nt > 0ull) {
+        unsigned long long rem = nt - 1ull;
+        int s = max_k;
+        while (s > 1) {
+            const unsigned long long cnt = fw_binom_u64(a, s);
+            if (rem < cnt) break;
+            rem -= cnt;
+            --s;
+        }
+        int pos[FW_MAX_K_FAST];
+        fw_unrank_comb(rem, a, s, pos);
+        r.n_zs = s;
+#pragma unroll
+        for (int q = 0; q < FW_MAX_K_FAST; ++q)
+            if (q < s) r.zs[q] = acc[pos[q]];
+    }
+    r.df = nt > 0ull ? df : 0;
+    r.suff_power = pow;
+    r.phase = x.phase;
+    r.n_acc = a;
+    r.num_tests = (long long)nt;
+    r.frac = 0.0;
+    r.stat = stat;
+    r.pval = p;
+    A.rej[x.nb_off + lo] = r;
 }
 
 // dh_alg_bytes for the discrete kinds with max_k <= 3 and short lists: the same sum in integers (bytes per test of size s are
@@ -309,9 +361,11 @@ struct DhMerge {
     unsigned long long nt;  // stop: tests up to and including the stopping one
     unsigned long long ev;  // tests executed by the segments
     double g;               // mi_merge, !stop: G^2 and df of the maximum-p test (the seed of later records of the job)
-    int df;
+    int df;                 // dh_merge, stop: df of the stopping test (the rejection log)
 };
 
+// TR (rejection log): the stopping test's df comes back as well; the default instantiation is the merge as it was
+template <bool TR = false>
 __device__ __forceinline__ DhMerge dh_merge(const FwSegOut *__restrict__ so, long long base, int nseg, int lane)
 {
     unsigned long long ev = 0ull;
@@ -364,6 +418,7 @@ __device__ __forceinline__ DhMerge dh_merge(const FwSegOut *__restrict__ so, lon
         M.nt = __shfl(st_rank, owner) + 1ull;
         // fz_nz: too few rows with T != 0 and candidate != 0 -> (0, 1, 0, false) with ZERO tests (tests.jl:294-296; marker of fz_seg_body)
         if (__shfl(st_df, owner) == -2) M.nt = 0ull;
+        if constexpr (TR) M.df = __shfl(st_df, owner);
     } else {
         M.stop = false;
         M.stat = bs;
@@ -372,7 +427,8 @@ __device__ __forceinline__ DhMerge dh_merge(const FwSegOut *__restrict__ so, lon
         M.nt = 0ull;
     }
     M.g = 0.0;
-    M.df = 0;
+    if constexpr (!TR) M.df = 0;
+    else if (!M.stop) M.df = 0;
     return M;
 }
 
@@ -380,13 +436,19 @@ __device__ __forceinline__ DhMerge dh_merge(const FwSegOut *__restrict__ so, lon
 // or is dropped.  Every lane computes the same state; lane 0 writes.  Returns whether the candidate joined the accepted list.
 // exact (fast_elim = false, hiton.jl:67-70): a rejected elimination-phase member re-enters the pool all the same, without
 // entering PC -- the pool of the next member no longer depends on this verdict.
+// TR (rejection log, a compile-time instantiation: the default one is the commit as it was): a rejection -- the stopping test was
+// number r_nt of the enumeration, with r_df degrees of freedom -- leaves its record (dh_rej_write).
+template <bool TR = false>
 __device__ __forceinline__ bool dh_commit(DhTgt &x, const DhArrays &A, int lane, int d1, double r_stat, double r_p, int r_pow,
-                                          double alpha, bool exact = false)
+                                          double alpha, bool exact = false, int max_k_rej = 0, unsigned long long r_nt = 0ull, int r_df = 0)
 {
     const int32_t *cands = x.phase == 0 ? A.cand0 + x.cand_off : A.tpc_key + x.co;
     const int32_t cand = cands[x.pos];
     ++x.pos;
     if (!(r_p < alpha && r_pow)) {
+        if constexpr (TR) {  // (the list entries were written by this lane or by an earlier kernel: nothing to order)
+            if (lane == 0) dh_rej_write(x, A, max_k_rej, cand, A.acc + DH_ACC_OFF(x, x.cur, d1), x.na, r_nt, r_stat, r_p, r_df, r_pow);
+        }
         if (!(exact && x.phase == 1)) return false;
         if (lane == 0) A.acc[DH_ACC_OFF(x, x.cur, d1) + x.na] = cand;
         ++x.na;
@@ -565,7 +627,8 @@ __device__ __forceinline__ unsigned long long mi_rfl_lane64(unsigned long long v
 // ranks [r0, r1) of the job (T, cand | subsets of acc[0..a)) in enumeration order, one test after the other (whole wavefront).
 // Called, not inlined: the kernel reaches it from four places (own jobs, own board, other boards while waiting / between
 // jobs / at the end) and four copies of the test made 168 KB of code -- against a 64 KB instruction cache.
-template <int L, int NXY, int PRE>
+// STOP_P: the stopping test's p-value is evaluated (mi_account: need_stop_p) -- the rejection log's second look at a stopping test
+template <int L, int NXY, int PRE, bool STOP_P = false>
 __device__ __noinline__ void mi_run_ranks(int T, int cand, const int32_t *__restrict__ acc_in, int a, int max_k,
                                           long long max_tests, unsigned long long r0, unsigned long long r1,
                                           const unsigned long long *stop_min_in, int remote_acc, const MiBest *seed_in)
@@ -664,7 +727,7 @@ __device__ __noinline__ void mi_run_ranks(int T, int cand, const int32_t *__rest
 #ifdef FW_MI_TICKS
         const unsigned long long tkc = wall_clock64();
 #endif
-        const int ev = mi_account(M, t, max_tests > 0 && r + 1ull >= (unsigned long long)max_tests, mb, false);  // tests.jl:326-341
+        const int ev = mi_account(M, t, max_tests > 0 && r + 1ull >= (unsigned long long)max_tests, mb, STOP_P);  // tests.jl:326-341
 #ifdef FW_MI_TICKS
         {
             const unsigned long long tkd = wall_clock64();
@@ -721,7 +784,7 @@ __device__ __noinline__ void mi_run_ranks(int T, int cand, const int32_t *__rest
 // per stratum): the four tests of a step are ranks r .. r + 3 of the same size; they are accounted for in rank order exactly as the
 // sequential loop would (first stop wins, `>=` maximum before it), so the tests behind a stop inside a step are the only
 // speculation (counted in `evaluated`).
-template <int L>
+template <int L, bool STOP_P = false>
 __device__ __noinline__ void mi_run_ranks4(int T, int cand, const int32_t *__restrict__ acc_in, int a, int max_k,
                                            long long max_tests, unsigned long long r0, unsigned long long r1,
                                            const unsigned long long *stop_min_in, int remote_acc, const MiBest *seed_in)
@@ -851,7 +914,7 @@ __device__ __noinline__ void mi_run_ranks4(int T, int cand, const int32_t *__res
             tt.power = __builtin_amdgcn_readlane(mine.power, src);
             tt.n_obs = (long long)mi_rfl_lane64((unsigned long long)mine.n_obs, src);
             const unsigned long long rr = r + (unsigned long long)t;
-            const int ev = mi_account(M, tt, max_tests > 0 && rr + 1ull >= (unsigned long long)max_tests, mb, false);  // tests.jl:326-341
+            const int ev = mi_account(M, tt, max_tests > 0 && rr + 1ull >= (unsigned long long)max_tests, mb, STOP_P);  // tests.jl:326-341
             if (ev == 1) {
                 o.stop_rank = rr;
                 o.stop_stat = tt.stat;
@@ -964,15 +1027,15 @@ __device__ __noinline__ void mi_first4(int T, int pos0, const int32_t *__restric
 }
 
 // R4: the four-subsets-per-step form (host: n <= MI4_N, max_k <= 3, 2 x 2 cells); one of the two routines per instantiation
-template <int L, int NXY, int PRE, bool R4>
+template <int L, int NXY, int PRE, bool R4, bool STOP_P = false>
 __device__ __forceinline__ FwSegOut mi_run_ranks_sel(int T, int cand, const int32_t *__restrict__ acc, int a, int max_k,
                                                      long long max_tests, unsigned long long r0, unsigned long long r1,
                                                      const unsigned long long *stop_min, int remote_acc, const MiBest *seed)
 {
     if constexpr (R4)
-        mi_run_ranks4<L>(T, cand, acc, a, max_k, max_tests, r0, r1, stop_min, remote_acc, seed);
+        mi_run_ranks4<L, STOP_P>(T, cand, acc, a, max_k, max_tests, r0, r1, stop_min, remote_acc, seed);
     else
-        mi_run_ranks<L, NXY, PRE>(T, cand, acc, a, max_k, max_tests, r0, r1, stop_min, remote_acc, seed);
+        mi_run_ranks<L, NXY, PRE, STOP_P>(T, cand, acc, a, max_k, max_tests, r0, r1, stop_min, remote_acc, seed);
     return dh_mi_out[threadIdx.x >> 6];  // (inlined: the record comes back through LDS, not through a by-value return)
 }
 
@@ -1228,7 +1291,27 @@ __device__ __forceinline__ bool mi_publish(MiQueue *__restrict__ Q, MiBoard *__r
 // the persistent kernel's own clock reads (per job: phase times for FW_TRACE_HOST): a wall_clock64() is a scalar memory round trip,
 // four of them per job were ~5 % of a light job -- taken only when the host asks for the trace (DhParams::mi_trace)
 #define MI_CLK() (P.mi_trace ? wall_clock64() : 0ull)
-template <int L, int NXY, int PRE, bool R4, bool EX>
+// Rejection log of the persistent kernel (TR instantiations only): the verdict of a job carries the stopping test's statistic and
+// power through the look-ahead slots, the lock-step records and the boards, but neither its degrees of freedom nor its p-value (HITON-PC
+// drops a rejected candidate without looking at p, so mi_account does not evaluate Q(a, x) for it) -- the stopping test (rank nt - 1 of
+// the enumeration over acc[0..a), the list the job ran on) is evaluated once more by this wavefront, with its p-value, and lane 0
+// writes the record (dh_rej_write).  One extra test per rejected candidate, in the tracking instantiations only.
+template <int L, int NXY, int PRE, bool R4>
+__device__ __forceinline__ void mi_rej_record(MiQueue *__restrict__ Q, const DhTgt &x, int T, int cand, const int32_t *acc, int a, unsigned long long nt,
+                                              double r_stat, double r_p, int r_pow, int lane)
+{
+    const DhArrays &A = dh_mi_ctx.A;
+    const DhParams &P = dh_mi_ctx.P;
+    const FwSegOut q = mi_run_ranks_sel<L, NXY, PRE, R4, true>(T, cand, acc, a, P.max_k, P.max_tests, nt - 1ull, nt, nullptr, 0, nullptr);
+    // the same arithmetic on the same words: the test stops again.  If it ever did not, the record would carry another test's p and df:
+    // the launch is failed through the queue's error word (like the watchdogs), nothing is written
+    if (q.stop_rank == FW_RANK_NONE) {
+        if (lane == 0) atomicExch(&Q->pad[0], 4u);
+        return;
+    }
+    if (lane == 0) dh_rej_write(x, A, P.max_k, cand, acc, a, nt, r_stat, q.stop_pval, q.stop_df, r_pow);
+}
+template <int L, int NXY, int PRE, bool R4, bool EX, bool TR>
 __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, MiQueue *__restrict__ Q,
                                         MiBoard *__restrict__ boards, FwSegOut *__restrict__ res, int32_t *__restrict__ bacc)
 {
@@ -1246,7 +1329,7 @@ __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, 
     const unsigned long long per = R4 ? 4ull : 1ull;  // ranks per wavefront and lock-step round
     for (;;) {
         if (wave == 0) {
-            const bool more = dh_advance(x, A, lane, 1, EX && P.elim_mode == 2);
+            const bool more = dh_advance(x, A, lane, 1, (EX || TR) && P.elim_mode == 2);
             if (lane == 0) {
                 J.go = more ? 1 : 0;
                 if (more) {
@@ -1517,7 +1600,12 @@ __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, 
             x.c_eval += ev;
             x.c_alg += (P.max_k <= 3 && a <= FW_UNRANK32_A) ? dh_alg_bytes_disc32(a, ev, P.max_k, P.disc_bytes_per_col)
                                                             : dh_alg_bytes(a, ev, P.max_k, P.disc_bytes_per_col);
-            dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, EX);
+            if constexpr (TR) {
+                if (stopped && !(r_p < P.alpha && r_pow)) mi_rej_record<L, NXY, PRE, R4>(Q, x, T, cand, acc, a, nt, r_stat, r_p, r_pow, lane);  // (wavefront 0 alone: the routine touches only its own wavefront's LDS slots, and the others wait at the next job's first barrier)
+                dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, P.elim_mode != 0);
+            } else {
+                dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, EX);
+            }
         }
     }
     if (wave == 0 && lane == 0) {
@@ -1538,7 +1626,8 @@ __device__ __noinline__ void dh_mi_team(DhTgt *__restrict__ tg, int ntg, int t, 
 #endif
 // EX: exact elimination (fw_learn_opts.elim_mode 1 / 2) -- a compile-time instantiation, so that the default one keeps its
 // register allocation
-template <int L, int NXY, int PRE, bool R4, bool EX>
+// TR: the rejection log (fw_set_track_rejections) -- likewise; the tracking instantiation reads the elimination mode at run time
+template <int L, int NXY, int PRE, bool R4, bool EX, bool TR>
 __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__restrict__ tg, int ntg, const int32_t *__restrict__ order,
                                                            DhArrays A, MiDev M, DhParams P, MiQueue *__restrict__ Q,
                                                            MiBoard *__restrict__ boards, FwSegOut *__restrict__ res,
@@ -1569,7 +1658,7 @@ __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__r
         const unsigned int ts = (unsigned int)dh_mi_tj.go;
         __syncthreads();  // (dh_mi_team rewrites the descriptor)
         if (ts >= P.mi_team) break;
-        dh_mi_team<L, NXY, PRE, R4, EX>(tg, ntg, order[ts], Q, boards, res, bacc);
+        dh_mi_team<L, NXY, PRE, R4, EX, TR>(tg, ntg, order[ts], Q, boards, res, bacc);
     }
     unsigned int jobctr = 0u;
     bool tail_seen = false;
@@ -1589,7 +1678,7 @@ __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__r
         __builtin_amdgcn_wave_barrier();
         for (;;) {
             const unsigned long long tka0 = MI_CLK();
-            const bool more_jobs = dh_advance(x, A, lane, 1, EX && P.elim_mode == 2);
+            const bool more_jobs = dh_advance(x, A, lane, 1, (EX || TR) && P.elim_mode == 2);
             MI_TICK(6, tka0);
             if (!more_jobs) break;
             // other targets' big enumerations first: they are the critical path of the pass
@@ -1779,7 +1868,12 @@ __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__r
             x.c_eval += ev;
             x.c_alg += (P.max_k <= 3 && a <= FW_UNRANK32_A) ? dh_alg_bytes_disc32(a, ev, P.max_k, P.disc_bytes_per_col)
                                                             : dh_alg_bytes(a, ev, P.max_k, P.disc_bytes_per_col);
-            dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, EX);
+            if constexpr (TR) {
+                if (stopped && !(r_p < P.alpha && r_pow)) mi_rej_record<L, NXY, PRE, R4>(Q, x, x.T, cand, A.acc + acc_off, a, nt, r_stat, r_p, r_pow, lane);
+                dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, P.elim_mode != 0);
+            } else {
+                dh_commit(x, A, lane, 1, r_stat, r_p, r_pow, P.alpha, EX);
+            }
             MI_TICK(8, tkc0);
         }
         if (lane == 0) {
@@ -1832,6 +1926,7 @@ __global__ __launch_bounds__(256, DH_MI_OCC) void dh_mi_target_kernel(DhTgt *__r
 // L_{j+1} = (L_j + [c_j]) \ {c_{j+1}} (hiton.jl:134-149: a kept member re-enters the pool at its end), each in its own
 // accepted-list buffer.  The step kernel commits them in order; the first dropped member ends the chain (the later
 // look-ahead jobs saw a pool that still held it: their results are discarded and they run again).
+template <bool TR>
 __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhGlobal *__restrict__ g, const DhArrays &A,
                                             const FwSegOut *__restrict__ so, const long long *__restrict__ seg0,
                                             unsigned long long *__restrict__ win, unsigned int *__restrict__ sp,
@@ -1861,12 +1956,14 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
         if (x.jactive) {
             if (x.phase == 0) (x.jnext == 0ull ? x.r_first0 : x.r_more0) += 1u;
             else (x.jnext == 0ull ? x.r_first1 : x.r_more1) += 1u;
-            const DhMerge M = dh_merge(so, jseg0, jnseg, lane);
+            const DhMerge M = dh_merge<TR>(so, jseg0, jnseg, lane);
             double r_stat = 0.0, r_p = 1.0;
             int r_pow = 0;
+            [[maybe_unused]] int r_df = 0;
             unsigned long long r_nt = 0ull;
             bool done = false;
             if (M.stop) {
+                if constexpr (TR) r_df = M.df;
                 r_stat = M.stat;
                 r_p = M.p;
                 r_pow = M.pow;
@@ -1898,7 +1995,8 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
                 x.c_eval_short += x.na <= FW_HK_A ? x.jevaluated : 0ull;
                 x.na_max = x.na > x.na_max ? x.na : x.na_max;
                 x.c_alg += dh_alg_bytes(x.na, x.jevaluated, P.max_k, P.disc_bytes_per_col);
-                kept = dh_commit(x, A, lane, d1, r_stat, r_p, r_pow, P.alpha, P.elim_mode != 0);
+                if constexpr (TR) kept = dh_commit<true>(x, A, lane, d1, r_stat, r_p, r_pow, P.alpha, P.elim_mode != 0, P.max_k, r_nt, r_df);
+                else kept = dh_commit(x, A, lane, d1, r_stat, r_p, r_pow, P.alpha, P.elim_mode != 0);
             }
         }
         if (nsp_done > 0) {
@@ -1915,7 +2013,7 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
             if (acc_mode) x.jN = x.jN2;  // the enumeration the look-ahead jobs belong to (accepted list one entry longer)
             bool valid = finished && ((ph1 || acc_mode) ? kept : !kept);
             for (int j = 1; j <= nsp_done; ++j) {
-                const DhMerge M = dh_merge(so, jseg0 + (long long)jnseg + (long long)(j - 1) * jnseg2, jnseg2, lane);
+                const DhMerge M = dh_merge<TR>(so, jseg0 + (long long)jnseg + (long long)(j - 1) * jnseg2, jnseg2, lane);
                 if (!valid) {  // built on an assumption that failed: executed for nothing
                     x.c_eval += M.ev;
                     continue;
@@ -1942,7 +2040,9 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
                 x.c_eval += M.ev;
                 x.c_eval_short += n <= FW_HK_A ? M.ev : 0ull;
                 x.c_alg += dh_alg_bytes(n, M.ev, P.max_k, P.disc_bytes_per_col);
-                const bool k = dh_commit(x, A, lane, d1, r_stat, r_p, M.stop ? M.pow : 1, P.alpha, P.elim_mode != 0);
+                bool k;
+                if constexpr (TR) k = dh_commit<true>(x, A, lane, d1, r_stat, r_p, M.stop ? M.pow : 1, P.alpha, P.elim_mode != 0, P.max_k, M.nt, M.df);
+                else k = dh_commit(x, A, lane, d1, r_stat, r_p, M.stop ? M.pow : 1, P.alpha, P.elim_mode != 0);
                 valid = ph1 ? k : !k;
             }
         }
@@ -2073,12 +2173,13 @@ __device__ __forceinline__ void dh_step_dev(DhTgt *__restrict__ tg, int ntg, DhG
     }
 }
 
+template <bool TR>
 __global__ __launch_bounds__(256) void dh_step_kernel(DhTgt *__restrict__ tg, int ntg, DhGlobal *__restrict__ g, DhArrays A,
                                                       const FwSegOut *__restrict__ so, const long long *__restrict__ seg0,
                                                       unsigned long long *__restrict__ win, unsigned int *__restrict__ sp,
                                                       unsigned long long *__restrict__ win2, const int32_t *__restrict__ act, DhParams P)
 {
-    dh_step_dev(tg, ntg, g, A, so, seg0, win, sp, win2, act, P, (int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+    dh_step_dev<TR>(tg, ntg, g, A, so, seg0, win, sp, win2, act, P, (int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
 }
 
 // one workgroup: totals of the coming launch, its segment length, per-target segment counts and their exclusive scan.
@@ -2554,12 +2655,15 @@ static unsigned dh_mi_launch(fw_ctx *c, hipStream_t st, DhTgt *d_tg, int ntg, co
 #endif
 #define DH_MI_LAUNCH(LL, NN, PP, RR)                                                                                                  \
     do {                                                                                                                              \
-        if (P.elim_mode != 0)                                                                                                         \
-            hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR, true>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order, A, M, \
-                               P, d_mq, d_boards, d_mres, d_bacc);                                                                    \
+        if (A.rej)                                                                                                                    \
+            hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR, false, true>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order, \
+                               A, M, P, d_mq, d_boards, d_mres, d_bacc);                                                              \
+        else if (P.elim_mode != 0)                                                                                                    \
+            hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR, true, false>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order, \
+                               A, M, P, d_mq, d_boards, d_mres, d_bacc);                                                              \
         else                                                                                                                          \
-            hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR, false>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order, A, M, \
-                               P, d_mq, d_boards, d_mres, d_bacc);                                                                    \
+            hipLaunchKernelGGL((dh_mi_target_kernel<LL, NN, PP, RR, false, false>), dim3(grid), dim3(256), 0, st, d_tg, ntg, d_order,\
+                               A, M, P, d_mq, d_boards, d_mres, d_bacc);                                                              \
     } while (0)
     const bool pre = c->P.n <= MI_PRE_N && c->P.max_k <= MI_PRE_K;
     // four subsets per wavefront step (mi_test_core4): n <= 5120, max_k <= 3, 2 x 2 cells per stratum.  FW_MI_ROW4=0: one per step
@@ -2805,6 +2909,7 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
         A.nb_stat = s1;
         A.nb_p = s2;
     }
+    A.rej = c->d_rej_run;
     A.tmat = d_tmat;
     if (d_tmat) {
         hipLaunchKernelGGL(dh_tmat_build_kernel, dim3((unsigned)ntg, 8u), dim3(256), 0, st, (const DhTgt *)d_tg, ntg, A.nb_idx, (const float *)c->d_cor, p, d_tmat);
@@ -2895,8 +3000,12 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
             (void)hipEventRecord(c->dh_hp_ev[chain][0], st);
             (void)hipStreamWaitEvent(hs, c->dh_hp_ev[chain][0], 0);
         }
-        hipLaunchKernelGGL(dh_step_kernel, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, d_tg, ntg, d_g, A,
-                           (const FwSegOut *)d_so, (const long long *)d_seg0, d_win, d_sp, d_win2, (const int32_t *)d_act, P);
+        if (A.rej)  // (the rejection log: its own instantiation, so that the default one keeps its registers)
+            hipLaunchKernelGGL(dh_step_kernel<true>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, d_tg, ntg, d_g, A,
+                               (const FwSegOut *)d_so, (const long long *)d_seg0, d_win, d_sp, d_win2, (const int32_t *)d_act, P);
+        else
+            hipLaunchKernelGGL(dh_step_kernel<false>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, d_tg, ntg, d_g, A,
+                               (const FwSegOut *)d_so, (const long long *)d_seg0, d_win, d_sp, d_win2, (const int32_t *)d_act, P);
         if (compact)  // between step and plan: seg0 of the coming launch is built on the new list
             hipLaunchKernelGGL(dh_compact_kernel, dim3(1), dim3(1024), 0, hs, (const DhTgt *)d_tg, ntg, d_g, d_act);
         if (plan_small)
@@ -3210,6 +3319,7 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     A.tpc_p = (double *)carve(8 * nnz + 8);
     A.pc_stat = (double *)carve(8 * nnz + 8);
     A.pc_p = (double *)carve(8 * nnz + 8);
+    A.rej = c->d_rej_run;
     A.nb_off = c->d_nb_off;
     A.nb_idx = c->d_nb_idx;
     A.nb_stat = c->d_nb_stat;

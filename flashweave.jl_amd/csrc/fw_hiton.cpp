@@ -15,6 +15,7 @@
 #include <unordered_map>
 
 #include "fw_internal.h"
+#include "fw_unrank.h"
 
 namespace {
 
@@ -121,6 +122,27 @@ static bool advance(const fw_ctx *c, Target &t)
             t.phase = 2;
         }
     }
+}
+
+// update_sig_result! (hiton.jl:71-76) with track_rejections: the job of (T, cand) against t.acc ended with a test that is not
+// significant -> its record goes to the candidate's slot of T's level-0 list (fw_internal.h: rej_slots)
+static void rej_store(fw_ctx *c, const Target &t, int32_t cand, const FwJobOut &o)
+{
+    const int64_t b = c->nb_off[t.T];
+    const int32_t *lo = c->nb_idx.data() + b, *hi = c->nb_idx.data() + c->nb_off[t.T + 1];
+    fw_rejection &r = c->rej_slots[(size_t)(b + (std::lower_bound(lo, hi, cand) - lo))];
+    r = fw_rejection{};
+    r.target = t.T;
+    r.candidate = cand;
+    r.n_zs = o.n_zs;
+    for (int q = 0; q < o.n_zs; ++q) r.zs[q] = o.zs[q];
+    r.df = o.df;
+    r.suff_power = o.suff_power;
+    r.phase = t.phase;
+    r.n_acc = (int32_t)t.acc.size();
+    r.num_tests = o.num_tests;
+    r.stat = o.stat;
+    r.pval = o.pval;
 }
 
 static double maxweight(double w1, double w2)
@@ -340,6 +362,28 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
     } elim_guard{c};
     c->elim_mode = opt.elim_mode;
     const int p = c->P.p;
+    // rejection log (fw_set_track_rejections): one slot per directed level-0 entry, on the host for the job pool and in device memory for
+    // the paths whose state machine lives there; merged and compacted behind the conditional stage
+    struct RejGuard {
+        fw_ctx *c;
+        ~RejGuard()
+        {
+            c->d_rej_run = nullptr;
+            std::vector<fw_rejection>().swap(c->rej_slots);
+        }
+    } rej_guard{c};
+    c->rej.clear();
+    const bool track = c->track_rej != 0;
+    const size_t rej_n = track && c->P.max_k > 0 ? (size_t)c->nb_off[p] : 0;
+    if (rej_n) {
+        fw_rejection none;
+        memset(&none, 0xff, sizeof(none));  // n_zs = -1: no record
+        c->rej_slots.assign(rej_n, none);
+        if (int rc = fw_dev_reserve(c, c->d_rej, sizeof(fw_rejection) * rej_n)) return rc;
+        FW_HIP(c, hipMemset(c->d_rej.ptr, 0xff, sizeof(fw_rejection) * rej_n));
+        FW_HIP(c, hipDeviceSynchronize());  // (the device paths run on non-blocking streams of their own)
+        c->d_rej_run = (fw_rejection *)c->d_rej.ptr;
+    }
     const bool discrete = c->P.kind == FW_MI || c->P.kind == FW_MI_NZ;
     const double t0 = now_s();
 
@@ -589,6 +633,7 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
 
             long n_unfinished = (long)tg.size();
             FwPool pool;
+            pool.want_zs = rej_n != 0;  // the rejection log keeps the conditioning set of the stopping test
             std::vector<int32_t> epoch(tg.size(), 0);
             pool.owner_epoch = &epoch;
             std::vector<FwPoolJob> fin;
@@ -624,8 +669,9 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                                 t.ready.clear();
                                 t.posted_end = t.pos;
                             }
-                        } else if (exact) {  // hiton.jl:67-70
-                            t.acc.push_back(cand);
+                        } else {
+                            if (rej_n) rej_store(c, t, cand, o);  // hiton.jl:71-76
+                            if (exact) t.acc.push_back(cand);     // hiton.jl:67-70
                         }
                     }
                     if (t.phase == 2) {
@@ -742,6 +788,21 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
             dirty.clear();
         }
     }
+    if (rej_n) {
+        // device records win their slot (a target ran on one path only: at most one of the two copies is filled)
+        std::vector<fw_rejection> dev(rej_n);
+        FW_HIP(c, hipMemcpy(dev.data(), c->d_rej.ptr, sizeof(fw_rejection) * rej_n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < rej_n; ++i) {
+            fw_rejection r = dev[i].n_zs >= 0 ? dev[i] : c->rej_slots[i];
+            if (r.n_zs < 0) continue;
+            double total = 0.0;  // tests.jl:313,327-332: every subset of sizes max_k .. 1, not capped by max_tests (integer binomials)
+            for (int s = c->P.max_k; s >= 1; --s) total += (double)fw_binom_any(r.n_acc, s);
+            r.frac = r.num_tests > 0 && total > 0.0 ? (double)r.num_tests / total : 0.0;
+            for (int q = r.n_zs; q < FW_MAX_K; ++q) r.zs[q] = 0;
+            c->rej.push_back(r);
+        }
+    }
+    if (track) c->have_rej = true;
     c->cnt.t_cond_s += now_s() - t0;
     if (fw_knob("FW_TRACE_HOST")) fprintf(stderr, "[fw] conditional stage: %.2f ms\n", 1e3 * (now_s() - t0));
 

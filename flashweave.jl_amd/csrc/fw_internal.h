@@ -191,6 +191,16 @@ struct fw_ctx {
     std::vector<int32_t> pc_idx;
     std::vector<double> pc_w, pc_p;
 
+    // ---- rejection log (fw_set_track_rejections) ----
+    // One slot per directed level-0 entry: the record of (T, candidate) lives at the candidate's position in T's level-0 list
+    // (nb_off[T] + index of the candidate in the ascending list), n_zs = -1 while empty.  The host job pool fills rej_slots, the device
+    // paths the device copy; fw_learn_network merges the two and compacts them into rej (ascending target, candidate).
+    int track_rej = 0;
+    bool have_rej = false;
+    std::vector<fw_rejection> rej, rej_slots;
+    FwDevBuf d_rej;
+    fw_rejection *d_rej_run = nullptr;  // non-null while a tracked fw_learn_network runs (read by fw_devhiton.hip)
+
     fw_counters cnt{};
 
     // grow-only scratch

@@ -38,6 +38,27 @@ class _SubsetsResult(C.Structure):
                 ("num_tests", C.c_int64), ("frac", C.c_double)]
 
 
+class _Rejection(C.Structure):  # fw_rejection
+    _fields_ = [("target", C.c_int32), ("candidate", C.c_int32), ("n_zs", C.c_int32), ("zs", C.c_int32 * FW_MAX_K),
+                ("df", C.c_int32), ("suff_power", C.c_int32), ("phase", C.c_int32), ("n_acc", C.c_int32),
+                ("num_tests", C.c_int64), ("frac", C.c_double), ("stat", C.c_double), ("pval", C.c_double)]
+
+
+REJECTION_DTYPE = np.dtype([("target", "<i4"), ("candidate", "<i4"), ("n_zs", "<i4"), ("zs", "<i4", (FW_MAX_K,)), ("df", "<i4"),
+                            ("suff_power", "<i4"), ("phase", "<i4"), ("n_acc", "<i4"), ("num_tests", "<i8"), ("frac", "<f8"),
+                            ("stat", "<f8"), ("pval", "<f8")])
+
+
+def rejections_dict(records):
+    """fw_rejection records -> {target: {candidate: (Zs, (stat, pval, df, suff_power), (num_tests, frac))}}, the shape of the
+    reference's rejections(net_result) (Dict{T, RejDict}, types.jl:152) with 0-based ids."""
+    out = {}
+    cols = [records[f].tolist() for f in ("target", "candidate", "n_zs", "zs", "stat", "pval", "df", "suff_power", "num_tests", "frac")]
+    for T, c, k, zs, stat, pval, df, pw, nt, frac in zip(*cols):  # (columns as Python lists first: 350 000 records in ~0.3 s)
+        out.setdefault(T, {})[c] = (tuple(zs[:k]), (stat, pval, df, bool(pw)), (nt, frac))
+    return out
+
+
 class _Counters(C.Structure):
     _fields_ = [("level0_tests", C.c_int64), ("cond_tests_ref", C.c_int64), ("cond_tests_evaluated", C.c_int64),
                 ("subsets_calls", C.c_int64), ("kernel_launches", C.c_int64), ("subsets_launches", C.c_int64), ("t_level0_s", C.c_double), ("t_level0_host_s", C.c_double),
@@ -113,6 +134,9 @@ def load_library():
     L.fw_level0.argtypes = [vp, C.POINTER(C.c_int64)]
     L.fw_level0_get.argtypes = [vp, vp, vp, vp, vp]
     L.fw_set_row_views.argtypes = [vp, C.c_int32]
+    L.fw_set_track_rejections.argtypes = [vp, C.c_int32]
+    L.fw_rejections_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.fw_rejections_get.argtypes = [vp, vp]
     L.fw_normalize_counts.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32)]
     L.fw_level0_sharded.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int64)]
@@ -321,13 +345,15 @@ class Engine:
     def cor_allgather_comm(self, rows_per_rank):
         self._ck(self.L.fw_cor_mat_allgather_comm(self.h, int(rows_per_rank)))
 
-    def lgl_comm(self, feed_forward=True, round_size=1, max_targets=0, edge_dict=True, fast_elim=True, no_red_tests=True):
+    def lgl_comm(self, feed_forward=True, round_size=1, max_targets=0, edge_dict=True, fast_elim=True, no_red_tests=True,
+                 track_rejections=False):
         """fw_learn_network_comm: LGL of a target-sharded run, the per-round exchange issued by the library (rank / world_size are the
-        communicator's).  fast_elim / no_red_tests: as in lgl."""
+        communicator's).  fast_elim / no_red_tests / track_rejections: as in lgl (every rank gets the rejections of its own targets)."""
+        self._set_track(track_rejections)
         opts = _LearnOpts(int(feed_forward), int(round_size), 0, 1, int(max_targets), elim_mode(fast_elim, no_red_tests))
         ne = C.c_int64(0)
         self._ck(self.L.fw_learn_network_comm(self.h, C.byref(opts), C.byref(ne)))
-        return self._network(ne.value, edge_dict)
+        return self._network(ne.value, edge_dict, track_rejections)
 
     # -- row-block sharding of cor() ------------------------------------------------------------------
     def use_cor_buffer(self, device_ptr, capacity_floats):
@@ -399,12 +425,18 @@ class Engine:
 
     # -- LGL -----------------------------------------------------------------------------------------
     def lgl(self, feed_forward=True, round_size=1, rank=0, world_size=1, max_targets=0, allgather=None, edge_dict=True, dev_exchange=None,
-            fast_elim=True, no_red_tests=True):
+            fast_elim=True, no_red_tests=True, track_rejections=False):
         """LGL minus normalisation (src/learning.jl:203-279).  Returns dict(edges={(i,j): w}, directed=CSR);
         edge_dict=False leaves the edges as the three arrays fw_network_get fills (edge_src, edge_dst, edge_weight) and
         skips the Python dictionary (48 000 tuples cost ~8 ms at cfg3).
         fast_elim=False: exact HITON-PC elimination (hiton.jl:67-70: a rejected member stays in the conditioning pool);
-        no_red_tests=False (with fast_elim=False only): PC keeps the elimination-phase statistics (hiton.jl:388-390)."""
+        no_red_tests=False (with fast_elim=False only): PC keeps the elimination-phase statistics (hiton.jl:388-390).
+        track_rejections=True (learning.jl:446): the result also holds "rejections" = {target: {candidate: (Zs, (stat, pval, df,
+        suff_power), (num_tests, frac))}} -- for every candidate a conditional test removed, the first non-significant test in the
+        reference's order -- and "rejection_records", the same as a structured array (REJECTION_DTYPE, with the phase and the length
+        of the accepted list; ascending target, candidate); edge_dict=False returns the array only.  The network is the same bytes
+        either way."""
+        self._set_track(track_rejections)
         opts = _LearnOpts(int(feed_forward), int(round_size), int(rank), int(world_size), int(max_targets), elim_mode(fast_elim, no_red_tests))
         ne = C.c_int64(0)
         cb = None
@@ -417,9 +449,22 @@ class Engine:
             self._ck(self.L.fw_learn_network_dev(self.h, C.byref(opts), C.byref(x), C.byref(ne)))
         else:
             self._ck(self.L.fw_learn_network(self.h, C.byref(opts), C.cast(cb, C.c_void_p) if cb else None, None, C.byref(ne)))
-        return self._network(ne.value, edge_dict)
+        return self._network(ne.value, edge_dict, track_rejections)
 
-    def _network(self, n_edges, edge_dict):
+    def _set_track(self, on):
+        if bool(on) != getattr(self, "_track", False):  # (the switch of the context is only touched when it changes)
+            self._ck(self.L.fw_set_track_rejections(self.h, int(bool(on))))
+            self._track = bool(on)
+
+    def rejection_records(self):
+        """The rejection log of the last tracked lgl as a structured array (fw_rejections_count / fw_rejections_get)."""
+        n = C.c_int64(0)
+        self._ck(self.L.fw_rejections_count(self.h, C.byref(n)))
+        rec = np.zeros(max(n.value, 1), REJECTION_DTYPE)
+        self._ck(self.L.fw_rejections_get(self.h, _ptr(rec)))
+        return rec[:n.value]
+
+    def _network(self, n_edges, edge_dict, track_rejections=False):
         ne = C.c_int64(n_edges)
         k = max(ne.value, 1)
         src, dst, w = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.float64)
@@ -434,6 +479,11 @@ class Engine:
                    pc_weight=pw[:off[-1]], pc_pval=pp[:off[-1]])
         if edge_dict:
             out["edges"] = dict(zip(zip(src[:m].tolist(), dst[:m].tolist()), w[:m].tolist()))  # python ints / floats
+        out["rejections"] = {}
+        if track_rejections:
+            out["rejection_records"] = self.rejection_records()
+            if edge_dict:  # (edge_dict=False skips this dictionary as well: rejections_dict(net["rejection_records"]) builds it later)
+                out["rejections"] = rejections_dict(out["rejection_records"])
         return out
 
     def counters(self):

@@ -172,3 +172,47 @@ def save_network(path, edges, header=None, meta_mask=None):
 
 def load_network(path):
     return read_gml(path) if path.endswith(".gml") else read_edgelist(path)
+
+
+# ---- rejection logs (src/io.jl:248-273 load_rejections, :296-318 save_rejections) ---------------------------------------------------
+_REJ_HEADER = ["Edge", "Rejecting_set", "Stat", "P_value", "Num_tests", "Perc_tested", "Df", "SuffPower"]
+_REJ_EMPTY = "# No rejections found, you may have forgotten to specify 'track_rejections' when running FlashWeave"
+
+
+def save_rejections(path, result, digits=5):
+    """result: what learn_network(track_rejections=True) returned, or its "rejections" dictionary {target: {candidate: (Zs, (stat,
+    pval, df, suff_power), (num_tests, frac))}} with 0-based ids.  One line per (target, candidate): `A <-> B`, the comma-joined
+    rejecting set, statistic, p-value, number of tests, fraction tested, df, true / false; floats rounded to `digits`.  Variable ids
+    are written 1-based, as the reference numbers them, so that the files interchange with it."""
+    rej = result["rejections"] if "rejections" in result else result
+    with open(path, "w") as f:
+        if not rej:
+            f.write(_REJ_EMPTY)
+            return
+        f.write("\t".join(_REJ_HEADER) + "\n")
+        for a in sorted(rej):
+            for b in sorted(rej[a]):
+                zs, (stat, pval, df, suff_power), (num_tests, frac) = rej[a][b]
+                items = ["%d <-> %d" % (a + 1, b + 1), ",".join(str(z + 1) for z in zs), repr(round(float(stat), digits)),
+                         repr(round(float(pval), digits)), str(int(num_tests)), repr(round(float(frac), digits)), str(int(df)),
+                         "true" if suff_power else "false"]
+                f.write("\t".join(items) + "\n")
+
+
+def load_rejections(path):
+    """-> {target: {candidate: (Zs, (stat, pval, df, suff_power), (num_tests, frac))}} with 0-based ids ({} for the file of an empty
+    log)."""
+    rej = {}
+    with open(path) as f:
+        first = f.readline()
+        if first.startswith("#"):
+            return rej
+        for line in f:
+            line = line.rstrip("\n")
+            if not line:
+                continue
+            it = line.split("\t")
+            a, b = (int(v) - 1 for v in it[0].split(" <-> "))
+            zs = tuple(int(v) - 1 for v in it[1].split(",")) if it[1] else ()
+            rej.setdefault(a, {})[b] = (zs, (float(it[2]), float(it[3]), int(it[6]), it[7] == "true"), (int(it[4]), float(it[5])))
+    return rej

@@ -301,6 +301,34 @@ int fw_network_get(const fw_ctx *ctx, int32_t *src, int32_t *dst, double *weight
 /* directed per-target results (state_results of every HitonState): CSR over targets */
 int fw_network_get_directed(const fw_ctx *ctx, int64_t *off, int32_t *idx, double *weight, double *pval);
 
+/* ---- rejection log: learn_network(track_rejections = true), src/learning.jl:446,469 --------------------------------------------
+ * One entry of rejections(net_result)[target][candidate] (RejDict, src/types.jl:152): update_sig_result! (src/hiton.jl:53-78) stores
+ * it when a candidate is tested against a non-empty accepted list and the returned test is not significant -- the FIRST such test in
+ * the order of test_subsets (src/tests.jl:281-346).  zs is that test's conditioning set in the order `combinations` yields it,
+ * num_tests the count up to and including it, frac = num_tests / (number of subsets of sizes 1..max_k of the n_acc accepted variables,
+ * not capped by max_tests).  A job that ends without a test (src/tests.jl:293-296) gives n_zs = 0, num_tests = 0, frac = 0.
+ * Whitelisted candidates, the empty-pool acceptance and univariate non-significance leave no entry; a candidate is rejected at most
+ * once per target.  88 bytes, no padding. */
+typedef struct fw_rejection {
+    int32_t target, candidate;
+    int32_t n_zs;
+    int32_t zs[FW_MAX_K];
+    int32_t df, suff_power;
+    int32_t phase;  /* 0 interleaving, 1 elimination (the reference does not keep it) */
+    int32_t n_acc;  /* length of the accepted list the candidate was tested against (the reference does not keep it) */
+    int64_t num_tests;
+    double frac;
+    double stat, pval;
+} fw_rejection;
+/* on = 1: the following fw_learn_network* calls keep the log (default 0; a switch of the context like fw_set_row_views, so that
+ * fw_learn_opts keeps its layout).  The log is a diagnostic mode: the network is the same bytes either way.  In a target-sharded run
+ * every rank holds the entries of its own targets; gathering them across ranks is left to the caller. */
+int fw_set_track_rejections(fw_ctx *ctx, int32_t on);
+/* entries of the last fw_learn_network* (0 if it ran with tracking off); FW_ERR_STATE before the first tracked run */
+int fw_rejections_count(const fw_ctx *ctx, int64_t *n);
+/* out[0 .. n): ascending (target, candidate) */
+int fw_rejections_get(const fw_ctx *ctx, fw_rejection *out);
+
 /* ---- normalisation front-end on the device -------------------------------------- */
 
 /* replaces: normalize_data / preprocess_data (src/preprocessing.jl:412-563) for a count table without meta variables:
