@@ -12,6 +12,7 @@
 // at dh_step_kernel (elimination phase: next members against the pools they will see if every earlier one is kept;
 // interleaving phase: first windows of the next candidates), switched on only while launches are small.
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cstring>
 #include <mutex>
@@ -2315,7 +2316,7 @@ __global__ __launch_bounds__(1024) void dh_plan_kernel(int ntg, DhGlobal *__rest
 // nothing left to dispatch -- cfg5: 3.1 ms per call, 7 588 calls (profiles/r05_cfg5_kernel_stats.csv; stream priority does not help: r06_cfg5_plan_kernel.txt).
 // 256 threads fit beside two resident segment wavefronts as soon as one workgroup leaves.  cfg5 59.1 -> 57.8 s; and at cfg3, whose size-3 kernel fills the register
 // file with 4 x 128, the two chains stop holding each other's rounds up: plan 27 -> 8 us per call in the two-chain pass, headline 159.6 -> 152.2 ms
-// (profiles/r06_cfg5_plan_kernel.txt, r06_cfg3_plan_kernel.txt).  The default (FW_DH_PLAN_SMALL=0: the 1 024-thread form).
+// (profiles/r06_cfg5_plan_kernel.txt, r06_cfg3_plan_kernel.txt).  This 256-thread form is the default (FW_DH_PLAN_SMALL=0: the 1 024-thread form).
 __global__ __launch_bounds__(256) void dh_plan_small_kernel(int ntg, DhGlobal *__restrict__ g, const unsigned long long *__restrict__ win,
                                                             const unsigned int *__restrict__ sp, const unsigned long long *__restrict__ win2,
                                                             const int32_t *__restrict__ act_all, long long *__restrict__ seg0, DhPlanArgs PA)
@@ -2558,54 +2559,94 @@ __global__ __launch_bounds__(256) void dh_mi_pack_kernel(const DhTgt *__restrict
 
 }  // namespace
 
-// window / look-ahead / board policy of a run (the sweeps that chose the defaults are quoted where each value is set)
+// ---- host side ----
+
+static double dh_wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static std::mutex dh_cnt_mu;  // concurrent chains share the context's counters
+
+// A device arena described ONCE: the layout function runs twice over the same code -- without a base pointer it only adds up the
+// size (every take() returns nullptr), with one it hands out the buffers.  Every buffer starts on a 256-byte boundary.
+struct DhArena {
+    char *base = nullptr;
+    size_t used = 0;
+    template <class T>
+    T *take(size_t count, size_t extra_bytes = 0)
+    {
+        T *q = base ? (T *)(base + used) : nullptr;
+        used += (sizeof(T) * count + extra_bytes + 255) & ~(size_t)255;
+        return q;
+    }
+};
+template <class Bufs, class Sizes>
+static int dh_arena_reserve(fw_ctx *c, FwDevBuf &b, Bufs (*layout)(DhArena &, const Sizes &), const Sizes &z, Bufs *out)
+{
+    DhArena sizing;
+    layout(sizing, z);
+    if (int rc = fw_dev_reserve(c, b, sizing.used)) return rc;
+    DhArena a{(char *)b.ptr};
+    *out = layout(a, z);
+    assert(a.used == sizing.used);
+    return FW_OK;
+}
+
+// timing events (+ end-of-batch events without timing) of one call: the destructor synchronises the stream and destroys them on EVERY
+// exit path (error returns and the watchdog of the persistent kernel included: r02 leaked 66 events per failed call and left the
+// stream running)
+struct DhEvents {
+    hipStream_t st;
+    std::vector<hipEvent_t> ev, ev_end;
+    bool ok = true;
+    DhEvents(hipStream_t s, int n_timing, int n_end) : st(s), ev((size_t)n_timing, nullptr), ev_end((size_t)n_end, nullptr)
+    {
+        for (hipEvent_t &e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+        for (hipEvent_t &e : ev_end) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    }
+    ~DhEvents()
+    {
+        (void)hipStreamSynchronize(st);
+        for (hipEvent_t &e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t &e : ev_end)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// window / look-ahead / board policy of a run (the sweeps that chose the defaults are quoted where each value is set; every knob is
+// read per call)
 static DhParams dh_make_params(fw_ctx *c, int ntg, int spec_depth, int spec0_depth)
 {
     DhParams P{};
     P.alpha = c->P.alpha;
     P.max_k = c->P.max_k;
     P.max_tests = c->P.max_tests;
-    {
-        const char *e = fw_knob("FW_SMALL_LAUNCH");
-        P.small_launch = e ? (unsigned long long)atoll(e) : (1ull << 22);
-        const char *w = fw_knob("FW_W0_BIG");
-        P.w0_big = w ? (unsigned long long)atoll(w) : 16384ull;
-    }
-    {
-        const char *e = fw_knob("FW_ELIM_FULL");
-        P.elim_full = e ? atoi(e) : 1;
-    }
-    {
-        auto envu = [](const char *n, unsigned long long d) { const char *e = getenv(n); return e && atoll(e) > 0 ? (unsigned long long)atoll(e) : d; };
-        P.growth_small = envu("FW_DH_GROWTH_SMALL", 256ull);
-        P.growth = envu("FW_DH_GROWTH", 4ull);  // cfg3 sweeps: r01 4 -> 322 ms, 8 -> 321.5, 16 -> 331, 32 -> 350; r02 (three chains) 2 -> 219.6, 4 -> 218.3, 8 -> 219.7, 16 -> 241 (the host pool uses 16: its rounds cost 3x more)
-        P.growth_busy = envu("FW_DH_GROWTH_BUSY", 4ull);
-        P.busy_jobs = (unsigned int)envu("FW_DH_BUSY_JOBS", 2048ull);
-        P.spec_depth = spec_depth;
-        P.spec_below = envu("FW_DH_SPEC_BELOW", (c->P.max_k <= 3 && ntg >= 256) ? 30000000ull : 12000000ull);  // chains of few targets (a rank of 4 / 8: 98 / 49 per chain) are latency-bound and pay for it: slowest of 8 ranks 83.9 -> 91.0 ms with 30 M;  // max_k 4-5: whole enumerations of the look-ahead pools are too dear in big launches (cfg5, first 40 000 targets: 0.97 -> 1.95 s with 30 M)  // (r03, after the job-count gate of the interleaving look-ahead moved: 12 M -> 199.8 ms, 20 M 193.6, 30 M 193.4, 50 M 194.7, none 193.6; cfg3 without feed-forward 172.1 -> 168.4)
-        P.spec0_depth = spec0_depth;
-        P.spec0_below = envu("FW_DH_SPEC0_BELOW", 12000000ull);
-        { const char *e = fw_knob("FW_DH_SPEC0_LIGHT"); P.spec0_depth_light = spec0_depth > 0 ? std::min(std::max(e ? atoi(e) : spec0_depth, spec0_depth), DH_MAX_SPEC) : 0; }
-        P.spec0_light_below = envu("FW_DH_SPEC0_LIGHT_BELOW", 400000ull);
-        P.spec0_jobs = (unsigned int)envu("FW_DH_SPEC0_JOBS", 4096ull);  // (r03: 512 kept it off in the light feed-forward rounds of 1 024 targets: cfg3 204.8 -> 198.6 ms, 9 222 -> 7 966 launches)
-        {   // look-ahead behind a candidate that is about to be accepted (dh_step_kernel, spmode 1)
-            const char *e = fw_knob("FW_DH_SPEC1");
-            P.spec1_depth = c->P.kind == FW_FZ ? std::min(std::max(e ? atoi(e) : 2, 0), DH_MAX_SPEC) : 0;
-        }
-        P.mi_seq = (unsigned int)envu("FW_MI_SEQ", 48ull);  // r04 sweep on the final kernels (cfg4, ms with / without feed-forward, two runs each): 8: 149 / 106, 16 (r02-r03): 111.0 / 72.5, 24: 118 / 71.8, 32: 102.4 / 70.9, 48: 102.4 / 70.5, 64: 102.2 / 70.8, 128: 112.9 / 72.6, never a board: 111.5 / 79.1; cfg2 neutral
-        P.mi_win0 = (unsigned int)envu("FW_MI_WIN0", 128ull);
-        P.mi_chunk_div = (unsigned int)envu("FW_MI_CHUNK_DIV", 256ull);
-        P.mi_chunk_min = (unsigned int)envu("FW_MI_CHUNK_MIN", 8ull);
-        P.mi_chunk_max = (unsigned int)envu("FW_MI_CHUNK_MAX", 64ull);
-        { const char *e = fw_knob("FW_MI_HELP_JOBS"); P.mi_help_jobs = e ? (unsigned int)atoi(e) : 1u; }
-        { const char *e = fw_knob("FW_MI_ELIM_MIN"); P.mi_elim_min = e ? (unsigned int)atoi(e) : 64u; }
-        { const char *e = fw_knob("FW_MI_HEAVY"); P.mi_heavy = e ? (unsigned int)atoi(e) : 48u; }
-        { const char *e = fw_knob("FW_MI_SEQ_HEAVY"); P.mi_seq_heavy = e ? (unsigned int)atoi(e) : P.mi_seq; }
-        { const char *e = fw_knob("FW_MI_SEQ_TAIL"); P.mi_seq_tail = e ? (unsigned int)atoi(e) : 4u; }
-        { const char *e = fw_knob("FW_MI_AHEAD"); P.mi_ahead = e ? (unsigned int)atoi(e) : 1u; }
-        { const char *e = fw_knob("FW_MI_CHUNK_TAIL"); P.mi_chunk_tail = e ? (unsigned int)std::max(1, atoi(e)) : P.mi_chunk_min; }
-        { const char *e = fw_knob("FW_MI_WIN0_TAIL"); P.mi_win0_tail = e ? (unsigned int)std::max(1, atoi(e)) : 1024u; }
-    }
+    P.small_launch = fw_small_launch();
+    P.elim_full = fw_knob_int(knob::FW_ELIM_FULL, 1);
+    P.growth_small = fw_knob_pos(knob::FW_DH_GROWTH_SMALL, 256ull);
+    P.growth = fw_knob_pos(knob::FW_DH_GROWTH, 4ull);  // cfg3 sweeps: r01 4 -> 322 ms, 8 -> 321.5, 16 -> 331, 32 -> 350; r02 (three chains) 2 -> 219.6, 4 -> 218.3, 8 -> 219.7, 16 -> 241 (the host pool uses 16: its rounds cost 3x more)
+    P.growth_busy = fw_knob_pos(knob::FW_DH_GROWTH_BUSY, 4ull);
+    P.busy_jobs = (unsigned int)fw_knob_pos(knob::FW_DH_BUSY_JOBS, 2048ull);
+    P.spec_depth = spec_depth;
+    P.spec_below = fw_knob_pos(knob::FW_DH_SPEC_BELOW, (c->P.max_k <= 3 && ntg >= 256) ? 30000000ull : 12000000ull);  // chains of few targets (a rank of 4 / 8: 98 / 49 per chain) are latency-bound and pay for it: slowest of 8 ranks 83.9 -> 91.0 ms with 30 M;  // max_k 4-5: whole enumerations of the look-ahead pools are too dear in big launches (cfg5, first 40 000 targets: 0.97 -> 1.95 s with 30 M)  // (r03, after the job-count gate of the interleaving look-ahead moved: 12 M -> 199.8 ms, 20 M 193.6, 30 M 193.4, 50 M 194.7, none 193.6; cfg3 without feed-forward 172.1 -> 168.4)
+    P.spec0_depth = spec0_depth;
+    P.spec0_below = fw_knob_pos(knob::FW_DH_SPEC0_BELOW, 12000000ull);
+    P.spec0_depth_light = spec0_depth > 0 ? std::min(std::max(fw_knob_int(knob::FW_DH_SPEC0_LIGHT, spec0_depth), spec0_depth), DH_MAX_SPEC) : 0;
+    P.spec0_light_below = fw_knob_pos(knob::FW_DH_SPEC0_LIGHT_BELOW, 400000ull);
+    P.spec0_jobs = (unsigned int)fw_knob_pos(knob::FW_DH_SPEC0_JOBS, 4096ull);  // (r03: 512 kept it off in the light feed-forward rounds of 1 024 targets: cfg3 204.8 -> 198.6 ms, 9 222 -> 7 966 launches)
+    // look-ahead behind a candidate that is about to be accepted (dh_step_kernel, spmode 1)
+    P.spec1_depth = c->P.kind == FW_FZ ? std::min(std::max(fw_knob_int(knob::FW_DH_SPEC1, 2), 0), DH_MAX_SPEC) : 0;
+    P.mi_seq = (unsigned int)fw_knob_pos(knob::FW_MI_SEQ, 48ull);  // r04 sweep on the final kernels (cfg4, ms with / without feed-forward, two runs each): 8: 149 / 106, 16 (r02-r03): 111.0 / 72.5, 24: 118 / 71.8, 32: 102.4 / 70.9, 48: 102.4 / 70.5, 64: 102.2 / 70.8, 128: 112.9 / 72.6, never a board: 111.5 / 79.1; cfg2 neutral
+    P.mi_win0 = (unsigned int)fw_knob_pos(knob::FW_MI_WIN0, 128ull);
+    P.mi_chunk_div = (unsigned int)fw_knob_pos(knob::FW_MI_CHUNK_DIV, 256ull);
+    P.mi_chunk_min = (unsigned int)fw_knob_pos(knob::FW_MI_CHUNK_MIN, 8ull);
+    P.mi_chunk_max = (unsigned int)fw_knob_pos(knob::FW_MI_CHUNK_MAX, 64ull);
+    P.mi_help_jobs = (unsigned int)fw_knob_int(knob::FW_MI_HELP_JOBS, 1);
+    P.mi_elim_min = (unsigned int)fw_knob_int(knob::FW_MI_ELIM_MIN, 64);
+    P.mi_heavy = (unsigned int)fw_knob_int(knob::FW_MI_HEAVY, 48);
+    P.mi_seq_heavy = (unsigned int)fw_knob_int(knob::FW_MI_SEQ_HEAVY, (int)P.mi_seq);
+    P.mi_seq_tail = (unsigned int)fw_knob_int(knob::FW_MI_SEQ_TAIL, 4);
+    P.mi_ahead = (unsigned int)fw_knob_int(knob::FW_MI_AHEAD, 1);
+    P.mi_chunk_tail = (unsigned int)std::max(1, fw_knob_int(knob::FW_MI_CHUNK_TAIL, (int)P.mi_chunk_min));
+    P.mi_win0_tail = (unsigned int)std::max(1, fw_knob_int(knob::FW_MI_WIN0_TAIL, 1024));
     const bool fz = c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ;  // (fz_nz: the same segment kernels on job-local matrices)
     // first window of an interleaving-phase job with fewer than 64 accepted variables.  r04 sweep at cfg3 (two chains, look-ahead 4 / 2,
     // growth 4; ms per pass / launches): 64: 198.7 / 9 790, 128: 194.8, 256 (r01-r03): 189.1 / 8 090, 512: 186.3, 1 024: 183.9, 2 048: 184.7,
@@ -2613,13 +2654,9 @@ static DhParams dh_make_params(fw_ctx *c, int ntg, int spec_depth, int spec0_dep
     // so within its first wavefront steps whatever the window), the launches by 25 %.  max_k > 3 keeps 256 (not measured at full cfg5 size).
     // Second sweep (first window 4 096): first window of jobs with 64 accepted variables or more 8 192: 191.2, 16 384 (r01-r03): 183.8,
     // 24 576: 182.4, 32 768: 178.1 - 179.9, 49 152: 182.4, 65 536: 191.4; with 32 768 the small window 2 048: 177.3, 4 096: 178.1, 8 192: 181.7.
-    P.w0_small = fz ? (c->P.max_k <= 3 ? 2048ull : 256ull) : 16ull;
-    if (fz && c->P.max_k <= 3 && !fw_knob("FW_W0_BIG")) P.w0_big = 32768ull;
-    if (fz) {
-        const char *e = fw_knob("FW_W0_SMALL");  // first window (ranks) of a job with fewer than 64 accepted variables (r04 sweep: DESIGN section 4)
-        if (e && atoll(e) > 0) P.w0_small = (unsigned long long)atoll(e);
-    }
-    if (!fz) P.w0_big = 16ull;
+    // (FW_W0_SMALL, FW_W0_BIG: fz only; r04 sweep: DESIGN section 4)
+    P.w0_small = fz ? fw_knob_pos(knob::FW_W0_SMALL, c->P.max_k <= 3 ? 2048ull : 256ull) : 16ull;
+    P.w0_big = fz ? fw_knob_u64(knob::FW_W0_BIG, c->P.max_k <= 3 ? 32768ull : 16384ull) : 16ull;
     P.seg_q = fz ? 256u : 4u;
     P.seg_min = fz ? 256u : 8u;
     P.disc_bytes_per_col = fz ? 0.0 : (double)c->P.n * (c->P.kind == FW_MI ? 1.0 : 2.0) / 8.0;
@@ -2627,8 +2664,108 @@ static DhParams dh_make_params(fw_ctx *c, int ntg, int spec_depth, int spec0_dep
     return P;
 }
 
-static unsigned dh_team_min() { static const unsigned v = [] { const char *e = fw_knob("FW_MI_TEAM_MIN"); return e ? (unsigned)atoi(e) : 96u; }(); return v; }
-static unsigned dh_team_max() { static const unsigned v = [] { const char *e = fw_knob("FW_MI_TEAM_MAX"); return e ? (unsigned)atoi(e) : 192u; }(); return v; }  // (64 / 256: cfg2 10.5 ms, cfg4 161.7; 128 / 128: 9.4, 162.7; 96 / 192: 9.3, 159.6)
+// launch policy of one call of fwi_devhiton_run: derived from (kind, max_k, ntg, elim_mode) and the knobs, which are latched at the
+// first call
+struct DhPolicy {
+    bool nzk;         // fz_nz (r05): rounds like fz, with the sub-matrix kernel in front of the segment kernel
+    bool fz;          // the rounds over the Fisher-z segment kernels (fz_nz: on job-local matrices)
+    bool per_target;  // discrete kinds: one persistent launch (dh_mi_target_kernel) instead of rounds
+    bool use_hp, plan_small;
+    unsigned seg_target, grid_seg;
+    unsigned long long seg_a, seg_b;
+    int spec_depth, spec0_depth;
+    int nb;          // rounds per batch
+    int time_every;  // one segment launch in this many is timed
+    int tm_min;      // smallest degree of a target that gets a local correlation matrix (0: none)
+    const char *log_path;
+};
+constexpr int DH_BATCH = 16;
+constexpr unsigned DH_LOG_CAP = 1u << 16;
+
+static DhPolicy dh_policy(const fw_ctx *c, int ntg)
+{
+    DhPolicy y{};
+    const bool fz_kind = c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ;
+    // fz rounds (r06): local correlation matrices for the targets whose jobs can be long (dh_tmat_build_kernel); FW_FZ_TMAT=0: none
+    static const int tm_env = fw_knob_int(knob::FW_FZ_TMAT, -1);            // smallest degree that gets one (0: off)
+    y.tm_min = tm_env >= 0 ? tm_env : (c->P.max_k > 3 ? 1 : 16);  // (cfg3 sweep: 16; cfg5: 1 -- 54.6 -> 53.8 s)
+    static const unsigned seg_target_env = (unsigned)fw_seg_target();
+    y.seg_target = seg_target_env ? seg_target_env : (fz_kind ? (c->P.max_k > 3 ? 8192u : 3072u) : 4096u);  // cfg3 sweep: 3072; cfg5 (max_k 5, launches of 10^8 ranks and more): 8192 (r06: 53.9 -> 52.4 s)
+    // elimination-phase look-ahead (fz, FW_ELIM_FULL windows; see dh_step_kernel): FW_DH_SPEC = members tested ahead per
+    // target, FW_DH_SPEC_BELOW = only while the last launch held fewer ranks than this.  cfg3 sweep (ms per pass, one
+    // GPU / one rank of 8): off 326.7 / 112.0; depth 4 always 338 / 103; depth 4 below 4M 318.5 / 104.4, below 8M
+    // 317.3 / 104.6, below 12M 314.8 / 103.6, below 16M 341 -- a launch that already fills the GPU only pays for the
+    // jobs wasted behind every dropped member (3.7 % of the members at cfg3)
+    // Exact elimination (elim_mode 1 / 2): no look-ahead job is ever discarded (a rejected member re-enters the pool as well), so
+    // the chain of a target with m members takes about m / (depth + 1) rounds; default DH_SPEC_EXACT (DESIGN section 5)
+    static const int spec_env = fw_knob_int(knob::FW_DH_SPEC, -1);
+    const int spec_dflt = c->elim_mode != 0 ? DH_SPEC_EXACT : 4;
+    y.spec_depth = c->P.kind == FW_FZ ? std::min(std::max(spec_env >= 0 ? spec_env : spec_dflt, 0), DH_MAX_SPEC) : 0;
+    // discrete kinds: persistent wavefronts + boards (dh_mi_target_kernel); FW_MI_ROUNDS=1 keeps the level-synchronous rounds over
+    // the segment kernels (the path of the ABI's fw_test_subsets_batch) for comparison.  Fisher-z always runs as rounds (a
+    // persistent-workgroup variant was built in r02, lost 140 vs 58 ms on the heavy rounds, and was removed in r03).
+    static const bool mi_rounds = fw_mi_rounds();
+    // (more than 65 535 samples: 32-bit cell counts -- r04: the persistent kernel has a 32-bit-count form too, PRE = 2)
+    y.nzk = c->P.kind == FW_FZ_NZ;
+    y.fz = fz_kind;
+    y.per_target = !fz_kind && !mi_rounds;
+    // interleaving-phase look-ahead (first windows of the next candidates, same accepted list): FW_DH_SPEC0 candidates,
+    // only while the last launch held fewer than FW_DH_SPEC0_BELOW ranks and fewer than FW_DH_SPEC0_JOBS jobs -- it
+    // pays where the rounds are latency-bound, i.e. on a rank of a multi-GPU job (one rank of 8: 103.6 -> 95.2 ms,
+    // one of 2: 208 -> 204.7 ms) and in the tail of a single-GPU pass (315.8 -> 314.2 ms)
+    static const int spec0_env = fw_knob_int(knob::FW_DH_SPEC0, 2);
+    y.spec0_depth = c->P.kind == FW_FZ ? std::min(std::max(spec0_env, 0), DH_MAX_SPEC) : 0;
+    // segments per launch by launch size (fz): below FW_SEG_A ranks a third of seg_target, below FW_SEG_B two thirds.
+    // cfg3, ms per pass on one GPU / one rank of 2 / of 8: fixed 3 072: 298.8 / 200.3 / 94.9; A, B = 4M, 8M: 295.8 /
+    // 194.4 / 82.3; 6M, 10M: 295.8 / 192.8 / 80.3; 8M, 12M: 295.1 / 193.7 / 79.8 (fixed 1 024: 81.1 for the rank of 8
+    // but 221 for the rank of 2; 512: 102)
+    static const unsigned long long seg_a_env = fw_knob_u64(knob::FW_SEG_A, 8000000ull);
+    static const unsigned long long seg_b_env = fw_knob_u64(knob::FW_SEG_B, 12000000ull);
+    y.seg_a = fz_kind ? seg_a_env : 0ull;
+    y.seg_b = fz_kind ? seg_b_env : 0ull;
+    // striding workgroups of the segment kernel.  FW_SEG_GRID caps them (experiment: with fewer workgroups than resident
+    // slots the one-workgroup step / plan kernels of the OTHER chain find a free CU at once instead of queueing behind
+    // this launch's pending workgroups -- cfg5 profile: dh_plan_kernel 6.3 ms per call, all of it waiting)
+    static const unsigned seg_grid_env = (unsigned)fw_knob_pos(knob::FW_SEG_GRID, 0ull);
+    // r06 (cfg3, one box): 3 584 workgroups 152.6 ms / ff = 0 135.2; 2 560: 151.6 / 133.3; 2 304: 150.6 / 132.2; **2 048: 149.3 / 131.8**; 1 792: 151.7 / 135.6; 1 536: 157.6; 1 024: 164 -- two
+    // resident sets of the size-3 table kernel (256 CUs x 4 workgroups), the rest of the list by striding (profiles/r06_cfg3_segment_grid.txt).  max_k > 3 and fz_nz: not measured, as before.
+    const unsigned grid_dflt = (c->P.kind == FW_FZ && c->P.max_k <= 3) ? std::min(y.seg_target + 512u, 2048u) : y.seg_target + 512u;
+    y.grid_seg = seg_grid_env ? std::min(y.seg_target + 512u, seg_grid_env) : grid_dflt;
+    // FW_DH_LOG=<file>: one line per planned launch (ranks, live jobs, segments) -- profiling aid, see profiles/README.md
+    static const char *log_path = fw_knob_str(knob::FW_DH_LOG);
+    y.log_path = log_path;
+    // Rounds per batch.  The host sees "every target has finished" one batch late, so a pass of few, light targets (a rank of an
+    // 8-rank job holds 128 targets per feed-forward round at cfg3, 15 dependent rounds) ran 33 rounds, half of them empty: short
+    // batches for short lists (r03: 1.05 -> 0.75 ms per light round; the host enqueues 4 rounds in ~60 us, a round takes 25-100 us)
+    static const int nb_env = std::min((int)fw_knob_pos(knob::FW_DH_BATCH, 0ull), DH_BATCH);
+    y.nb = nb_env ? nb_env : (ntg <= 1024 ? 4 : DH_BATCH);
+    // Kernel timing (fw_counters.t_dev_subsets_s): HIP events around one segment launch in FW_DH_TIME_EVERY (default 4),
+    // the sampled slot rotating from batch to batch so that every position of the 16-round batch is covered; the
+    // sampled average is scaled to all non-empty launches.  Every event pair costs ~12 us of idle GPU around the launch
+    // (rocprofv3 trace: 5.9 us before + 5.7 us after, back-to-back otherwise): cfg3, ms per pass / average launch us at
+    // k = 1: 275.3 / 224.2, k = 2: 272.2 / 224.5, k = 4: 270.4 / 224.5, k = 8: 270.2 / 224.8 -- same average, 2 % less time.
+    static const int time_every = (int)fw_knob_pos(knob::FW_DH_TIME_EVERY, 4ull);
+    y.time_every = time_every;
+    // FW_DH_HP=1: the small kernels of a round on the chain's high-priority stream (fw_ctx::dh_hp_stream) -- an experiment kept behind its knob
+    static const int hp_env = fw_knob_int(knob::FW_DH_HP, -1);
+    y.use_hp = !y.per_target && hp_env > 0;  // (measured at cfg5: no effect -- what held the plan kernel back was its size, not its queue; default off)
+    static const bool plan_small = fw_knob_on(knob::FW_DH_PLAN_SMALL);  // (0: the 1 024-thread dh_plan_kernel)
+    y.plan_small = plan_small;
+    return y;
+}
+
+static unsigned dh_team_min() { static const unsigned v = (unsigned)fw_knob_int(knob::FW_MI_TEAM_MIN, 96); return v; }
+static unsigned dh_team_max() { static const unsigned v = (unsigned)fw_knob_int(knob::FW_MI_TEAM_MAX, 192); return v; }  // (64 / 256: cfg2 10.5 ms, cfg4 161.7; 128 / 128: 9.4, 162.7; 96 / 192: 9.3, 159.6)
+// the first targets of `order` (heaviest first; deg(t) = candidates of target t) with at least FW_MI_TEAM_MIN candidates, at most
+// FW_MI_TEAM_MAX of them: a workgroup each
+template <class Deg>
+static unsigned dh_team_size(const int32_t *order, Deg deg, int n)
+{
+    const unsigned team_min = dh_team_min(), team_max = dh_team_max();
+    unsigned team = 0u;
+    while (team_min > 0u && team < team_max && (int)team < n && (unsigned)deg(order[team]) >= team_min) ++team;
+    return team;
+}
 
 // launches the persistent discrete kernel over targets tg[0 .. ntg) taken in the order d_order (heaviest first; the first `team` of
 // them by a workgroup each); returns the grid.  The queue and the boards must be zero (the caller's memsets on the same stream).
@@ -2639,12 +2776,12 @@ static unsigned dh_mi_launch(fw_ctx *c, hipStream_t st, DhTgt *d_tg, int ntg, co
     M.view = M.dense && M.nzmode && c->mi_view;  // HITON-PC under the dense rules tests on row views (hiton.jl:41-50)
     // as many workgroups as stay resident (one per CU: the test routine needs ~260 VGPRs, one wavefront per SIMD; cfg4:
     // 62 ms with one, 71 ms with two requested): the wavefronts fetch targets themselves
-    static const unsigned wg_per_cu = [] { const char *e = fw_knob("FW_MI_WG_PER_CU"); return e && atoi(e) > 0 ? (unsigned)atoi(e) : 1u; }();
+    static const unsigned wg_per_cu = (unsigned)fw_knob_pos(knob::FW_MI_WG_PER_CU, 1ull);
     int n_cu = 256;
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->P.device);
     const unsigned grid = std::min((unsigned)((ntg + 3) / 4), wg_per_cu * (unsigned)n_cu);
-    static const unsigned team_steps = [] { const char *e = fw_knob("FW_MI_TEAM_STEPS"); return e ? (unsigned)atoi(e) : 2u; }();
-    static const unsigned team_tail = [] { const char *e = fw_knob("FW_MI_TEAM_TAIL"); return e ? (unsigned)atoi(e) : 0u; }();
+    static const unsigned team_steps = (unsigned)fw_knob_int(knob::FW_MI_TEAM_STEPS, 2);
+    static const unsigned team_tail = (unsigned)fw_knob_int(knob::FW_MI_TEAM_TAIL, 0);
     P.mi_team = team;
     P.mi_team_steps = team_steps;
     P.mi_team_tail = team_tail;
@@ -2667,12 +2804,12 @@ static unsigned dh_mi_launch(fw_ctx *c, hipStream_t st, DhTgt *d_tg, int ntg, co
     } while (0)
     const bool pre = c->P.n <= MI_PRE_N && c->P.max_k <= MI_PRE_K;
     // four subsets per wavefront step (mi_test_core4): n <= 5120, max_k <= 3, 2 x 2 cells per stratum.  FW_MI_ROW4=0: one per step
-    static const bool row4_env = [] { const char *e = fw_knob("FW_MI_ROW4"); return !(e && atoi(e) == 0); }();
+    static const bool row4_env = fw_knob_on(knob::FW_MI_ROW4);
     // ... used up to 2048 samples (four words per lane): cfg2 (n = 500) 15.2 -> 12.5 ms.  At cfg4's n = 5000 a step of four
     // tests takes as long as four one-test steps (34 us: ten words per lane, 390 registers with the spills parked in AGPRs),
     // and since most jobs stop at their first test the three speculative ones are pure cost: measured 56.2 vs 56.8 ms on one
     // GPU, 35.3 vs 39.2 ms for one rank of eight -- FW_MI_ROW4=2 forces it on up to MI4_N for such experiments
-    static const bool row4_force = [] { const char *e = fw_knob("FW_MI_ROW4"); return e && atoi(e) == 2; }();
+    static const bool row4_force = fw_knob_int(knob::FW_MI_ROW4, 1) == 2;
     const bool r4 = row4_env && pre && c->P.n <= (row4_force ? MI4_N : 2048) && (c->L == 2 || c->mi_nxy == 2);
     const bool wide = c->P.n > 65535;  // cell counts beyond 16 bits: one count per register, 32-bit tables (mi_test_core<.., WIDE>)
     if (c->L == 2) {
@@ -2706,287 +2843,306 @@ static void dh_mi_trace(const MiQueue &hq, unsigned grid)
             ms * ((double)hq.t_total - (double)hq.t_body - (double)hq.t_ctl - (double)hq.t_sleep) / nw, ms * hq.n_seg / nw);
 }
 
-// One round of targets on the device.  in: T ids, interleaving candidates and (sorted) whitelists per target;
-// out: PC (keys, statistics, p-values) per target in insertion order.
-int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<FwDhResult> &out, FwDhFlat &flat, int chain)
+// watchdog word of a finished persistent launch -> error; else its trace under FW_TRACE_HOST
+static int dh_mi_check(fw_ctx *c, const MiQueue &hq, unsigned grid, int round, int ntg, bool trace_host)
 {
-    const int ntg = (int)in.size();
-    out.assign((size_t)ntg, FwDhResult{});
-    if (ntg == 0) return FW_OK;
-    static const bool trace_host = fw_knob("FW_TRACE_HOST") != nullptr;  // host-side phase times on stderr
-    auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double th0 = wall();
-    // chain > 0: a second (third, ...) instance running concurrently from its own host thread on its own stream / arena
-    if (chain > 0 && !c->dh_stream[chain]) FW_HIP(c, hipStreamCreateWithFlags(&c->dh_stream[chain], hipStreamNonBlocking));
-    hipStream_t st = chain == 0 ? c->pb[0].stream : c->dh_stream[chain];
-    const int p = c->P.p;
-    // ---- host-side layout ----
-    const bool use_devc = in[0].nc_dev >= 0 && c->d_cand != nullptr;  // candidate lists built on the device (fw_bh.hip)
-    std::vector<DhTgt> tg((size_t)ntg);
+    if (hq.pad[0])
+        return fw_fail(c, FW_ERR_DEVICE, "discrete HITON kernel, round %d: watchdog %u (boards %u, targets done %u of %d)", round, hq.pad[0], hq.n_boards, hq.targets_done, ntg);
+    if (trace_host) dh_mi_trace(hq, grid);
+    return FW_OK;
+}
+
+// ---- one round of targets (fwi_devhiton_run) ----
+
+// what sizes the arena of a round
+struct DhRunSizes {
+    size_t ntg, tot, d1, n_wl, max_ns, tm_floats, nz_arena, p, nnz;
+    bool log, per_target, nzk, own_nb;
+};
+struct DhRunBufs {
+    DhTgt *tg;
+    DhGlobal *g;
+    long long *seg0;
+    unsigned long long *win, *win2;
+    unsigned int *sp;
+    int32_t *act;  // ping-pong list of the unfinished targets
+    int32_t *cand0, *tpc_key, *pc_key, *acc, *wl;
+    double *tpc_stat, *tpc_p, *pc_stat, *pc_p;
+    FwSeg *segs;
+    FwSegOut *so;
+    float *tmat;
+    ulonglong2 *log;
+    MiQueue *mq;  // persistent kernel only
+    MiBoard *boards;
+    FwSegOut *mres;
+    int32_t *bacc;
+    FwNzJob *nzrecs;  // fz_nz only
+    long long *nzaoff;
+    float *nzarena;
+    long long *nb_off;  // own copy of the level-0 lists: only when the context holds none on the device
+    int32_t *nb_idx;
+    double *nb_stat, *nb_p;
+};
+static DhRunBufs dh_run_layout(DhArena &a, const DhRunSizes &z)
+{
+    DhRunBufs b{};
+    b.tg = a.take<DhTgt>(z.ntg);
+    b.g = a.take<DhGlobal>(1);
+    b.seg0 = a.take<long long>(z.ntg + 1);
+    b.win = a.take<unsigned long long>(z.ntg + 1);
+    b.sp = a.take<unsigned int>(z.ntg + 1);
+    b.win2 = a.take<unsigned long long>(z.ntg + 1);
+    b.act = a.take<int32_t>(2 * z.ntg);
+    b.cand0 = a.take<int32_t>(z.tot, 4);
+    b.tpc_key = a.take<int32_t>(z.tot, 4);
+    b.pc_key = a.take<int32_t>(z.tot, 4);
+    b.acc = a.take<int32_t>(2 * z.tot * z.d1, 4);
+    b.tpc_stat = a.take<double>(z.tot, 8);
+    b.tpc_p = a.take<double>(z.tot, 8);
+    b.pc_stat = a.take<double>(z.tot, 8);
+    b.pc_p = a.take<double>(z.tot, 8);
+    b.wl = a.take<int32_t>(z.n_wl, 4);
+    b.segs = a.take<FwSeg>(z.max_ns);
+    b.so = a.take<FwSegOut>(z.max_ns);
+    if (z.tm_floats) b.tmat = a.take<float>(z.tm_floats, 4);
+    if (z.log) b.log = a.take<ulonglong2>(DH_LOG_CAP);
+    if (z.per_target) {
+        b.mq = a.take<MiQueue>(1);
+        b.boards = a.take<MiBoard>(MI_BOARD_CAP);
+        b.mres = a.take<FwSegOut>(MI_REC_CAP);
+        b.bacc = a.take<int32_t>(MI_BACC_CAP);
+    }
+    if (z.nzk) {
+        b.nzrecs = a.take<FwNzJob>(z.ntg);
+        b.nzaoff = a.take<long long>(z.ntg);
+        b.nzarena = a.take<float>(z.nz_arena, 4);
+    }
+    if (z.own_nb) {
+        b.nb_off = a.take<long long>(z.p + 1);
+        b.nb_idx = a.take<int32_t>(z.nnz, 4);
+        b.nb_stat = a.take<double>(z.nnz, 8);
+        b.nb_p = a.take<double>(z.nnz, 8);
+    }
+    return b;
+}
+
+struct DhRun {
+    fw_ctx *c;
+    int chain, ntg;
+    hipStream_t st;
+    bool trace_host;
+    DhPolicy y;
+    // host-side layout (dh_build_targets)
+    bool use_devc;  // candidate lists built on the device (fw_bh.hip)
+    std::vector<DhTgt> tg;
     std::vector<int32_t> cand0, wl;
-    long long co = 0, wo = 0;
+    std::vector<long long> nz_aoff;
+    size_t tot = 0, tm_floats = 0, nz_arena = 0;
     int max_cap = 0, max_wl = 0;  // most candidates / most whitelisted neighbours of one target
-    unsigned max_a_seen = 0;      // longest accepted list reported so far (lags by up to two batches)
-    unsigned max_ab_seen = 0;     // ... and the largest accepted + whitelisted-to-come
+    unsigned max_ns = 0;          // capacity of the segment list (a job + its look-ahead jobs each round up)
+    // device side (dh_upload)
+    DhRunBufs D{};
+    DhGlobal *hg = nullptr;  // two pinned copies of the device record (one per batch in flight)
+    DhArrays A{};
+    DhParams P{};
+    // what the launches report
+    double timed_s = 0.0;
+    long timed_n = 0, launches_n = 0;
+    std::vector<float> log_ms;  // FW_DH_LOG: segment-kernel time of launch i (planned by plan #i)
+    unsigned max_a_seen = 0;    // longest accepted list reported so far (lags by up to two batches)
+    unsigned max_ab_seen = 0;   // ... and the largest accepted + whitelisted-to-come
+};
+
+// targets, candidate lists and whitelists in one flat layout each; offsets of the local matrices
+static void dh_build_targets(DhRun &R, const std::vector<FwDhTarget> &in)
+{
+    const fw_ctx *c = R.c;
+    const int ntg = R.ntg;
+    R.use_devc = in[0].nc_dev >= 0 && c->d_cand != nullptr;
+    R.tg.resize((size_t)ntg);
+    long long co = 0, wo = 0;
     for (int t = 0; t < ntg; ++t) {
         DhTgt x{};
         x.T = in[t].T;
-        x.nc = use_devc ? in[t].nc_dev : (int32_t)in[t].cands.size();
+        x.nc = R.use_devc ? in[t].nc_dev : (int32_t)in[t].cands.size();
         x.cap = x.nc;
-        x.cand_off = use_devc ? c->nb_off[in[t].T] : co;
+        x.cand_off = R.use_devc ? c->nb_off[in[t].T] : co;
         x.phase = x.nc == 0 ? 2 : 0;
         x.co = co;
         x.wl_off = wo;
         x.wl_n = in[t].wl_n;
         x.nb_off = c->nb_off[x.T];
         x.nb_n = (int32_t)(c->nb_off[x.T + 1] - c->nb_off[x.T]);
-        if (!use_devc) cand0.insert(cand0.end(), in[t].cands.begin(), in[t].cands.end());
-        if (in[t].wl_n) wl.insert(wl.end(), in[t].wl, in[t].wl + in[t].wl_n);
+        if (!R.use_devc) R.cand0.insert(R.cand0.end(), in[t].cands.begin(), in[t].cands.end());
+        if (in[t].wl_n) R.wl.insert(R.wl.end(), in[t].wl, in[t].wl + in[t].wl_n);
         co += x.nc;
         wo += in[t].wl_n;
-        max_cap = std::max(max_cap, x.nc);
-        max_wl = std::max(max_wl, (int)in[t].wl_n);
-        tg[t] = x;
+        R.max_cap = std::max(R.max_cap, x.nc);
+        R.max_wl = std::max(R.max_wl, (int)in[t].wl_n);
+        R.tg[t] = x;
     }
-    const size_t tot = (size_t)co;
-    // fz rounds (r06): local correlation matrices for the targets whose jobs can be long (dh_tmat_build_kernel); FW_FZ_TMAT=0: none
-    size_t tm_floats = 0;
-    {
-        static const int tm_env = [] { const char *e = fw_knob("FW_FZ_TMAT"); return e ? atoi(e) : -1; }();  // smallest degree that gets one (0: off)
-        const int tm_min = tm_env >= 0 ? tm_env : (c->P.max_k > 3 ? 1 : 16);                                   // (cfg3 sweep: 16; cfg5: 1 -- 54.6 -> 53.8 s)
-        const bool tm_on = c->P.kind == FW_FZ && c->P.max_k <= 5 && c->d_cor != nullptr && tm_min > 0;  // (max_k 6-7: the general-form kernel reads the p x p matrix)
-        for (int t = 0; t < ntg; ++t) {
-            tg[t].tm_off = -1;
-            const size_t m = (size_t)tg[t].nb_n + 1;
-            if (!tm_on || tg[t].nb_n < tm_min || m > 4096 || tm_floats + m * m > (size_t)1 << 32) continue;  // (<= 16 GB per chain; ids of a target staged in 16 KB of LDS)
-            tg[t].tm_off = (long long)tm_floats;
-            tm_floats += m * m;
-        }
+    R.tot = (size_t)co;
+    const bool tm_on = c->P.kind == FW_FZ && c->P.max_k <= 5 && c->d_cor != nullptr && R.y.tm_min > 0;  // (max_k 6-7: the general-form kernel reads the p x p matrix)
+    for (int t = 0; t < ntg; ++t) {
+        R.tg[t].tm_off = -1;
+        const size_t m = (size_t)R.tg[t].nb_n + 1;
+        if (!tm_on || R.tg[t].nb_n < R.y.tm_min || m > 4096 || R.tm_floats + m * m > (size_t)1 << 32) continue;  // (<= 16 GB per chain; ids of a target staged in 16 KB of LDS)
+        R.tg[t].tm_off = (long long)R.tm_floats;
+        R.tm_floats += m * m;
     }
-    // ---- device buffers (one arena) ----
-    const bool nb_on_dev = c->d_nb_idx != nullptr;
-    const size_t nnz = (size_t)c->nb_off[p];
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    static const unsigned seg_target_env = [] { const char *e = fw_knob("FW_SEG_TARGET"); return e && atoi(e) > 0 ? (unsigned)atoi(e) : 0u; }();
-    const unsigned seg_target = seg_target_env ? seg_target_env : ((c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) ? (c->P.max_k > 3 ? 8192u : 3072u) : 4096u);  // cfg3 sweep: 3072; cfg5 (max_k 5, launches of 10^8 ranks and more): 8192 (r06: 53.9 -> 52.4 s)
-    // elimination-phase look-ahead (fz, FW_ELIM_FULL windows; see dh_step_kernel): FW_DH_SPEC = members tested ahead per
-    // target, FW_DH_SPEC_BELOW = only while the last launch held fewer ranks than this.  cfg3 sweep (ms per pass, one
-    // GPU / one rank of 8): off 326.7 / 112.0; depth 4 always 338 / 103; depth 4 below 4M 318.5 / 104.4, below 8M
-    // 317.3 / 104.6, below 12M 314.8 / 103.6, below 16M 341 -- a launch that already fills the GPU only pays for the
-    // jobs wasted behind every dropped member (3.7 % of the members at cfg3)
-    // Exact elimination (elim_mode 1 / 2): no look-ahead job is ever discarded (a rejected member re-enters the pool as well), so
-    // the chain of a target with m members takes about m / (depth + 1) rounds; default DH_SPEC_EXACT (DESIGN section 5)
-    static const int spec_env = [] { const char *e = fw_knob("FW_DH_SPEC"); return e ? atoi(e) : -1; }();
-    const int spec_dflt = c->elim_mode != 0 ? DH_SPEC_EXACT : 4;
-    // discrete kinds: persistent wavefronts + boards (dh_mi_target_kernel); FW_MI_ROUNDS=1 keeps the level-synchronous rounds over
-    // the segment kernels (the path of the ABI's fw_test_subsets_batch) for comparison.  Fisher-z always runs as rounds (a
-    // persistent-workgroup variant was built in r02, lost 140 vs 58 ms on the heavy rounds, and was removed in r03).
-    static const bool mi_rounds = [] { const char *e = fw_knob("FW_MI_ROUNDS"); return e && atoi(e) != 0; }();
-    // (more than 65 535 samples: 32-bit cell counts -- only the segment kernels have that form, so such data takes the rounds)
-    const bool nzk = c->P.kind == FW_FZ_NZ;  // fz_nz (r05): rounds like fz, with the sub-matrix kernel in front of the segment kernel
-    const bool per_target = c->P.kind != FW_FZ && !nzk && !mi_rounds;  // (r04: the persistent kernel has a 32-bit-count form too, PRE = 2)
-    const int spec_depth = c->P.kind == FW_FZ ? std::min(std::max(spec_env >= 0 ? spec_env : spec_dflt, 0), DH_MAX_SPEC) : 0;
-    const int d1 = spec_depth + 1;
-    // interleaving-phase look-ahead (first windows of the next candidates, same accepted list): FW_DH_SPEC0 candidates,
-    // only while the last launch held fewer than FW_DH_SPEC0_BELOW ranks and fewer than FW_DH_SPEC0_JOBS jobs -- it
-    // pays where the rounds are latency-bound, i.e. on a rank of a multi-GPU job (one rank of 8: 103.6 -> 95.2 ms,
-    // one of 2: 208 -> 204.7 ms) and in the tail of a single-GPU pass (315.8 -> 314.2 ms)
-    static const int spec0_env = [] { const char *e = fw_knob("FW_DH_SPEC0"); return e ? atoi(e) : 2; }();
-    const int spec0_depth = c->P.kind == FW_FZ ? std::min(std::max(spec0_env, 0), DH_MAX_SPEC) : 0;
-    // segments per launch by launch size (fz): below FW_SEG_A ranks a third of seg_target, below FW_SEG_B two thirds.
-    // cfg3, ms per pass on one GPU / one rank of 2 / of 8: fixed 3 072: 298.8 / 200.3 / 94.9; A, B = 4M, 8M: 295.8 /
-    // 194.4 / 82.3; 6M, 10M: 295.8 / 192.8 / 80.3; 8M, 12M: 295.1 / 193.7 / 79.8 (fixed 1 024: 81.1 for the rank of 8
-    // but 221 for the rank of 2; 512: 102)
-    static const unsigned long long seg_a_env = [] { const char *e = fw_knob("FW_SEG_A"); return e ? (unsigned long long)atoll(e) : 8000000ull; }();
-    static const unsigned long long seg_b_env = [] { const char *e = fw_knob("FW_SEG_B"); return e ? (unsigned long long)atoll(e) : 12000000ull; }();
-    const unsigned long long seg_a = (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) ? seg_a_env : 0ull, seg_b = (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) ? seg_b_env : 0ull;
-    const unsigned max_ns = seg_target + (unsigned)ntg * (unsigned)(1 + DH_MAX_SPEC) + 256u;  // capacity of the segment list (a job + its look-ahead jobs each round up)
-    // striding workgroups of the segment kernel.  FW_SEG_GRID caps them (experiment: with fewer workgroups than resident
-    // slots the one-workgroup step / plan kernels of the OTHER chain find a free CU at once instead of queueing behind
-    // this launch's pending workgroups -- cfg5 profile: dh_plan_kernel 6.3 ms per call, all of it waiting)
-    static const unsigned seg_grid_env = [] { const char *e = fw_knob("FW_SEG_GRID"); return e && atoi(e) > 0 ? (unsigned)atoi(e) : 0u; }();
-    // r06 (cfg3, one box): 3 584 workgroups 152.6 ms / ff = 0 135.2; 2 560: 151.6 / 133.3; 2 304: 150.6 / 132.2; **2 048: 149.3 / 131.8**; 1 792: 151.7 / 135.6; 1 536: 157.6; 1 024: 164 -- two
-    // resident sets of the size-3 table kernel (256 CUs x 4 workgroups), the rest of the list by striding (profiles/r06_cfg3_segment_grid.txt).  max_k > 3 and fz_nz: not measured, as before.
-    const unsigned grid_dflt = (c->P.kind == FW_FZ && c->P.max_k <= 3) ? std::min(seg_target + 512u, 2048u) : seg_target + 512u;
-    const unsigned grid_seg = seg_grid_env ? std::min(seg_target + 512u, seg_grid_env) : grid_dflt;
-    // FW_DH_LOG=<file>: one line per planned launch (ranks, live jobs, segments) -- profiling aid, see profiles/README.md
-    static const char *log_path = fw_knob("FW_DH_LOG");
-    constexpr unsigned LOG_CAP = 1u << 16;
-    size_t need = (log_path ? pad(sizeof(ulonglong2) * LOG_CAP) : 0) + pad(sizeof(int32_t) * 2 * (size_t)ntg) + pad(sizeof(unsigned int) * ((size_t)ntg + 1)) + pad(sizeof(DhTgt) * ntg) + pad(sizeof(DhGlobal)) + 3 * pad(sizeof(long long) * ((size_t)ntg + 1));
-    need += pad(4 * tot + 4) * 3 + pad(4 * 2 * tot * (size_t)d1 + 4) + pad(8 * tot + 8) * 4 + pad(4 * wl.size() + 4);
-    need += pad(sizeof(FwSeg) * max_ns) + pad(sizeof(FwSegOut) * max_ns) + pad(sizeof(float) * tm_floats + 4);
-    if (!nb_on_dev) need += pad(8 * ((size_t)p + 1)) + pad(4 * nnz + 4) + 2 * pad(8 * nnz + 8);
-    const size_t rec_cap = MI_REC_CAP, bacc_cap = MI_BACC_CAP;
-    if (per_target) need += pad(sizeof(MiQueue)) + pad(sizeof(MiBoard) * MI_BOARD_CAP) + pad(sizeof(FwSegOut) * rec_cap) + pad(sizeof(int32_t) * bacc_cap);
     // fz_nz: a record and an arena slice of (longest list + 2)^2 floats per target.  Without whitelists an accepted list never outgrows
     // the candidate list; with whitelists (feed-forward) a whitelisted member of the elimination pool is pushed a second time
     // (hiton.jl:24-26), so a list can reach twice the candidates -- the capacity of the accepted buffers (DH_ACC_OFF: 2 x cap)
-    std::vector<long long> nz_aoff;
-    size_t nz_arena = 0;
-    if (nzk) {
-        nz_aoff.resize((size_t)ntg);
+    if (R.y.nzk) {
+        R.nz_aoff.resize((size_t)ntg);
         for (int t = 0; t < ntg; ++t) {
-            nz_aoff[t] = (long long)nz_arena;
-            const size_t mt = (size_t)(wl.empty() ? 1 : 2) * (size_t)tg[t].nc + 2;
-            nz_arena += mt * mt;
+            R.nz_aoff[t] = (long long)R.nz_arena;
+            const size_t mt = (size_t)(R.wl.empty() ? 1 : 2) * (size_t)R.tg[t].nc + 2;
+            R.nz_arena += mt * mt;
         }
-        need += pad(sizeof(FwNzJob) * (size_t)ntg) + pad(sizeof(long long) * (size_t)ntg) + pad(sizeof(float) * nz_arena + 4);
     }
+    R.max_ns = R.y.seg_target + (unsigned)ntg * (unsigned)(1 + DH_MAX_SPEC) + 256u;
+}
+
+// device buffers (one arena), the round's inputs, the local correlation matrices, the run's parameters
+static int dh_upload(DhRun &R)
+{
+    fw_ctx *c = R.c;
+    hipStream_t st = R.st;
+    const int ntg = R.ntg, p = c->P.p;
+    const size_t tot = R.tot, nnz = (size_t)c->nb_off[p];
+    const bool nb_on_dev = c->d_nb_idx != nullptr;
+    const DhRunSizes z{(size_t)ntg, tot, (size_t)R.y.spec_depth + 1, R.wl.size(), R.max_ns, R.tm_floats, R.nz_arena, (size_t)p, nnz,
+                       R.y.log_path != nullptr, R.y.per_target, R.y.nzk, !nb_on_dev};
     int rc;
-    if ((rc = fw_dev_reserve(c, c->d_dh[chain], need))) return rc;
-    if ((rc = fw_pin_reserve(c, c->h_dh[chain], 4096))) return rc;
-    DhGlobal *hg = (DhGlobal *)c->h_dh[chain].ptr;  // two pinned copies of the device record (one per batch in flight)
+    if ((rc = dh_arena_reserve(c, c->d_dh[R.chain], dh_run_layout, z, &R.D))) return rc;
+    if ((rc = fw_pin_reserve(c, c->h_dh[R.chain], 4096))) return rc;
+    const DhRunBufs &D = R.D;
+    DhGlobal *hg = R.hg = (DhGlobal *)c->h_dh[R.chain].ptr;
     memset(hg, 0, 2 * sizeof(DhGlobal));
-    char *B = (char *)c->d_dh[chain].ptr;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        char *q = B + off;
-        off += pad(bytes);
-        return q;
-    };
-    DhTgt *d_tg = (DhTgt *)carve(sizeof(DhTgt) * ntg);
-    DhGlobal *d_g = (DhGlobal *)carve(sizeof(DhGlobal));
-    long long *d_seg0 = (long long *)carve(sizeof(long long) * ((size_t)ntg + 1));
-    unsigned long long *d_win = (unsigned long long *)carve(sizeof(unsigned long long) * ((size_t)ntg + 1));
-    unsigned int *d_sp = (unsigned int *)carve(sizeof(unsigned int) * ((size_t)ntg + 1));
-    unsigned long long *d_win2 = (unsigned long long *)carve(sizeof(unsigned long long) * ((size_t)ntg + 1));
-    int32_t *d_act = (int32_t *)carve(sizeof(int32_t) * 2 * (size_t)ntg);  // ping-pong list of the unfinished targets
-    DhArrays A{};
-    int32_t *d_cand0 = (int32_t *)carve(4 * tot + 4);
-    A.cand0 = use_devc ? c->d_cand : d_cand0;
-    A.tpc_key = (int32_t *)carve(4 * tot + 4);
-    A.pc_key = (int32_t *)carve(4 * tot + 4);
-    A.acc = (int32_t *)carve(4 * 2 * tot * (size_t)d1 + 4);
-    A.tpc_stat = (double *)carve(8 * tot + 8);
-    A.tpc_p = (double *)carve(8 * tot + 8);
-    A.pc_stat = (double *)carve(8 * tot + 8);
-    A.pc_p = (double *)carve(8 * tot + 8);
-    int32_t *d_wl = (int32_t *)carve(4 * wl.size() + 4);
-    A.wl = d_wl;
-    FwSeg *d_segs = (FwSeg *)carve(sizeof(FwSeg) * max_ns);
-    FwSegOut *d_so = (FwSegOut *)carve(sizeof(FwSegOut) * max_ns);
-    float *d_tmat = tm_floats ? (float *)carve(sizeof(float) * tm_floats + 4) : nullptr;
-    ulonglong2 *d_log = log_path ? (ulonglong2 *)carve(sizeof(ulonglong2) * LOG_CAP) : nullptr;
-    MiQueue *d_mq = per_target ? (MiQueue *)carve(sizeof(MiQueue)) : nullptr;
-    MiBoard *d_boards = per_target ? (MiBoard *)carve(sizeof(MiBoard) * MI_BOARD_CAP) : nullptr;
-    FwSegOut *d_mres = per_target ? (FwSegOut *)carve(sizeof(FwSegOut) * rec_cap) : nullptr;
-    int32_t *d_bacc = per_target ? (int32_t *)carve(sizeof(int32_t) * bacc_cap) : nullptr;
-    FwNzJob *d_nzrecs = nzk ? (FwNzJob *)carve(sizeof(FwNzJob) * (size_t)ntg) : nullptr;
-    long long *d_nzaoff = nzk ? (long long *)carve(sizeof(long long) * (size_t)ntg) : nullptr;
-    float *d_nzarena = nzk ? (float *)carve(sizeof(float) * nz_arena + 4) : nullptr;
-    if (nzk) {
-        FW_HIP(c, hipMemcpyAsync(d_nzaoff, nz_aoff.data(), sizeof(long long) * (size_t)ntg, hipMemcpyHostToDevice, st));
-        FW_HIP(c, hipMemsetAsync(d_nzrecs, 0xff, sizeof(FwNzJob) * (size_t)ntg, st));  // (pad bit 0 set: nothing to compute until a job writes its record)
+    if (R.y.nzk) {
+        FW_HIP(c, hipMemcpyAsync(D.nzaoff, R.nz_aoff.data(), sizeof(long long) * (size_t)ntg, hipMemcpyHostToDevice, st));
+        FW_HIP(c, hipMemsetAsync(D.nzrecs, 0xff, sizeof(FwNzJob) * (size_t)ntg, st));  // (pad bit 0 set: nothing to compute until a job writes its record)
     }
-    FW_HIP(c, hipMemcpyAsync(d_tg, tg.data(), sizeof(DhTgt) * ntg, hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemcpyAsync(D.tg, R.tg.data(), sizeof(DhTgt) * ntg, hipMemcpyHostToDevice, st));
     hg[0].n_act = (unsigned int)ntg;  // every target starts on the list (the pinned page is the staging copy: stream-ordered)
-    FW_HIP(c, hipMemcpyAsync(d_g, hg, sizeof(DhGlobal), hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemcpyAsync(D.g, hg, sizeof(DhGlobal), hipMemcpyHostToDevice, st));
     {
         std::vector<int32_t> iota((size_t)ntg);
         for (int t = 0; t < ntg; ++t) iota[t] = t;
-        FW_HIP(c, hipMemcpy(d_act, iota.data(), sizeof(int32_t) * (size_t)ntg, hipMemcpyHostToDevice));
+        FW_HIP(c, hipMemcpy(D.act, iota.data(), sizeof(int32_t) * (size_t)ntg, hipMemcpyHostToDevice));
     }
-    FW_HIP(c, hipMemsetAsync(d_seg0, 0, sizeof(long long) * ((size_t)ntg + 1), st));
-    if (tot && !use_devc) FW_HIP(c, hipMemcpyAsync(d_cand0, cand0.data(), 4 * tot, hipMemcpyHostToDevice, st));
-    if (!wl.empty()) FW_HIP(c, hipMemcpyAsync(d_wl, wl.data(), 4 * wl.size(), hipMemcpyHostToDevice, st));
-    if (nb_on_dev) {
-        A.nb_off = c->d_nb_off;
-        A.nb_idx = c->d_nb_idx;
-        A.nb_stat = c->d_nb_stat;
-        A.nb_p = c->d_nb_p;
-    } else {
-        long long *o = (long long *)carve(8 * ((size_t)p + 1));
-        int32_t *ix = (int32_t *)carve(4 * nnz + 4);
-        double *s1 = (double *)carve(8 * nnz + 8), *s2 = (double *)carve(8 * nnz + 8);
-        FW_HIP(c, hipMemcpyAsync(o, c->nb_off.data(), 8 * ((size_t)p + 1), hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemsetAsync(D.seg0, 0, sizeof(long long) * ((size_t)ntg + 1), st));
+    if (tot && !R.use_devc) FW_HIP(c, hipMemcpyAsync(D.cand0, R.cand0.data(), 4 * tot, hipMemcpyHostToDevice, st));
+    if (!R.wl.empty()) FW_HIP(c, hipMemcpyAsync(D.wl, R.wl.data(), 4 * R.wl.size(), hipMemcpyHostToDevice, st));
+    if (!nb_on_dev) {
+        FW_HIP(c, hipMemcpyAsync(D.nb_off, c->nb_off.data(), 8 * ((size_t)p + 1), hipMemcpyHostToDevice, st));
         if (nnz) {
-            FW_HIP(c, hipMemcpyAsync(ix, c->nb_idx.data(), 4 * nnz, hipMemcpyHostToDevice, st));
-            FW_HIP(c, hipMemcpyAsync(s1, c->nb_stat.data(), 8 * nnz, hipMemcpyHostToDevice, st));
-            FW_HIP(c, hipMemcpyAsync(s2, c->nb_p.data(), 8 * nnz, hipMemcpyHostToDevice, st));
+            FW_HIP(c, hipMemcpyAsync(D.nb_idx, c->nb_idx.data(), 4 * nnz, hipMemcpyHostToDevice, st));
+            FW_HIP(c, hipMemcpyAsync(D.nb_stat, c->nb_stat.data(), 8 * nnz, hipMemcpyHostToDevice, st));
+            FW_HIP(c, hipMemcpyAsync(D.nb_p, c->nb_p.data(), 8 * nnz, hipMemcpyHostToDevice, st));
         }
-        A.nb_off = o;
-        A.nb_idx = ix;
-        A.nb_stat = s1;
-        A.nb_p = s2;
     }
+    DhArrays &A = R.A;
+    A.cand0 = R.use_devc ? c->d_cand : D.cand0;
+    A.tpc_key = D.tpc_key;
+    A.pc_key = D.pc_key;
+    A.acc = D.acc;
+    A.tpc_stat = D.tpc_stat;
+    A.tpc_p = D.tpc_p;
+    A.pc_stat = D.pc_stat;
+    A.pc_p = D.pc_p;
+    A.wl = D.wl;
+    A.nb_off = nb_on_dev ? c->d_nb_off : D.nb_off;
+    A.nb_idx = nb_on_dev ? c->d_nb_idx : D.nb_idx;
+    A.nb_stat = nb_on_dev ? c->d_nb_stat : D.nb_stat;
+    A.nb_p = nb_on_dev ? c->d_nb_p : D.nb_p;
     A.rej = c->d_rej_run;
-    A.tmat = d_tmat;
-    if (d_tmat) {
-        hipLaunchKernelGGL(dh_tmat_build_kernel, dim3((unsigned)ntg, 8u), dim3(256), 0, st, (const DhTgt *)d_tg, ntg, A.nb_idx, (const float *)c->d_cor, p, d_tmat);
+    A.tmat = D.tmat;
+    if (D.tmat) {
+        hipLaunchKernelGGL(dh_tmat_build_kernel, dim3((unsigned)ntg, 8u), dim3(256), 0, st, (const DhTgt *)D.tg, ntg, A.nb_idx, (const float *)c->d_cor, p, D.tmat);
         FW_HIP(c, hipGetLastError());
-        if (trace_host) fprintf(stderr, "[fw] chain %d: local correlation matrices: %.1f MB\n", chain, 4e-6 * (double)tm_floats);
+        if (R.trace_host) fprintf(stderr, "[fw] chain %d: local correlation matrices: %.1f MB\n", R.chain, 4e-6 * (double)R.tm_floats);
     }
-    const bool fz = c->P.kind == FW_FZ || nzk;  // the rounds over the Fisher-z segment kernels (fz_nz: on job-local matrices)
-    DhParams P = dh_make_params(c, ntg, spec_depth, spec0_depth);
+    R.P = dh_make_params(c, ntg, R.y.spec_depth, R.y.spec0_depth);
+    return FW_OK;
+}
+
+// discrete kinds: the whole round as one persistent launch (dh_mi_target_kernel)
+static int dh_run_persistent(DhRun &R, DhEvents &E)
+{
+    fw_ctx *c = R.c;
+    hipStream_t st = R.st;
+    const int ntg = R.ntg;
+    const DhRunBufs &D = R.D;
+    const std::vector<DhTgt> &tg = R.tg;
+    std::vector<int32_t> order((size_t)ntg);
+    for (int t = 0; t < ntg; ++t) order[t] = t;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t u, int32_t v) { return tg[u].nc > tg[v].nc; });  // heaviest first
+    FW_HIP(c, hipMemcpyAsync(D.act, order.data(), sizeof(int32_t) * (size_t)ntg, hipMemcpyHostToDevice, st));
+    const unsigned team = dh_team_size(order.data(), [&](int32_t t) { return tg[t].nc; }, ntg);
+    if (R.trace_host) {
+        int c32 = 0, c64 = 0, c128 = 0, c192 = 0;
+        for (int t = 0; t < ntg; ++t) c32 += tg[t].nc >= 32, c64 += tg[t].nc >= 64, c128 += tg[t].nc >= 128, c192 += tg[t].nc >= 192;
+        fprintf(stderr, "[fw] chain %d: %u targets run by a workgroup each (>= %u candidates); targets with >= 32 / 64 / 128 / 192 candidates: %d / %d / %d / %d; "
+                        "candidates of the 1st / 64th / 256th heaviest: %d / %d / %d\n", R.chain, team, dh_team_min(), c32, c64, c128, c192,
+                tg[order[0]].nc, ntg > 63 ? tg[order[63]].nc : -1, ntg > 255 ? tg[order[255]].nc : -1);
+    }
+    FW_HIP(c, hipMemsetAsync(D.mq, 0, sizeof(MiQueue), st));
+    FW_HIP(c, hipMemsetAsync(D.boards, 0, sizeof(MiBoard) * MI_BOARD_CAP, st));  // ready flags, claimed / finished counts
+    FW_HIP(c, hipEventRecord(E.ev[0], st));
+    const unsigned grid = dh_mi_launch(c, st, D.tg, ntg, (const int32_t *)D.act, R.A, R.P, team, R.trace_host, D.mq, D.boards, D.mres, D.bacc);
+    FW_HIP(c, hipGetLastError());
+    FW_HIP(c, hipEventRecord(E.ev[1], st));
+    FW_HIP(c, hipStreamSynchronize(st));
+    MiQueue hq{};
+    FW_HIP(c, hipMemcpy(&hq, D.mq, sizeof(hq), hipMemcpyDeviceToHost));
+    if (int rc = dh_mi_check(c, hq, grid, 0, ntg, R.trace_host)) return rc;
+    float ms = 0.0f;
+    FW_HIP(c, hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
+    R.timed_s = 1e-3 * (double)ms;
+    R.timed_n = R.launches_n = 1;
+    return FW_OK;
+}
+
+// Fisher-z kinds (and the discrete ones under FW_MI_ROUNDS): rounds of segment kernel -> step -> (compact) -> plan -> fill, enqueued in
+// batches.  Two batches are kept in flight: the host enqueues batch b + 1 before it waits for the end of batch b, so the GPU
+// never runs dry while the host looks at the round record (a stream synchronisation per batch left ~200 us of
+// idle GPU per 16 rounds).  Rounds after the last one are no-ops (no live segment, nothing to merge).
+struct DhRounds {
+    DhRun &R;
+    DhEvents &E;  // E.ev[(q * DH_BATCH + r) * 2 + 0 / 1] around the segment launch of round r of batch slot q; E.ev_end[q]
+    fw_ctx *c = R.c;
+    const DhRunBufs &D = R.D;
+    const DhPolicy &y = R.y;
+    const int ntg = R.ntg;
+    hipStream_t st = R.st, hs = R.st;  // hs: stream of the small kernels (FW_DH_HP: the chain's high-priority stream)
+    DhPlanArgs PA{};
     // The in-lane kernel (accepted lists beyond FW_TAB_A) is only launched when such a list can exist in the coming batch:
     // without whitelists an accepted list grows by at most one entry per round, so max_a (longest list so far, read
     // back once per batch) + BATCH bounds it; with whitelists a round can append several entries -> static bound.
-    const bool any_wl = !wl.empty();
-    const bool any_big_static = (any_wl ? 2 * max_cap : max_cap) > FW_TAB_A;
-    const unsigned g_fill = (max_ns + 255) / 256;
-    unsigned n_act_bound = (unsigned)ntg;  // unfinished targets as of the last record read (only ever shrinks)
-    const unsigned *d_ns = &d_g->ns;
-    // ---- rounds ----
-    // Kernel timing (fw_counters.t_dev_subsets_s): HIP events around one segment launch in FW_DH_TIME_EVERY (default 4),
-    // the sampled slot rotating from batch to batch so that every position of the 16-round batch is covered; the
-    // sampled average is scaled to all non-empty launches.  Every event pair costs ~12 us of idle GPU around the launch
-    // (rocprofv3 trace: 5.9 us before + 5.7 us after, back-to-back otherwise): cfg3, ms per pass / average launch us at
-    // k = 1: 275.3 / 224.2, k = 2: 272.2 / 224.5, k = 4: 270.4 / 224.5, k = 8: 270.2 / 224.8 -- same average, 2 % less time.
-    // Two batches are kept in flight: the host enqueues batch b + 1 before it waits for the end of batch b, so the GPU
-    // never runs dry while the host looks at the round record (a stream synchronisation per batch left ~200 us of
-    // idle GPU per 16 rounds).  Rounds after the last one are no-ops (no live segment, nothing to merge).
-    constexpr int BATCH = 16;
-    // Rounds per batch.  The host sees "every target has finished" one batch late, so a pass of few, light targets (a rank of an
-    // 8-rank job holds 128 targets per feed-forward round at cfg3, 15 dependent rounds) ran 33 rounds, half of them empty: short
-    // batches for short lists (r03: 1.05 -> 0.75 ms per light round; the host enqueues 4 rounds in ~60 us, a round takes 25-100 us)
-    static const int nb_env = [] { const char *e = fw_knob("FW_DH_BATCH"); return e && atoi(e) > 0 ? std::min(atoi(e), 16) : 0; }();
-    const int nb = nb_env ? nb_env : (ntg <= 1024 ? 4 : BATCH);
-    static const int time_every = [] { const char *e = fw_knob("FW_DH_TIME_EVERY"); return e && atoi(e) > 0 ? atoi(e) : 4; }();
-    // events live in a holder whose destructor synchronises the stream and destroys them on EVERY exit path (error returns
-    // and the watchdog of the persistent kernel included: r02 leaked 66 events per failed call and left the stream running)
-    struct EvHolder {
-        hipStream_t st;
-        hipEvent_t ev[2][2 * BATCH], ev_end[2];
-        bool ok = true;
-        explicit EvHolder(hipStream_t s) : st(s)
-        {
-            for (int q = 0; q < 2; ++q) {
-                for (hipEvent_t &e : ev[q]) e = nullptr;
-                ev_end[q] = nullptr;
-            }
-            for (int q = 0; q < 2 && ok; ++q) {
-                for (hipEvent_t &e : ev[q]) ok = ok && hipEventCreate(&e) == hipSuccess;
-                ok = ok && hipEventCreateWithFlags(&ev_end[q], hipEventDisableTiming) == hipSuccess;
-            }
-        }
-        ~EvHolder()
-        {
-            (void)hipStreamSynchronize(st);
-            for (int q = 0; q < 2; ++q) {
-                for (hipEvent_t &e : ev[q])
-                    if (e) (void)hipEventDestroy(e);
-                if (ev_end[q]) (void)hipEventDestroy(ev_end[q]);
-            }
-        }
-    } evh(st);
-    if (!evh.ok) return fw_fail(c, FW_ERR_DEVICE, "device HITON: hipEventCreate failed");
-    auto &ev = evh.ev;
-    auto &ev_end = evh.ev_end;
-    DhPlanArgs PA{};
-    PA.seg_target = seg_target;
-    PA.seg_q = P.seg_q;
-    PA.seg_min = P.seg_min;
-    PA.log_cap = LOG_CAP;
-    PA.log = d_log;
-    PA.seg_a = seg_a;
-    PA.seg_b = seg_b;
-    // FW_DH_HP=1: the small kernels of a round on the chain's high-priority stream (fw_ctx::dh_hp_stream) -- an experiment kept behind its knob
-    static const int hp_env = [] { const char *e = fw_knob("FW_DH_HP"); return e ? atoi(e) : -1; }();
-    const bool use_hp = !per_target && hp_env > 0;  // (measured at cfg5: no effect -- what held the plan kernel back was its size, not its queue; default off)
-    static const int ps_env = [] { const char *e = fw_knob("FW_DH_PLAN_SMALL"); return e ? atoi(e) : -1; }();
-    const bool plan_small = ps_env >= 0 ? ps_env != 0 : true;
-    hipStream_t hs = st;
-    if (use_hp) {
+    const bool any_wl = !R.wl.empty();
+    const bool any_big_static = (any_wl ? 2 * R.max_cap : R.max_cap) > FW_TAB_A;
+    const unsigned g_fill = (R.max_ns + 255) / 256;
+    unsigned n_act_bound = (unsigned)R.ntg;  // unfinished targets as of the last record read (only ever shrinks)
+    bool big_skipped[2] = {false, false};    // per batch slot: some round of it ran without the in-lane kernel
+
+    DhRounds(DhRun &r, DhEvents &e) : R(r), E(e)
+    {
+        PA.seg_target = y.seg_target;
+        PA.seg_q = R.P.seg_q;
+        PA.seg_min = R.P.seg_min;
+        PA.log_cap = DH_LOG_CAP;
+        PA.log = D.log;
+        PA.seg_a = y.seg_a;
+        PA.seg_b = y.seg_b;
+    }
+    hipEvent_t &ev(int q, int i) { return E.ev[(size_t)(q * 2 * DH_BATCH + i)]; }
+    bool timed(unsigned b, int r) const { return ((r + (int)(b % (unsigned)y.time_every)) % y.time_every) == 0; }  // the sampled slot rotates from batch to batch
+
+    int hp_stream()
+    {
+        const int chain = R.chain;
         if (!c->dh_hp_stream[chain]) {
             int lo = 0, hi = 0;
             FW_HIP(c, hipDeviceGetStreamPriorityRange(&lo, &hi));  // (hi: numerically lowest = highest priority)
@@ -2994,260 +3150,313 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
             for (int e = 0; e < 2; ++e) FW_HIP(c, hipEventCreateWithFlags(&c->dh_hp_ev[chain][e], hipEventDisableTiming));
         }
         hs = c->dh_hp_stream[chain];
+        return FW_OK;
     }
-    auto planfill = [&](bool compact) {
-        if (use_hp) {  // behind the segment kernel of this round ...
-            (void)hipEventRecord(c->dh_hp_ev[chain][0], st);
-            (void)hipStreamWaitEvent(hs, c->dh_hp_ev[chain][0], 0);
+    // the small kernels between two segment launches: merge + advance, (compact,) plan, fill
+    int planfill(bool compact)
+    {
+        const DhArrays &A = R.A;
+        if (y.use_hp) {  // behind the segment kernel of this round ...
+            FW_HIP(c, hipEventRecord(c->dh_hp_ev[R.chain][0], st));
+            FW_HIP(c, hipStreamWaitEvent(hs, c->dh_hp_ev[R.chain][0], 0));
         }
         if (A.rej)  // (the rejection log: its own instantiation, so that the default one keeps its registers)
-            hipLaunchKernelGGL(dh_step_kernel<true>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, d_tg, ntg, d_g, A,
-                               (const FwSegOut *)d_so, (const long long *)d_seg0, d_win, d_sp, d_win2, (const int32_t *)d_act, P);
+            hipLaunchKernelGGL(dh_step_kernel<true>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, D.tg, ntg, D.g, A,
+                               (const FwSegOut *)D.so, (const long long *)D.seg0, D.win, D.sp, D.win2, (const int32_t *)D.act, R.P);
         else
-            hipLaunchKernelGGL(dh_step_kernel<false>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, d_tg, ntg, d_g, A,
-                               (const FwSegOut *)d_so, (const long long *)d_seg0, d_win, d_sp, d_win2, (const int32_t *)d_act, P);
+            hipLaunchKernelGGL(dh_step_kernel<false>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, D.tg, ntg, D.g, A,
+                               (const FwSegOut *)D.so, (const long long *)D.seg0, D.win, D.sp, D.win2, (const int32_t *)D.act, R.P);
         if (compact)  // between step and plan: seg0 of the coming launch is built on the new list
-            hipLaunchKernelGGL(dh_compact_kernel, dim3(1), dim3(1024), 0, hs, (const DhTgt *)d_tg, ntg, d_g, d_act);
-        if (plan_small)
-            hipLaunchKernelGGL(dh_plan_small_kernel, dim3(1), dim3(256), 0, hs, ntg, d_g, (const unsigned long long *)d_win,
-                               (const unsigned int *)d_sp, (const unsigned long long *)d_win2, (const int32_t *)d_act, d_seg0, PA);
+            hipLaunchKernelGGL(dh_compact_kernel, dim3(1), dim3(1024), 0, hs, (const DhTgt *)D.tg, ntg, D.g, D.act);
+        if (y.plan_small)
+            hipLaunchKernelGGL(dh_plan_small_kernel, dim3(1), dim3(256), 0, hs, ntg, D.g, (const unsigned long long *)D.win,
+                               (const unsigned int *)D.sp, (const unsigned long long *)D.win2, (const int32_t *)D.act, D.seg0, PA);
         else
-            hipLaunchKernelGGL(dh_plan_kernel, dim3(1), dim3(1024), 0, hs, ntg, d_g, (const unsigned long long *)d_win,
-                               (const unsigned int *)d_sp, (const unsigned long long *)d_win2, (const int32_t *)d_act, d_seg0, PA);
-        hipLaunchKernelGGL(dh_fill_kernel, dim3(g_fill), dim3(256), 0, hs, (const DhTgt *)d_tg, ntg, d_g,
-                           (const long long *)d_seg0, A, d_segs, d1, (const int32_t *)d_act);
-        if (use_hp) {  // ... and in front of the next one
-            (void)hipEventRecord(c->dh_hp_ev[chain][1], hs);
-            (void)hipStreamWaitEvent(st, c->dh_hp_ev[chain][1], 0);
+            hipLaunchKernelGGL(dh_plan_kernel, dim3(1), dim3(1024), 0, hs, ntg, D.g, (const unsigned long long *)D.win,
+                               (const unsigned int *)D.sp, (const unsigned long long *)D.win2, (const int32_t *)D.act, D.seg0, PA);
+        hipLaunchKernelGGL(dh_fill_kernel, dim3(g_fill), dim3(256), 0, hs, (const DhTgt *)D.tg, ntg, D.g,
+                           (const long long *)D.seg0, A, D.segs, y.spec_depth + 1, (const int32_t *)D.act);
+        if (y.use_hp) {  // ... and in front of the next one
+            FW_HIP(c, hipEventRecord(c->dh_hp_ev[R.chain][1], hs));
+            FW_HIP(c, hipStreamWaitEvent(st, c->dh_hp_ev[R.chain][1], 0));
         }
-    };
-    const double th1 = wall();
-    int rc2 = FW_OK;
-    double timed_s = 0.0;
-    long timed_n = 0, launches_n = 0;
-    std::vector<float> log_ms;  // FW_DH_LOG: segment-kernel time of launch i (planned by plan #i)
-    if (per_target) {
-        std::vector<int32_t> order((size_t)ntg);
-        for (int t = 0; t < ntg; ++t) order[t] = t;
-        std::stable_sort(order.begin(), order.end(), [&](int32_t u, int32_t v) { return tg[u].nc > tg[v].nc; });  // heaviest first
-        FW_HIP(c, hipMemcpyAsync(d_act, order.data(), sizeof(int32_t) * (size_t)ntg, hipMemcpyHostToDevice, st));
-        {
-        unsigned team = 0u;
-        {   // targets with at least FW_MI_TEAM_MIN candidates (at most FW_MI_TEAM_MAX of them): a workgroup each
-            const unsigned team_min = dh_team_min(), team_max = dh_team_max();
-            while (team_min > 0u && team < team_max && (int)team < ntg && (unsigned)tg[order[team]].nc >= team_min) ++team;
-            if (trace_host) {
-                int c32 = 0, c64 = 0, c128 = 0, c192 = 0;
-                for (int t = 0; t < ntg; ++t) c32 += tg[t].nc >= 32, c64 += tg[t].nc >= 64, c128 += tg[t].nc >= 128, c192 += tg[t].nc >= 192;
-                fprintf(stderr, "[fw] chain %d: %u targets run by a workgroup each (>= %u candidates); targets with >= 32 / 64 / 128 / 192 candidates: %d / %d / %d / %d; "
-                                "candidates of the 1st / 64th / 256th heaviest: %d / %d / %d\n", chain, team, team_min, c32, c64, c128, c192,
-                        tg[order[0]].nc, ntg > 63 ? tg[order[63]].nc : -1, ntg > 255 ? tg[order[255]].nc : -1);
-            }
-        }
-        FW_HIP(c, hipMemsetAsync(d_mq, 0, sizeof(MiQueue), st));
-        FW_HIP(c, hipMemsetAsync(d_boards, 0, sizeof(MiBoard) * MI_BOARD_CAP, st));  // ready flags, claimed / finished counts
-        FW_HIP(c, hipEventRecord(ev[0][0], st));
-        const unsigned grid = dh_mi_launch(c, st, d_tg, ntg, (const int32_t *)d_act, A, P, team, trace_host, d_mq, d_boards, d_mres, d_bacc);
-        FW_HIP(c, hipGetLastError());
-        FW_HIP(c, hipEventRecord(ev[0][1], st));
-        FW_HIP(c, hipStreamSynchronize(st));
-        MiQueue hq{};
-        FW_HIP(c, hipMemcpy(&hq, d_mq, sizeof(hq), hipMemcpyDeviceToHost));
-        if (hq.pad[0]) return fw_fail(c, FW_ERR_DEVICE, "discrete HITON kernel: watchdog %u (boards %u, targets done %u of %d)", hq.pad[0], hq.n_boards, hq.targets_done, ntg);
-        if (trace_host) dh_mi_trace(hq, grid);
-        float ms = 0.0f;
-        FW_HIP(c, hipEventElapsedTime(&ms, ev[0][0], ev[0][1]));
-        timed_s = 1e-3 * (double)ms;
-        timed_n = launches_n = 1;
-        }
-    } else {
-    planfill(true);  // nothing to merge yet: creates the first jobs and the first launch (plan #0)
-    max_a_seen = 0;
-    max_ab_seen = (unsigned)max_wl;  // before any record: all whitelisted neighbours are still to come
-    bool big_skipped[2] = {false, false};  // per batch slot: some round of it ran without the in-lane kernel
-    auto enqueue_batch = [&](unsigned b) -> int {
+        return FW_OK;
+    }
+    int enqueue_batch(unsigned b)
+    {
+        const DhArrays &A = R.A;
         const int q = (int)(b & 1u);
-        for (int r = 0; r < nb; ++r) {
-            const bool timed = ((r + (int)(b % (unsigned)time_every)) % time_every) == 0;  // the sampled slot rotates from batch to batch
+        const unsigned *d_ns = &D.g->ns;
+        for (int r = 0; r < y.nb; ++r) {
             // lists grow by at most one entry per round: 3 batches cover the lag of the record plus this batch
             // ... and a whitelisted neighbour is appended at most once per target: max_ab (accepted + whitelisted neighbours
             // still to come, maximum over the targets, kept by dh_step_kernel) bounds what whitelists can add.  (r02
             // profile: with whitelists the in-lane kernel was launched every round "in case" and left on the device flag --
             // 16 us of every round's critical path, 26 ms per chain and pass at cfg3.)
-            const bool any_big = any_big_static && max_ab_seen + 3u * (unsigned)BATCH + 1u > (unsigned)FW_TAB_A;
+            const bool any_big = any_big_static && R.max_ab_seen + 3u * (unsigned)DH_BATCH + 1u > (unsigned)FW_TAB_A;
             if (r == 0) big_skipped[q] = false;
             if (!any_big) big_skipped[q] = true;
-            if (timed) (void)hipEventRecord(ev[q][2 * r], st);
+            if (timed(b, r)) (void)hipEventRecord(ev(q, 2 * r), st);
             // discrete segment kernel: one workgroup per record, no stride loop -> the grid follows the bound on the list
-            const unsigned grid_mi = std::min(max_ns, seg_target + n_act_bound * (unsigned)(1 + std::max(spec_depth, spec0_depth)) + 256u);
+            const unsigned grid_mi = std::min(R.max_ns, y.seg_target + n_act_bound * (unsigned)(1 + std::max(y.spec_depth, y.spec0_depth)) + 256u);
             int rc;
-            if (nzk) {
+            if (y.nzk) {
                 // this round's fresh jobs: records (one thread per unfinished target), their matrices, then the enumeration
-                hipLaunchKernelGGL(dh_nz_recs_kernel, dim3((n_act_bound + 255u) / 256u), dim3(256), 0, st, (const DhTgt *)d_tg, ntg, (const DhGlobal *)d_g,
-                                   (const int32_t *)d_act, A, d_nzrecs, (const long long *)d_nzaoff);
-                rc = fwi_fznz_submatrices_dev(c, ntg, d_nzrecs, A.acc, d_nzarena, (any_wl ? 2 * max_cap : max_cap) + 2, true, st);
-                if (!rc) rc = fwi_fznz_segments_dev(c, grid_seg, d_segs, A.acc, d_so, d_ns, any_big, &d_g->any_big, d_nzrecs, d_nzarena, st);
+                hipLaunchKernelGGL(dh_nz_recs_kernel, dim3((n_act_bound + 255u) / 256u), dim3(256), 0, st, (const DhTgt *)D.tg, ntg, (const DhGlobal *)D.g,
+                                   (const int32_t *)D.act, A, D.nzrecs, (const long long *)D.nzaoff);
+                rc = fwi_fznz_submatrices_dev(c, ntg, D.nzrecs, A.acc, D.nzarena, (any_wl ? 2 * R.max_cap : R.max_cap) + 2, true, st);
+                if (!rc) rc = fwi_fznz_segments_dev(c, y.grid_seg, D.segs, A.acc, D.so, d_ns, any_big, &D.g->any_big, D.nzrecs, D.nzarena, st);
             } else {
-                rc = fz ? fwi_fz_segments_dev(c, grid_seg, d_segs, A.acc, d_so, d_ns, any_big, &d_g->any_big, st)
-                        : fwi_mi_segments_dev(c, grid_mi, d_segs, A.acc, d_so, d_ns, st);
+                rc = y.fz ? fwi_fz_segments_dev(c, y.grid_seg, D.segs, A.acc, D.so, d_ns, any_big, &D.g->any_big, st)
+                          : fwi_mi_segments_dev(c, grid_mi, D.segs, A.acc, D.so, d_ns, st);
             }
             if (rc) return rc;
-            if (timed) (void)hipEventRecord(ev[q][2 * r + 1], st);
-            planfill((b * (unsigned)nb + (unsigned)r) % 16u == 0u);  // the list of unfinished targets is compacted every 16 rounds
+            if (timed(b, r)) (void)hipEventRecord(ev(q, 2 * r + 1), st);
+            if ((rc = planfill((b * (unsigned)y.nb + (unsigned)r) % 16u == 0u))) return rc;  // the list of unfinished targets is compacted every 16 rounds
         }
         FW_HIP(c, hipGetLastError());
-        FW_HIP(c, hipMemcpyAsync(hg + q, d_g, sizeof(DhGlobal), hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipEventRecord(ev_end[q], st));
+        FW_HIP(c, hipMemcpyAsync(R.hg + q, D.g, sizeof(DhGlobal), hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipEventRecord(E.ev_end[q], st));
         return FW_OK;
-    };
-    // returns 1 when the record of batch b says that every target has finished
-    auto retire_batch = [&](unsigned b, int *done) -> int {
+    }
+    // *done: the record of batch b says that every target has finished
+    int retire_batch(unsigned b, int *done)
+    {
         const int q = (int)(b & 1u);
-        FW_HIP(c, hipEventSynchronize(ev_end[q]));
-        const DhGlobal &rec = hg[q];
-        for (int r = 0; r < nb; ++r) {
-            if (rec.ns_ring[(b * (unsigned)nb + (unsigned)r) & 63u] == 0) continue;  // empty launch after the last round
-            ++launches_n;
-            if (((r + (int)(b % (unsigned)time_every)) % time_every) != 0) continue;
+        FW_HIP(c, hipEventSynchronize(E.ev_end[q]));
+        const DhGlobal &rec = R.hg[q];
+        for (int r = 0; r < y.nb; ++r) {
+            if (rec.ns_ring[(b * (unsigned)y.nb + (unsigned)r) & 63u] == 0) continue;  // empty launch after the last round
+            ++R.launches_n;
+            if (!timed(b, r)) continue;
             float ms = 0.0f;
-            FW_HIP(c, hipEventElapsedTime(&ms, ev[q][2 * r], ev[q][2 * r + 1]));
-            timed_s += 1e-3 * (double)ms;
-            ++timed_n;
-            if (log_path) {
-                const size_t idx = (size_t)b * (size_t)nb + (size_t)r;
-                if (log_ms.size() <= idx) log_ms.resize(idx + 1, 0.0f);
-                log_ms[idx] = ms;
+            FW_HIP(c, hipEventElapsedTime(&ms, ev(q, 2 * r), ev(q, 2 * r + 1)));
+            R.timed_s += 1e-3 * (double)ms;
+            ++R.timed_n;
+            if (y.log_path) {
+                const size_t idx = (size_t)b * (size_t)y.nb + (size_t)r;
+                if (R.log_ms.size() <= idx) R.log_ms.resize(idx + 1, 0.0f);
+                R.log_ms[idx] = ms;
             }
         }
-        if (fz && c->P.max_k <= 3 && big_skipped[q] && rec.max_a > (unsigned)FW_TAB_A)  // the bound above failed: fail loudly
+        if (y.fz && c->P.max_k <= 3 && big_skipped[q] && rec.max_a > (unsigned)FW_TAB_A)  // the bound above failed: fail loudly
             return fw_fail(c, FW_ERR_DEVICE, "device rounds: an accepted list of %u entries met a batch without the in-lane kernel", rec.max_a);
-        max_a_seen = rec.max_a > max_a_seen ? rec.max_a : max_a_seen;
-        max_ab_seen = rec.max_ab > max_ab_seen ? rec.max_ab : max_ab_seen;
-        n_act_bound = rec.n_act < n_act_bound ? rec.n_act : n_act_bound;
+        R.max_a_seen = std::max(R.max_a_seen, rec.max_a);
+        R.max_ab_seen = std::max(R.max_ab_seen, rec.max_ab);
+        n_act_bound = std::min(n_act_bound, rec.n_act);
         *done = rec.done != 0u;
         return FW_OK;
-    };
+    }
+    int run()
     {
+        int rc = y.use_hp ? hp_stream() : FW_OK;
+        if (rc) return rc;
+        R.max_ab_seen = (unsigned)R.max_wl;  // before any record: all whitelisted neighbours are still to come
         unsigned b = 0;
         int done = 0;
-        rc2 = enqueue_batch(0);
-        while (!rc2) {
-            if ((rc2 = enqueue_batch(b + 1))) break;   // keep the GPU fed ...
-            if ((rc2 = retire_batch(b, &done))) break;  // ... while the host reads the previous batch's record
+        if (!(rc = planfill(true)))  // nothing to merge yet: creates the first jobs and the first launch (plan #0)
+            rc = enqueue_batch(0);
+        while (!rc) {
+            if ((rc = enqueue_batch(b + 1))) break;   // keep the GPU fed ...
+            if ((rc = retire_batch(b, &done))) break;  // ... while the host reads the previous batch's record
             ++b;
             if (done) {
                 int d2 = 0;
-                rc2 = retire_batch(b, &d2);  // the batch still in flight holds only no-op rounds
+                rc = retire_batch(b, &d2);  // the batch still in flight holds only no-op rounds
                 break;
             }
             if (b > 250000u) {  // every round finishes at least one window: this is a logic error, not a workload
-                rc2 = fw_fail(c, FW_ERR_DEVICE, "device HITON: no convergence after %u rounds", b * (unsigned)nb);
+                rc = fw_fail(c, FW_ERR_DEVICE, "device HITON: no convergence after %u rounds", b * (unsigned)y.nb);
                 break;
             }
         }
-        if (rc2) (void)hipStreamSynchronize(st);
+        if (rc) (void)hipStreamSynchronize(st);
+        return rc;
     }
-    }  // rounds
-    static std::mutex cnt_mu;  // concurrent chains share the context's counters
-    {
-        std::lock_guard<std::mutex> lk(cnt_mu);
-        if (timed_n > 0) c->cnt.t_dev_subsets_s += timed_s * (double)launches_n / (double)timed_n;
-        c->cnt.subsets_launches += launches_n;
-        c->cnt.kernel_launches += per_target ? launches_n : (nzk ? 7 : 4) * launches_n;
+};
+
+// FW_DH_LOG: one line per planned launch, appended to the file
+static int dh_write_log(const DhRun &R)
+{
+    fw_ctx *c = R.c;
+    std::vector<ulonglong2> lg(DH_LOG_CAP);
+    DhGlobal fin{};
+    FW_HIP(c, hipMemcpy(&fin, R.D.g, sizeof(DhGlobal), hipMemcpyDeviceToHost));
+    FW_HIP(c, hipMemcpy(lg.data(), R.D.log, sizeof(ulonglong2) * DH_LOG_CAP, hipMemcpyDeviceToHost));
+    long long n_tpc = 0, n_pc = 0;  // interleaving survivors / elimination survivors
+    for (const DhTgt &x : R.tg) {
+        n_tpc += x.ntpc;
+        n_pc += x.npc;
     }
-    if (rc2) return rc2;
-    const double th2 = wall();
-    // ---- results ----
-    FW_HIP(c, hipMemcpy(tg.data(), d_tg, sizeof(DhTgt) * ntg, hipMemcpyDeviceToHost));
-    if (d_log) {
-        std::vector<ulonglong2> lg(LOG_CAP);
-        DhGlobal fin{};
-        FW_HIP(c, hipMemcpy(&fin, d_g, sizeof(DhGlobal), hipMemcpyDeviceToHost));
-        FW_HIP(c, hipMemcpy(lg.data(), d_log, sizeof(ulonglong2) * LOG_CAP, hipMemcpyDeviceToHost));
-        long long n_tpc = 0, n_pc = 0;  // interleaving survivors / elimination survivors
-        for (const DhTgt &x : tg) {
-            n_tpc += x.ntpc;
-            n_pc += x.npc;
-        }
-        if (FILE *f = fopen(log_path, "a")) {
-            fprintf(f, "# targets %d rounds %u tpc %lld pc %lld\n", ntg, fin.rounds, n_tpc, n_pc);
-            for (unsigned r = 0; r < fin.rounds && r < LOG_CAP; ++r)
-                fprintf(f, "%u %llu %llu %llu %.1f\n", r, lg[r].x, lg[r].y >> 32, lg[r].y & 0xffffffffull,
-                        r < log_ms.size() ? 1e3 * (double)log_ms[r] : 0.0);
-            fclose(f);
-        }
+    if (FILE *f = fopen(R.y.log_path, "a")) {
+        fprintf(f, "# targets %d rounds %u tpc %lld pc %lld\n", R.ntg, fin.rounds, n_tpc, n_pc);
+        for (unsigned r = 0; r < fin.rounds && r < DH_LOG_CAP; ++r)
+            fprintf(f, "%u %llu %llu %llu %.1f\n", r, lg[r].x, lg[r].y >> 32, lg[r].y & 0xffffffffull,
+                    r < R.log_ms.size() ? 1e3 * (double)R.log_ms[r] : 0.0);
+        fclose(f);
     }
-    std::vector<int32_t> &pk = flat.key;
-    std::vector<double> &ps = flat.stat, &pp = flat.pval;
-    pk.resize(tot);
-    ps.resize(tot);
-    pp.resize(tot);
+    return FW_OK;
+}
+
+// per-target states and PC lists back to the host
+static int dh_download(DhRun &R, std::vector<FwDhResult> &out, FwDhFlat &flat)
+{
+    fw_ctx *c = R.c;
+    const size_t tot = R.tot;
+    FW_HIP(c, hipMemcpy(R.tg.data(), R.D.tg, sizeof(DhTgt) * R.ntg, hipMemcpyDeviceToHost));
+    if (R.D.log)
+        if (int rc = dh_write_log(R)) return rc;
+    flat.key.resize(tot);
+    flat.stat.resize(tot);
+    flat.pval.resize(tot);
     if (tot) {
-        FW_HIP(c, hipMemcpy(pk.data(), A.pc_key, 4 * tot, hipMemcpyDeviceToHost));
-        FW_HIP(c, hipMemcpy(ps.data(), A.pc_stat, 8 * tot, hipMemcpyDeviceToHost));
-        FW_HIP(c, hipMemcpy(pp.data(), A.pc_p, 8 * tot, hipMemcpyDeviceToHost));
+        FW_HIP(c, hipMemcpy(flat.key.data(), R.A.pc_key, 4 * tot, hipMemcpyDeviceToHost));
+        FW_HIP(c, hipMemcpy(flat.stat.data(), R.A.pc_stat, 8 * tot, hipMemcpyDeviceToHost));
+        FW_HIP(c, hipMemcpy(flat.pval.data(), R.A.pc_p, 8 * tot, hipMemcpyDeviceToHost));
     }
-    for (int t = 0; t < ntg; ++t) {
-        const DhTgt &x = tg[t];
+    for (int t = 0; t < R.ntg; ++t) {
+        const DhTgt &x = R.tg[t];
         if (x.phase != 2) return fw_fail(c, FW_ERR_DEVICE, "device HITON: target %d did not finish (phase %d)", x.T, x.phase);
         out[t].off = x.co;
         out[t].n = x.npc;
     }
-    if (trace_host) {  // chain statistics: the longest per-target sequences bound the pass from below
-        unsigned long long mx_ref = 0, mx_calls = 0, tot_ref = 0, tot_calls = 0;
-        int t_ref = -1, t_calls = -1;
-        for (const DhTgt &x : tg) {
-            tot_ref += x.c_ref;
-            tot_calls += x.c_calls;
-            if (x.c_ref > mx_ref) mx_ref = x.c_ref, t_ref = x.T;
-            if (x.c_calls > mx_calls) mx_calls = x.c_calls, t_calls = x.T;
-        }
-        fprintf(stderr, "[fw] chain %d: tests %llu jobs %llu; most tests in one target %llu (T=%d), most jobs in one target %llu (T=%d)\n",
-                chain, tot_ref, tot_calls, mx_ref, t_ref, mx_calls, t_calls);
-        unsigned long long ev_all = 0, ev_short = 0;
-        int na_max = 0;
-        for (const DhTgt &x : tg) {
-            ev_all += x.c_eval;
-            ev_short += x.c_eval_short;
-            na_max = std::max(na_max, x.na_max);
-        }
-        fprintf(stderr, "[fw] chain %d: executed tests %llu, of them in jobs with at most %d accepted variables %llu; longest accepted list %d\n",
-                chain, ev_all, (int)FW_HK_A, ev_short, na_max);
-        if (per_target) {  // the targets that finished last: when they were taken, how long they ran, what they ran
-            unsigned int t0 = ~0u;
-            for (const DhTgt &x : tg) t0 = std::min(t0, x.r_first0);
-            std::vector<const DhTgt *> by_end;
-            for (const DhTgt &x : tg) by_end.push_back(&x);
-            std::sort(by_end.begin(), by_end.end(), [&](const DhTgt *a, const DhTgt *b) { return a->r_more0 - t0 > b->r_more0 - t0; });
-            for (size_t i = 0; i < by_end.size() && i < 6; ++i) {
-                const DhTgt *w = by_end[i];
-                fprintf(stderr, "[fw]   finished at %.2f ms (taken at %.2f): T=%d, %d candidates, %d in PC, %llu jobs, %llu tests (%llu executed); "
-                                "sequential prefixes %.2f ms, board phases %.2f ms (%llu jobs went to a board; %llu team rounds)\n",
-                        1e-5 * (w->r_more0 - t0), 1e-5 * (w->r_first0 - t0), w->T, w->cap, w->npc, w->c_calls, w->c_ref, w->c_eval,
-                        1e-5 * w->r_first1, 1e-5 * w->r_more1, w->c_eval_short & 0xffffffffull, w->c_eval_short >> 32);
-            }
-        } else {  // the target that was busy for the most rounds: where its rounds went
-            const DhTgt *w = &tg[0];
-            for (const DhTgt &x : tg)
-                if (x.r_first0 + x.r_more0 + x.r_first1 + x.r_more1 > w->r_first0 + w->r_more0 + w->r_first1 + w->r_more1) w = &x;
-            fprintf(stderr, "[fw] chain %d: longest-busy target T=%d: %d candidates, %d in TPC, %d in PC, %llu jobs; rounds: interleaving first windows %u, later windows %u; elimination first %u, later %u\n",
-                    chain, w->T, w->cap, w->ntpc, w->npc, w->c_calls, w->r_first0, w->r_more0, w->r_first1, w->r_more1);
-        }
-    }
-    if (trace_host)
-        fprintf(stderr, "[fw] chain %d: longest accepted list %u, accepted + whitelisted to come %u (most whitelisted neighbours of one target %d)\n",
-                chain, max_a_seen, max_ab_seen, max_wl);
-    if (trace_host)
-        fprintf(stderr, "[fw] device rounds chain %d: %d targets, set-up %.2f ms, rounds %.2f ms, results %.2f ms\n", chain, ntg,
-                1e3 * (th1 - th0), 1e3 * (th2 - th1), 1e3 * (wall() - th2));
-    std::lock_guard<std::mutex> lk(cnt_mu);
+    return FW_OK;
+}
+
+// FW_TRACE_HOST: chain statistics (the longest per-target sequences bound the pass from below) and the phase times
+static void dh_trace_run(const DhRun &R, double t_setup, double t_rounds, double t_results)
+{
+    const std::vector<DhTgt> &tg = R.tg;
+    const int chain = R.chain;
+    unsigned long long mx_ref = 0, mx_calls = 0, tot_ref = 0, tot_calls = 0;
+    int t_ref = -1, t_calls = -1;
     for (const DhTgt &x : tg) {
+        tot_ref += x.c_ref;
+        tot_calls += x.c_calls;
+        if (x.c_ref > mx_ref) mx_ref = x.c_ref, t_ref = x.T;
+        if (x.c_calls > mx_calls) mx_calls = x.c_calls, t_calls = x.T;
+    }
+    fprintf(stderr, "[fw] chain %d: tests %llu jobs %llu; most tests in one target %llu (T=%d), most jobs in one target %llu (T=%d)\n",
+            chain, tot_ref, tot_calls, mx_ref, t_ref, mx_calls, t_calls);
+    unsigned long long ev_all = 0, ev_short = 0;
+    int na_max = 0;
+    for (const DhTgt &x : tg) {
+        ev_all += x.c_eval;
+        ev_short += x.c_eval_short;
+        na_max = std::max(na_max, x.na_max);
+    }
+    fprintf(stderr, "[fw] chain %d: executed tests %llu, of them in jobs with at most %d accepted variables %llu; longest accepted list %d\n",
+            chain, ev_all, (int)FW_HK_A, ev_short, na_max);
+    if (R.y.per_target) {  // the targets that finished last: when they were taken, how long they ran, what they ran
+        unsigned int t0 = ~0u;
+        for (const DhTgt &x : tg) t0 = std::min(t0, x.r_first0);
+        std::vector<const DhTgt *> by_end;
+        for (const DhTgt &x : tg) by_end.push_back(&x);
+        std::sort(by_end.begin(), by_end.end(), [&](const DhTgt *a, const DhTgt *b) { return a->r_more0 - t0 > b->r_more0 - t0; });
+        for (size_t i = 0; i < by_end.size() && i < 6; ++i) {
+            const DhTgt *w = by_end[i];
+            fprintf(stderr, "[fw]   finished at %.2f ms (taken at %.2f): T=%d, %d candidates, %d in PC, %llu jobs, %llu tests (%llu executed); "
+                            "sequential prefixes %.2f ms, board phases %.2f ms (%llu jobs went to a board; %llu team rounds)\n",
+                    1e-5 * (w->r_more0 - t0), 1e-5 * (w->r_first0 - t0), w->T, w->cap, w->npc, w->c_calls, w->c_ref, w->c_eval,
+                    1e-5 * w->r_first1, 1e-5 * w->r_more1, w->c_eval_short & 0xffffffffull, w->c_eval_short >> 32);
+        }
+    } else {  // the target that was busy for the most rounds: where its rounds went
+        const DhTgt *w = &tg[0];
+        for (const DhTgt &x : tg)
+            if (x.r_first0 + x.r_more0 + x.r_first1 + x.r_more1 > w->r_first0 + w->r_more0 + w->r_first1 + w->r_more1) w = &x;
+        fprintf(stderr, "[fw] chain %d: longest-busy target T=%d: %d candidates, %d in TPC, %d in PC, %llu jobs; rounds: interleaving first windows %u, later windows %u; elimination first %u, later %u\n",
+                chain, w->T, w->cap, w->ntpc, w->npc, w->c_calls, w->r_first0, w->r_more0, w->r_first1, w->r_more1);
+    }
+    fprintf(stderr, "[fw] chain %d: longest accepted list %u, accepted + whitelisted to come %u (most whitelisted neighbours of one target %d)\n",
+            chain, R.max_a_seen, R.max_ab_seen, R.max_wl);
+    fprintf(stderr, "[fw] device rounds chain %d: %d targets, set-up %.2f ms, rounds %.2f ms, results %.2f ms\n", chain, R.ntg,
+            1e3 * t_setup, 1e3 * t_rounds, 1e3 * t_results);
+}
+
+// One round of targets on the device.  in: T ids, interleaving candidates and (sorted) whitelists per target;
+// out: PC (keys, statistics, p-values) per target in insertion order.
+int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<FwDhResult> &out, FwDhFlat &flat, int chain)
+{
+    const int ntg = (int)in.size();
+    out.assign((size_t)ntg, FwDhResult{});
+    if (ntg == 0) return FW_OK;
+    static const bool trace_host = fw_trace_host();  // host-side phase times on stderr
+    const double th0 = dh_wall();
+    // chain > 0: a second (third, ...) instance running concurrently from its own host thread on its own stream / arena
+    if (chain > 0 && !c->dh_stream[chain]) FW_HIP(c, hipStreamCreateWithFlags(&c->dh_stream[chain], hipStreamNonBlocking));
+    DhRun R{c, chain, ntg, chain == 0 ? c->pb[0].stream : c->dh_stream[chain], trace_host, dh_policy(c, ntg)};
+    dh_build_targets(R, in);
+    int rc;
+    if ((rc = dh_upload(R))) return rc;
+    DhEvents E(R.st, 2 * 2 * DH_BATCH, 2);
+    if (!E.ok) return fw_fail(c, FW_ERR_DEVICE, "device HITON: hipEventCreate failed");
+    const double th1 = dh_wall();
+    rc = R.y.per_target ? dh_run_persistent(R, E) : DhRounds(R, E).run();
+    {
+        std::lock_guard<std::mutex> lk(dh_cnt_mu);
+        if (R.timed_n > 0) c->cnt.t_dev_subsets_s += R.timed_s * (double)R.launches_n / (double)R.timed_n;
+        c->cnt.subsets_launches += R.launches_n;
+        c->cnt.kernel_launches += R.y.per_target ? R.launches_n : (R.y.nzk ? 7 : 4) * R.launches_n;
+    }
+    if (rc) return rc;
+    const double th2 = dh_wall();
+    if ((rc = dh_download(R, out, flat))) return rc;
+    if (trace_host) dh_trace_run(R, th1 - th0, th2 - th1, dh_wall() - th2);
+    std::lock_guard<std::mutex> lk(dh_cnt_mu);
+    for (const DhTgt &x : R.tg) {
         c->cnt.cond_tests_ref += (int64_t)x.c_ref;
         c->cnt.subsets_calls += (int64_t)x.c_calls;
         c->cnt.cond_tests_evaluated += (int64_t)x.c_eval;
         c->cnt.alg_bytes_subsets += x.c_alg;
     }
     return FW_OK;
+}
+
+// ---- the whole feed-forward schedule of the discrete kinds (fwi_devhiton_mi_schedule) ----
+
+struct DhSchedSizes {
+    size_t nt, p, nnz, nrounds;
+};
+struct DhSchedBufs {
+    DhTgt *tg;
+    int32_t *sched, *order, *round_of;
+    unsigned int *wl_cnt;
+    int32_t *tpc_key, *pc_key, *wl, *acc;
+    double *tpc_stat, *tpc_p, *pc_stat, *pc_p;
+    MiQueue *mq;  // one per round
+    MiBoard *boards;
+    FwSegOut *mres;
+    int32_t *bacc;
+    int32_t *ot, *ou;  // packed results: target, neighbour, statistic, p
+    double *os, *op;
+    unsigned long long *tot;  // [0..4] integers, [5] the Float64 sum of algorithmic bytes
+};
+static DhSchedBufs dh_sched_layout(DhArena &a, const DhSchedSizes &z)
+{
+    DhSchedBufs b{};
+    b.tg = a.take<DhTgt>(z.nt);
+    b.sched = a.take<int32_t>(z.nt);
+    b.order = a.take<int32_t>(z.nt);
+    b.round_of = a.take<int32_t>(z.p);
+    b.wl_cnt = a.take<unsigned int>(z.p);
+    b.tpc_key = a.take<int32_t>(z.nnz, 4);
+    b.pc_key = a.take<int32_t>(z.nnz, 4);
+    b.wl = a.take<int32_t>(z.nnz, 4);
+    b.acc = a.take<int32_t>(2 * z.nnz, 4);
+    b.tpc_stat = a.take<double>(z.nnz, 8);
+    b.tpc_p = a.take<double>(z.nnz, 8);
+    b.pc_stat = a.take<double>(z.nnz, 8);
+    b.pc_p = a.take<double>(z.nnz, 8);
+    b.mq = a.take<MiQueue>(z.nrounds);
+    b.boards = a.take<MiBoard>(MI_BOARD_CAP);
+    b.mres = a.take<FwSegOut>(MI_REC_CAP);
+    b.bacc = a.take<int32_t>(MI_BACC_CAP);
+    b.ot = a.take<int32_t>(z.nnz, 4);
+    b.ou = a.take<int32_t>(z.nnz, 4);
+    b.os = a.take<double>(z.nnz, 8);
+    b.op = a.take<double>(z.nnz, 8);
+    b.tot = a.take<unsigned long long>(8);
+    return b;
 }
 
 // The WHOLE feed-forward schedule of the discrete kinds on the device (r05; one GPU, no exchange between the rounds).  r02-r04 ran one
@@ -3263,9 +3472,8 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
 {
     if (nt == 0) return FW_OK;
     if (!c->d_cand || !c->d_nb_idx) return fw_fail(c, FW_ERR_STATE, "device schedule: the level-0 lists are not on the device");
-    static const bool trace_host = fw_knob("FW_TRACE_HOST") != nullptr;
-    auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double th0 = wall();
+    static const bool trace_host = fw_trace_host();
+    const double th0 = dh_wall();
     hipStream_t st = c->pb[0].stream;
     const int p = c->P.p;
     const size_t nnz = (size_t)c->nb_off[p];
@@ -3283,106 +3491,65 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
         const int r0 = r * R, r1 = std::min(nt, r0 + R);
         for (int i = r0; i < r1; ++i) order[i] = i - r0;
         std::stable_sort(order.begin() + r0, order.begin() + r1, [&](int32_t u, int32_t v) { return deg[r0 + u] > deg[r0 + v]; });
-        unsigned tm = 0u;
-        const unsigned team_min = dh_team_min(), team_max = dh_team_max();
-        while (team_min > 0u && tm < team_max && (int)tm < r1 - r0 && (unsigned)deg[r0 + order[r0 + tm]] >= team_min) ++tm;
-        team[r] = tm;
+        team[r] = dh_team_size(order.data() + r0, [&](int32_t i) { return deg[r0 + i]; }, r1 - r0);
     }
     // ---- device arena ----
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t need = pad(sizeof(DhTgt) * (size_t)nt) + 2 * pad(4 * (size_t)nt) + pad(4 * (size_t)p) * 2 + pad(4 * nnz + 4) * 3 + pad(4 * 2 * nnz + 4) +
-                  pad(8 * nnz + 8) * 4 + pad(sizeof(MiQueue) * (size_t)nrounds) + pad(sizeof(MiBoard) * MI_BOARD_CAP) +
-                  pad(sizeof(FwSegOut) * (size_t)MI_REC_CAP) + pad(sizeof(int32_t) * (size_t)MI_BACC_CAP) + 2 * pad(4 * nnz + 4) + 2 * pad(8 * nnz + 8) + pad(64);
-    int rc;
-    if ((rc = fw_dev_reserve(c, c->d_dh[0], need))) return rc;
-    char *B = (char *)c->d_dh[0].ptr;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) {
-        char *q = B + off;
-        off += pad(bytes);
-        return q;
-    };
-    DhTgt *d_tg = (DhTgt *)carve(sizeof(DhTgt) * (size_t)nt);
-    int32_t *d_sched = (int32_t *)carve(4 * (size_t)nt);
-    int32_t *d_order = (int32_t *)carve(4 * (size_t)nt);
-    int32_t *d_round_of = (int32_t *)carve(4 * (size_t)p);
-    unsigned int *d_wl_cnt = (unsigned int *)carve(4 * (size_t)p);
+    DhSchedBufs D;
+    if (int rc = dh_arena_reserve(c, c->d_dh[0], dh_sched_layout, DhSchedSizes{(size_t)nt, (size_t)p, nnz, (size_t)nrounds}, &D)) return rc;
     DhArrays A{};
     A.cand0 = c->d_cand;
-    A.tpc_key = (int32_t *)carve(4 * nnz + 4);
-    A.pc_key = (int32_t *)carve(4 * nnz + 4);
-    int32_t *d_wl = (int32_t *)carve(4 * nnz + 4);
-    A.wl = d_wl;
-    A.wl_cnt = feed_forward ? d_wl_cnt : nullptr;
-    A.acc = (int32_t *)carve(4 * 2 * nnz + 4);
-    A.tpc_stat = (double *)carve(8 * nnz + 8);
-    A.tpc_p = (double *)carve(8 * nnz + 8);
-    A.pc_stat = (double *)carve(8 * nnz + 8);
-    A.pc_p = (double *)carve(8 * nnz + 8);
+    A.tpc_key = D.tpc_key;
+    A.pc_key = D.pc_key;
+    A.wl = D.wl;
+    A.wl_cnt = feed_forward ? D.wl_cnt : nullptr;
+    A.acc = D.acc;
+    A.tpc_stat = D.tpc_stat;
+    A.tpc_p = D.tpc_p;
+    A.pc_stat = D.pc_stat;
+    A.pc_p = D.pc_p;
     A.rej = c->d_rej_run;
     A.nb_off = c->d_nb_off;
     A.nb_idx = c->d_nb_idx;
     A.nb_stat = c->d_nb_stat;
     A.nb_p = c->d_nb_p;
-    MiQueue *d_mq = (MiQueue *)carve(sizeof(MiQueue) * (size_t)nrounds);
-    MiBoard *d_boards = (MiBoard *)carve(sizeof(MiBoard) * MI_BOARD_CAP);
-    FwSegOut *d_mres = (FwSegOut *)carve(sizeof(FwSegOut) * (size_t)MI_REC_CAP);
-    int32_t *d_bacc = (int32_t *)carve(sizeof(int32_t) * (size_t)MI_BACC_CAP);
-    int32_t *d_ot = (int32_t *)carve(4 * nnz + 4), *d_ou = (int32_t *)carve(4 * nnz + 4);
-    double *d_os = (double *)carve(8 * nnz + 8), *d_op = (double *)carve(8 * nnz + 8);
-    unsigned long long *d_tot = (unsigned long long *)carve(64);  // [0..4] integers, [5] the Float64 sum of algorithmic bytes
-    FW_HIP(c, hipMemsetAsync(d_tot, 0, 64, st));
-    FW_HIP(c, hipMemcpyAsync(d_sched, sched, 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    FW_HIP(c, hipMemcpyAsync(d_order, order.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    FW_HIP(c, hipMemcpyAsync(d_round_of, round_of.data(), 4 * (size_t)p, hipMemcpyHostToDevice, st));
-    FW_HIP(c, hipMemsetAsync(d_wl_cnt, 0, 4 * (size_t)p, st));
-    FW_HIP(c, hipMemsetAsync(d_mq, 0, sizeof(MiQueue) * (size_t)nrounds, st));
-    hipLaunchKernelGGL(dh_mi_init_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_tg, nt, (const int32_t *)d_sched, c->d_nb_off,
+    FW_HIP(c, hipMemsetAsync(D.tot, 0, 64, st));
+    FW_HIP(c, hipMemcpyAsync(D.sched, sched, 4 * (size_t)nt, hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemcpyAsync(D.order, order.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemcpyAsync(D.round_of, round_of.data(), 4 * (size_t)p, hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemsetAsync(D.wl_cnt, 0, 4 * (size_t)p, st));
+    FW_HIP(c, hipMemsetAsync(D.mq, 0, sizeof(MiQueue) * (size_t)nrounds, st));
+    hipLaunchKernelGGL(dh_mi_init_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, D.tg, nt, (const int32_t *)D.sched, c->d_nb_off,
                        (const int32_t *)c->d_levels);
     const DhParams P = dh_make_params(c, R, 0, 0);
-    struct Ev2 {
-        hipStream_t st;
-        hipEvent_t e[2] = {nullptr, nullptr};
-        bool ok;
-        explicit Ev2(hipStream_t s) : st(s) { ok = hipEventCreate(&e[0]) == hipSuccess && hipEventCreate(&e[1]) == hipSuccess; }
-        ~Ev2()
-        {
-            (void)hipStreamSynchronize(st);
-            for (hipEvent_t &q : e)
-                if (q) (void)hipEventDestroy(q);
-        }
-    } ev(st);
-    if (!ev.ok) return fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventCreate failed");
-    const double th1 = wall();
-    FW_HIP(c, hipEventRecord(ev.e[0], st));
+    DhEvents E(st, 2, 0);
+    if (!E.ok) return fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventCreate failed");
+    const double th1 = dh_wall();
+    FW_HIP(c, hipEventRecord(E.ev[0], st));
     std::vector<unsigned> grids((size_t)nrounds, 0u);
     for (int r = 0; r < nrounds; ++r) {
         const int r0 = r * R, ntg = std::min(nt, r0 + R) - r0;
-        FW_HIP(c, hipMemsetAsync(d_boards, 0, sizeof(MiBoard) * MI_BOARD_CAP, st));  // ready flags, claimed / finished counts
-        grids[r] = dh_mi_launch(c, st, d_tg + r0, ntg, (const int32_t *)(d_order + r0), A, P, team[r], trace_host, d_mq + r, d_boards, d_mres, d_bacc);
+        FW_HIP(c, hipMemsetAsync(D.boards, 0, sizeof(MiBoard) * MI_BOARD_CAP, st));  // ready flags, claimed / finished counts
+        grids[r] = dh_mi_launch(c, st, D.tg + r0, ntg, (const int32_t *)(D.order + r0), A, P, team[r], trace_host, D.mq + r, D.boards, D.mres, D.bacc);
         if (feed_forward && r + 1 < nrounds)
-            hipLaunchKernelGGL(dh_wl_append_kernel, dim3((unsigned)((ntg + 3) / 4)), dim3(256), 0, st, (const DhTgt *)(d_tg + r0), ntg,
-                               (const int32_t *)A.pc_key, (const int32_t *)d_round_of, r, d_wl, c->d_nb_off, d_wl_cnt);
+            hipLaunchKernelGGL(dh_wl_append_kernel, dim3((unsigned)((ntg + 3) / 4)), dim3(256), 0, st, (const DhTgt *)(D.tg + r0), ntg,
+                               (const int32_t *)A.pc_key, (const int32_t *)D.round_of, r, D.wl, c->d_nb_off, D.wl_cnt);
     }
     FW_HIP(c, hipGetLastError());
-    FW_HIP(c, hipEventRecord(ev.e[1], st));
+    FW_HIP(c, hipEventRecord(E.ev[1], st));
     // ---- results: packed on the device, one small download ----
-    hipLaunchKernelGGL(dh_mi_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)d_tg, nt, (const int32_t *)A.pc_key,
-                       (const double *)A.pc_stat, (const double *)A.pc_p, d_ot, d_ou, d_os, d_op, d_tot, (double *)(d_tot + 5));
+    hipLaunchKernelGGL(dh_mi_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)D.tg, nt, (const int32_t *)A.pc_key,
+                       (const double *)A.pc_stat, (const double *)A.pc_p, D.ot, D.ou, D.os, D.op, D.tot, (double *)(D.tot + 5));
     FW_HIP(c, hipGetLastError());
     std::vector<MiQueue> hq((size_t)nrounds);
     unsigned long long htot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FW_HIP(c, hipMemcpyAsync(hq.data(), d_mq, sizeof(MiQueue) * (size_t)nrounds, hipMemcpyDeviceToHost, st));
-    FW_HIP(c, hipMemcpyAsync(htot, d_tot, 64, hipMemcpyDeviceToHost, st));
+    FW_HIP(c, hipMemcpyAsync(hq.data(), D.mq, sizeof(MiQueue) * (size_t)nrounds, hipMemcpyDeviceToHost, st));
+    FW_HIP(c, hipMemcpyAsync(htot, D.tot, 64, hipMemcpyDeviceToHost, st));
     FW_HIP(c, hipStreamSynchronize(st));
-    const double th2 = wall();
-    for (int r = 0; r < nrounds; ++r) {
-        if (hq[r].pad[0])
-            return fw_fail(c, FW_ERR_DEVICE, "discrete HITON kernel, round %d: watchdog %u (boards %u, targets done %u)", r, hq[r].pad[0], hq[r].n_boards, hq[r].targets_done);
-        if (trace_host) dh_mi_trace(hq[r], grids[r]);
-    }
+    const double th2 = dh_wall();
+    for (int r = 0; r < nrounds; ++r)
+        if (int rc = dh_mi_check(c, hq[r], grids[r], r, std::min(nt, r * R + R) - r * R, trace_host)) return rc;
     float ms = 0.0f;
-    FW_HIP(c, hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    FW_HIP(c, hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
     if (htot[4]) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %llu targets did not finish", htot[4]);
     const size_t nres = (size_t)htot[0], at0 = all_t.size();
     if (nres > nnz) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %zu result entries for %zu level-0 entries", nres, nnz);
@@ -3391,10 +3558,10 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     all_s.resize(at0 + nres);
     all_p.resize(at0 + nres);
     if (nres) {
-        FW_HIP(c, hipMemcpyAsync(all_t.data() + at0, d_ot, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all_u.data() + at0, d_ou, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all_s.data() + at0, d_os, 8 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all_p.data() + at0, d_op, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all_t.data() + at0, D.ot, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all_u.data() + at0, D.ou, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all_s.data() + at0, D.os, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all_p.data() + at0, D.op, 8 * nres, hipMemcpyDeviceToHost, st));
         FW_HIP(c, hipStreamSynchronize(st));
     }
     c->cnt.cond_tests_ref += (int64_t)htot[1];
@@ -3410,6 +3577,6 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     c->cnt.kernel_launches += 2 * nrounds + 1;
     if (trace_host)
         fprintf(stderr, "[fw] device schedule: %d targets in %d rounds, set-up %.2f ms, launches + download %.2f ms (kernels %.2f ms), results %.2f ms\n", nt, nrounds,
-                1e3 * (th1 - th0), 1e3 * (th2 - th1), (double)ms, 1e3 * (wall() - th2));
+                1e3 * (th1 - th0), 1e3 * (th2 - th1), (double)ms, 1e3 * (dh_wall() - th2));
     return FW_OK;
 }

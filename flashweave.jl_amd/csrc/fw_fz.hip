@@ -895,8 +895,7 @@ extern "C" void fwi_fz_fastdbg_print()
 static int fz_ensure_thresholds(fw_ctx *ctx, hipStream_t stream)
 {
     if (!ctx->d_thr) {
-        const char *dbg = fw_knob("FW_FZ_DBG");
-        const int flags = dbg ? atoi(dbg) : 0;
+        const int flags = fw_knob_int(knob::FW_FZ_DBG, 0);
         FW_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(fz_dbg_flags), &flags, sizeof(int)));
         FW_HIP(ctx, hipMalloc((void **)&ctx->d_thr, 12 * sizeof(double)));
         hipLaunchKernelGGL(fz_thresholds_kernel, dim3(1), dim3(64), 0, stream, ctx->P.alpha, fz_zscale(ctx), ctx->d_thr);
@@ -921,7 +920,7 @@ int fwi_fz_segments_dev(fw_ctx *ctx, unsigned grid, const FwSeg *d_segs, const i
     const unsigned grid_big = grid < 512u ? grid : 512u;  // accepted sets beyond FZ_TAB_A are rare: few striding workgroups
     if (ctx->P.max_k > 3) {
         // level-2 table variant for |accepted| <= FZ_HK_A, generic variant for the longer lists (both stride the list)
-        const bool no_hk = fw_knob("FW_NO_HK") != nullptr;  // profiling / test knob (read per call)
+        const bool no_hk = fw_no_hk();  // profiling / test knob (read per call)
         if (!no_hk)
             hipLaunchKernelGGL((fz_subsets_seg_kernel<true, false, true>), dim3(grid), dim3(256), 0, stream, ctx->d_cor, ctx->P.p, d_segs,
                                d_acc, d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests, ctx->d_thr,
@@ -1533,7 +1532,7 @@ int fwi_fznz_submatrices(fw_ctx *ctx, int64_t njobs, const FwNzJob *recs_host, s
                          hipStream_t stream, bool f64)
 {
     int rc;
-    static const bool nz_trace = fw_knob("FW_NZ_TRACE") != nullptr;  // profiling: shape of every sub-matrix launch
+    static const bool nz_trace = fw_knob_set(knob::FW_NZ_TRACE);  // profiling: shape of every sub-matrix launch
     if (nz_trace) {
         long long mmax = 0, pairs = 0, uni = 0;
         for (int64_t j = 0; j < njobs; ++j) {

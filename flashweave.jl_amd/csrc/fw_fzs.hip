@@ -800,7 +800,7 @@ int fwi_fzs_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32
     if (int rc = fzs_ensure_stat(ctx, pb.launch_stream)) return rc;
     // job-local correlation matrices (fzs_gram_kernel) unless FW_FZS_GRAM=0 (profiling / parity knob: every test streams its columns)
     // or the launch's matrices would not fit a sensible arena
-    const bool gram_env = !(fw_knob("FW_FZS_GRAM") && atoi(fw_knob("FW_FZS_GRAM")) == 0);  // (read per launch: the tests switch it)
+    const bool gram_env = fw_knob_on(knob::FW_FZS_GRAM);  // (read per launch: the tests switch it)
     const bool gram = gram_env && recs_host && njobs > 0 && arena_doubles * sizeof(double) <= ((size_t)8 << 30);
     int lds_m = 0;
     if (gram) {

@@ -308,10 +308,9 @@ static bool mi_schedule_on_device(const fw_ctx *c, const fw_learn_opts &opt, boo
 {
     if (!(c->P.kind == FW_MI || c->P.kind == FW_MI_NZ) || c->mi_generic || has_exchange || opt.world_size > 1 || c->P.max_k > FW_MAX_K_FAST) return false;
     if (!c->d_cand || !c->d_nb_idx || !c->d_nb_off) return false;
-    const char *hh = fw_knob("FW_HOST_HITON"), *mr = fw_knob("FW_MI_ROUNDS"), *sc = fw_knob("FW_MI_SCHED"), *mt = fw_knob("FW_DEV_MIN_TARGETS");
-    if ((hh && atoi(hh) == 1) || (mr && atoi(mr) != 0) || (sc && atoi(sc) == 0)) return false;
+    if (fw_host_hiton() || fw_mi_rounds() || !fw_knob_on(knob::FW_MI_SCHED)) return false;  // (read per call: the tests switch them)
     const int R = (opt.round_size <= 0 || opt.round_size > nt) ? nt : opt.round_size;
-    const int min_targets = mt ? atoi(mt) : 256;
+    const int min_targets = fw_knob_int(knob::FW_DEV_MIN_TARGETS, 256);
     // (R = 1 is the reference's single_il master, whose first round holds TWO targets -- interleaved.jl:62,76-86: the per-round loop
     // below knows that rule, the device schedule cuts rounds of exactly R; r05 fuzz, 3 of 4 500 networks with the threshold forced to 1)
     return R >= min_targets && R >= 2;
@@ -459,17 +458,15 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
             // keeps the host pool below for every kind (it is also what rounds of fewer than 64 targets use: the
             // reference's single_il schedule posts one target per round and would pay the device set-up each time).
             // Discrete kinds run as one persistent launch (dh_mi_target_kernel): worth it from a few hundred targets on.
-            const char *hh = fw_knob("FW_HOST_HITON");
-            const bool host_only = hh && atoi(hh) == 1;
+            const bool host_only = fw_host_hiton();
             const bool no_power = c->P.kind == FW_FZ && c->P.n < c->n_obs_min_eff;  // no device work at all
-            const char *mt = fw_knob("FW_DEV_MIN_TARGETS");  // test knob
-            const size_t min_targets = mt ? (size_t)atol(mt) : ((c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) ? 64 : 256);  // cfg2 (1000 targets): 19 ms on the device, 28 ms through the host pool
+            const size_t min_targets = (size_t)fw_knob_u64(knob::FW_DEV_MIN_TARGETS, (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) ? 64 : 256);  // (test knob)  // cfg2 (1000 targets): 19 ms on the device, 28 ms through the host pool
             const bool stream = c->P.kind == FW_FZ && !c->P.recursive_pcor;  // streamed-column tests: host pool over fw_fzs.hip
             // (discrete data with more than three levels -- the generic form of fw_mi_core.h -- runs through the host job pool as well)
             // fz_nz (r05): device rounds too when its tests run on job-local Float32 matrices (recursive_pcor) and the longest possible
             // list fits the sub-matrix kernel's LDS; FW_NZ_DEV=0 keeps the host pool (A/B, tests)
             bool nz_dev = false;
-            if (c->P.kind == FW_FZ_NZ && c->P.recursive_pcor && !(fw_knob("FW_NZ_DEV") && atoi(fw_knob("FW_NZ_DEV")) == 0)) {
+            if (c->P.kind == FW_FZ_NZ && c->P.recursive_pcor && fw_knob_on(knob::FW_NZ_DEV)) {
                 int64_t dmax = 0;
                 for (int i = r0; i < r1; ++i) dmax = std::max<int64_t>(dmax, c->nb_off[order[i] + 1] - c->nb_off[order[i]]);
                 // (feed-forward: a whitelisted member of the elimination pool is pushed a second time, hiton.jl:24-26 -- a list can reach
@@ -537,19 +534,19 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                     std::vector<std::vector<FwDhResult>> pres;
                     std::vector<FwDhFlat> pflat;
                     const double tdev0 = now_s();
-                    if (fw_knob("FW_TRACE_HOST")) fprintf(stderr, "[fw] round set-up on the host: %.2f ms\n", 1e3 * (tdev0 - t0));
+                    if (fw_trace_host()) fprintf(stderr, "[fw] round set-up on the host: %.2f ms\n", 1e3 * (tdev0 - t0));
                     // FW_DH_CHAINS = K (default 2, FlashWeave-S): the round's targets are dealt to K independent chains of device
                     // rounds that run concurrently (own host thread, stream and arena each): while one chain is between
                     // two launches (step / plan / fill, the thinning tail of its segment kernel) the other keeps the CUs
                     // busy.  cfg3, ms per pass with 1 / 2 / 3 / 4 chains: 261.8 / 229.4 / 224.2 / 274.3 on one GPU,
                     // 70.5 / 62.4 / 63.7 for one rank of eight; the per-launch duration of the segment kernel grows with
                     // the overlap (224 -> 167 us for launches half the size), which is what HIP events and rocprofv3 see
-                    const int dh_chains = [] { const char *e = fw_knob("FW_DH_CHAINS"); return std::min(std::max(e ? atoi(e) : 2, 1), FW_DH_MAX_CHAINS); }();  /* read per round: bench.py times a one-chain pass for the per-kernel figures */  // r02: cfg3 227 / 218 / 268 ms with 2 / 3 / 4 in a bare process, but 226 / 298 under torch.distributed.run and 325 with GPU_MAX_HW_QUEUES=8: the third stream's hardware queue is not ours to choose -> 2
-                    static const size_t dh_chain_min = [] { const char *e = fw_knob("FW_DH_CHAIN_MIN"); return e && atol(e) > 0 ? (size_t)atol(e) : (size_t)48; }();  // r03: 256 -> 48 (one rank of eight holds 98 targets in cfg3's last round: 75 -> 69 ms with two chains)
-                    static const int dh_chains_disc = [] { const char *e = fw_knob("FW_DH_CHAINS_DISC"); return std::min(std::max(e ? atoi(e) : 2, 1), FW_DH_MAX_CHAINS); }();  // cfg4: 248.7 / 232.9 / 227.2 / 253.1 ms with 1 / 2 / 3 / 4
+                    const int dh_chains = std::min(std::max(fw_knob_int(knob::FW_DH_CHAINS, 2), 1), FW_DH_MAX_CHAINS);  /* read per round: bench.py times a one-chain pass for the per-kernel figures */  // r02: cfg3 227 / 218 / 268 ms with 2 / 3 / 4 in a bare process, but 226 / 298 under torch.distributed.run and 325 with GPU_MAX_HW_QUEUES=8: the third stream's hardware queue is not ours to choose -> 2
+                    static const size_t dh_chain_min = (size_t)fw_knob_pos(knob::FW_DH_CHAIN_MIN, 48);  // r03: 256 -> 48 (one rank of eight holds 98 targets in cfg3's last round: 75 -> 69 ms with two chains)
+                    static const int dh_chains_disc = std::min(std::max(fw_knob_int(knob::FW_DH_CHAINS_DISC, 2), 1), FW_DH_MAX_CHAINS);  // cfg4: 248.7 / 232.9 / 227.2 / 253.1 ms with 1 / 2 / 3 / 4
                     // discrete kinds run as ONE persistent launch that fills the GPU by itself (dh_mi_target_kernel); concurrent
                     // chains only apply to their level-synchronous form (FW_MI_ROUNDS=1)
-                    static const bool mi_rounds = [] { const char *e = fw_knob("FW_MI_ROUNDS"); return e && atoi(e) != 0; }();
+                    static const bool mi_rounds = fw_mi_rounds();
                     const int want = c->P.kind == FW_FZ ? dh_chains : (mi_rounds ? dh_chains_disc : 1);
                     const int K = din.size() >= (size_t)want * dh_chain_min ? want : 1;
                     int rc = FW_OK;
@@ -565,8 +562,8 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                         // which chain target i goes to (and its index there).  Default: dealt in schedule order.  Few targets (the
                         // latency-bound regime: a rank of a multi-GPU job, the last feed-forward round): the heaviest FW_DH_HEAVY_FRAC of
                         // them get chain 0 to themselves -- its launches stay small, so the rounds of the longest chains are short
-                        static const int heavy_pct = [] { const char *e = fw_knob("FW_DH_HEAVY_PCT"); return e ? atoi(e) : 0; }();
-                        static const size_t heavy_below = [] { const char *e = fw_knob("FW_DH_HEAVY_BELOW"); return e ? (size_t)atol(e) : (size_t)512; }();
+                        static const int heavy_pct = fw_knob_int(knob::FW_DH_HEAVY_PCT, 0);
+                        static const size_t heavy_below = (size_t)fw_knob_u64(knob::FW_DH_HEAVY_BELOW, 512);
                         chain_of.assign(din.size(), 0);
                         chain_idx.assign(din.size(), 0);
                         {
@@ -597,7 +594,7 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
                             if (rcs[q]) rc = rcs[q];
                     }
                     if (rc) return rc;
-                    if (fw_knob("FW_TRACE_HOST")) fprintf(stderr, "[fw] device rounds (all chains): %.2f ms\n", 1e3 * (now_s() - tdev0));
+                    if (fw_trace_host()) fprintf(stderr, "[fw] device rounds (all chains): %.2f ms\n", 1e3 * (now_s() - tdev0));
                     // this round's directed results straight from the chains' flat arrays (target i went to chain i % K)
                     {
                         size_t nres = 0;
@@ -628,8 +625,8 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
             // first acceptance bumps the target's epoch, which cancels / voids everything posted after it.  The sequence
             // of committed (T, candidate, accepted) jobs is therefore exactly the reference's; only the number of
             // latency-bound rounds shrinks.  Every pool round = one window of every in-flight job = ONE kernel launch.
-            static const int FW_SPEC_DEPTH = [] { const char *e = fw_knob("FW_SPEC_DEPTH"); return e ? atoi(e) : 8; }();
-            static const long FW_SPEC_TARGETS = [] { const char *e = fw_knob("FW_SPEC_TARGETS"); return e ? atol(e) : 512l; }();
+            static const int FW_SPEC_DEPTH = fw_knob_int(knob::FW_SPEC_DEPTH, 8);
+            static const long FW_SPEC_TARGETS = (long)fw_knob_u64(knob::FW_SPEC_TARGETS, 512);
 
             long n_unfinished = (long)tg.size();
             FwPool pool;
@@ -804,13 +801,13 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
     }
     if (track) c->have_rej = true;
     c->cnt.t_cond_s += now_s() - t0;
-    if (fw_knob("FW_TRACE_HOST")) fprintf(stderr, "[fw] conditional stage: %.2f ms\n", 1e3 * (now_s() - t0));
+    if (fw_trace_host()) fprintf(stderr, "[fw] conditional stage: %.2f ms\n", 1e3 * (now_s() - t0));
 
     const double tp0 = now_s();
     if (discrete)
         if (int rc = fwi_nb_host_ensure(c)) return rc;
     const double tp1 = now_s();
-    if (fw_knob("FW_TRACE_HOST")) fprintf(stderr, "[fw] neighbour lists to the host: %.2f ms\n", 1e3 * (tp1 - tp0));
+    if (fw_trace_host()) fprintf(stderr, "[fw] neighbour lists to the host: %.2f ms\n", 1e3 * (tp1 - tp0));
     // CSR over targets (stable: arrival order inside a target = PC insertion order)
     const size_t ne = all_t.size();
     c->pc_off.assign((size_t)p + 1, 0);
@@ -947,10 +944,10 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
         c->e_w.insert(c->e_w.end(), bw[(size_t)w].begin(), bw[(size_t)w].end());
     }
     c->have_network = true;
-    if (fw_knob("FW_TRACE_HOST"))
+    if (fw_trace_host())
         fprintf(stderr, "[fw] weights + symmetric graph on the host: %.2f ms (directed CSR %.2f, signs %.2f, transpose %.2f, edges %.2f; %d threads)\n",
                 1e3 * (now_s() - tp1), 1e3 * (tq1 - tp1), 1e3 * (tq2 - tq1), 1e3 * (tq3 - tq2), 1e3 * (now_s() - tq3), n_thr);
-    if (fw_knob("FW_TRACE_HOST")) {
+    if (fw_trace_host()) {
         double d0 = 0, d1 = 0, lmax = 0;
         for (int w = 0; w < n_thr; ++w) {
             d0 = std::max(d0, w_t0[(size_t)w] - tq3);

@@ -227,14 +227,9 @@ struct fw_ctx {
     FwPoolBuf pb[2];
 };
 
-// Tuning / test knobs (environment variables FW_*: DESIGN.md section 5 lists them) are read ONLY when FW_KNOBS=1 is set.  The
-// compiled-in defaults are the product; a stray FW_* variable in a user's environment must not change what the library does.
-// tests/conftest.py, bench.py (for its one-chain / host-seam passes) and the scripts under profiles/tools set FW_KNOBS=1.
-inline const char *fw_knob(const char *name)
-{
-    const char *on = getenv("FW_KNOBS");
-    return (on && on[0] == '1') ? getenv(name) : nullptr;
-}
+// Tuning / test knobs (environment variables FW_*, read ONLY when FW_KNOBS=1 is set): the list, the gate and the readers are in
+// fw_knobs.h; DESIGN.md section 5 carries the same table.
+#include "fw_knobs.h"
 
 int fw_fail(const fw_ctx *ctx, int code, const char *fmt, ...);
 int fw_dev_reserve(fw_ctx *ctx, FwDevBuf &b, size_t bytes);

@@ -1253,7 +1253,7 @@ static MiDev mi_dev(const fw_ctx *ctx)
     P.vals = ctx->mi_generic ? ctx->d_vals : nullptr;
     P.gtab = nullptr;
     P.gtab_words = 0ull;
-    static const int rowk = fw_knob("FW_MI_ROWK") ? atoi(fw_knob("FW_MI_ROWK")) : 2;  // 99: popcount form only (A/B)
+    static const int rowk = fw_knob_int(knob::FW_MI_ROWK, 2);  // 99: popcount form only (A/B)
     P.rowk = rowk;
     return P;
 }
@@ -1639,7 +1639,7 @@ int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
     // matrix-core form of kernel 1: three-valued data whose counts fit 16 bits (FW_L0_MFMA=0: the popcount form, for A/B runs)
     // Default: the nz-adjusted kind (its pairs are decided by the branch-free first pass of the epilogue) from 1 024 variables on.
     // FW_L0_MFMA=2 forces it wherever it is defined (tests: small tables, the plain three-valued kind through the overflow path).
-    const int l0_mfma_knob = fw_knob("FW_L0_MFMA") ? atoi(fw_knob("FW_L0_MFMA")) : 1;
+    const int l0_mfma_knob = fw_knob_int(knob::FW_L0_MFMA, 1);
     const bool l0_mfma = l0_mfma_knob != 0 && ctx->d_hibits && ctx->P.n <= 65535 &&
                          (l0_mfma_knob == 2 || (ctx->P.kind == FW_MI_NZ && p >= 1024));
     const int l0_tile = l0_mfma ? L0M_T : L0_T;
@@ -1676,7 +1676,7 @@ int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
     }
     const MiDev P = mi_dev(ctx);
     // ---- kernel 1: popcounts + exact reliability/df + Float32 screen -> candidate records ----
-    static const int l0_dbg = fw_knob("FW_L0_DBG") ? atoi(fw_knob("FW_L0_DBG")) : 0;  // profiling only (invalid results)
+    static const int l0_dbg = fw_knob_int(knob::FW_L0_DBG, 0);  // profiling only (invalid results)
     unsigned long long cap_c = (unsigned long long)std::min<long long>(npairs, 8ll << 20);
     if (cap_c < ctx->l0_cap_hint) cap_c = ctx->l0_cap_hint;  // a repeated call does not overflow (and re-run the kernel) again
     if (cap_c == 0) cap_c = 1;
@@ -1688,7 +1688,7 @@ int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
         FW_HIP(ctx, hipMemsetAsync(ctx->d_tmp0.ptr, 0, 2 * sizeof(MiL0Counters), ctx->stream));
         d_gthr = (double *)((char *)ctx->d_tmp0.ptr + 2 * sizeof(MiL0Counters));
         unsigned long long *d_prof = (unsigned long long *)(d_gthr + 8);
-        const bool l0_prof = l0_mfma && fw_knob("FW_L0_VERBOSE");
+        const bool l0_prof = l0_mfma && fw_l0_verbose();
         if (l0_prof) FW_HIP(ctx, hipMemsetAsync(d_prof, 0, 8 * sizeof(unsigned long long), ctx->stream));
         FW_HIP(ctx, hipMemcpyAsync(d_gthr, gthr, sizeof(gthr), hipMemcpyHostToDevice, ctx->stream));
         if (nblk == 0)
@@ -1729,7 +1729,7 @@ int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
     }
     const unsigned long long ncand = h1.n_sig;
     *m_reliable = npairs - (long long)h1.n_unreliable;
-    if (fw_knob("FW_L0_VERBOSE")) fprintf(stderr, "[fw] discrete level-0: pairs %lld reliable %lld candidates %llu\n", npairs, (long long)*m_reliable, ncand);
+    if (fw_l0_verbose()) fprintf(stderr, "[fw] discrete level-0: pairs %lld reliable %lld candidates %llu\n", npairs, (long long)*m_reliable, ncand);
     pi.clear();
     pj.clear();
     stat.clear();
@@ -1832,7 +1832,7 @@ int fwi_mi_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y
     int kmax = 0;
     for (int64_t t = 0; t < m; ++t) kmax = std::max<int>(kmax, (int)(zoff[t + 1] - zoff[t]));
     MiDev Pd = mi_dev(ctx);
-    static const bool prof = fw_knob("FW_MI_PROF") != nullptr;
+    static const bool prof = fw_knob_set(knob::FW_MI_PROF);
     if (prof) {
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp0, (size_t)m * 8 * sizeof(unsigned long long)))) return rc;
         FW_HIP(ctx, hipMemsetAsync(ctx->d_tmp0.ptr, 0, (size_t)m * 8 * sizeof(unsigned long long), ctx->stream));
