@@ -2,7 +2,6 @@
 // extern "C" entry points of include/flashweave_amd.h.  Device work lives in fw_fz.hip / fw_mi.hip,
 // the HITON-PC host driver in fw_hiton.cpp.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <numeric>
@@ -56,11 +55,6 @@ int fw_pin_reserve(fw_ctx *ctx, FwPinned &b, size_t bytes)
     if (e != hipSuccess) return fw_fail(ctx, FW_ERR_NOMEM, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
     b.cap = want;
     return FW_OK;
-}
-
-static double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 extern "C" {
@@ -439,7 +433,7 @@ static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_a
                           const fw_dev_exchange *xdev)
 {
     CHECK_CTX(c);
-    const double t0 = now_s();
+    const double t0 = fwi_now_s();
     const int p = c->P.p;
     if (c->P.kind == FW_FZ && !c->P.no_cor_mat) {
         if (!c->have_cor) {
@@ -544,13 +538,13 @@ static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_a
         }
     }
     if (!host_bh) {
-        const double t_bh0 = now_s();
+        const double t_bh0 = fwi_now_s();
         if ((rc = fwi_bh_csr_device(c, dev, m))) return rc;
-        c->cnt.t_level0_host_s += now_s() - t_bh0;  // here: the device epilogue incl. its device-to-host copies
+        c->cnt.t_level0_host_s += fwi_now_s() - t_bh0;  // here: the device epilogue incl. its device-to-host copies
         c->have_level0 = true;
         c->have_network = false;
         c->cnt.level0_tests += (int64_t)p * (p - 1) / 2;
-        c->cnt.t_level0_s += now_s() - t0;
+        c->cnt.t_level0_s += fwi_now_s() - t0;
         if (nnz_out) *nnz_out = c->nb_off[p];
         return FW_OK;
     }
@@ -560,7 +554,7 @@ static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_a
     c->d_cand = nullptr;
     c->nb_host_valid = true;
     const size_t k = pi.size();
-    const double t_host0 = now_s();
+    const double t_host0 = fwi_now_s();
     if (c->P.fdr && k > 0) {
         // statfuns.jl:326-350.  Ascending sort by p: LSD radix sort on the IEEE bit pattern (p >= 0 -> order preserving).
         // Ties need no stable order: the backward cumulative minimum gives every member of a tie group the same value.
@@ -645,11 +639,11 @@ static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_a
         c->nb_stat[b] = stat[t];
         c->nb_p[b] = pval[t];
     }
-    c->cnt.t_level0_host_s += now_s() - t_host0;
+    c->cnt.t_level0_host_s += fwi_now_s() - t_host0;
     c->have_level0 = true;
     c->have_network = false;
     c->cnt.level0_tests += (int64_t)p * (p - 1) / 2;
-    c->cnt.t_level0_s += now_s() - t0;
+    c->cnt.t_level0_s += fwi_now_s() - t0;
     if (nnz_out) *nnz_out = tot;
     return FW_OK;
 }
@@ -887,7 +881,7 @@ int fwi_pool_launch(fw_ctx *c, FwPool &pool)
             pool.gram_top = 0;
         }
     }
-    const double tb0 = now_s();
+    const double tb0 = fwi_now_s();
     FwPoolBuf &pb = c->pb[pool.buf];
     // window of every live job, then a segment length that yields a few thousand workgroups
     uint64_t total = 0, acc_total = 0;
@@ -1030,7 +1024,7 @@ int fwi_pool_launch(fw_ctx *c, FwPool &pool)
         }
         arena_floats = pool.gram_top;
     }
-    const double tb1 = now_s();
+    const double tb1 = fwi_now_s();
     c->cnt.t_host_build_s += tb1 - tb0;
     FW_HIP(c, hipMemcpyAsync(pb.d_in.ptr, pb.h_in.ptr, ns * sizeof(FwSeg), hipMemcpyHostToDevice, pb.launch_stream));
     if (staged)
@@ -1063,7 +1057,7 @@ int fwi_pool_launch(fw_ctx *c, FwPool &pool)
     FW_HIP(c, hipEventRecord(pb.evd, pb.launch_stream));
     pool.ns = ns;
     pool.inflight = true;
-    pool.t_launch = now_s();
+    pool.t_launch = fwi_now_s();
     c->cnt.t_host_launch_s += pool.t_launch - tb1;
     return FW_OK;
 }
@@ -1082,9 +1076,9 @@ int fwi_pool_collect(fw_ctx *c, FwPool &pool, std::vector<FwPoolJob> &finished)
         return FW_OK;
     }
     FwPoolBuf &pb = c->pb[pool.buf];
-    const double tb1 = now_s();
+    const double tb1 = fwi_now_s();
     FW_HIP(c, hipEventSynchronize(pb.evd));
-    const double tb2 = now_s();
+    const double tb2 = fwi_now_s();
     c->cnt.t_host_wait_s += tb2 - tb1;
     float ms = 0.0f;
     FW_HIP(c, hipEventElapsedTime(&ms, pb.ev0, pb.ev1));
@@ -1167,7 +1161,7 @@ int fwi_pool_collect(fw_ctx *c, FwPool &pool, std::vector<FwPoolJob> &finished)
         }
     }
     pool.live.resize(w);
-    c->cnt.t_host_merge_s += now_s() - tb2;
+    c->cnt.t_host_merge_s += fwi_now_s() - tb2;
     return FW_OK;
 }
 

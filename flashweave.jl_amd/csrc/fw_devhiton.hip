@@ -13,7 +13,6 @@
 // interleaving phase: first windows of the next candidates), switched on only while launches are small.
 #include <algorithm>
 #include <cassert>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -2561,7 +2560,6 @@ __global__ __launch_bounds__(256) void dh_mi_pack_kernel(const DhTgt *__restrict
 
 // ---- host side ----
 
-static double dh_wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static std::mutex dh_cnt_mu;  // concurrent chains share the context's counters
 
 // A device arena described ONCE: the layout function runs twice over the same code -- without a base pointer it only adds up the
@@ -3381,7 +3379,7 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
     out.assign((size_t)ntg, FwDhResult{});
     if (ntg == 0) return FW_OK;
     static const bool trace_host = fw_trace_host();  // host-side phase times on stderr
-    const double th0 = dh_wall();
+    const double th0 = fwi_now_s();
     // chain > 0: a second (third, ...) instance running concurrently from its own host thread on its own stream / arena
     if (chain > 0 && !c->dh_stream[chain]) FW_HIP(c, hipStreamCreateWithFlags(&c->dh_stream[chain], hipStreamNonBlocking));
     DhRun R{c, chain, ntg, chain == 0 ? c->pb[0].stream : c->dh_stream[chain], trace_host, dh_policy(c, ntg)};
@@ -3390,7 +3388,7 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
     if ((rc = dh_upload(R))) return rc;
     DhEvents E(R.st, 2 * 2 * DH_BATCH, 2);
     if (!E.ok) return fw_fail(c, FW_ERR_DEVICE, "device HITON: hipEventCreate failed");
-    const double th1 = dh_wall();
+    const double th1 = fwi_now_s();
     rc = R.y.per_target ? dh_run_persistent(R, E) : DhRounds(R, E).run();
     {
         std::lock_guard<std::mutex> lk(dh_cnt_mu);
@@ -3399,9 +3397,9 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
         c->cnt.kernel_launches += R.y.per_target ? R.launches_n : (R.y.nzk ? 7 : 4) * R.launches_n;
     }
     if (rc) return rc;
-    const double th2 = dh_wall();
+    const double th2 = fwi_now_s();
     if ((rc = dh_download(R, out, flat))) return rc;
-    if (trace_host) dh_trace_run(R, th1 - th0, th2 - th1, dh_wall() - th2);
+    if (trace_host) dh_trace_run(R, th1 - th0, th2 - th1, fwi_now_s() - th2);
     std::lock_guard<std::mutex> lk(dh_cnt_mu);
     for (const DhTgt &x : R.tg) {
         c->cnt.cond_tests_ref += (int64_t)x.c_ref;
@@ -3467,13 +3465,12 @@ static DhSchedBufs dh_sched_layout(DhArena &a, const DhSchedSizes &z)
 // later round reads it), and the launches of all rounds are enqueued back to back; the host reads the results once.  Semantics per
 // round are those of fwi_devhiton_run (same kernel, same per-round order and team size).  sched[0 .. nt): the targets in schedule order
 // (learning.jl:97-98); rounds of R targets.  Appends (target, neighbour, statistic, p): a target's entries together, in PC insertion order.
-int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, bool feed_forward, std::vector<int32_t> &all_t,
-                             std::vector<int32_t> &all_u, std::vector<double> &all_s, std::vector<double> &all_p)
+int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, bool feed_forward, FwDirected &all)
 {
     if (nt == 0) return FW_OK;
     if (!c->d_cand || !c->d_nb_idx) return fw_fail(c, FW_ERR_STATE, "device schedule: the level-0 lists are not on the device");
     static const bool trace_host = fw_trace_host();
-    const double th0 = dh_wall();
+    const double th0 = fwi_now_s();
     hipStream_t st = c->pb[0].stream;
     const int p = c->P.p;
     const size_t nnz = (size_t)c->nb_off[p];
@@ -3523,7 +3520,7 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     const DhParams P = dh_make_params(c, R, 0, 0);
     DhEvents E(st, 2, 0);
     if (!E.ok) return fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventCreate failed");
-    const double th1 = dh_wall();
+    const double th1 = fwi_now_s();
     FW_HIP(c, hipEventRecord(E.ev[0], st));
     std::vector<unsigned> grids((size_t)nrounds, 0u);
     for (int r = 0; r < nrounds; ++r) {
@@ -3545,23 +3542,20 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     FW_HIP(c, hipMemcpyAsync(hq.data(), D.mq, sizeof(MiQueue) * (size_t)nrounds, hipMemcpyDeviceToHost, st));
     FW_HIP(c, hipMemcpyAsync(htot, D.tot, 64, hipMemcpyDeviceToHost, st));
     FW_HIP(c, hipStreamSynchronize(st));
-    const double th2 = dh_wall();
+    const double th2 = fwi_now_s();
     for (int r = 0; r < nrounds; ++r)
         if (int rc = dh_mi_check(c, hq[r], grids[r], r, std::min(nt, r * R + R) - r * R, trace_host)) return rc;
     float ms = 0.0f;
     FW_HIP(c, hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
     if (htot[4]) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %llu targets did not finish", htot[4]);
-    const size_t nres = (size_t)htot[0], at0 = all_t.size();
+    const size_t nres = (size_t)htot[0], at0 = all.size();
     if (nres > nnz) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %zu result entries for %zu level-0 entries", nres, nnz);
-    all_t.resize(at0 + nres);
-    all_u.resize(at0 + nres);
-    all_s.resize(at0 + nres);
-    all_p.resize(at0 + nres);
+    all.resize(at0 + nres);
     if (nres) {
-        FW_HIP(c, hipMemcpyAsync(all_t.data() + at0, D.ot, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all_u.data() + at0, D.ou, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all_s.data() + at0, D.os, 8 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all_p.data() + at0, D.op, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.t.data() + at0, D.ot, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.u.data() + at0, D.ou, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.s.data() + at0, D.os, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.p.data() + at0, D.op, 8 * nres, hipMemcpyDeviceToHost, st));
         FW_HIP(c, hipStreamSynchronize(st));
     }
     c->cnt.cond_tests_ref += (int64_t)htot[1];
@@ -3577,6 +3571,6 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     c->cnt.kernel_launches += 2 * nrounds + 1;
     if (trace_host)
         fprintf(stderr, "[fw] device schedule: %d targets in %d rounds, set-up %.2f ms, launches + download %.2f ms (kernels %.2f ms), results %.2f ms\n", nt, nrounds,
-                1e3 * (th1 - th0), 1e3 * (th2 - th1), (double)ms, 1e3 * (dh_wall() - th2));
+                1e3 * (th1 - th0), 1e3 * (th2 - th1), (double)ms, 1e3 * (fwi_now_s() - th2));
     return FW_OK;
 }

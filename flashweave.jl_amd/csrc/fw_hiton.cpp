@@ -7,12 +7,9 @@
 // Every target is a small state machine; one step of the loop collects the pending (T, candidate, accepted)
 // job of every active target and runs them as ONE fw_test_subsets batch on the device.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <numeric>
-#include <functional>
 #include <thread>
-#include <unordered_map>
 
 #include "fw_internal.h"
 #include "fw_unrank.h"
@@ -59,21 +56,12 @@ struct Target {
     bool in_wl(int32_t v) const { return wl_n > 0 && std::binary_search(wl, wl + wl_n, v); }
 };
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-}  // namespace
+// the level-0 lists of the context as the host algorithms of fw_graph.h read them (idx / stat / pval: after fwi_nb_host_ensure)
+FwLevel0 level0_view(const fw_ctx *c) { return FwLevel0{c->P.p, c->nb_off.data(), c->nb_idx.data(), c->nb_stat.data(), c->nb_p.data()}; }
 
 // Advance a target until it needs a device test (returns true, job = (T, cands[pos], acc)) or finishes.
-static bool advance(const fw_ctx *c, Target &t)
+bool advance(const FwLevel0 &l0, Target &t)
 {
-    const int64_t o = c->nb_off[t.T];
-    const int deg = (int)(c->nb_off[t.T + 1] - o);
-    auto univar = [&](int32_t v, double &s, double &p) {
-        const int32_t *b = c->nb_idx.data() + o;
-        const int32_t *it = std::lower_bound(b, b + deg, v);
-        s = c->nb_stat[o + (it - b)];
-        p = c->nb_p[o + (it - b)];
-    };
     for (;;) {
         if (t.phase == 2) return false;
         ODict &dict = t.phase == 0 ? t.TPC : t.PC;
@@ -90,7 +78,9 @@ static bool advance(const fw_ctx *c, Target &t)
             if (t.acc.empty()) {  // tests.jl:285 sentinel + hiton.jl:57-59
                 double s, p;
                 if (t.phase == 0) {
-                    univar(cand, s, p);
+                    const int64_t q = l0.find(t.T, cand);
+                    s = l0.stat[q];
+                    p = l0.pval[q];
                 } else {
                     const int i = t.TPC.find(cand);
                     s = t.TPC.stat[i];
@@ -124,13 +114,38 @@ static bool advance(const fw_ctx *c, Target &t)
     }
 }
 
+// ---- rejection log (fw_set_track_rejections): one slot per directed level-0 entry, on the host for the job pool and in device memory
+// for the paths whose state machine lives there; merged and compacted behind the conditional stage ----
+struct RejGuard {
+    fw_ctx *c;
+    ~RejGuard()
+    {
+        c->d_rej_run = nullptr;
+        std::vector<fw_rejection>().swap(c->rej_slots);
+    }
+};
+
+// empties the slots on both sides; *rej_n: number of slots (0: nothing is logged)
+int rej_begin(fw_ctx *c, size_t *rej_n)
+{
+    c->rej.clear();
+    *rej_n = c->track_rej != 0 && c->P.max_k > 0 ? (size_t)c->nb_off[c->P.p] : 0;
+    if (!*rej_n) return FW_OK;
+    fw_rejection none;
+    memset(&none, 0xff, sizeof(none));  // n_zs = -1: no record
+    c->rej_slots.assign(*rej_n, none);
+    if (int rc = fw_dev_reserve(c, c->d_rej, sizeof(fw_rejection) * *rej_n)) return rc;
+    FW_HIP(c, hipMemset(c->d_rej.ptr, 0xff, sizeof(fw_rejection) * *rej_n));
+    FW_HIP(c, hipDeviceSynchronize());  // (the device paths run on non-blocking streams of their own)
+    c->d_rej_run = (fw_rejection *)c->d_rej.ptr;
+    return FW_OK;
+}
+
 // update_sig_result! (hiton.jl:71-76) with track_rejections: the job of (T, cand) against t.acc ended with a test that is not
 // significant -> its record goes to the candidate's slot of T's level-0 list (fw_internal.h: rej_slots)
-static void rej_store(fw_ctx *c, const Target &t, int32_t cand, const FwJobOut &o)
+void rej_store(fw_ctx *c, const FwLevel0 &l0, const Target &t, int32_t cand, const FwJobOut &o)
 {
-    const int64_t b = c->nb_off[t.T];
-    const int32_t *lo = c->nb_idx.data() + b, *hi = c->nb_idx.data() + c->nb_off[t.T + 1];
-    fw_rejection &r = c->rej_slots[(size_t)(b + (std::lower_bound(lo, hi, cand) - lo))];
+    fw_rejection &r = c->rej_slots[(size_t)l0.find(t.T, cand)];
     r = fw_rejection{};
     r.target = t.T;
     r.candidate = cand;
@@ -145,19 +160,474 @@ static void rej_store(fw_ctx *c, const Target &t, int32_t cand, const FwJobOut &
     r.pval = o.pval;
 }
 
-static double maxweight(double w1, double w2)
-{  // misc.jl:201-218
-    if (std::isnan(w1)) return w2;
-    if (std::isnan(w2)) return w1;
-    const double s1 = (w1 > 0) - (w1 < 0), s2 = (w2 > 0) - (w2 < 0);
-    if (s1 * s2 < 0) return w1;  // "arbitrarily choosing one": the lower-index endpoint's direction
-    return std::max(std::fabs(w1), std::fabs(w2)) * s1;
+// device records win their slot (a target ran on one path only: at most one of the two copies is filled)
+int rej_finish(fw_ctx *c, size_t rej_n)
+{
+    if (rej_n) {
+        std::vector<fw_rejection> dev(rej_n);
+        FW_HIP(c, hipMemcpy(dev.data(), c->d_rej.ptr, sizeof(fw_rejection) * rej_n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < rej_n; ++i) {
+            fw_rejection r = dev[i].n_zs >= 0 ? dev[i] : c->rej_slots[i];
+            if (r.n_zs < 0) continue;
+            double total = 0.0;  // tests.jl:313,327-332: every subset of sizes max_k .. 1, not capped by max_tests (integer binomials)
+            for (int s = c->P.max_k; s >= 1; --s) total += (double)fw_binom_any(r.n_acc, s);
+            r.frac = r.num_tests > 0 && total > 0.0 ? (double)r.num_tests / total : 0.0;
+            for (int q = r.n_zs; q < FW_MAX_K; ++q) r.zs[q] = 0;
+            c->rej.push_back(r);
+        }
+    }
+    if (c->track_rej != 0) c->have_rej = true;
+    return FW_OK;
+}
+
+// ---- which path a round takes (DESIGN.md section 4.5 has the table) ----
+enum Path { PATH_DEV_SCHEDULE, PATH_DEV_ROUNDS, PATH_HOST_POOL };
+const char *const path_name[] = {"device schedule", "device rounds", "host pool"};
+struct PathChoice {
+    Path path;
+    bool dev_cands;   // device rounds: the candidate order already built on the device (fw_bh.hip) is used
+    const char *why;  // host pool: the first condition that keeps the round off the device
+};
+
+// round == nullptr asks for the whole run: PATH_DEV_SCHEDULE (fwi_devhiton_mi_schedule: discrete kinds on bit planes, one rank, no
+// exchange callback, level-0 lists and candidate order on the device, rounds the persistent kernel is worth launching for), else the
+// rounds are asked one by one (`why` then says what kept the schedule off): order[r0 .. r1), n_my of them this rank's.
+// Knobs are read per call: the tests and bench.py switch them inside a live process.
+PathChoice choose_path(fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, const int32_t *order, int nt, const int *round, size_t n_my)
+{
+    auto host = [](const char *why) { return PathChoice{PATH_HOST_POOL, false, why}; };
+    const int kind = c->P.kind;
+    const bool discrete = kind == FW_MI || kind == FW_MI_NZ;
+    if (fw_host_hiton()) return host("FW_HOST_HITON=1");
+    if (!discrete && !c->P.recursive_pcor) return host("streamed columns (recursive_pcor = 0): fw_fzs.hip serves the host pool");
+    if (!discrete && c->P.n < c->n_obs_min_eff) return host("no power: fewer observations than n_obs_min, no device work at all");
+    if (c->mi_generic) return host("generic discrete form (a variable with more than three levels, fw_mi_core.h)");
+    if (c->P.max_k > FW_MAX_K_FAST) return host("max_k above FW_MAX_K_FAST: conditioning sets of 6 and 7 variables take the general-form kernels");
+    // (test knob)  cfg2 (1000 targets): 19 ms on the device, 28 ms through the host pool; the reference's single_il schedule posts one
+    // target per round and would pay the device set-up each time.  Discrete kinds run as one persistent launch (dh_mi_target_kernel):
+    // worth it from a few hundred targets on.  (a negative value: every round of the schedule, no round of the per-round paths)
+    const long long min_targets = (long long)fw_knob_u64(knob::FW_DEV_MIN_TARGETS, discrete ? 256 : 64);
+    if (!round) {
+        if (!discrete) return host("device schedule: discrete kinds only");
+        if (has_exchange || opt.world_size > 1) return host("device schedule: exchange callback present");
+        if (!c->d_cand || !c->d_nb_idx || !c->d_nb_off) return host("device schedule: level-0 lists not on the device (FW_HOST_BH)");
+        if (fw_mi_rounds()) return host("device schedule: FW_MI_ROUNDS=1");
+        if (!fw_knob_on(knob::FW_MI_SCHED)) return host("device schedule: FW_MI_SCHED=0");  // (A/B runs, tests/test_gpu_mi.py compares the two)
+        const int R = (opt.round_size <= 0 || opt.round_size > nt) ? nt : opt.round_size;
+        // (R = 1 is the reference's single_il master, whose first round holds TWO targets -- fw_round_end knows that rule, the device
+        // schedule cuts rounds of exactly R; r05 fuzz, 3 of 4 500 networks with the threshold forced to 1)
+        if (R < min_targets || R < 2) return host("device schedule: rounds of fewer targets than FW_DEV_MIN_TARGETS (or single_il)");
+        return PathChoice{PATH_DEV_SCHEDULE, true, ""};
+    }
+    // fz_nz (r05): device rounds when the longest possible list fits the sub-matrix kernel's LDS; FW_NZ_DEV=0 keeps the host pool (A/B, tests)
+    if (kind == FW_FZ_NZ) {
+        if (!fw_knob_on(knob::FW_NZ_DEV)) return host("FW_NZ_DEV=0");
+        int64_t dmax = 0;
+        for (int i = round[0]; i < round[1]; ++i) dmax = std::max<int64_t>(dmax, c->nb_off[order[i] + 1] - c->nb_off[order[i]]);
+        // (feed-forward: a whitelisted member of the elimination pool is pushed a second time, hiton.jl:24-26 -- a list can reach twice
+        // the candidates)
+        if (fwi_fznz_dev_limits(c, (int)(opt.feed_forward ? 2 * dmax : dmax) + 2) != FW_OK) return host("fz_nz list too long for the sub-matrix kernel's LDS");
+    }
+    if ((unsigned long long)n_my < (unsigned long long)min_targets) return host("fewer targets than FW_DEV_MIN_TARGETS");
+    return PathChoice{PATH_DEV_ROUNDS, c->d_cand != nullptr, c->d_cand ? "candidate order from the device" : "candidate order built on the host"};
+}
+
+// What the stages of one fw_learn_network call share.
+struct Learn {
+    fw_ctx *c;
+    fw_learn_opts opt;
+    fw_allgather_fn allgather;
+    void *user;
+    bool discrete;
+    size_t rej_n = 0;
+    double t0 = 0.0;             // start of the conditional stage
+    std::vector<int32_t> order;  // learning.jl:97-98
+    int nt = 0;                  // targets of the schedule (fw_learn_opts.max_targets)
+    FwDirected all;              // directed results of every target; all ranks hold all of them after each round's exchange
+};
+
+// This rank's targets of the round order[r0 .. r1) with their candidate lists (on the host, or nc_dev: the device's) and whitelists.
+int build_targets(Learn &L, const FwRunningGraph &graph, const std::vector<int32_t> &owner, int r0, int r1, bool dev_cands, std::vector<Target> &tg)
+{
+    fw_ctx *c = L.c;
+    if (!dev_cands)
+        if (int rc = fwi_nb_host_ensure(c)) return rc;
+    const FwLevel0 l0 = level0_view(c);
+    for (int i = r0; i < r1; ++i) {
+        if (owner[i - r0] != L.opt.rank) continue;
+        Target t;
+        t.T = L.order[i];
+        t.elim_mode = L.opt.elim_mode;
+        if (L.discrete && c->levels[t.T] < 2) {  // hiton.jl:182-184
+            t.phase = 2;
+            tg.push_back(std::move(t));
+            continue;
+        }
+        // hiton.jl:211-217: candidates with adj p < alpha, stable sort by p
+        const int64_t o = l0.off[t.T];
+        const int deg = (int)l0.deg(t.T);
+        if (dev_cands) {
+            t.nc_dev = deg;  // every stored neighbour has adj p < alpha; the sorted list lives in c->d_cand
+            if (deg == 0) t.phase = 2;
+        } else {
+            std::vector<int32_t> idx;
+            for (int q = 0; q < deg; ++q)
+                if (l0.pval[o + q] < c->P.alpha) idx.push_back(q);
+            std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return l0.pval[o + a] < l0.pval[o + b]; });
+            for (int32_t q : idx) t.cands.push_back(l0.idx[o + q]);
+            if (t.cands.empty()) t.phase = 2;  // hiton.jl:336-338
+        }
+        if (L.opt.feed_forward) t.wl = graph.whitelist(t.T, &t.wl_n);  // the running graph is only modified between rounds
+        tg.push_back(std::move(t));
+    }
+    return FW_OK;
+}
+
+// ---- device leg (fw_devhiton.hip): no host round trip per window ----
+// FW_DH_CHAINS = K (default 2, FlashWeave-S): the round's targets are dealt to K independent chains of device rounds that run
+// concurrently (own host thread, stream and arena each): while one chain is between two launches (step / plan / fill, the thinning tail
+// of its segment kernel) the other keeps the CUs busy.  cfg3, ms per pass with 1 / 2 / 3 / 4 chains: 261.8 / 229.4 / 224.2 / 274.3 on
+// one GPU, 70.5 / 62.4 / 63.7 for one rank of eight; the per-launch duration of the segment kernel grows with the overlap (224 -> 167 us
+// for launches half the size), which is what HIP events and rocprofv3 see
+int chain_count(const fw_ctx *c, size_t n_targets)
+{
+    // read per round: bench.py times a one-chain pass for the per-kernel figures.  r02: cfg3 227 / 218 / 268 ms with 2 / 3 / 4 in a bare
+    // process, but 226 / 298 under torch.distributed.run and 325 with GPU_MAX_HW_QUEUES=8: the third stream's hardware queue is not ours
+    // to choose -> 2
+    const int dh_chains = std::min(std::max(fw_knob_int(knob::FW_DH_CHAINS, 2), 1), FW_DH_MAX_CHAINS);
+    static const size_t dh_chain_min = (size_t)fw_knob_pos(knob::FW_DH_CHAIN_MIN, 48);  // r03: 256 -> 48 (one rank of eight holds 98 targets in cfg3's last round: 75 -> 69 ms with two chains)
+    static const int dh_chains_disc = std::min(std::max(fw_knob_int(knob::FW_DH_CHAINS_DISC, 2), 1), FW_DH_MAX_CHAINS);  // cfg4: 248.7 / 232.9 / 227.2 / 253.1 ms with 1 / 2 / 3 / 4
+    // discrete kinds run as ONE persistent launch that fills the GPU by itself (dh_mi_target_kernel); concurrent chains only apply to
+    // their level-synchronous form (FW_MI_ROUNDS=1)
+    static const bool mi_rounds = fw_mi_rounds();
+    const int want = c->P.kind == FW_FZ ? dh_chains : (mi_rounds ? dh_chains_disc : 1);
+    return n_targets >= (size_t)want * dh_chain_min ? want : 1;
+}
+
+// Which chain target i goes to (and its index there).  Default: dealt in schedule order.  Few targets (the latency-bound regime: a rank
+// of a multi-GPU job, the last feed-forward round): the heaviest FW_DH_HEAVY_PCT of them get chain 0 to themselves -- its launches stay
+// small, so the rounds of the longest chains are short
+void deal_chains(size_t n, int K, std::vector<int> &chain_of, std::vector<size_t> &chain_idx)
+{
+    static const int heavy_pct = fw_knob_int(knob::FW_DH_HEAVY_PCT, 0);
+    static const size_t heavy_below = (size_t)fw_knob_u64(knob::FW_DH_HEAVY_BELOW, 512);
+    chain_of.assign(n, 0);
+    chain_idx.assign(n, 0);
+    std::vector<size_t> cnt((size_t)K, 0);
+    const bool split = K >= 2 && heavy_pct > 0 && n <= heavy_below;
+    const size_t n_heavy = split ? std::max<size_t>(1, n * (size_t)heavy_pct / 100) : 0;
+    for (size_t i = 0; i < n; ++i) {
+        int q;
+        if (split)  // schedule order = ascending degree: the last n_heavy targets are the heaviest
+            q = i >= n - n_heavy ? 0 : 1 + (int)(i % (size_t)(K - 1));
+        else
+            q = (int)(i % (size_t)K);
+        chain_of[i] = q;
+        chain_idx[i] = cnt[(size_t)q]++;
+    }
+}
+
+// chain q runs the targets dealt to it, chains 1.. on threads of their own
+int run_chains(fw_ctx *c, std::vector<FwDhTarget> &din, const std::vector<int> &chain_of, std::vector<std::vector<FwDhResult>> &pres,
+               std::vector<FwDhFlat> &pflat)
+{
+    const int K = (int)pres.size();
+    if (K == 1) return fwi_devhiton_run(c, din, pres[0], pflat[0]);
+    std::vector<std::vector<FwDhTarget>> part((size_t)K);
+    for (size_t i = 0; i < din.size(); ++i) part[(size_t)chain_of[i]].push_back(std::move(din[i]));
+    std::vector<int> rcs((size_t)K, FW_OK);
+    std::vector<std::thread> th;
+    for (int q = 1; q < K; ++q)
+        th.emplace_back([&, q] {
+            (void)hipSetDevice(c->P.device);
+            rcs[q] = fwi_devhiton_run(c, part[q], pres[q], pflat[q], q);
+        });
+    rcs[0] = fwi_devhiton_run(c, part[0], pres[0], pflat[0], 0);
+    for (std::thread &t : th) t.join();
+    int rc = FW_OK;
+    for (int q = 0; q < K; ++q)
+        if (rcs[q]) rc = rcs[q];
+    return rc;
+}
+
+// the round on the device: its directed results go to `out` straight from the chains' flat arrays, every target ends finished
+int run_device_round(Learn &L, std::vector<Target> &tg, bool dev_cands, FwDirected &out)
+{
+    fw_ctx *c = L.c;
+    std::vector<FwDhTarget> din(tg.size());
+    for (size_t i = 0; i < tg.size(); ++i) {
+        din[i].T = tg[i].T;
+        if (tg[i].phase != 2) {
+            din[i].cands = tg[i].cands;
+            din[i].nc_dev = tg[i].nc_dev;
+        } else if (dev_cands) {
+            din[i].nc_dev = 0;
+        }
+        din[i].wl = tg[i].wl;
+        din[i].wl_n = tg[i].wl_n;
+    }
+    const double tdev0 = fwi_now_s();
+    if (fw_trace_host()) fprintf(stderr, "[fw] round set-up on the host: %.2f ms\n", 1e3 * (tdev0 - L.t0));
+    const int K = chain_count(c, din.size());
+    std::vector<int> chain_of;
+    std::vector<size_t> chain_idx;
+    deal_chains(din.size(), K, chain_of, chain_idx);
+    std::vector<std::vector<FwDhResult>> pres((size_t)K);
+    std::vector<FwDhFlat> pflat((size_t)K);
+    if (int rc = run_chains(c, din, chain_of, pres, pflat)) return rc;
+    if (fw_trace_host()) fprintf(stderr, "[fw] device rounds (all chains): %.2f ms\n", 1e3 * (fwi_now_s() - tdev0));
+    size_t nres = 0;
+    for (size_t i = 0; i < tg.size(); ++i) nres += (size_t)pres[(size_t)chain_of[i]][chain_idx[i]].n;
+    out.reserve(nres);
+    for (size_t i = 0; i < tg.size(); ++i) {
+        const FwDhResult &r = pres[(size_t)chain_of[i]][chain_idx[i]];
+        const FwDhFlat &f = pflat[(size_t)chain_of[i]];
+        for (int32_t j = 0; j < r.n; ++j) out.push(tg[i].T, f.key[(size_t)r.off + j], f.stat[(size_t)r.off + j], f.pval[(size_t)r.off + j]);
+        tg[i].phase = 2;
+    }
+    return FW_OK;
+}
+
+// ---- host leg: asynchronous job pool with speculative candidates ----
+// A rejected candidate leaves the accepted set unchanged (hiton.jl:67-70), so during the interleaving phase the next FW_SPEC_DEPTH
+// candidates of a target are posted together against the current accepted set; results are committed strictly in candidate order, and
+// the first acceptance bumps the target's epoch, which cancels / voids everything posted after it.  The sequence of committed
+// (T, candidate, accepted) jobs is therefore exactly the reference's; only the number of latency-bound rounds shrinks.  Every pool
+// round = one window of every in-flight job = ONE kernel launch.
+struct HostPool {
+    std::vector<Target> &tg;
+    FwLevel0 l0;
+    bool log_rej;  // the rejection log keeps the conditioning set of the stopping test
+    FwPool pool;
+    std::vector<int32_t> epoch;  // per target: bumped when its accepted set changes
+    std::vector<int> touched;    // targets with new results (at first: all)
+    std::vector<uint8_t> is_touched;
+    long n_unfinished;
+};
+
+// commit the finished results of target ti in candidate order; false: the target has finished
+bool pool_commit(fw_ctx *c, HostPool &S, int ti)
+{
+    Target &t = S.tg[ti];
+    while (advance(S.l0, t)) {
+        int ri = -1;
+        for (size_t q = 0; q < t.ready.size(); ++q)
+            if ((size_t)t.ready[q].first == t.pos) {
+                ri = (int)q;
+                break;
+            }
+        if (ri < 0) break;
+        const FwJobOut o = t.ready[ri].second;
+        t.ready.erase(t.ready.begin() + ri);
+        c->cnt.cond_tests_ref += o.num_tests;
+        c->cnt.subsets_calls += 1;
+        const int32_t cand = t.cands[t.pos];
+        ++t.pos;
+        const bool exact = t.elim_mode != 0 && t.phase == 1;  // the pool grows either way: nothing posted is void
+        if (o.pval < c->P.alpha && o.suff_power) {  // issig, tests.jl:1-3; hiton.jl:61-63
+            t.acc.push_back(cand);
+            (t.phase == 0 ? t.TPC : t.PC).set(cand, o.stat, o.pval);
+            if (!exact) {
+                ++S.epoch[ti];  // accepted set changed: later speculative jobs / results are void
+                t.ready.clear();
+                t.posted_end = t.pos;
+            }
+        } else {
+            if (S.log_rej) rej_store(c, S.l0, t, cand, o);  // hiton.jl:71-76
+            if (exact) t.acc.push_back(cand);               // hiton.jl:67-70
+        }
+    }
+    return t.phase != 2;
+}
+
+void pool_post_job(fw_ctx *c, HostPool &S, int ti, size_t ci, const std::vector<int32_t> &acc)
+{
+    fwi_pool_add(c, S.pool, S.tg[ti].T, S.tg[ti].cands[ci], acc.data(), (int)acc.size(), ti);
+    S.pool.live.back().aux = (int32_t)ci;
+    S.pool.live.back().epoch = S.epoch[ti];
+}
+
+// post the next jobs of target ti: the current candidate, plus speculative ones while interleaving.  Speculation is only used once few
+// targets are left (the latency-bound tail); with thousands of active targets the launches are full anyway and the extra host
+// bookkeeping would cost more than the saved rounds.
+void pool_post(fw_ctx *c, HostPool &S, int ti)
+{
+    static const int FW_SPEC_DEPTH = fw_knob_int(knob::FW_SPEC_DEPTH, 8);
+    static const long FW_SPEC_TARGETS = (long)fw_knob_u64(knob::FW_SPEC_TARGETS, 512);
+    Target &t = S.tg[ti];
+    if (t.elim_mode != 0 && t.phase == 1) {
+        // exact elimination: every member's job at once, each against its own pool (they are independent)
+        if (t.posted_end < t.pos) {  // (members advance() settled without a test: t.acc is the pool before t.pos)
+            t.posted_end = t.pos;
+            t.post_acc = t.acc;
+        }
+        for (; t.posted_end < t.cands.size(); ++t.posted_end) {
+            const int32_t cand = t.cands[t.posted_end];
+            if (t.in_wl(cand)) {  // hiton.jl:20-30: pushed once more, no test (advance() records it)
+                t.post_acc.push_back(cand);
+                continue;
+            }
+            t.post_acc.erase(std::remove(t.post_acc.begin(), t.post_acc.end(), cand), t.post_acc.end());
+            if (!t.post_acc.empty()) pool_post_job(c, S, ti, t.posted_end, t.post_acc);  // (an empty pool is the sentinel of advance(): no test)
+            t.post_acc.push_back(cand);
+        }
+        return;
+    }
+    if (t.posted_end < t.pos) t.posted_end = t.pos;
+    const size_t depth = S.n_unfinished <= FW_SPEC_TARGETS ? (size_t)FW_SPEC_DEPTH : 1;
+    const size_t limit = t.phase == 0 ? std::min(t.cands.size(), t.pos + depth) : t.pos + 1;
+    for (; t.posted_end < limit; ++t.posted_end) {
+        if (t.posted_end > t.pos && t.in_wl(t.cands[t.posted_end])) break;  // a whitelisted candidate will change the accepted set
+        pool_post_job(c, S, ti, t.posted_end, t.acc);
+    }
+}
+
+// the round through the job pool: every target ends finished, its results in its PC
+int run_host_pool(Learn &L, std::vector<Target> &tg)
+{
+    fw_ctx *c = L.c;
+    HostPool S{tg, level0_view(c), L.rej_n != 0, {}, std::vector<int32_t>(tg.size(), 0), std::vector<int>(tg.size()), std::vector<uint8_t>(tg.size(), 0),
+               (long)tg.size()};
+    S.pool.want_zs = S.log_rej;
+    S.pool.owner_epoch = &S.epoch;
+    std::iota(S.touched.begin(), S.touched.end(), 0);
+    std::vector<FwPoolJob> fin;
+    for (;;) {
+        const double ta0 = fwi_now_s();
+        for (int ti : S.touched) {
+            S.is_touched[ti] = 0;
+            if (pool_commit(c, S, ti))
+                pool_post(c, S, ti);
+            else
+                --S.n_unfinished;
+        }
+        S.touched.clear();
+        // a speculative job (not the head candidate of its target) only ever runs its first window: most rejections happen within the
+        // first few tests, and a voided long job would be pure waste (exact elimination: no job is speculative)
+        for (FwPoolJob &j : S.pool.live) {
+            const Target &t = tg[(size_t)j.tag];
+            j.hold = (size_t)j.aux != t.pos && j.next > 0 && !(t.elim_mode != 0 && t.phase == 1);
+        }
+        c->cnt.t_host_advance_s += fwi_now_s() - ta0;
+        if (S.pool.live.empty()) break;
+        fin.clear();
+        if (int rc = fwi_pool_round(c, S.pool, fin)) return rc;
+        const double ta1 = fwi_now_s();
+        for (FwPoolJob &j : fin) {
+            const int ti = (int)j.tag;
+            c->cnt.cond_tests_evaluated += j.out.evaluated;
+            c->cnt.alg_bytes_subsets += fwi_alg_bytes(c, (int)j.acc.size(), j.out.evaluated);
+            if (j.epoch != S.epoch[ti]) continue;  // posted before an acceptance: void
+            tg[ti].ready.emplace_back(j.aux, j.out);
+            if (!S.is_touched[ti]) {
+                S.is_touched[ti] = 1;
+                S.touched.push_back(ti);
+            }
+        }
+        c->cnt.t_host_advance_s += fwi_now_s() - ta1;
+    }
+    c->cnt.cond_tests_evaluated += S.pool.dropped_evaluated;
+    c->cnt.alg_bytes_subsets += S.pool.dropped_alg_bytes;
+    return FW_OK;
+}
+
+// exchange this round's directed results (mine: the device leg's, plus the PCs of the host leg's targets) and keep the running graph
+int exchange_round(Learn &L, const std::vector<Target> &tg, FwDirected &mine, FwRunningGraph &graph, bool need_graph)
+{
+    for (const Target &t : tg)
+        for (size_t i = 0; i < t.PC.key.size(); ++i) mine.push(t.T, t.PC.key[i], t.PC.stat[i], t.PC.pval[i]);
+    int64_t ntot = (int64_t)mine.size();
+    const int32_t *at = mine.t.data(), *an = mine.u.data();
+    const double *as = mine.s.data(), *ap = mine.p.data();
+    if (L.allgather) {  // also with world_size = 1 (the callback then returns what it was given): one code path
+        int rc = L.allgather(L.user, (int64_t)mine.size(), mine.t.data(), mine.u.data(), mine.s.data(), mine.p.data(), &ntot, &at, &an, &as, &ap);
+        if (rc) return fw_fail(L.c, FW_ERR_ARG, "fw_learn_network: allgather callback failed (%d)", rc);
+    }
+    L.all.append(at, an, as, ap, (size_t)ntot);
+    if (need_graph) graph.add(at, an, ntot);
+    return FW_OK;
+}
+
+// the feed-forward rounds (interleaved.jl:112-183 as level-synchronous rounds): deal, path, targets, one leg, exchange
+int run_rounds(Learn &L)
+{
+    fw_ctx *c = L.c;
+    const FwLevel0 l0 = level0_view(c);  // (offsets only: the lists may still live on the device)
+    FwRunningGraph graph(c->P.p);
+    for (int r0 = 0, r1 = 0; r0 < L.nt; r0 = r1) {
+        r1 = fw_round_end(r0, L.opt.round_size, L.nt);
+        const std::vector<int32_t> owner = fw_deal_round(l0, L.order.data(), r0, r1, L.opt.world_size, c->P.max_k);
+        const size_t n_my = (size_t)std::count(owner.begin(), owner.end(), L.opt.rank);
+        const int round[2] = {r0, r1};
+        const PathChoice path = choose_path(c, L.opt, L.allgather != nullptr, L.order.data(), L.nt, round, n_my);
+        if (fw_trace_host()) fprintf(stderr, "[fw] round of targets %d..%d (%zu here): %s (%s)\n", r0, r1, n_my, path_name[path.path], path.why);
+        std::vector<Target> tg;
+        tg.reserve(n_my);
+        if (int rc = build_targets(L, graph, owner, r0, r1, path.dev_cands, tg)) return rc;
+        FwDirected mine;
+        if (int rc = path.path == PATH_DEV_ROUNDS ? run_device_round(L, tg, path.dev_cands, mine) : run_host_pool(L, tg)) return rc;
+        // (only the whitelists of later rounds read the running graph: nothing to maintain after the last round or without
+        // feed-forward -- cfg4, one round: 380 000 appends and 50 000 sorts for nothing)
+        if (int rc = exchange_round(L, tg, mine, graph, L.opt.feed_forward && r1 < L.nt)) return rc;
+    }
+    return FW_OK;
+}
+
+// learning.jl:171-172 (max_k = 0): the level-0 lists are the network
+int level0_as_directed(fw_ctx *c, FwDirected &all)
+{
+    if (int rc = fwi_nb_host_ensure(c)) return rc;
+    const FwLevel0 l0 = level0_view(c);
+    for (int v = 0; v < l0.p; ++v)
+        for (int64_t q = l0.off[v]; q < l0.off[v + 1]; ++q) all.push(v, l0.idx[q], l0.stat[q], l0.pval[q]);
+    return FW_OK;
+}
+
+// max_k = 0 / device schedule of the whole run / round loop -> L.all
+int conditional_stage(Learn &L)
+{
+    fw_ctx *c = L.c;
+    if (c->P.max_k == 0) return level0_as_directed(c, L.all);
+    const PathChoice whole = choose_path(c, L.opt, L.allgather != nullptr, L.order.data(), L.nt, nullptr, 0);
+    if (whole.path != PATH_DEV_SCHEDULE) {
+        if (fw_trace_host() && L.discrete) fprintf(stderr, "[fw] no %s\n", whole.why);
+        return run_rounds(L);
+    }
+    // the whole schedule stays on the device (whitelists built between the launches, one download at the end) -- same kernel, order
+    // and team sizes per round as the round loop
+    return fwi_devhiton_mi_schedule(c, L.order.data(), L.nt, L.opt.round_size <= 0 ? L.nt : L.opt.round_size, L.opt.feed_forward != 0, L.all);
+}
+
+// make_weights / make_symmetric_graph (fw_graph.h) on the host threads of the context
+int graph_stage(fw_ctx *c, const FwDirected &all, bool discrete)
+{
+    const double tp0 = fwi_now_s();
+    if (discrete)
+        if (int rc = fwi_nb_host_ensure(c)) return rc;
+    const double tp1 = fwi_now_s();
+    if (fw_trace_host()) fprintf(stderr, "[fw] neighbour lists to the host: %.2f ms\n", 1e3 * (tp1 - tp0));
+    const size_t ne = all.size();
+    const int n_thr = ne < 20000 ? 1 : (int)std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency()));
+    if (n_thr > 1 && (!c->host_workers || c->host_workers->blocks() != n_thr)) {
+        fwi_host_workers_free(c);
+        c->host_workers = new FwHostWorkers(n_thr);
+    }
+    FwGraphTimes tm;
+    if (!fw_graph_passes(level0_view(c), all, discrete, n_thr, c->host_workers, c->net, tm))
+        return fw_fail(c, FW_ERR_NOMEM, "weights / symmetric graph: a host block ran out of memory");
+    c->have_network = true;
+    if (fw_trace_host()) {
+        fprintf(stderr, "[fw] weights + symmetric graph on the host: %.2f ms (directed CSR %.2f, signs %.2f, transpose %.2f, edges %.2f; %d threads)\n",
+                1e3 * (fwi_now_s() - tp1), 1e3 * tm.csr, 1e3 * tm.signs, 1e3 * tm.transpose, 1e3 * tm.edges, n_thr);
+        fprintf(stderr, "[fw]   edges pass: latest start %.3f ms after the call, longest block %.3f ms, return %.3f ms, concatenation %.3f ms (ne %zu)\n",
+                1e3 * tm.latest_start, 1e3 * tm.longest_block, 1e3 * tm.edges_return, 1e3 * tm.concatenation, ne);
+    }
+    return FW_OK;
 }
 
 // The per-round exchange of fw_learn_network through a fw_dev_exchange (fw_learn_network_dev): the round's directed entries are
 // packed into 24-byte records here (no numpy on the way), copied into the caller's device send buffer, all-gathered by the caller's
 // collective (RCCL on torch tensors in bench.py) and unpacked from the gathered buffer.  Implements fw_allgather_fn.
-namespace {
 struct DevXRec {
     int32_t t, u;
     double s, p;
@@ -168,8 +638,7 @@ struct DevXAdapter {
     const fw_dev_exchange *x;
     int world;
     std::vector<DevXRec> stage;
-    std::vector<int32_t> t, u;
-    std::vector<double> s, p;
+    FwDirected got;
 };
 int devx_allgather(void *user, int64_t n, const int32_t *tgt, const int32_t *nbr, const double *stat, const double *pval, int64_t *n_total,
                    const int32_t **tgt_all, const int32_t **nbr_all, const double **stat_all, const double **pval_all)
@@ -198,143 +667,46 @@ int devx_allgather(void *user, int64_t n, const int32_t *tgt, const int32_t *nbr
             return 6;
         off += k;
     }
-    A->t.resize((size_t)std::max<int64_t>(total, 1));
-    A->u.resize(A->t.size());
-    A->s.resize(A->t.size());
-    A->p.resize(A->t.size());
+    FwDirected &g = A->got;
+    g.resize((size_t)std::max<int64_t>(total, 1));
     for (int64_t i = 0; i < total; ++i) {
         const DevXRec &q = A->stage[(size_t)i];
-        A->t[(size_t)i] = q.t;
-        A->u[(size_t)i] = q.u;
-        A->s[(size_t)i] = q.s;
-        A->p[(size_t)i] = q.p;
+        g.t[(size_t)i] = q.t, g.u[(size_t)i] = q.u, g.s[(size_t)i] = q.s, g.p[(size_t)i] = q.p;
     }
     *n_total = total;
-    *tgt_all = A->t.data();
-    *nbr_all = A->u.data();
-    *stat_all = A->s.data();
-    *pval_all = A->p.data();
+    *tgt_all = g.t.data();
+    *nbr_all = g.u.data();
+    *stat_all = g.s.data();
+    *pval_all = g.p.data();
     return 0;
 }
+
+// dense rules + mi_nz: HITON-PC hands test_subsets a row view of the data (prepare_nzdata, hiton.jl:41-50,85,193); the kernels apply
+// it as one more AND plane.  Restored on every exit path by the guard.
+struct ViewGuard {
+    fw_ctx *c;
+    int old;
+    ~ViewGuard() { c->mi_view = old; }
+};
+struct ElimGuard {  // the device rounds read the mode from the context (fw_devhiton.hip)
+    fw_ctx *c;
+    ~ElimGuard() { c->elim_mode = 0; }
+};
+
 }  // namespace
 
-// fwi_devhiton_mi_schedule serves: FW_MI / FW_MI_NZ on bit planes, one rank, no exchange callback, level-0 lists and candidate order on
-// the device, rounds the persistent kernel is worth launching for (the reference's single_il rounds of one target stay on the host pool).
-// FW_MI_SCHED=0 keeps the per-round loop (A/B runs, tests/test_gpu_mi.py compares the two).
-// Host threads of the graph passes at the end of fw_learn_network, kept for the life of the context: starting fifteen threads per pass
-// cost more than the passes' work at cfg3 (2.4 of 2.8 ms for 48 040 edges; r05).  run(fn): fn(w, lo[w], hi[w]) for every block w, block 0
-// on the caller.
-#include <condition_variable>
-#include <mutex>
-struct FwHostWorkers {
-    std::vector<std::thread> th;
-    std::mutex mu;
-    std::condition_variable cv_go, cv_done;
-    const std::function<void(int, int, int)> *fn = nullptr;
-    const int *blk = nullptr;
-    unsigned long long gen = 0;
-    int pending = 0;
-    bool quit = false, failed = false;
-    explicit FwHostWorkers(int n)
-    {
-        for (int w = 1; w < n; ++w)
-            th.emplace_back([this, w] {
-                unsigned long long seen = 0;
-                for (;;) {
-                    const std::function<void(int, int, int)> *f;
-                    const int *b;
-                    {
-                        std::unique_lock<std::mutex> lk(mu);
-                        cv_go.wait(lk, [&] { return quit || gen != seen; });
-                        if (quit) return;
-                        seen = gen;
-                        f = fn;
-                        b = blk;
-                    }
-                    bool ok = true;
-                    try {
-                        (*f)(w, b[w], b[w + 1]);
-                    } catch (...) {  // (std::bad_alloc of a block-local vector: an exception that leaves a thread is std::terminate)
-                        ok = false;
-                    }
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        if (!ok) failed = true;
-                        if (--pending == 0) cv_done.notify_one();
-                    }
-                }
-            });
-    }
-    // false: a block threw (out of memory).  The workers hold pointers to the caller's function object and block list, so the call
-    // never leaves -- normally or by an exception of block 0 -- before every worker has finished its block (r05 unwound past them).
-    bool run(const std::function<void(int, int, int)> &f, const int *b)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            fn = &f;
-            blk = b;
-            pending = (int)th.size();
-            failed = false;
-            ++gen;
-        }
-        cv_go.notify_all();
-        bool ok0 = true;
-        try {
-            f(0, b[0], b[1]);
-        } catch (...) {
-            ok0 = false;
-        }
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return pending == 0; });
-        return ok0 && !failed;
-    }
-    ~FwHostWorkers()
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            quit = true;
-        }
-        cv_go.notify_all();
-        for (std::thread &t : th) t.join();
-    }
-};
 void fwi_host_workers_free(fw_ctx *c)
 {
     delete c->host_workers;
     c->host_workers = nullptr;
 }
 
-static bool mi_schedule_on_device(const fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, int nt)
-{
-    if (!(c->P.kind == FW_MI || c->P.kind == FW_MI_NZ) || c->mi_generic || has_exchange || opt.world_size > 1 || c->P.max_k > FW_MAX_K_FAST) return false;
-    if (!c->d_cand || !c->d_nb_idx || !c->d_nb_off) return false;
-    if (fw_host_hiton() || fw_mi_rounds() || !fw_knob_on(knob::FW_MI_SCHED)) return false;  // (read per call: the tests switch them)
-    const int R = (opt.round_size <= 0 || opt.round_size > nt) ? nt : opt.round_size;
-    const int min_targets = fw_knob_int(knob::FW_DEV_MIN_TARGETS, 256);
-    // (R = 1 is the reference's single_il master, whose first round holds TWO targets -- interleaved.jl:62,76-86: the per-round loop
-    // below knows that rule, the device schedule cuts rounds of exactly R; r05 fuzz, 3 of 4 500 networks with the threshold forced to 1)
-    return R >= min_targets && R >= 2;
-}
-
-extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allgather_fn allgather, void *user, int64_t *n_edges_out);
-
-extern "C" int fw_learn_network_dev(fw_ctx *c, const fw_learn_opts *opts_in, const fw_dev_exchange *x, int64_t *n_edges_out)
-{
-    if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
-    const int world = opts_in ? std::max(opts_in->world_size, 1) : 1;
-    if (world > 1 && (!x || !x->prepare || !x->exchange)) return fw_fail(c, FW_ERR_ARG, "fw_learn_network_dev: world_size > 1 needs both exchange callbacks");
-    if (!x) return fw_learn_network(c, opts_in, nullptr, nullptr, n_edges_out);
-    (void)hipSetDevice(c->P.device);
-    DevXAdapter A{c, x, world, {}, {}, {}, {}, {}};
-    return fw_learn_network(c, opts_in, devx_allgather, &A, n_edges_out);
-}
-
-extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allgather_fn allgather, void *user,
-                                int64_t *n_edges_out)
+extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allgather_fn allgather, void *user, int64_t *n_edges_out)
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
     (void)hipSetDevice(c->P.device);
-    fw_learn_opts opt{};
+    Learn L{c, fw_learn_opts{}, allgather, user, c->P.kind == FW_MI || c->P.kind == FW_MI_NZ};
+    fw_learn_opts &opt = L.opt;
     opt.feed_forward = 1;
     opt.round_size = 1;
     opt.world_size = 1;
@@ -343,636 +715,52 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
     if (opt.rank < 0 || opt.rank >= opt.world_size) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: rank %d outside world of %d", opt.rank, opt.world_size);
     if (opt.world_size > 1 && !allgather) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: world_size > 1 needs an allgather callback");
     if (opt.elim_mode < 0 || opt.elim_mode > 2) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: elim_mode %d is not 0, 1 or 2", opt.elim_mode);
-    if (!c->have_level0) {
-        int rc = fw_level0(c, nullptr);
-        if (rc) return rc;
-    }
-    // dense rules + mi_nz: HITON-PC hands test_subsets a row view of the data (prepare_nzdata, hiton.jl:41-50,85,193); the
-    // kernels apply it as one more AND plane.  Restored on every exit path by the guard.
-    struct ViewGuard {
-        fw_ctx *c;
-        int old;
-        ~ViewGuard() { c->mi_view = old; }
-    } view_guard{c, c->mi_view};
+    if (!c->have_level0)
+        if (int rc = fw_level0(c, nullptr)) return rc;
+    ViewGuard view_guard{c, c->mi_view};
     c->mi_view = 1;
-    struct ElimGuard {  // the device rounds read the mode from the context (fw_devhiton.hip)
-        fw_ctx *c;
-        ~ElimGuard() { c->elim_mode = 0; }
-    } elim_guard{c};
+    ElimGuard elim_guard{c};
     c->elim_mode = opt.elim_mode;
-    const int p = c->P.p;
-    // rejection log (fw_set_track_rejections): one slot per directed level-0 entry, on the host for the job pool and in device memory for
-    // the paths whose state machine lives there; merged and compacted behind the conditional stage
-    struct RejGuard {
-        fw_ctx *c;
-        ~RejGuard()
-        {
-            c->d_rej_run = nullptr;
-            std::vector<fw_rejection>().swap(c->rej_slots);
-        }
-    } rej_guard{c};
-    c->rej.clear();
-    const bool track = c->track_rej != 0;
-    const size_t rej_n = track && c->P.max_k > 0 ? (size_t)c->nb_off[p] : 0;
-    if (rej_n) {
-        fw_rejection none;
-        memset(&none, 0xff, sizeof(none));  // n_zs = -1: no record
-        c->rej_slots.assign(rej_n, none);
-        if (int rc = fw_dev_reserve(c, c->d_rej, sizeof(fw_rejection) * rej_n)) return rc;
-        FW_HIP(c, hipMemset(c->d_rej.ptr, 0xff, sizeof(fw_rejection) * rej_n));
-        FW_HIP(c, hipDeviceSynchronize());  // (the device paths run on non-blocking streams of their own)
-        c->d_rej_run = (fw_rejection *)c->d_rej.ptr;
-    }
-    const bool discrete = c->P.kind == FW_MI || c->P.kind == FW_MI_NZ;
-    const double t0 = now_s();
+    RejGuard rej_guard{c};
+    if (int rc = rej_begin(c, &L.rej_n)) return rc;
+    L.t0 = fwi_now_s();
+    L.order = fw_target_order(level0_view(c));
+    L.nt = opt.max_targets > 0 && opt.max_targets < c->P.p ? opt.max_targets : c->P.p;
 
-    // learning.jl:97-98: ascending univariate degree, stable
-    std::vector<int32_t> order(p);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-        return (c->nb_off[a + 1] - c->nb_off[a]) < (c->nb_off[b + 1] - c->nb_off[b]);
-    });
-    int nt = p;
-    if (opt.max_targets > 0 && opt.max_targets < p) nt = opt.max_targets;
+    if (int rc = conditional_stage(L)) return rc;
+    if (int rc = rej_finish(c, L.rej_n)) return rc;
+    c->cnt.t_cond_s += fwi_now_s() - L.t0;
+    if (fw_trace_host()) fprintf(stderr, "[fw] conditional stage: %.2f ms\n", 1e3 * (fwi_now_s() - L.t0));
 
-    // per-target directed results (all ranks hold all of them after each round's exchange)
-    // directed results of every target in arrival order (a target's entries arrive together, in PC insertion order); the
-    // CSR over targets is built once at the end (vectors of vectors cost 120 000 small allocations per cfg4 pass)
-    std::vector<int32_t> all_t, all_u;
-    std::vector<double> all_s, all_p;
-    std::vector<std::vector<int32_t>> adj(p);  // running graph, sorted
-    std::vector<uint8_t> adj_dirty((size_t)p, 0);
-    std::vector<int32_t> dirty;
-
-    if (c->P.max_k == 0) {  // learning.jl:171-172
-        if (int rc = fwi_nb_host_ensure(c)) return rc;
-        for (int v = 0; v < p; ++v) {
-            const int64_t o = c->nb_off[v];
-            const int deg = (int)(c->nb_off[v + 1] - o);
-            for (int q = 0; q < deg; ++q) {
-                all_t.push_back(v);
-                all_u.push_back(c->nb_idx[o + q]);
-                all_s.push_back(c->nb_stat[o + q]);
-                all_p.push_back(c->nb_p[o + q]);
-            }
-        }
-    } else if (mi_schedule_on_device(c, opt, allgather != nullptr, nt)) {
-        // discrete kinds, one GPU, rounds of a few hundred targets or more: the whole schedule stays on the device (whitelists built
-        // between the launches, one download at the end) -- same kernel, order and team sizes per round as the loop below
-        const int R = (opt.round_size <= 0) ? nt : opt.round_size;
-        if (int rc = fwi_devhiton_mi_schedule(c, order.data(), nt, R, opt.feed_forward != 0, all_t, all_u, all_s, all_p)) return rc;
-    } else {
-        const int R = (opt.round_size <= 0) ? nt : opt.round_size;
-        for (int r0 = 0, r1 = 0; r0 < nt; r0 = r1) {
-            // R = 1 is the reference's single_il master: job_q_buff_size = 1, so the first TWO targets of the schedule are
-            // enqueued up front with an empty whitelist (interleaved.jl:62,76-86); from the third target on a job sees
-            // neighbors(graph, T).  The first round therefore holds two targets.
-            r1 = std::min(nt, r0 + ((R == 1 && r0 == 0) ? 2 : R));
-            // this rank's targets of the round.  The targets of a round are independent of each other (whitelists only change
-            // between rounds), so any deal gives the same network; what matters is the balance.  r02 dealt them round-robin in
-            // schedule order, and at cfg3 / 8 ranks the heaviest rank carried 1.86e9 of the round's tests against a mean of
-            // 1.49e9.  Now: longest-processing-time-first on an estimate of a target's work -- the number of conditioning
-            // subsets its candidate list can span, C(deg, <= max_k) ~ deg^max_k (+ a constant for the chain of jobs every
-            // target pays) -- heaviest first, each to the least loaded rank, ties to the lower rank.  Every rank computes the
-            // same deal from the replicated level-0 lists.
-            std::vector<int32_t> owner((size_t)(r1 - r0), 0);
-            if (opt.world_size > 1) {
-                // the schedule is sorted by ascending degree, and the estimate is monotone in the degree: heaviest first = the
-                // round's targets in REVERSE schedule order (no sort; r03's first version sorted with pow() in the comparator:
-                // 15 ms per cfg4 round on every rank)
-                const int kk = std::min(std::max(c->P.max_k, 1), 3);
-                std::vector<double> load((size_t)opt.world_size, 0.0);
-                for (int32_t j = r1 - r0 - 1; j >= 0; --j) {
-                    const double d = (double)(c->nb_off[order[r0 + j] + 1] - c->nb_off[order[r0 + j]]);
-                    const double est = (kk == 1 ? d : kk == 2 ? d * d : d * d * d) + 64.0;
-                    int best = 0;
-                    for (int w = 1; w < opt.world_size; ++w)
-                        if (load[w] < load[best]) best = w;
-                    owner[j] = best;
-                    load[best] += est;
-                }
-            }
-            size_t n_my = 0;
-            for (int i = r0; i < r1; ++i) n_my += (owner[i - r0] == opt.rank);
-            // Device-resident rounds (fw_devhiton.hip; every kind but fz_nz): no host round trip per window.  FW_HOST_HITON=1
-            // keeps the host pool below for every kind (it is also what rounds of fewer than 64 targets use: the
-            // reference's single_il schedule posts one target per round and would pay the device set-up each time).
-            // Discrete kinds run as one persistent launch (dh_mi_target_kernel): worth it from a few hundred targets on.
-            const bool host_only = fw_host_hiton();
-            const bool no_power = c->P.kind == FW_FZ && c->P.n < c->n_obs_min_eff;  // no device work at all
-            const size_t min_targets = (size_t)fw_knob_u64(knob::FW_DEV_MIN_TARGETS, (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) ? 64 : 256);  // (test knob)  // cfg2 (1000 targets): 19 ms on the device, 28 ms through the host pool
-            const bool stream = c->P.kind == FW_FZ && !c->P.recursive_pcor;  // streamed-column tests: host pool over fw_fzs.hip
-            // (discrete data with more than three levels -- the generic form of fw_mi_core.h -- runs through the host job pool as well)
-            // fz_nz (r05): device rounds too when its tests run on job-local Float32 matrices (recursive_pcor) and the longest possible
-            // list fits the sub-matrix kernel's LDS; FW_NZ_DEV=0 keeps the host pool (A/B, tests)
-            bool nz_dev = false;
-            if (c->P.kind == FW_FZ_NZ && c->P.recursive_pcor && fw_knob_on(knob::FW_NZ_DEV)) {
-                int64_t dmax = 0;
-                for (int i = r0; i < r1; ++i) dmax = std::max<int64_t>(dmax, c->nb_off[order[i] + 1] - c->nb_off[order[i]]);
-                // (feed-forward: a whitelisted member of the elimination pool is pushed a second time, hiton.jl:24-26 -- a list can reach
-                // twice the candidates)
-                nz_dev = fwi_fznz_dev_limits(c, (int)(opt.feed_forward ? 2 * dmax : dmax) + 2) == FW_OK && c->P.n >= c->n_obs_min_eff;
-            }
-            // (conditioning sets of 6 and 7 variables: general-form kernels, host job pool)
-            const bool use_dev = !host_only && (c->P.kind != FW_FZ_NZ || nz_dev) && !stream && !no_power && !c->mi_generic && n_my >= min_targets &&
-                                 c->P.max_k <= FW_MAX_K_FAST;
-            const bool dev_cands = use_dev && c->d_cand != nullptr;  // candidate order already built on the device (fw_bh.hip)
-            if (!dev_cands)
-                if (int rc = fwi_nb_host_ensure(c)) return rc;
-            std::vector<Target> tg;
-            tg.reserve(n_my);
-            for (int i = r0; i < r1; ++i) {
-                if (owner[i - r0] != opt.rank) continue;
-                Target t;
-                t.T = order[i];
-                t.elim_mode = opt.elim_mode;
-                if (discrete && c->levels[t.T] < 2) {  // hiton.jl:182-184
-                    t.phase = 2;
-                    tg.push_back(std::move(t));
-                    continue;
-                }
-                // hiton.jl:211-217: candidates with adj p < alpha, stable sort by p
-                const int64_t o = c->nb_off[t.T];
-                const int deg = (int)(c->nb_off[t.T + 1] - o);
-                if (dev_cands) {
-                    t.nc_dev = deg;  // every stored neighbour has adj p < alpha; the sorted list lives in c->d_cand
-                    if (deg == 0) t.phase = 2;
-                } else {
-                    std::vector<int32_t> idx;
-                    for (int q = 0; q < deg; ++q)
-                        if (c->nb_p[o + q] < c->P.alpha) idx.push_back(q);
-                    std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return c->nb_p[o + a] < c->nb_p[o + b]; });
-                    for (int32_t q : idx) t.cands.push_back(c->nb_idx[o + q]);
-                    if (t.cands.empty()) t.phase = 2;  // hiton.jl:336-338
-                }
-                if (opt.feed_forward && !adj[t.T].empty()) {
-                    t.wl = adj[t.T].data();  // adj is only modified between rounds
-                    t.wl_n = (int)adj[t.T].size();
-                }
-                tg.push_back(std::move(t));
-            }
-            bool ran_dev = false;
-            std::vector<int32_t> dev_lt, dev_ln;  // device rounds: the round's directed results (target, neighbour, stat, p)
-            std::vector<double> dev_ls, dev_lp;
-            {
-                if (use_dev) {
-                    std::vector<FwDhTarget> din(tg.size());
-                    for (size_t i = 0; i < tg.size(); ++i) {
-                        din[i].T = tg[i].T;
-                        if (tg[i].phase != 2) {
-                            din[i].cands = tg[i].cands;
-                            din[i].nc_dev = tg[i].nc_dev;
-                        } else if (dev_cands) {
-                            din[i].nc_dev = 0;
-                        }
-                        din[i].wl = tg[i].wl;
-                        din[i].wl_n = tg[i].wl_n;
-                    }
-                    std::vector<FwDhResult> dres;
-                    std::vector<int> chain_of;
-                    std::vector<size_t> chain_idx;
-                    std::vector<std::vector<FwDhResult>> pres;
-                    std::vector<FwDhFlat> pflat;
-                    const double tdev0 = now_s();
-                    if (fw_trace_host()) fprintf(stderr, "[fw] round set-up on the host: %.2f ms\n", 1e3 * (tdev0 - t0));
-                    // FW_DH_CHAINS = K (default 2, FlashWeave-S): the round's targets are dealt to K independent chains of device
-                    // rounds that run concurrently (own host thread, stream and arena each): while one chain is between
-                    // two launches (step / plan / fill, the thinning tail of its segment kernel) the other keeps the CUs
-                    // busy.  cfg3, ms per pass with 1 / 2 / 3 / 4 chains: 261.8 / 229.4 / 224.2 / 274.3 on one GPU,
-                    // 70.5 / 62.4 / 63.7 for one rank of eight; the per-launch duration of the segment kernel grows with
-                    // the overlap (224 -> 167 us for launches half the size), which is what HIP events and rocprofv3 see
-                    const int dh_chains = std::min(std::max(fw_knob_int(knob::FW_DH_CHAINS, 2), 1), FW_DH_MAX_CHAINS);  /* read per round: bench.py times a one-chain pass for the per-kernel figures */  // r02: cfg3 227 / 218 / 268 ms with 2 / 3 / 4 in a bare process, but 226 / 298 under torch.distributed.run and 325 with GPU_MAX_HW_QUEUES=8: the third stream's hardware queue is not ours to choose -> 2
-                    static const size_t dh_chain_min = (size_t)fw_knob_pos(knob::FW_DH_CHAIN_MIN, 48);  // r03: 256 -> 48 (one rank of eight holds 98 targets in cfg3's last round: 75 -> 69 ms with two chains)
-                    static const int dh_chains_disc = std::min(std::max(fw_knob_int(knob::FW_DH_CHAINS_DISC, 2), 1), FW_DH_MAX_CHAINS);  // cfg4: 248.7 / 232.9 / 227.2 / 253.1 ms with 1 / 2 / 3 / 4
-                    // discrete kinds run as ONE persistent launch that fills the GPU by itself (dh_mi_target_kernel); concurrent
-                    // chains only apply to their level-synchronous form (FW_MI_ROUNDS=1)
-                    static const bool mi_rounds = fw_mi_rounds();
-                    const int want = c->P.kind == FW_FZ ? dh_chains : (mi_rounds ? dh_chains_disc : 1);
-                    const int K = din.size() >= (size_t)want * dh_chain_min ? want : 1;
-                    int rc = FW_OK;
-                    pres.resize((size_t)K);
-                    pflat.resize((size_t)K);
-                    if (K == 1) {
-                        chain_of.assign(din.size(), 0);
-                        chain_idx.resize(din.size());
-                        std::iota(chain_idx.begin(), chain_idx.end(), (size_t)0);
-                        rc = fwi_devhiton_run(c, din, pres[0], pflat[0]);
-                    } else {
-                        std::vector<std::vector<FwDhTarget>> part((size_t)K);
-                        // which chain target i goes to (and its index there).  Default: dealt in schedule order.  Few targets (the
-                        // latency-bound regime: a rank of a multi-GPU job, the last feed-forward round): the heaviest FW_DH_HEAVY_FRAC of
-                        // them get chain 0 to themselves -- its launches stay small, so the rounds of the longest chains are short
-                        static const int heavy_pct = fw_knob_int(knob::FW_DH_HEAVY_PCT, 0);
-                        static const size_t heavy_below = (size_t)fw_knob_u64(knob::FW_DH_HEAVY_BELOW, 512);
-                        chain_of.assign(din.size(), 0);
-                        chain_idx.assign(din.size(), 0);
-                        {
-                            std::vector<size_t> cnt((size_t)K, 0);
-                            const bool split = K >= 2 && heavy_pct > 0 && din.size() <= heavy_below;
-                            const size_t n_heavy = split ? std::max<size_t>(1, din.size() * (size_t)heavy_pct / 100) : 0;
-                            for (size_t i = 0; i < din.size(); ++i) {
-                                int q;
-                                if (split)  // schedule order = ascending degree: the last n_heavy targets are the heaviest
-                                    q = i >= din.size() - n_heavy ? 0 : 1 + (int)(i % (size_t)(K - 1));
-                                else
-                                    q = (int)(i % (size_t)K);
-                                chain_of[i] = q;
-                                chain_idx[i] = cnt[(size_t)q]++;
-                            }
-                        }
-                        for (size_t i = 0; i < din.size(); ++i) part[(size_t)chain_of[i]].push_back(std::move(din[i]));
-                        std::vector<int> rcs((size_t)K, FW_OK);
-                        std::vector<std::thread> th;
-                        for (int q = 1; q < K; ++q)
-                            th.emplace_back([&, q] {
-                                (void)hipSetDevice(c->P.device);
-                                rcs[q] = fwi_devhiton_run(c, part[q], pres[q], pflat[q], q);
-                            });
-                        rcs[0] = fwi_devhiton_run(c, part[0], pres[0], pflat[0], 0);
-                        for (std::thread &t : th) t.join();
-                        for (int q = 0; q < K; ++q)
-                            if (rcs[q]) rc = rcs[q];
-                    }
-                    if (rc) return rc;
-                    if (fw_trace_host()) fprintf(stderr, "[fw] device rounds (all chains): %.2f ms\n", 1e3 * (now_s() - tdev0));
-                    // this round's directed results straight from the chains' flat arrays (target i went to chain i % K)
-                    {
-                        size_t nres = 0;
-                        for (size_t i = 0; i < tg.size(); ++i) nres += (size_t)pres[(size_t)chain_of[i]][chain_idx[i]].n;
-                        dev_lt.reserve(nres);
-                        dev_ln.reserve(nres);
-                        dev_ls.reserve(nres);
-                        dev_lp.reserve(nres);
-                    }
-                    for (size_t i = 0; i < tg.size(); ++i) {
-                        const FwDhResult &r = pres[(size_t)chain_of[i]][chain_idx[i]];
-                        const FwDhFlat &f = pflat[(size_t)chain_of[i]];
-                        for (int32_t j = 0; j < r.n; ++j) {
-                            dev_lt.push_back(tg[i].T);
-                            dev_ln.push_back(f.key[(size_t)r.off + j]);
-                            dev_ls.push_back(f.stat[(size_t)r.off + j]);
-                            dev_lp.push_back(f.pval[(size_t)r.off + j]);
-                        }
-                        tg[i].phase = 2;
-                    }
-                    ran_dev = true;
-                }
-            }
-            if (!ran_dev) {
-            // Asynchronous job pool with speculative candidates.  A rejected candidate leaves the accepted set unchanged
-            // (hiton.jl:67-70), so during the interleaving phase the next FW_SPEC_DEPTH candidates of a target are posted
-            // together against the current accepted set; results are committed strictly in candidate order, and the
-            // first acceptance bumps the target's epoch, which cancels / voids everything posted after it.  The sequence
-            // of committed (T, candidate, accepted) jobs is therefore exactly the reference's; only the number of
-            // latency-bound rounds shrinks.  Every pool round = one window of every in-flight job = ONE kernel launch.
-            static const int FW_SPEC_DEPTH = fw_knob_int(knob::FW_SPEC_DEPTH, 8);
-            static const long FW_SPEC_TARGETS = (long)fw_knob_u64(knob::FW_SPEC_TARGETS, 512);
-
-            long n_unfinished = (long)tg.size();
-            FwPool pool;
-            pool.want_zs = rej_n != 0;  // the rejection log keeps the conditioning set of the stopping test
-            std::vector<int32_t> epoch(tg.size(), 0);
-            pool.owner_epoch = &epoch;
-            std::vector<FwPoolJob> fin;
-            std::vector<int> touched(tg.size());
-            std::iota(touched.begin(), touched.end(), 0);
-            std::vector<uint8_t> is_touched(tg.size(), 0);
-            for (;;) {
-                const double ta0 = now_s();
-                for (int ti : touched) {
-                    Target &t = tg[ti];
-                    is_touched[ti] = 0;
-                    // commit finished results in candidate order
-                    while (advance(c, t)) {
-                        int ri = -1;
-                        for (size_t q = 0; q < t.ready.size(); ++q)
-                            if ((size_t)t.ready[q].first == t.pos) {
-                                ri = (int)q;
-                                break;
-                            }
-                        if (ri < 0) break;
-                        const FwJobOut o = t.ready[ri].second;
-                        t.ready.erase(t.ready.begin() + ri);
-                        c->cnt.cond_tests_ref += o.num_tests;
-                        c->cnt.subsets_calls += 1;
-                        const int32_t cand = t.cands[t.pos];
-                        ++t.pos;
-                        const bool exact = t.elim_mode != 0 && t.phase == 1;  // the pool grows either way: nothing posted is void
-                        if (o.pval < c->P.alpha && o.suff_power) {  // issig, tests.jl:1-3; hiton.jl:61-63
-                            t.acc.push_back(cand);
-                            (t.phase == 0 ? t.TPC : t.PC).set(cand, o.stat, o.pval);
-                            if (!exact) {
-                                ++epoch[ti];  // accepted set changed: later speculative jobs / results are void
-                                t.ready.clear();
-                                t.posted_end = t.pos;
-                            }
-                        } else {
-                            if (rej_n) rej_store(c, t, cand, o);  // hiton.jl:71-76
-                            if (exact) t.acc.push_back(cand);     // hiton.jl:67-70
-                        }
-                    }
-                    if (t.phase == 2) {
-                        --n_unfinished;
-                        continue;
-                    }
-                    // post: the current candidate, plus speculative ones while interleaving.  Speculation is only used
-                    // once few targets are left (the latency-bound tail); with thousands of active targets the launches
-                    // are full anyway and the extra host bookkeeping would cost more than the saved rounds.
-                    if (t.elim_mode != 0 && t.phase == 1) {
-                        // exact elimination: every member's job at once, each against its own pool (they are independent)
-                        if (t.posted_end < t.pos) {  // (members advance() settled without a test: t.acc is the pool before t.pos)
-                            t.posted_end = t.pos;
-                            t.post_acc = t.acc;
-                        }
-                        for (; t.posted_end < t.cands.size(); ++t.posted_end) {
-                            const size_t ci = t.posted_end;
-                            const int32_t cand = t.cands[ci];
-                            if (t.in_wl(cand)) {  // hiton.jl:20-30: pushed once more, no test (advance() records it)
-                                t.post_acc.push_back(cand);
-                                continue;
-                            }
-                            t.post_acc.erase(std::remove(t.post_acc.begin(), t.post_acc.end(), cand), t.post_acc.end());
-                            if (!t.post_acc.empty()) {  // (an empty pool is the sentinel of advance(): no test)
-                                fwi_pool_add(c, pool, t.T, cand, t.post_acc.data(), (int)t.post_acc.size(), ti);
-                                pool.live.back().aux = (int32_t)ci;
-                                pool.live.back().epoch = epoch[ti];
-                            }
-                            t.post_acc.push_back(cand);
-                        }
-                        continue;
-                    }
-                    if (t.posted_end < t.pos) t.posted_end = t.pos;
-                    const size_t depth = n_unfinished <= FW_SPEC_TARGETS ? (size_t)FW_SPEC_DEPTH : 1;
-                    const size_t limit = t.phase == 0 ? std::min(t.cands.size(), t.pos + depth) : t.pos + 1;
-                    while (t.posted_end < limit) {
-                        const size_t ci = t.posted_end;
-                        if (ci > t.pos && t.in_wl(t.cands[ci])) break;  // a whitelisted candidate will change the accepted set
-                        fwi_pool_add(c, pool, t.T, t.cands[ci], t.acc.data(), (int)t.acc.size(), ti);
-                        pool.live.back().aux = (int32_t)ci;
-                        pool.live.back().epoch = epoch[ti];
-                        ++t.posted_end;
-                    }
-                }
-                touched.clear();
-                // a speculative job (not the head candidate of its target) only ever runs its first window: most
-                // rejections happen within the first few tests, and a voided long job would be pure waste
-                // (exact elimination: no job is speculative)
-                for (FwPoolJob &j : pool.live) {
-                    const Target &t = tg[(size_t)j.tag];
-                    j.hold = (size_t)j.aux != t.pos && j.next > 0 && !(t.elim_mode != 0 && t.phase == 1);
-                }
-                c->cnt.t_host_advance_s += now_s() - ta0;
-                if (pool.live.empty()) break;
-                fin.clear();
-                int rc = fwi_pool_round(c, pool, fin);
-                if (rc) return rc;
-                const double ta1 = now_s();
-                for (FwPoolJob &j : fin) {
-                    const int ti = (int)j.tag;
-                    c->cnt.cond_tests_evaluated += j.out.evaluated;
-                    c->cnt.alg_bytes_subsets += fwi_alg_bytes(c, (int)j.acc.size(), j.out.evaluated);
-                    if (j.epoch != epoch[ti]) continue;  // posted before an acceptance: void
-                    tg[ti].ready.emplace_back(j.aux, j.out);
-                    if (!is_touched[ti]) {
-                        is_touched[ti] = 1;
-                        touched.push_back(ti);
-                    }
-                }
-                c->cnt.t_host_advance_s += now_s() - ta1;
-            }
-            c->cnt.cond_tests_evaluated += pool.dropped_evaluated;
-            c->cnt.alg_bytes_subsets += pool.dropped_alg_bytes;
-            }  // host pool
-            // exchange this round's directed results (target, neighbour, stat, p)
-            std::vector<int32_t> lt = std::move(dev_lt), ln = std::move(dev_ln);
-            std::vector<double> ls = std::move(dev_ls), lp = std::move(dev_lp);
-            for (Target &t : tg)
-                for (size_t i = 0; i < t.PC.key.size(); ++i) {
-                    lt.push_back(t.T);
-                    ln.push_back(t.PC.key[i]);
-                    ls.push_back(t.PC.stat[i]);
-                    lp.push_back(t.PC.pval[i]);
-                }
-            int64_t ntot = (int64_t)lt.size();
-            const int32_t *at = lt.data(), *an = ln.data();
-            const double *as = ls.data(), *ap = lp.data();
-            if (allgather) {  // also with world_size = 1 (the callback then returns what it was given): one code path
-                int rc = allgather(user, (int64_t)lt.size(), lt.data(), ln.data(), ls.data(), lp.data(), &ntot, &at, &an, &as, &ap);
-                if (rc) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: allgather callback failed (%d)", rc);
-            }
-            all_t.insert(all_t.end(), at, at + ntot);
-            all_u.insert(all_u.end(), an, an + ntot);
-            all_s.insert(all_s.end(), as, as + ntot);
-            all_p.insert(all_p.end(), ap, ap + ntot);
-            // interleaved.jl:136-140 add_edge! (idempotent): both directions appended, the touched lists sorted and
-            // de-duplicated once per round (sorted inserts one entry at a time were 15 ms of a 170 ms cfg4 pass)
-            // (only the whitelists of later rounds read the running graph: nothing to maintain after the last round or
-            // without feed-forward -- cfg4, one round: 380 000 appends and 50 000 sorts for nothing)
-            const bool need_adj = opt.feed_forward && r1 < nt;
-            for (int64_t i = 0; need_adj && i < ntot; ++i) {
-                const int32_t T = at[i], u = an[i];
-                adj[T].push_back(u);
-                adj[u].push_back(T);
-                if (!adj_dirty[T]) adj_dirty[T] = 1, dirty.push_back(T);
-                if (!adj_dirty[u]) adj_dirty[u] = 1, dirty.push_back(u);
-            }
-            for (int32_t v : dirty) {
-                std::vector<int32_t> &l = adj[v];
-                std::sort(l.begin(), l.end());
-                l.erase(std::unique(l.begin(), l.end()), l.end());
-                adj_dirty[v] = 0;
-            }
-            dirty.clear();
-        }
-    }
-    if (rej_n) {
-        // device records win their slot (a target ran on one path only: at most one of the two copies is filled)
-        std::vector<fw_rejection> dev(rej_n);
-        FW_HIP(c, hipMemcpy(dev.data(), c->d_rej.ptr, sizeof(fw_rejection) * rej_n, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < rej_n; ++i) {
-            fw_rejection r = dev[i].n_zs >= 0 ? dev[i] : c->rej_slots[i];
-            if (r.n_zs < 0) continue;
-            double total = 0.0;  // tests.jl:313,327-332: every subset of sizes max_k .. 1, not capped by max_tests (integer binomials)
-            for (int s = c->P.max_k; s >= 1; --s) total += (double)fw_binom_any(r.n_acc, s);
-            r.frac = r.num_tests > 0 && total > 0.0 ? (double)r.num_tests / total : 0.0;
-            for (int q = r.n_zs; q < FW_MAX_K; ++q) r.zs[q] = 0;
-            c->rej.push_back(r);
-        }
-    }
-    if (track) c->have_rej = true;
-    c->cnt.t_cond_s += now_s() - t0;
-    if (fw_trace_host()) fprintf(stderr, "[fw] conditional stage: %.2f ms\n", 1e3 * (now_s() - t0));
-
-    const double tp0 = now_s();
-    if (discrete)
-        if (int rc = fwi_nb_host_ensure(c)) return rc;
-    const double tp1 = now_s();
-    if (fw_trace_host()) fprintf(stderr, "[fw] neighbour lists to the host: %.2f ms\n", 1e3 * (tp1 - tp0));
-    // CSR over targets (stable: arrival order inside a target = PC insertion order)
-    const size_t ne = all_t.size();
-    c->pc_off.assign((size_t)p + 1, 0);
-    for (size_t i = 0; i < ne; ++i) c->pc_off[(size_t)all_t[i] + 1]++;
-    for (int T = 0; T < p; ++T) c->pc_off[T + 1] += c->pc_off[T];
-    c->pc_idx.resize(ne);
-    c->pc_w.resize(ne);
-    c->pc_p.resize(ne);
-    // The passes below walk the directed CSR with data-dependent look-ups: contiguous blocks of variables on a few host threads (kept
-    // in the context), every block into its own vectors, concatenated in block order -- the same edge list as the sequential loop.
-    const int n_thr = ne < 20000 ? 1 : (int)std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency()));
-    if (n_thr > 1 && (!c->host_workers || (int)c->host_workers->th.size() + 1 != n_thr)) {
-        fwi_host_workers_free(c);
-        c->host_workers = new FwHostWorkers(n_thr);
-    }
-    std::vector<int> blk((size_t)n_thr + 1, p);
-    blk[0] = 0;
-    for (int w = 1; w < n_thr; ++w) {  // block w starts where the entries before it reach w / n_thr of the total
-        const int64_t want = (int64_t)ne * w / n_thr;
-        blk[w] = (int)(std::lower_bound(c->pc_off.begin(), c->pc_off.end(), want) - c->pc_off.begin());
-        if (blk[w] > p) blk[w] = p;
-    }
-    bool blocks_ok = true;  // a block ran out of memory: reported as FW_ERR_NOMEM behind the passes (no exception crosses the C ABI)
-    auto run_blocks = [&](const std::function<void(int, int, int)> &fn) {
-        if (!blocks_ok) return;
-        if (n_thr == 1) {
-            try {
-                fn(0, 0, p);
-            } catch (...) {
-                blocks_ok = false;
-            }
-            return;
-        }
-        blocks_ok = c->host_workers->run(fn, blk.data());
-    };
-    // the scatter into the CSR: every block reads the whole arrival list and places the entries of its own targets, in arrival order
-    // (one thread: 1.2 ms of random writes for cfg4's 157 000 entries)
-    run_blocks([&](int, int lo, int hi) {
-        if (lo >= hi) return;
-        std::vector<int64_t> fill(c->pc_off.begin() + lo, c->pc_off.begin() + hi);
-        for (size_t i = 0; i < ne; ++i) {
-            const int32_t T = all_t[i];
-            if (T < lo || T >= hi) continue;
-            const int64_t d = fill[(size_t)(T - lo)]++;
-            c->pc_idx[d] = all_u[i];
-            c->pc_w[d] = all_s[i];
-            c->pc_p[d] = all_p[i];
-        }
-    });
-    const double tq1 = now_s();
-    // misc.jl:137-159 make_weights ("cond_stat"): discrete tests take the sign of the univariate statistic
-    if (discrete)
-        run_blocks([&](int, int lo, int hi) {
-            for (int T = lo; T < hi; ++T) {
-                const int64_t o = c->nb_off[T];
-                const int deg = (int)(c->nb_off[T + 1] - o);
-                const int32_t *b = c->nb_idx.data() + o;
-                for (int64_t i = c->pc_off[T]; i < c->pc_off[T + 1]; ++i) {
-                    const int32_t *it = std::lower_bound(b, b + deg, c->pc_idx[i]);
-                    const double us = (it != b + deg && *it == c->pc_idx[i]) ? c->nb_stat[o + (it - b)] : NAN;
-                    const double sg = std::isnan(us) ? NAN : (double)((us > 0) - (us < 0));
-                    c->pc_w[i] = sg * std::fabs(c->pc_w[i]);
-                }
-            }
-        });
-    const double tq2 = now_s();
-    // misc.jl:230-272 make_symmetric_graph (OR rule, maxweight merge, NaN edges dropped)
-    c->e_src.clear();
-    c->e_dst.clear();
-    c->e_w.clear();
-    // incoming lists (b -> a for every a) with their weights, ascending in b: the transpose of the CSR by counting sort.  The pass below
-    // then reads two contiguous ranges per variable; looking the reverse direction up in b's own list instead cost two or three
-    // cache lines from another core per entry (cfg4: 3.1-5.0 ms on 16 / 8 threads for 380 000 entries; r05).
-    std::vector<int64_t> in_off((size_t)p + 1, 0);
-    std::vector<int32_t> in_idx(ne);
-    std::vector<double> in_w(ne);
-    {
-        for (size_t i = 0; i < ne; ++i) in_off[(size_t)c->pc_idx[i] + 1]++;
-        for (int T = 0; T < p; ++T) in_off[T + 1] += in_off[T];
-        std::vector<int64_t> fill(in_off.begin(), in_off.end() - 1);
-        for (int T = 0; T < p; ++T)  // sources visited in ascending order -> every incoming list comes out sorted
-            for (int64_t i = c->pc_off[T]; i < c->pc_off[T + 1]; ++i) {
-                const int64_t d = fill[c->pc_idx[i]]++;
-                in_idx[(size_t)d] = T;
-                in_w[(size_t)d] = c->pc_w[i];
-            }
-    }
-    const double tq3 = now_s();
-    std::vector<std::vector<int32_t>> bs((size_t)n_thr), bd((size_t)n_thr);
-    std::vector<std::vector<double>> bw((size_t)n_thr);
-    std::vector<double> w_t0((size_t)n_thr, 0.0), w_t1((size_t)n_thr, 0.0);
-    run_blocks([&](int w, int lo, int hi) {
-        w_t0[(size_t)w] = now_s();
-        std::vector<int32_t> es, ed;  // block-local, handed over at the end: the headers of bs[w], bs[w + 1] share cache lines and every
-        std::vector<double> ew;       // push_back writes one (150 ns per entry on 8 threads; r05)
-        const size_t room = (size_t)(c->pc_off[hi] - c->pc_off[lo]);
-        es.reserve(room);
-        ed.reserve(room);
-        ew.reserve(room);
-        std::vector<int32_t> out_of((size_t)p, -1);  // out_of[b] == a: the direction a -> b exists
-        for (int a = lo; a < hi; ++a) {
-            const int32_t *ib = in_idx.data() + in_off[a], *ie = in_idx.data() + in_off[a + 1];
-            for (int64_t i = c->pc_off[a]; i < c->pc_off[a + 1]; ++i) {  // direction a -> b exists
-                const int32_t b = c->pc_idx[i];
-                out_of[(size_t)b] = a;
-                if (b <= a) continue;
-                const int32_t *it = std::lower_bound(ib, ie, b);
-                const double ww = maxweight(c->pc_w[i], (it != ie && *it == b) ? in_w[(size_t)(in_off[a] + (it - ib))] : NAN);
-                if (std::isnan(ww)) continue;
-                es.push_back(a);
-                ed.push_back(b);
-                ew.push_back(ww);
-            }
-            for (int64_t q = in_off[a]; q < in_off[a + 1]; ++q) {  // only b -> a exists
-                const int32_t b = in_idx[(size_t)q];
-                if (b <= a || out_of[(size_t)b] == a) continue;
-                const double ww = maxweight(in_w[(size_t)q], NAN);
-                if (std::isnan(ww)) continue;
-                es.push_back(a);
-                ed.push_back(b);
-                ew.push_back(ww);
-            }
-        }
-        bs[(size_t)w] = std::move(es);
-        bd[(size_t)w] = std::move(ed);
-        bw[(size_t)w] = std::move(ew);
-        w_t1[(size_t)w] = now_s();
-    });
-    const double tq4 = now_s();
-    if (!blocks_ok) return fw_fail(c, FW_ERR_NOMEM, "weights / symmetric graph: a host block ran out of memory");
-    for (int w = 0; w < n_thr; ++w) {
-        c->e_src.insert(c->e_src.end(), bs[(size_t)w].begin(), bs[(size_t)w].end());
-        c->e_dst.insert(c->e_dst.end(), bd[(size_t)w].begin(), bd[(size_t)w].end());
-        c->e_w.insert(c->e_w.end(), bw[(size_t)w].begin(), bw[(size_t)w].end());
-    }
-    c->have_network = true;
-    if (fw_trace_host())
-        fprintf(stderr, "[fw] weights + symmetric graph on the host: %.2f ms (directed CSR %.2f, signs %.2f, transpose %.2f, edges %.2f; %d threads)\n",
-                1e3 * (now_s() - tp1), 1e3 * (tq1 - tp1), 1e3 * (tq2 - tq1), 1e3 * (tq3 - tq2), 1e3 * (now_s() - tq3), n_thr);
-    if (fw_trace_host()) {
-        double d0 = 0, d1 = 0, lmax = 0;
-        for (int w = 0; w < n_thr; ++w) {
-            d0 = std::max(d0, w_t0[(size_t)w] - tq3);
-            d1 = std::max(d1, w_t1[(size_t)w] - w_t0[(size_t)w]);
-            lmax = std::max(lmax, tq4 - w_t1[(size_t)w]);
-        }
-        fprintf(stderr, "[fw]   edges pass: latest start %.3f ms after the call, longest block %.3f ms, return %.3f ms, concatenation %.3f ms (ne %zu)\n",
-                1e3 * d0, 1e3 * d1, 1e3 * (tq4 - tq3), 1e3 * (now_s() - tq4), ne);
-    }
+    if (int rc = graph_stage(c, L.all, L.discrete)) return rc;
 #ifdef FW_FZ_FASTDBG
     fwi_fz_fastdbg_print();
 #endif
-    if (n_edges_out) *n_edges_out = (int64_t)c->e_src.size();
+    if (n_edges_out) *n_edges_out = (int64_t)c->net.e_src.size();
     return FW_OK;
+}
+
+extern "C" int fw_learn_network_dev(fw_ctx *c, const fw_learn_opts *opts_in, const fw_dev_exchange *x, int64_t *n_edges_out)
+{
+    if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
+    const int world = opts_in ? std::max(opts_in->world_size, 1) : 1;
+    if (world > 1 && (!x || !x->prepare || !x->exchange)) return fw_fail(c, FW_ERR_ARG, "fw_learn_network_dev: world_size > 1 needs both exchange callbacks");
+    if (!x) return fw_learn_network(c, opts_in, nullptr, nullptr, n_edges_out);
+    (void)hipSetDevice(c->P.device);
+    DevXAdapter A{c, x, world, {}, {}};
+    return fw_learn_network(c, opts_in, devx_allgather, &A, n_edges_out);
 }
 
 extern "C" int fw_network_get(const fw_ctx *c, int32_t *src, int32_t *dst, double *weight)
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
     if (!c->have_network) return fw_fail(c, FW_ERR_STATE, "fw_network_get: fw_learn_network has not run");
-    const size_t k = c->e_src.size();
+    const FwNetwork &g = c->net;
+    const size_t k = g.e_src.size();
     if (k) {
-        if (src) memcpy(src, c->e_src.data(), sizeof(int32_t) * k);
-        if (dst) memcpy(dst, c->e_dst.data(), sizeof(int32_t) * k);
-        if (weight) memcpy(weight, c->e_w.data(), sizeof(double) * k);
+        if (src) memcpy(src, g.e_src.data(), sizeof(int32_t) * k);
+        if (dst) memcpy(dst, g.e_dst.data(), sizeof(int32_t) * k);
+        if (weight) memcpy(weight, g.e_w.data(), sizeof(double) * k);
     }
     return FW_OK;
 }
@@ -981,12 +769,13 @@ extern "C" int fw_network_get_directed(const fw_ctx *c, int64_t *off, int32_t *i
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
     if (!c->have_network) return fw_fail(c, FW_ERR_STATE, "fw_network_get_directed: fw_learn_network has not run");
-    if (off) memcpy(off, c->pc_off.data(), sizeof(int64_t) * c->pc_off.size());
-    const size_t k = c->pc_idx.size();
+    const FwNetwork &g = c->net;
+    if (off) memcpy(off, g.pc_off.data(), sizeof(int64_t) * g.pc_off.size());
+    const size_t k = g.pc_idx.size();
     if (k) {
-        if (idx) memcpy(idx, c->pc_idx.data(), sizeof(int32_t) * k);
-        if (weight) memcpy(weight, c->pc_w.data(), sizeof(double) * k);
-        if (pval) memcpy(pval, c->pc_p.data(), sizeof(double) * k);
+        if (idx) memcpy(idx, g.pc_idx.data(), sizeof(int32_t) * k);
+        if (weight) memcpy(weight, g.pc_w.data(), sizeof(double) * k);
+        if (pval) memcpy(pval, g.pc_p.data(), sizeof(double) * k);
     }
     return FW_OK;
 }

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/flashweave_amd.h"
+#include "fw_graph.h"  // host-only: FwDirected, FwNetwork, FwHostWorkers, fwi_now_s
 
 struct FwDevBuf {
     void *ptr = nullptr;
@@ -184,12 +185,8 @@ struct fw_ctx {
 
     // ---- network result ----
     bool have_network = false;
-    struct FwHostWorkers *host_workers = nullptr;  // host threads of the graph passes (fw_hiton.cpp), started at the first network that wants them
-    std::vector<int32_t> e_src, e_dst;
-    std::vector<double> e_w;
-    std::vector<int64_t> pc_off;
-    std::vector<int32_t> pc_idx;
-    std::vector<double> pc_w, pc_p;
+    FwHostWorkers *host_workers = nullptr;  // host threads of the graph passes (fw_graph.h), started at the first network that wants them
+    FwNetwork net;
 
     // ---- rejection log (fw_set_track_rejections) ----
     // One slot per directed level-0 entry: the record of (T, candidate) lives at the candidate's position in T's level-0 list
@@ -357,8 +354,7 @@ struct FwDhFlat {  // (one allocation per run instead of three per target: 150 0
 };
 int fwi_devhiton_run(fw_ctx *ctx, const std::vector<FwDhTarget> &in, std::vector<FwDhResult> &out, FwDhFlat &flat, int chain = 0);
 // the whole feed-forward schedule of the discrete kinds on the device: whitelists built between the launches, one download (r05)
-int fwi_devhiton_mi_schedule(fw_ctx *ctx, const int32_t *sched, int nt, int R, bool feed_forward, std::vector<int32_t> &all_t,
-                             std::vector<int32_t> &all_u, std::vector<double> &all_s, std::vector<double> &all_p);
+int fwi_devhiton_mi_schedule(fw_ctx *ctx, const int32_t *sched, int nt, int R, bool feed_forward, FwDirected &all);
 int fwi_mi_segments_dev(fw_ctx *ctx, unsigned grid, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns,
                         hipStream_t stream);
 int fwi_fz_thresholds(fw_ctx *ctx, hipStream_t stream, double *zscale);  // ensures ctx->d_thr (fz_thresholds_kernel)
