@@ -71,11 +71,22 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     track_rejections (learning.jl:446,469): True also returns, for every candidate a conditional test removed from a target's
     neighbourhood, the conditioning set that did it: result["rejections"] = {target: {candidate: (Zs, (stat, pval, df, suff_power),
     (num_tests, frac))}} with 0-based variable ids (the reference's rejections(net_result)); {} when off.  io.save_rejections writes
-    them in the reference's file format."""
+    them in the reference's file format.
+    prec (learning.jl:42-45, cont_type): 32 or 64 (16 and 128 are not served).  With the plain "fz" test, prec=64 runs the whole
+    continuous pipeline in Float64 on the device: the Pearson matrix, level 0 and pcor_rec with its five-digit rounding (what the
+    reference's golden networks were generated with); it needs recursive_pcor=True and dense_cor=True.  "fz_nz" keeps Float32 values
+    with Float64 arithmetic whatever prec says, and the discrete tests have no element type: parameters["prec"] records what ran."""
     if unsupported:
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
+    if prec not in (32, 64):
+        raise ValueError("learn_network: prec=%r is not supported (32 or 64; the reference's 16 and 128 are not served)" % (prec,))
     import time
     test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
+    eng_prec = 64 if (prec == 64 and test_name == "fz") else 32  # the element type of the device pipeline
+    if eng_prec == 64 and not (recursive_pcor and dense_cor):
+        raise ValueError("learn_network: prec=64 with %s is not supported: the Float64 path conditions on the resident Float64 "
+                         "Pearson matrix (recursive_pcor=True, dense_cor=True)"
+                         % ("recursive_pcor=False" if not recursive_pcor else "dense_cor=False"))
     if test_name != "fz":
         dense_cor = True  # (learning.jl:42: only the plain fz test ever builds a matrix; the engine takes the flag for fz alone)
     elif not dense_cor and recursive_pcor:
@@ -109,7 +120,7 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     if round_size is None:
         round_size = default_round_size(p)
     eng = Engine(test_name, n, p, max_k=max_k, alpha=alpha, hps=hps, n_obs_min=n_obs_min, max_tests=max_tests, FDR=FDR,
-                 device=device, recursive_pcor=recursive_pcor, dense_cor=dense_cor)
+                 device=device, recursive_pcor=recursive_pcor, dense_cor=dense_cor, prec=eng_prec)
     try:
         eng.set_data(mat)
         if test_name == "fz" and dense_cor:
@@ -125,7 +136,7 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
                     parameters=dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha,
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,
                                     recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
-                                    no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections),
+                                    no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections), prec=eng_prec,
                                     schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
                                               else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
                                               else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),

@@ -159,7 +159,7 @@ int fw_ctx_destroy(fw_ctx *c)
     fwi_fz_fastdbg_print();
 #endif
     if (c->cor_external) c->d_cor = nullptr;  // caller-owned (fw_use_cor_buffer)
-    void *ptrs[] = {c->d_data, c->d_xc, c->d_sd, c->d_cor, c->d_thr, c->d_fzs_stat, c->d_nzbits, c->d_hibits, c->d_levels, c->d_maxvals, c->d_firstnz, c->d_xlnx, c->d_gthr, c->d_vals};
+    void *ptrs[] = {c->d_data64, c->d_xc64, c->d_sd64, c->d_cor64, c->d_data, c->d_xc, c->d_sd, c->d_cor, c->d_thr, c->d_fzs_stat, c->d_nzbits, c->d_hibits, c->d_levels, c->d_maxvals, c->d_firstnz, c->d_xlnx, c->d_gthr, c->d_vals};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     free_dev(c->d_jobs);
@@ -218,6 +218,7 @@ int fw_set_data_dense_f32(fw_ctx *c, const float *data)
     CHECK_CTX(c);
     if (c->P.kind != FW_FZ && c->P.kind != FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_f32: context is not FW_FZ / FW_FZ_NZ");
     if (!data) return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_f32: NULL data");
+    if (c->f64) return fw_fail(c, FW_ERR_STATE, "fw_set_data_dense_f32: the context is in Float64 mode (fw_set_data_dense_f64 / fw_set_cor_mat_f64 came first); precisions do not mix");
     if (c->P.kind == FW_FZ_NZ) {
         int rc = fwi_fznz_upload(c, data);
         if (rc) return rc;
@@ -229,6 +230,7 @@ int fw_set_data_dense_f32(fw_ctx *c, const float *data)
     const size_t bytes = sizeof(float) * (size_t)c->P.n * c->P.p;
     if (!c->d_data) FW_HIP(c, hipMalloc(&c->d_data, bytes));
     FW_HIP(c, hipMemcpy(c->d_data, data, bytes, hipMemcpyHostToDevice));
+    c->f32_input = true;
     c->have_data = true;
     c->have_fzs_stat = false;
     c->have_cor = false;
@@ -243,6 +245,7 @@ int fw_set_cor_mat(fw_ctx *c, const float *cor)
     if (c->P.kind != FW_FZ) return fw_fail(c, FW_ERR_ARG, "fw_set_cor_mat: context is not FW_FZ");
     if (c->P.no_cor_mat) return fw_fail(c, FW_ERR_STATE, "fw_set_cor_mat: the context was created with no_cor_mat (dense_cor = false)");
     if (!cor) return fw_fail(c, FW_ERR_ARG, "fw_set_cor_mat: NULL matrix");
+    if (c->f64) return fw_fail(c, FW_ERR_STATE, "fw_set_cor_mat: the context is in Float64 mode (fw_set_cor_mat_f64 takes its matrix); precisions do not mix");
     const size_t cells = (size_t)c->P.p * c->P.p, bytes = sizeof(float) * cells;
     // the device arithmetic relies on |entries| <= 1 (what cor() produces, cov2cor clamps); NaN is allowed and propagates
     for (size_t t = 0; t < cells; ++t)
@@ -251,6 +254,7 @@ int fw_set_cor_mat(fw_ctx *c, const float *cor)
                            (double)cor[t]);
     if (!c->d_cor) FW_HIP(c, hipMalloc(&c->d_cor, bytes));
     FW_HIP(c, hipMemcpy(c->d_cor, cor, bytes, hipMemcpyHostToDevice));
+    c->f32_input = true;
     c->have_cor = true;
     c->have_level0 = false;
     c->have_network = false;
@@ -262,12 +266,69 @@ int fw_compute_cor_mat(fw_ctx *c)
     CHECK_CTX(c);
     if (c->P.kind != FW_FZ) return fw_fail(c, FW_ERR_ARG, "fw_compute_cor_mat: context is not FW_FZ");
     if (c->P.no_cor_mat) return fw_fail(c, FW_ERR_STATE, "fw_compute_cor_mat: the context was created with no_cor_mat (dense_cor = false)");
-    return fwi_fz_compute_cor(c);
+    return c->f64 ? fwi_fz64_compute_cor(c) : fwi_fz_compute_cor(c);
+}
+
+// ---- Float64 mode (learn_network(prec = 64): cont_type = Float64, learning.jl:42-45) ----
+// The first Float64 upload puts an FW_FZ context in Float64 mode; what the mode does not serve is refused here, by name.
+static int enter_f64(fw_ctx *c, const char *fn)
+{
+    if (c->P.kind != FW_FZ) return fw_fail(c, FW_ERR_ARG, "%s: context is not FW_FZ (Float64 inputs are served for the plain Fisher-z test only)", fn);
+    if (c->f64) return FW_OK;
+    if (c->f32_input)
+        return fw_fail(c, FW_ERR_STATE, "%s: the context already holds Float32 input (fw_set_data_dense_f32 / fw_set_cor_mat); precisions do not mix", fn);
+    if (c->cor_external) return fw_fail(c, FW_ERR_LIMIT, "%s: fw_use_cor_buffer (row-block sharding of the matrix) is not served in Float64 mode", fn);
+    if (c->comm) return fw_fail(c, FW_ERR_LIMIT, "%s: fw_comm_init (library-side collectives) is not served in Float64 mode", fn);
+    if (c->P.no_cor_mat) return fw_fail(c, FW_ERR_LIMIT, "%s: no_cor_mat = 1 (dense_cor = false) is not served in Float64 mode", fn);
+    if (!c->P.recursive_pcor) return fw_fail(c, FW_ERR_LIMIT, "%s: recursive_pcor = 0 is not served in Float64 mode", fn);
+    if (c->P.max_k > FW_MAX_K_FAST)
+        return fw_fail(c, FW_ERR_LIMIT, "%s: max_k = %d is not served in Float64 mode (max_k <= %d)", fn, c->P.max_k, FW_MAX_K_FAST);
+    c->f64 = true;
+    return FW_OK;
+}
+
+int fw_set_data_dense_f64(fw_ctx *c, const double *data)
+{
+    CHECK_CTX(c);
+    if (int rc = enter_f64(c, "fw_set_data_dense_f64")) return rc;
+    if (!data) return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_f64: NULL data");
+    if (int rc = fwi_fz64_set_data(c, data)) return rc;
+    c->have_data = true;
+    c->have_cor = false;
+    c->have_level0 = false;
+    c->have_network = false;
+    return FW_OK;
+}
+
+int fw_set_cor_mat_f64(fw_ctx *c, const double *cor)
+{
+    CHECK_CTX(c);
+    if (int rc = enter_f64(c, "fw_set_cor_mat_f64")) return rc;
+    if (!cor) return fw_fail(c, FW_ERR_ARG, "fw_set_cor_mat_f64: NULL matrix");
+    const size_t cells = (size_t)c->P.p * c->P.p;
+    for (size_t t = 0; t < cells; ++t)  // (as fw_set_cor_mat: NaN is allowed and propagates)
+        if (std::fabs(cor[t]) > 1.0)
+            return fw_fail(c, FW_ERR_ARG, "fw_set_cor_mat_f64: entry %zu = %g is outside [-1, 1]: not a correlation matrix", t, cor[t]);
+    if (int rc = fwi_fz64_set_cor(c, cor)) return rc;
+    c->have_cor = true;
+    c->have_level0 = false;
+    c->have_network = false;
+    return FW_OK;
+}
+
+int fw_get_cor_mat_f64(const fw_ctx *c, double *out)
+{
+    CHECK_CTX(c);
+    if (!c->f64) return fw_fail(c, FW_ERR_STATE, "fw_get_cor_mat_f64: the context is not in Float64 mode (fw_get_cor_mat returns its Float32 matrix)");
+    if (!c->have_cor) return fw_fail(c, FW_ERR_STATE, "fw_get_cor_mat_f64: no correlation matrix resident");
+    if (!out) return fw_fail(c, FW_ERR_ARG, "fw_get_cor_mat_f64: NULL output");
+    return fwi_fz64_get_cor(c, out);
 }
 
 int fw_get_cor_mat(const fw_ctx *c, float *out)
 {
     CHECK_CTX(c);
+    if (c->f64) return fw_fail(c, FW_ERR_STATE, "fw_get_cor_mat: the context is in Float64 mode (fw_get_cor_mat_f64 returns its matrix; nothing is cast)");
     if (!c->have_cor) return fw_fail(c, FW_ERR_STATE, "fw_get_cor_mat: no correlation matrix resident");
     if (!out) return fw_fail(c, FW_ERR_ARG, "fw_get_cor_mat: NULL output");
     FW_HIP(c, hipMemcpy(out, c->d_cor, sizeof(float) * (size_t)c->P.p * c->P.p, hipMemcpyDeviceToHost));
@@ -383,6 +444,7 @@ int fw_level0_sharded_dev(fw_ctx *c, int32_t rank, int32_t world_size, const fw_
     CHECK_CTX(c);
     if (world_size < 1 || rank < 0 || rank >= world_size) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded_dev: rank %d outside world of %d", rank, world_size);
     if (world_size > 1 && (!x || !x->prepare || !x->exchange)) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded_dev: world_size > 1 needs both exchange callbacks");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_level0_sharded_dev is not served in Float64 mode");
     return fw_level0_impl(c, nnz_out, rank, world_size, nullptr, nullptr, x);
 }
 
@@ -391,6 +453,7 @@ int fw_use_cor_buffer(fw_ctx *c, void *d_cor, int64_t capacity_floats)
     CHECK_CTX(c);
     if (c->P.kind != FW_FZ) return fw_fail(c, FW_ERR_ARG, "fw_use_cor_buffer: context is not FW_FZ");
     if (c->P.no_cor_mat) return fw_fail(c, FW_ERR_STATE, "fw_use_cor_buffer: the context was created with no_cor_mat (dense_cor = false)");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_use_cor_buffer is not served in Float64 mode");
     if (!d_cor || capacity_floats < (int64_t)c->P.p * c->P.p) return fw_fail(c, FW_ERR_ARG, "fw_use_cor_buffer: needs at least p * p floats of device memory");
     if (c->d_cor && !c->cor_external) (void)hipFree(c->d_cor);
     c->d_cor = (float *)d_cor;
@@ -408,6 +471,7 @@ int fw_compute_cor_mat_rows(fw_ctx *c, int32_t rank, int32_t world_size, int64_t
     if (c->P.kind != FW_FZ) return fw_fail(c, FW_ERR_ARG, "fw_compute_cor_mat_rows: context is not FW_FZ");
     if (c->P.no_cor_mat) return fw_fail(c, FW_ERR_STATE, "fw_compute_cor_mat_rows: the context was created with no_cor_mat (dense_cor = false)");
     if (world_size < 1 || rank < 0 || rank >= world_size || !row0 || !rows_per_rank) return fw_fail(c, FW_ERR_ARG, "fw_compute_cor_mat_rows: invalid argument");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_compute_cor_mat_rows is not served in Float64 mode");
     c->have_level0 = false;
     c->have_network = false;
     return fwi_fz_compute_cor_rows(c, rank, world_size, row0, rows_per_rank);
@@ -426,6 +490,7 @@ int fw_level0_sharded(fw_ctx *c, int32_t rank, int32_t world_size, fw_allgather_
     CHECK_CTX(c);
     if (world_size < 1 || rank < 0 || rank >= world_size) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded: rank %d outside world of %d", rank, world_size);
     if (world_size > 1 && !allgather) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded: world_size > 1 needs an allgather callback");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_level0_sharded is not served in Float64 mode");
     return fw_level0_impl(c, nnz_out, rank, world_size, allgather, user);
 }
 
@@ -437,7 +502,7 @@ static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_a
     const int p = c->P.p;
     if (c->P.kind == FW_FZ && !c->P.no_cor_mat) {
         if (!c->have_cor) {
-            int rc = fwi_fz_compute_cor(c);
+            int rc = c->f64 ? fwi_fz64_compute_cor(c) : fwi_fz_compute_cor(c);
             if (rc) return rc;
         }
     } else if (!c->have_data) {  // (no_cor_mat: the level-0 kernels multiply and screen the centred columns themselves)
@@ -463,7 +528,7 @@ static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_a
     const bool sharded = world > 1 && (c->P.kind == FW_MI || c->P.kind == FW_MI_NZ);
     c->l0_rank = sharded ? rank : 0;
     c->l0_world = sharded ? world : 1;
-    int rc = (c->P.kind == FW_FZ)      ? fwi_fz_level0(c, pi, pj, stat, pval, &m, devp)
+    int rc = (c->P.kind == FW_FZ)      ? (c->f64 ? fwi_fz64_level0(c, pi, pj, stat, pval, &m, devp) : fwi_fz_level0(c, pi, pj, stat, pval, &m, devp))
              : (c->P.kind == FW_FZ_NZ) ? fwi_fznz_level0(c, pi, pj, stat, pval, &m, devp)
                                        : fwi_mi_level0(c, pi, pj, stat, pval, &m, (sharded && !xdev) ? nullptr : devp);
     c->l0_rank = 0;
@@ -712,6 +777,13 @@ int fw_test_batch(fw_ctx *c, int64_t m, const int32_t *X, const int32_t *Y, cons
     }
     if (c->P.kind == FW_FZ) {
         if (!c->have_cor) return fw_fail(c, FW_ERR_STATE, "fw_test_batch: no correlation matrix (fw_compute_cor_mat / fw_set_cor_mat)");
+        if (c->f64) {
+            for (int64_t t = 0; t < m; ++t)
+                if (zoff[t + 1] - zoff[t] > FW_MAX_K_FAST)
+                    return fw_fail(c, FW_ERR_LIMIT, "fw_test_batch: test %lld has %lld conditioning variables; Float64 mode serves up to %d", (long long)t,
+                                   (long long)(zoff[t + 1] - zoff[t]), FW_MAX_K_FAST);
+            return fwi_fz64_test_batch(c, m, X, Y, zoff, zflat, out);
+        }
         return fwi_fz_test_batch(c, m, X, Y, zoff, zflat, out);
     }
     if (!c->have_data) return fw_fail(c, FW_ERR_STATE, "fw_test_batch: no data uploaded");
@@ -1046,6 +1118,7 @@ int fwi_pool_launch(fw_ctx *c, FwPool &pool)
         }
     } else {
         rc = stream ? fwi_fzs_segments(c, (int64_t)ns, dsegs, dacc, dout, pb, pool.nzrecs.data(), (int64_t)pool.nzrecs.size(), arena_floats)
+             : c->f64 ? fwi_fz64_segments(c, (int64_t)ns, dsegs, dacc, dout, pb)
              : fz   ? fwi_fz_segments(c, (int64_t)ns, (int64_t)ns_tab, dsegs, dacc, dout, pb)
                 : fwi_mi_segments(c, (int64_t)ns, dsegs, dacc, dout, pb);
     }

@@ -199,6 +199,7 @@ PathChoice choose_path(fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, c
     const int kind = c->P.kind;
     const bool discrete = kind == FW_MI || kind == FW_MI_NZ;
     if (fw_host_hiton()) return host("FW_HOST_HITON=1");
+    if (c->f64) return host("Float64 matrix (fw_fz64.hip): the general-form segment kernel serves the host pool");
     if (!discrete && !c->P.recursive_pcor) return host("streamed columns (recursive_pcor = 0): fw_fzs.hip serves the host pool");
     if (!discrete && c->P.n < c->n_obs_min_eff) return host("no power: fewer observations than n_obs_min, no device work at all");
     if (c->mi_generic) return host("generic discrete form (a variable with more than three levels, fw_mi_core.h)");
@@ -745,6 +746,7 @@ extern "C" int fw_learn_network_dev(fw_ctx *c, const fw_learn_opts *opts_in, con
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
     const int world = opts_in ? std::max(opts_in->world_size, 1) : 1;
     if (world > 1 && (!x || !x->prepare || !x->exchange)) return fw_fail(c, FW_ERR_ARG, "fw_learn_network_dev: world_size > 1 needs both exchange callbacks");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_learn_network_dev is not served in Float64 mode");
     if (!x) return fw_learn_network(c, opts_in, nullptr, nullptr, n_edges_out);
     (void)hipSetDevice(c->P.device);
     DevXAdapter A{c, x, world, {}, {}};

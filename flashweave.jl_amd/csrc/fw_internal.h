@@ -153,6 +153,10 @@ struct fw_ctx {
     bool have_fzs_stat = false;
     int n_pad = 0, p_pad = 0;
     bool have_data = false, have_cor = false;
+    // Float64 mode (fw_set_data_dense_f64 / fw_set_cor_mat_f64, fw_fz64.hip): its own buffers, nothing of the above but d_thr is used
+    bool f64 = false;       // the context is in Float64 mode
+    bool f32_input = false; // a Float32 matrix was uploaded (fw_set_data_dense_f32 / fw_set_cor_mat): the mode can no longer change
+    double *d_data64 = nullptr, *d_xc64 = nullptr, *d_sd64 = nullptr, *d_cor64 = nullptr;
 
     // ---- discrete (FW_MI / FW_MI_NZ) ----
     std::vector<int32_t> levels, max_vals;
@@ -248,6 +252,17 @@ int fwi_fz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
 int fwi_fz_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff,
                       const int32_t *zflat, fw_test_result *out);
 int fwi_fz_segments(fw_ctx *ctx, int64_t nseg, int64_t nseg_tab, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, FwPoolBuf &pb);
+
+// ---- fz in Float64 (fw_fz64.hip): the context's f64 mode ----
+int fwi_fz64_set_data(fw_ctx *ctx, const double *data);
+int fwi_fz64_set_cor(fw_ctx *ctx, const double *cor);
+int fwi_fz64_get_cor(const fw_ctx *ctx, double *out);
+int fwi_fz64_compute_cor(fw_ctx *ctx);
+int fwi_fz64_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat, std::vector<double> &pval,
+                    int64_t *m_reliable, FwL0Dev *dev);
+int fwi_fz64_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff, const int32_t *zflat,
+                        fw_test_result *out);
+int fwi_fz64_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, FwPoolBuf &pb);
 
 // ---- fz without a correlation matrix: streamed sample columns (fw_fzs.hip, fw_params.recursive_pcor = 0) ----
 int fwi_fzs_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff, const int32_t *zflat,

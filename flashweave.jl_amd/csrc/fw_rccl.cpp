@@ -223,6 +223,7 @@ int fw_comm_init(fw_ctx *c, const uint8_t *id128, int32_t rank, int32_t world_si
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
     if (!id128 || world_size < 1 || rank < 0 || rank >= world_size) return fw_fail(c, FW_ERR_ARG, "fw_comm_init: bad id / rank %d of %d", rank, world_size);
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_comm_init is not served in Float64 mode");
     std::string err;
     RcclApi *R = rccl_api(&err);
     if (!R) return fw_fail(c, FW_ERR_DEVICE, "fw_comm_init: %s", err.c_str());
@@ -263,6 +264,7 @@ int fw_comm_stats(const fw_ctx *c, int64_t *calls, int64_t *collectives, int64_t
 int fw_level0_comm(fw_ctx *c, int64_t *nnz_out)
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_level0_comm is not served in Float64 mode");
     if (!c->comm) return fw_fail(c, FW_ERR_STATE, "fw_level0_comm: no communicator (fw_comm_init)");
     CommX X{c, 0.0};
     fw_dev_exchange x{&X, comm_prepare, comm_exchange};
@@ -272,6 +274,7 @@ int fw_level0_comm(fw_ctx *c, int64_t *nnz_out)
 int fw_learn_network_comm(fw_ctx *c, const fw_learn_opts *opts_in, int64_t *n_edges_out)
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_learn_network_comm is not served in Float64 mode");
     if (!c->comm) return fw_fail(c, FW_ERR_STATE, "fw_learn_network_comm: no communicator (fw_comm_init)");
     fw_learn_opts opt{};
     opt.feed_forward = 1;
@@ -288,6 +291,7 @@ int fw_learn_network_comm(fw_ctx *c, const fw_learn_opts *opts_in, int64_t *n_ed
 int fw_cor_mat_allgather_comm(fw_ctx *c, int64_t rows_per_rank)
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
+    if (c->f64) return fw_fail(c, FW_ERR_LIMIT, "fw_cor_mat_allgather_comm is not served in Float64 mode");
     if (!c->comm) return fw_fail(c, FW_ERR_STATE, "fw_cor_mat_allgather_comm: no communicator (fw_comm_init)");
     if (!c->d_cor || !c->cor_external) return fw_fail(c, FW_ERR_STATE, "fw_cor_mat_allgather_comm: needs fw_use_cor_buffer + fw_compute_cor_mat_rows first");
     RcclApi *R = rccl_api(nullptr);

@@ -131,6 +131,10 @@ def load_library():
     L.fw_set_cor_mat.argtypes = [vp, vp]
     L.fw_compute_cor_mat.argtypes = [vp]
     L.fw_get_cor_mat.argtypes = [vp, vp]
+    if hasattr(L, "fw_set_data_dense_f64"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        L.fw_set_data_dense_f64.argtypes = [vp, vp]
+        L.fw_set_cor_mat_f64.argtypes = [vp, vp]
+        L.fw_get_cor_mat_f64.argtypes = [vp, vp]
     L.fw_level0.argtypes = [vp, C.POINTER(C.c_int64)]
     L.fw_level0_get.argtypes = [vp, vp, vp, vp, vp]
     L.fw_set_row_views.argtypes = [vp, C.c_int32]
@@ -202,10 +206,19 @@ class Engine:
     """One engine context on one GPU (replaces make_test_object, src/misc.jl:34-45).
 
     test_name: "mi" | "mi_nz" | "fz" (src/types.jl:64-72).  Keyword defaults are learn_network's
-    (src/learning.jl:466-473)."""
+    (src/learning.jl:466-473).
+
+    prec (learn_network's keyword): 32 (default) -- every continuous matrix handed in is cast to Float32, whatever its dtype; 64, "fz"
+    only -- set_data / set_cor_mat convert to Float64 and the context runs in Float64 mode (include/flashweave_amd.h): cor() /
+    cor_mat() return Float64, pcor_rec rounds in Float64.  The keyword decides, never the dtype of an array."""
 
     def __init__(self, test_name, n, p, max_k=3, alpha=0.01, hps=5, n_obs_min=-1, max_tests=10_000_000, FDR=True,
-                 device=0, dense_rules=False, recursive_pcor=True, dense_cor=True):
+                 device=0, dense_rules=False, recursive_pcor=True, dense_cor=True, prec=32):
+        if prec not in (32, 64):
+            raise ValueError("Engine: prec must be 32 or 64 (got %r)" % (prec,))
+        if prec == 64 and test_name != "fz":
+            raise ValueError("Engine: prec=64 is served for test_name \"fz\" only (got %r)" % (test_name,))
+        self.prec = prec
         self.L = load_library()
         self.test_name = test_name
         self.n, self.p = int(n), int(p)
@@ -244,9 +257,9 @@ class Engine:
         """fz: dense Float32 n x p; mi / mi_nz: integer n x p (dense ndarray) or a (colptr, rowval, nzval) CSC triple
         with 0-based rows."""
         if self.test_name in ("fz", "fz_nz"):
-            d = np.asfortranarray(np.asarray(data, dtype=np.float32))
+            d = np.asfortranarray(np.asarray(data, dtype=np.float64 if self.prec == 64 else np.float32))
             assert d.shape == (self.n, self.p)
-            self._ck(self.L.fw_set_data_dense_f32(self.h, _ptr(d)))
+            self._ck((self.L.fw_set_data_dense_f64 if self.prec == 64 else self.L.fw_set_data_dense_f32)(self.h, _ptr(d)))
         elif isinstance(data, tuple):
             colptr, rowval, nzval = (np.ascontiguousarray(data[0], dtype=np.int64),
                                      np.ascontiguousarray(data[1], dtype=np.int32),
@@ -258,12 +271,12 @@ class Engine:
             self._ck(self.L.fw_set_data_dense_i32(self.h, _ptr(d)))
 
     def set_cor_mat(self, cor_mat):
-        cm = np.asfortranarray(np.asarray(cor_mat, dtype=np.float32))
+        cm = np.asfortranarray(np.asarray(cor_mat, dtype=np.float64 if self.prec == 64 else np.float32))
         assert cm.shape == (self.p, self.p)
-        self._ck(self.L.fw_set_cor_mat(self.h, _ptr(cm)))
+        self._ck((self.L.fw_set_cor_mat_f64 if self.prec == 64 else self.L.fw_set_cor_mat)(self.h, _ptr(cm)))
 
     def cor(self):
-        """cor(data_dense) -> Float32 p x p, on the MFMA units (src/learning.jl:44)."""
+        """cor(data_dense) -> Float32 p x p (Float64 with prec=64), on the MFMA units (src/learning.jl:44)."""
         self._ck(self.L.fw_compute_cor_mat(self.h))
         return self.cor_mat()
 
@@ -272,6 +285,10 @@ class Engine:
         self._ck(self.L.fw_compute_cor_mat(self.h))
 
     def cor_mat(self):
+        if self.prec == 64:
+            out = np.zeros((self.p, self.p), dtype=np.float64, order="F")
+            self._ck(self.L.fw_get_cor_mat_f64(self.h, _ptr(out)))
+            return out
         out = np.zeros((self.p, self.p), dtype=np.float32, order="F")
         self._ck(self.L.fw_get_cor_mat(self.h, _ptr(out)))
         return out

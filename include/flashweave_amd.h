@@ -179,6 +179,20 @@ int fw_set_cor_mat(fw_ctx *ctx, const float *cor_mat);
 int fw_compute_cor_mat(fw_ctx *ctx);
 int fw_get_cor_mat(const fw_ctx *ctx, float *cor_mat_out); /* p*p floats */
 
+/* ---- Float64 mode of FW_FZ: learn_network(prec = 64), cont_type = Float64 (src/learning.jl:42-45; pcor_rec then runs and rounds in
+ * Float64, src/statfuns.jl:23-75).  The first call of fw_set_data_dense_f64 or fw_set_cor_mat_f64 puts the context in Float64 mode for
+ * good: the p x p matrix is resident as Float64 (8 p^2 bytes; FW_ERR_NOMEM beyond what the device has) and fw_compute_cor_mat,
+ * fw_level0, fw_level0_get, fw_test_batch, fw_test_subsets_batch, fw_learn_network, fw_network_get*, fw_set_track_rejections and the
+ * counters work on it with unchanged signatures (HITON-PC through the host job pool).
+ * Precisions never mix and nothing is cast: the _f64 setters on a context that holds Float32 input, fw_set_data_dense_f32 /
+ * fw_set_cor_mat / fw_get_cor_mat on a Float64 context and fw_get_cor_mat_f64 on a Float32 context fail with FW_ERR_STATE; the _f64
+ * setters on a context that is not FW_FZ with FW_ERR_ARG.
+ * Not served in Float64 mode (FW_ERR_LIMIT, the message names the option): recursive_pcor = 0, no_cor_mat = 1, max_k above 5,
+ * fw_use_cor_buffer, fw_compute_cor_mat_rows, fw_level0_sharded*, fw_learn_network_dev and the fw_*_comm entry points. */
+int fw_set_data_dense_f64(fw_ctx *ctx, const double *data);        /* n x p column-major, Matrix{Float64} */
+int fw_set_cor_mat_f64(fw_ctx *ctx, const double *cor_mat);        /* p x p, entries in [-1, 1] or NaN */
+int fw_get_cor_mat_f64(const fw_ctx *ctx, double *cor_mat_out);    /* p*p doubles */
+
 /* Exchange callback for target-sharded runs: called once per feed-forward round with this rank's newly found
  * directed neighbour entries (target, neighbour, weight-stat, p); must return the concatenation over all ranks
  * (rank order) through *out_* buffers allocated by the callee and valid until the next call.  NULL for
