@@ -5,7 +5,7 @@ import numpy as np
 
 from . import io as fio
 from . import preprocess as pre
-from .engine import Engine, normalize_counts
+from .engine import Engine, as_csc, is_sparse, normalize_counts
 
 
 class FWResult(dict):
@@ -49,7 +49,11 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
                   meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
                   no_red_tests=True, track_rejections=False, **unsupported):
-    """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False).
+    """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False); a numpy array or a scipy.sparse
+    matrix.  A sparse table stays sparse end to end (what the reference does with make_sparse, learning.jl:470): normalize=True runs
+    the device CSC front-end (integer counts only) and the sparse upload, normalize=False uploads the matrix as it is (Int32 levels
+    for mi / mi_nz, Float32 clr_nz values for fz_nz); counters["sparse_input"] records it.  Sparse data is refused (ValueError) with
+    device_normalize=False, prec=64, meta_data, and for the plain fz test with normalize=False: each of those needs the dense matrix.
     meta_data: optional samples x meta-variables table (numbers and / or string factors), handled like the reference's
     meta_data_path input: one-hot encoding, discretisation for the discrete tests, +1 shift for fz_nz (preprocess.py).
     round_size: targets per feed-forward round.  None (default) = default_round_size(p): the reference's `single_il` schedule
@@ -94,9 +98,33 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
         warnings.warn("learn_network: dense_cor=False leaves no correlation matrix for recursive partial correlations; "
                       "running with recursive_pcor=False (conditional tests from the data)", stacklevel=2)
         recursive_pcor = False
-    data = np.asarray(data)
+    sparse = is_sparse(data)
+    if sparse:
+        # a sparse table stays sparse from here to the device (fw_normalize_counts_csc, fw_set_data_csc_*); what would need the dense
+        # matrix is refused by name before any device call -- densifying silently would defeat the point
+        if not device_normalize:
+            raise ValueError("learn_network: sparse data with device_normalize=False is not supported: the host front-end "
+                             "(preprocess.py) is dense; pass data.toarray() or leave device_normalize=True")
+        if prec == 64:
+            raise ValueError("learn_network: sparse data with prec=64 is not supported: the Float64 path takes a dense matrix")
+        if meta_data is not None:
+            raise ValueError("learn_network: sparse data with meta_data is not supported: append the prepared meta columns to "
+                             "`data` yourself (preprocess.normalize_with_meta)")
+        if test_name == "fz" and not normalize:
+            raise ValueError("learn_network: sparse data with sensitive=True, heterogeneous=False, normalize=False is not supported: "
+                             "the plain fz test needs the dense matrix, pass one")
+        try:
+            data = as_csc(data, np.int32 if (normalize or test_name in ("mi", "mi_nz")) else np.float32)
+        except ValueError as e:
+            raise ValueError("learn_network: sparse data with normalize=%s needs %s (%s)"
+                             % (normalize, "integer counts in 0 .. 2^31 - 1: the device front-end takes nothing else" if normalize
+                                else "integer levels", e)) from None
+        n_cols = data[3][1]
+    else:
+        data = np.asarray(data)
+        n_cols = data.shape[1]
     if header is None:
-        header = ["X%d" % (i + 1) for i in range(data.shape[1])]
+        header = ["X%d" % (i + 1) for i in range(n_cols)]
     meta_mask = None
     if meta_data is not None and not normalize:
         # the reference appends the meta columns as they are and keeps their mask (learning.jl:500-520); here an already
@@ -104,7 +132,7 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
         raise ValueError("learn_network: meta_data with normalize=False is not supported: append the prepared meta columns to "
                          "`data` yourself (preprocess.normalize_with_meta) or pass normalize=True")
     t_norm0 = time.perf_counter()
-    on_device = bool(normalize and device_normalize and prec == 32 and _integral(data))
+    on_device = bool(normalize and device_normalize and prec == 32 and (sparse or _integral(data)))
     dev_norm = (lambda c, t: normalize_counts(c, t, device=device)) if on_device else None
     if normalize and meta_data is not None:
         r = pre.normalize_with_meta(data, test_name, meta_data, prec=prec, header=header, meta_header=meta_header,
@@ -113,16 +141,19 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     elif normalize:
         mat, row_mask, col_mask = dev_norm(data, test_name) if on_device else pre.normalize(data, test_name, prec=prec)
         header = [h for h, k in zip(header, col_mask) if k]
+    elif sparse:
+        mat = tuple(data[:3])  # the prepared matrix as it is: Int32 CSC for mi / mi_nz, Float32 CSC for fz_nz
     else:
         mat = data
     t_norm = time.perf_counter() - t_norm0
-    n, p = mat.shape
+    n, p = data[3] if (sparse and not normalize) else mat.shape
     if round_size is None:
         round_size = default_round_size(p)
     eng = Engine(test_name, n, p, max_k=max_k, alpha=alpha, hps=hps, n_obs_min=n_obs_min, max_tests=max_tests, FDR=FDR,
                  device=device, recursive_pcor=recursive_pcor, dense_cor=dense_cor, prec=eng_prec)
     try:
-        eng.set_data(mat)
+        # (what the device front-end returned is canonical already: its triple goes up as it is, stored 0.0f of clr_nz included)
+        eng.set_data((mat.indptr, mat.indices, mat.data) if (sparse and normalize and is_sparse(mat)) else mat)
         if test_name == "fz" and dense_cor:
             eng.compute_cor()
         net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests,
@@ -132,6 +163,7 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
         eng.close()
     counters["t_normalize_s"] = t_norm
     counters["normalized_on_device"] = on_device
+    counters["sparse_input"] = sparse
     return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header),
                     parameters=dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha,
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,

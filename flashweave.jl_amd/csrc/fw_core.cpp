@@ -367,6 +367,20 @@ int fw_set_data_csc_i32(fw_ctx *c, const int64_t *colptr, const int32_t *rowval,
     return FW_OK;
 }
 
+int fw_set_data_csc_f32(fw_ctx *c, const int64_t *colptr, const int32_t *rowval, const float *nzval)
+{
+    CHECK_CTX(c);
+    if (c->P.kind != FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_csc_f32: context is not FW_FZ_NZ");
+    if (!colptr || (colptr[c->P.p] > 0 && (!rowval || !nzval))) return fw_fail(c, FW_ERR_ARG, "fw_set_data_csc_f32: NULL array");
+    c->have_data = false;  // (a refused triple leaves the resident layout half written)
+    c->have_level0 = false;
+    c->have_network = false;
+    int rc = fwi_fznz_upload_csc(c, colptr, rowval, nzval);
+    if (rc) return rc;
+    c->have_data = true;
+    return FW_OK;
+}
+
 int fw_set_data_dense_i32(fw_ctx *c, const int32_t *data)
 {
     CHECK_CTX(c);

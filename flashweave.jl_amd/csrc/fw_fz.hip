@@ -8,6 +8,7 @@
 //   test_subsets                         tests.jl:281-346
 // Compiled with -ffp-contract=off: the reference never fuses a*b+c and the partial-correlation value must be
 // reproducible to the bit (only +,-,*,/,sqrt,rint are involved).
+#include "fw_csc.h"
 #include "fw_internal.h"
 #include "fw_unrank.h"
 
@@ -1453,6 +1454,72 @@ int fwi_fznz_upload(fw_ctx *ctx, const float *data)
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_nzbits, sizeof(uint64_t) * nzb.size()));
     FW_HIP(ctx, hipMemcpy(ctx->d_nzbits, nzb.data(), sizeof(uint64_t) * nzb.size(), hipMemcpyHostToDevice));
     ctx->W = W;
+    return FW_OK;
+}
+
+// fw_set_data_csc_f32: the CSC triple scattered on the device into the layout fwi_fznz_upload leaves (values [p][n], zero elsewhere,
+// and the plane of values != 0), one wavefront per column.  The column is checked first (fw_csc.h) and scattered only when it is
+// good, so no store leaves the layout.  Each plane word belongs to one lane, which finds the word's entries in the sorted run by
+// binary search and writes the whole word: no atomics, and the plane needs no clearing.
+__global__ __launch_bounds__(256) void fznz_csc_scatter_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                               const float *__restrict__ nzval, int n, int p, int W, long long nnz,
+                                                               float *__restrict__ data, unsigned long long *__restrict__ nzb,
+                                                               int32_t *__restrict__ colstat)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= p) return;
+    long long a, b;
+    const int bad = fw_csc_check_column(colptr, rowval, j, n, nnz, lane, &a, &b);
+    if (lane == 0) colstat[j] = bad;
+    if (bad) return;
+    for (long long e = a + lane; e < b; e += 64) data[(size_t)j * n + rowval[e]] = nzval[e];
+    for (int w = lane; w < W; w += 64) {
+        long long lo = a, hi = b;  // first entry with row >= 64 w
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (rowval[mid] < w * 64)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        unsigned long long word = 0;
+        for (long long e = lo; e < b && rowval[e] < w * 64 + 64; ++e)
+            if (nzval[e] != 0.0f) word |= 1ull << (rowval[e] & 63);
+        nzb[(size_t)j * W + w] = word;
+    }
+}
+
+int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval)
+{
+    const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
+    const long long nnz = colptr[p];
+    if (colptr[0] != 0 || nnz < 0) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32: colptr must run from 0 to nnz (column 0)");
+    const size_t bytes = sizeof(float) * (size_t)n * p;
+    if (!ctx->d_data) FW_HIP(ctx, hipMalloc(&ctx->d_data, bytes));
+    if (ctx->d_nzbits) (void)hipFree(ctx->d_nzbits);
+    ctx->d_nzbits = nullptr;
+    FW_HIP(ctx, hipMalloc((void **)&ctx->d_nzbits, sizeof(uint64_t) * (size_t)p * W));
+    ctx->W = W;
+    int rc;
+    const size_t o_row = ((sizeof(int64_t) * ((size_t)p + 1)) + 255) & ~(size_t)255, o_val = o_row + ((sizeof(int32_t) * (size_t)nnz + 255) & ~(size_t)255),
+                 o_stat = o_val + ((sizeof(float) * (size_t)nnz + 255) & ~(size_t)255);
+    if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, o_stat + sizeof(int32_t) * (size_t)p))) return rc;
+    char *B = (char *)ctx->d_tmp1.ptr;
+    FW_HIP(ctx, hipMemcpyAsync(B, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz > 0) {
+        FW_HIP(ctx, hipMemcpyAsync(B + o_row, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        FW_HIP(ctx, hipMemcpyAsync(B + o_val, nzval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    }
+    FW_HIP(ctx, hipMemsetAsync(ctx->d_data, 0, bytes, ctx->stream));
+    hipLaunchKernelGGL(fznz_csc_scatter_kernel, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row),
+                       (const float *)(B + o_val), n, p, W, nnz, (float *)ctx->d_data, (unsigned long long *)ctx->d_nzbits, (int32_t *)(B + o_stat));
+    FW_HIP(ctx, hipGetLastError());
+    std::vector<int32_t> colstat((size_t)p);
+    FW_HIP(ctx, hipMemcpyAsync(colstat.data(), B + o_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cnt.kernel_launches += 1;
+    for (int j = 0; j < p; ++j)
+        if (colstat[j]) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32: column %d: %s", j, fw_csc_reason(colstat[j]));
     return FW_OK;
 }
 

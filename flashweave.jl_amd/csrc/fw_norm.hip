@@ -14,6 +14,9 @@
 #include <cmath>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "fw_csc.h"
 #include "fw_internal.h"
 
 namespace {
@@ -133,6 +136,93 @@ __global__ __launch_bounds__(256) void norm_col_levels_kernel(const int32_t *__r
 // instead of LDS -- the stores of a pass are visible to the workgroup's other wavefronts behind the barrier, one L1 per CU), the
 // workgroups striding over the columns so that the scratch stays at gridDim.x * M doubles.
 #define NORM_BIN_MAX 16384
+
+// The sort keys of one workgroup: in LDS plain accesses; in device memory relaxed agent-scope accesses (they bypass the per-CU
+// vector cache, whose lines another wavefront's store does not refresh) and a device-scope fence in front of every barrier.
+struct NbKeys {
+    double *k;
+    bool glob;
+    __device__ double ld(int i) const
+    {
+        return glob ? __longlong_as_double(__hip_atomic_load((const long long *)&k[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : k[i];
+    }
+    __device__ void st(int i, double v) const
+    {
+        if (glob)
+            __hip_atomic_store((long long *)&k[i], __double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else
+            k[i] = v;
+    }
+    __device__ void sync() const
+    {
+        if (glob) __threadfence();
+        __syncthreads();
+    }
+};
+
+// The rank / bin code of binned_nz_clr, shared by the dense and the CSC form (all nt threads of the workgroup call nb_pad_sort).
+// keys[0 .. m) are filled and synchronised: pad to M (a power of two) with +inf and sort ascending (bitonic).
+__device__ inline void nb_pad_sort(const NbKeys &K, int m, int M, int tid, int nt)
+{
+    for (int i = m + tid; i < M; i += nt) K.st(i, INFINITY);
+    K.sync();
+    for (int k = 2; k <= M; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < M; i += nt) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const double a = K.ld(i), b = K.ld(l);
+                    const bool up = (i & k) == 0;
+                    if (up ? (a > b) : (a < b)) {
+                        K.st(i, b);
+                        K.st(l, a);
+                    }
+                }
+            }
+            K.sync();
+        }
+}
+
+// the largest tied rank among the m sorted keys: m - (e_max - 1) / 2
+__device__ inline double nb_rank_max(const NbKeys &K, int m)
+{
+    if (m <= 0) return 1.0;
+    const double top = K.ld(m - 1);
+    int lo = 0, hi = m;  // first index with key >= top
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (K.ld(mid) < top)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return (double)m - ((double)(m - lo) - 1.0) / 2.0;
+}
+
+// bin of the value c among the m sorted keys: tied rank (#smaller) + (#equal + 1) / 2, bin = floor((rank / max rank) / (1/2 + 1e-5)) + 1
+__device__ inline int nb_bin(const NbKeys &K, int m, double rmax, double c)
+{
+    const double step = (1.0 / 2.0) + 1e-5;
+    int lo = 0, hi = m;
+    while (lo < hi) {  // #smaller
+        const int mid = (lo + hi) >> 1;
+        if (K.ld(mid) < c)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    int lo2 = lo, hi2 = m;
+    while (lo2 < hi2) {  // first index with key > c
+        const int mid = (lo2 + hi2) >> 1;
+        if (K.ld(mid) <= c)
+            lo2 = mid + 1;
+        else
+            hi2 = mid;
+    }
+    const double rank = (double)lo + ((double)(lo2 - lo) + 1.0) / 2.0;
+    return (int)floor((rank / rmax) / step) + 1;
+}
+
 __global__ __launch_bounds__(1024) void norm_binned_kernel(const int32_t *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
                                                            const int32_t *__restrict__ cols, int pk, const double *__restrict__ gmean,
                                                            int32_t *__restrict__ out, int32_t *__restrict__ two, int M, double *gkeys)
@@ -140,90 +230,26 @@ __global__ __launch_bounds__(1024) void norm_binned_kernel(const int32_t *__rest
     extern __shared__ double s_key_lds[];
     __shared__ int s_cnt, s_b1, s_b2;
     const int tid = threadIdx.x;
-    double *s_key = gkeys ? gkeys + (size_t)blockIdx.x * (size_t)M : s_key_lds;
-    // keys in device memory: relaxed agent-scope accesses (they bypass the per-CU vector cache, whose lines another wavefront's
-    // store does not refresh) and a device-scope fence in front of every barrier; in LDS plain accesses
-    const bool glob = gkeys != nullptr;
-    auto KLD = [&](int i) -> double {
-        return glob ? __longlong_as_double(__hip_atomic_load((const long long *)&s_key[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : s_key[i];
-    };
-    auto KST = [&](int i, double v) {
-        if (glob)
-            __hip_atomic_store((long long *)&s_key[i], __double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
-            s_key[i] = v;
-    };
-#define NB_SYNC()                 \
-    {                             \
-        if (glob) __threadfence(); \
-        __syncthreads();          \
-    }
+    const NbKeys K{gkeys ? gkeys + (size_t)blockIdx.x * (size_t)M : s_key_lds, gkeys != nullptr};
   for (int q = blockIdx.x; q < pk; q += gridDim.x) {
     const int32_t *col = x + (size_t)cols[q] * n;
-    __syncthreads();  // (the previous column's last readers of s_key / s_b1 / s_b2)
+    __syncthreads();  // (the previous column's last readers of the keys / s_b1 / s_b2)
     if (tid == 0) s_cnt = s_b1 = s_b2 = 0;
     __syncthreads();
     for (int r = tid; r < nk; r += 1024) {
         const int32_t v = col[rows[r]];
-        if (v != 0) KST(atomicAdd(&s_cnt, 1), log((double)v / gmean[r]));  // order does not matter: sorted below
+        if (v != 0) K.st(atomicAdd(&s_cnt, 1), log((double)v / gmean[r]));  // order does not matter: sorted below
     }
-    NB_SYNC()
+    K.sync();
     const int m = s_cnt;
-    for (int i = m + tid; i < M; i += 1024) KST(i, INFINITY);
-    NB_SYNC()
-    for (int k = 2; k <= M; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < M; i += 1024) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const double a = KLD(i), b = KLD(l);
-                    const bool up = (i & k) == 0;
-                    if (up ? (a > b) : (a < b)) {
-                        KST(i, b);
-                        KST(l, a);
-                    }
-                }
-            }
-            NB_SYNC()
-        }
-    double rmax = 1.0;
-    if (m > 0) {
-        const double top = KLD(m - 1);
-        int lo = 0, hi = m;  // first index with key >= top
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (KLD(mid) < top)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        rmax = (double)m - ((double)(m - lo) - 1.0) / 2.0;
-    }
-    const double step = (1.0 / 2.0) + 1e-5;
+    nb_pad_sort(K, m, M, tid, 1024);
+    const double rmax = nb_rank_max(K, m);
     int b1 = 0, b2 = 0;
     for (int r = tid; r < nk; r += 1024) {
         const int32_t v = col[rows[r]];
         int bin = 0;
         if (v != 0) {
-            const double c = log((double)v / gmean[r]);  // the same operations as above: the same bits
-            int lo = 0, hi = m;
-            while (lo < hi) {  // #smaller
-                const int mid = (lo + hi) >> 1;
-                if (KLD(mid) < c)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            int lo2 = lo, hi2 = m;
-            while (lo2 < hi2) {  // first index with key > c
-                const int mid = (lo2 + hi2) >> 1;
-                if (KLD(mid) <= c)
-                    lo2 = mid + 1;
-                else
-                    hi2 = mid;
-            }
-            const double rank = (double)lo + ((double)(lo2 - lo) + 1.0) / 2.0;
-            bin = (int)floor((rank / rmax) / step) + 1;
+            bin = nb_bin(K, m, rmax, log((double)v / gmean[r]));  // the same operations as above: the same bits
             b1 |= bin == 1;
             b2 |= bin == 2;
         }
@@ -234,7 +260,6 @@ __global__ __launch_bounds__(1024) void norm_binned_kernel(const int32_t *__rest
     __syncthreads();
     if (tid == 0) two[q] = s_b1 && s_b2;
   }
-#undef NB_SYNC
 }
 
 // dst column q2 = src column sel[q2] (nk entries each)
@@ -256,6 +281,65 @@ __global__ __launch_bounds__(256) void norm_gather_cols_kernel(const int32_t *__
             goto done;                                                                                       \
         }                                                                                                    \
     } while (0)
+
+// Per-row totals over the kept columns -> kept samples and their parameters, on the host (n values each; shared by the dense
+// and the CSC front-end, so that both take the same libm calls on the same bits).  S read sum, SL sum of log over the non-zeros,
+// NZ number of zeros, RMIN smallest non-zero.  rows = samples with reads; FW_FZ: adaptive pseudo-counts (a sample whose
+// pseudo-count underflows to 0 is dropped) and the geometric mean of the filled row; FW_FZ_NZ / FW_MI_NZ: geometric mean of the
+// non-zeros.
+int norm_row_params(const char *fn, int kind, int n, int pk, const std::vector<double> &S, const std::vector<double> &SL,
+                    const std::vector<int64_t> &NZ, const std::vector<int32_t> &RMIN, uint8_t *row_mask, std::vector<int32_t> &rows,
+                    std::vector<double> &pseudo, std::vector<double> &g)
+{
+    rows.clear();
+    int32_t min_abund = 0x7fffffff;
+    for (int i = 0; i < n; ++i) {
+        row_mask[i] = S[i] > 0.0;  // sum(data, dims=2) .> 0
+        if (row_mask[i]) {
+            rows.push_back(i);
+            min_abund = std::min(min_abund, RMIN[i]);
+        }
+    }
+    int nk = (int)rows.size();
+    if (nk == 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: no sample has reads", fn);
+    pseudo.assign((size_t)nk, 0.0);
+    g.assign((size_t)nk, 1.0);
+    if (kind == FW_FZ) {  // adaptive_pseudocount! (:157-190): row of maximal depth as the anchor
+        int md = rows[0];
+        for (int i : rows)
+            if (S[i] > S[md]) md = i;
+        const double base = min_abund >= 1 ? 1.0 : (double)min_abund / 10.0;
+        const double k = (double)NZ[md], P = (double)pk, Nprod1 = SL[md];
+        std::vector<int32_t> rows2;
+        std::vector<double> ps2;
+        for (int i : rows) {
+            const double nz = (double)NZ[i];
+            if (!(nz < P && k < P)) return fw_fail(nullptr, FW_ERR_ARG, "%s: samples with all zero abundances are not allowed", fn);
+            const double ps = std::exp((1.0 / (nz - P)) * ((k - P) * std::log(base) + Nprod1 - SL[i]));
+            if (ps != 0.0) {
+                rows2.push_back(i);
+                ps2.push_back(ps);
+            } else {
+                row_mask[i] = 0;
+            }
+        }
+        rows.swap(rows2);
+        nk = (int)rows.size();
+        pseudo.assign(ps2.begin(), ps2.end());
+        g.resize((size_t)nk);
+        for (int r = 0; r < nk; ++r) {  // clr!(pseudo_count = 0): geometric mean of the filled row
+            const int i = rows[r];
+            g[r] = std::exp((SL[i] + (double)NZ[i] * std::log(pseudo[r])) / P);
+        }
+    } else if (kind == FW_FZ_NZ || kind == FW_MI_NZ) {  // geometric mean of the non-zeros
+        for (int r = 0; r < nk; ++r) {
+            const int i = rows[r];
+            const double cnt = (double)pk - (double)NZ[i];
+            g[r] = cnt > 0 ? std::exp(SL[i] / cnt) : 1.0;
+        }
+    }
+    return FW_OK;
+}
 
 }  // namespace
 
@@ -320,63 +404,18 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
         // chunk partials -> per-row totals, in chunk order (deterministic)
         std::vector<double> S((size_t)n, 0.0), SL((size_t)n, 0.0);
         std::vector<int64_t> NZ((size_t)n, 0);
-        int32_t min_abund = 0x7fffffff;
         for (int c = 0; c < NORM_CHUNKS; ++c)
             for (int i = 0; i < n; ++i) {
                 S[i] += rsum[(size_t)c * n + i];
                 SL[i] += rlog[(size_t)c * n + i];
                 NZ[i] += rzero[(size_t)c * n + i];
             }
-        for (int i = 0; i < n; ++i) {
-            row_mask[i] = S[i] > 0.0;  // sum(data, dims=2) .> 0
-            if (row_mask[i]) rows.push_back(i);
-        }
+        std::vector<int32_t> RMIN((size_t)n, 0x7fffffff);
         for (int c = 0; c < NORM_CHUNKS; ++c)
-            for (int i : rows) min_abund = std::min(min_abund, rmin[(size_t)c * n + i]);
+            for (int i = 0; i < n; ++i) RMIN[i] = std::min(RMIN[i], rmin[(size_t)c * n + i]);
+        std::vector<double> pseudo, g;
+        if ((rc = norm_row_params("fw_normalize_counts", kind, n, pk, S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
         nk = (int)rows.size();
-        if (nk == 0) {
-            rc = fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: no sample has reads");
-            goto done;
-        }
-        std::vector<double> pseudo((size_t)nk, 0.0), g((size_t)nk, 1.0);
-        if (kind == FW_FZ) {  // adaptive_pseudocount! (:157-190): row of maximal depth as the anchor
-            int md = rows[0];
-            for (int i : rows)
-                if (S[i] > S[md]) md = i;
-            const double base = min_abund >= 1 ? 1.0 : (double)min_abund / 10.0;
-            const double k = (double)NZ[md], P = (double)pk, Nprod1 = SL[md];
-            std::vector<int32_t> rows2;
-            std::vector<double> ps2;
-            for (int i : rows) {
-                const double nz = (double)NZ[i];
-                if (!(nz < P && k < P)) {
-                    rc = fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: samples with all zero abundances are not allowed");
-                    goto done;
-                }
-                const double ps = std::exp((1.0 / (nz - P)) * ((k - P) * std::log(base) + Nprod1 - SL[i]));
-                if (ps != 0.0) {
-                    rows2.push_back(i);
-                    ps2.push_back(ps);
-                } else {
-                    row_mask[i] = 0;
-                }
-            }
-            rows.swap(rows2);
-            nk = (int)rows.size();
-            pseudo.assign(ps2.begin(), ps2.end());
-            g.resize((size_t)nk);
-            for (int r = 0; r < nk; ++r) {  // clr!(pseudo_count = 0): geometric mean of the filled row
-                const int i = rows[r];
-                g[r] = std::exp((SL[i] + (double)NZ[i] * std::log(pseudo[r])) / P);
-            }
-        } else if (kind == FW_FZ_NZ || kind == FW_MI_NZ) {  // geometric mean of the non-zeros
-            g.resize((size_t)nk);
-            for (int r = 0; r < nk; ++r) {
-                const int i = rows[r];
-                const double cnt = (double)pk - (double)NZ[i];
-                g[r] = cnt > 0 ? std::exp(SL[i] / cnt) : 1.0;
-            }
-        }
         NHIP(hipMalloc((void **)&d_rows, sizeof(int32_t) * nk));
         NHIP(hipMemcpy(d_rows, rows.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice));
         if (kind == FW_MI) {
@@ -453,6 +492,370 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
     }
 done:
     void *ptrs[] = {d_x, d_cmin, d_cmax, d_cols, d_rows, d_rzero, d_rmin, d_two, d_oi, d_tmp, d_sel, d_rsum, d_rlog, d_pseudo, d_g, d_of, d_keys};
+    for (void *q : ptrs)
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
+// ---- the same front-end on a CSC count table (fw_normalize_counts_csc) ---------------------------------------------------------
+// The table stays sparse from the caller's triple to the output triple: the work is O(nnz) (FW_FZ: plus its dense output).
+//   csc_col_scan_kernel    one wavefront per column: structure and value check, min / max with the implicit zeros counted (the
+//                          variance filter), and the (column, count) payload of every entry for the sort            12 B / entry
+//   rocprim radix sort     stable, by row: the CSR view; inside a row the entries keep their ascending column order  ~24 B / entry and pass
+//   csc_row_stats_kernel   one thread per row over its CSR run: the sums of norm_row_stats_kernel in its order       12 B / entry
+//   csc_binned_kernel      one workgroup per kept column: norm_binned_kernel on the column's stored run              16 B / entry
+//   csc_emit_kernel        one wavefront per output column: renumbered rows + values                                 16 B / entry
+//   csc_adapt_*_kernel     FW_FZ: the dense clr_adapt matrix, pseudo-count cells first, stored entries over them
+// Bit-identity with the dense form: norm_row_stats_kernel adds a row's terms chunk by chunk of the kept-column index and the host adds
+// the 64 chunk partials in chunk order, each from 0.0.  An absent entry adds +0.0 to the read sum and nothing to the log sum, and
+// a chunk without entries contributes a partial of +0.0: neither changes a bit, so adding the stored terms in column order with a
+// fresh partial at every chunk boundary gives the same Float64 totals.  The per-row parameters come from the same host code
+// (norm_row_params), the values from the same device expressions.
+namespace {
+
+// colstat[j]: 1 kept, 0 constant (dropped), < 0: -(FW_CSC_* flags).  pay[e] = column << 32 | count.
+__global__ __launch_bounds__(256) void csc_col_scan_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                           const int32_t *__restrict__ nzval, int n, int p, long long nnz,
+                                                           int32_t *__restrict__ colstat, unsigned long long *__restrict__ pay)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= p) return;
+    long long a, b;
+    int bad = fw_csc_check_column(colptr, rowval, j, n, nnz, lane, &a, &b);
+    int32_t lo = 0x7fffffff, hi = (int32_t)0x80000000;
+    for (long long e = a + lane; e < b; e += 64) {
+        const int32_t v = nzval[e];
+        if (v <= 0) bad |= v == 0 ? FW_CSC_ZERO : FW_CSC_NEGATIVE;
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+        pay[e] = ((unsigned long long)(uint32_t)j << 32) | (uint32_t)v;
+    }
+    bad = fw_wave_or(bad);
+    for (int o = 32; o > 0; o >>= 1) {
+        const int32_t l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) {
+        const long long cnt = b - a;  // (cnt < n: the implicit zeros differ from the stored counts >= 1)
+        colstat[j] = bad ? -bad : (cnt == 0 || (cnt == (long long)n && lo == hi)) ? 0 : 1;
+    }
+}
+
+// one thread per row over its run of the row-sorted entries: the totals of norm_row_stats_kernel + the host's chunk reduction
+__global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__restrict__ krow, const unsigned long long *__restrict__ pay,
+                                                            long long nnz, int n, const int32_t *__restrict__ colq, int pk,
+                                                            double *__restrict__ S, double *__restrict__ SL, int32_t *__restrict__ CNT,
+                                                            int32_t *__restrict__ MN)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    long long lo = 0, hi = nnz;  // first entry of row i
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (krow[mid] < (uint32_t)i)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    const int per = (pk + NORM_CHUNKS - 1) / NORM_CHUNKS;
+    double s = 0.0, sl = 0.0, cs = 0.0, csl = 0.0;
+    int cc = 0, cnt = 0, mn = 0x7fffffff;
+    for (long long e = lo; e < nnz && krow[e] == (uint32_t)i; ++e) {
+        const unsigned long long w = pay[e];
+        const int q = colq[(int)(w >> 32)];
+        if (q < 0) continue;
+        const int32_t v = (int32_t)(uint32_t)w;
+        const int c = q / per;
+        if (c != cc) {  // chunk boundary of the dense kernel: its partial joins the total, the next starts from 0.0
+            s += cs;
+            sl += csl;
+            cs = csl = 0.0;
+            cc = c;
+        }
+        cs += (double)v;
+        csl += log((double)v);
+        ++cnt;
+        mn = v < mn ? v : mn;
+    }
+    S[i] = s + cs;
+    SL[i] = sl + csl;
+    CNT[i] = cnt;
+    MN[i] = mn;
+}
+
+// binned_nz_clr, one workgroup per kept column: norm_binned_kernel with the keys read from the column's stored run (every entry
+// of a kept column lies in a kept row: its count >= 1 gives the row reads).  bins[e] for the input entry e; M = the padded
+// length of the longest kept column (sizes the key storage), each column sorts its own power of two.  One kernel for both
+// launch shapes (256 threads while M <= 2 048, the HE case; 1 024 beyond): the bound of 1 024 caps it at 128 VGPRs, it uses 66, so
+// the short form loses no occupancy to the cap.
+__global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                          const int32_t *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
+                                                          const int32_t *__restrict__ rownew, const double *__restrict__ gmean,
+                                                          int32_t *__restrict__ bins, int32_t *__restrict__ two, int M, double *gkeys)
+{
+    extern __shared__ double s_key_lds[];
+    __shared__ int s_b1, s_b2;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const NbKeys K{gkeys ? gkeys + (size_t)blockIdx.x * (size_t)M : s_key_lds, gkeys != nullptr};
+    for (int q = blockIdx.x; q < pk; q += gridDim.x) {
+        const long long a = colptr[cols[q]];
+        const int m = (int)(colptr[cols[q] + 1] - a);
+        int Mq = 2;
+        while (Mq < m) Mq <<= 1;
+        __syncthreads();  // (the previous column's last readers of the keys / s_b1 / s_b2)
+        if (tid == 0) s_b1 = s_b2 = 0;
+        for (int k = tid; k < m; k += nt) K.st(k, log((double)nzval[a + k] / gmean[rownew[rowval[a + k]]]));
+        K.sync();
+        nb_pad_sort(K, m, Mq, tid, nt);
+        const double rmax = nb_rank_max(K, m);
+        int b1 = 0, b2 = 0;
+        for (int k = tid; k < m; k += nt) {
+            const int bin = nb_bin(K, m, rmax, log((double)nzval[a + k] / gmean[rownew[rowval[a + k]]]));
+            b1 |= bin == 1;
+            b2 |= bin == 2;
+            bins[a + k] = bin;
+        }
+        if (b1) s_b1 = 1;
+        if (b2) s_b2 = 1;
+        __syncthreads();
+        if (tid == 0) two[q] = s_b1 && s_b2;
+    }
+}
+
+// one wavefront per output column f = input column fcols[f]: rows renumbered, values by mode
+//   0 FW_MI: 1    1 FW_MI_NZ: bins[e]    2 FW_FZ_NZ: (float)log(x / g_row), as norm_clr_out_kernel's mode 1
+__global__ __launch_bounds__(256) void csc_emit_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                       const int32_t *__restrict__ nzval, const int32_t *__restrict__ fcols, int pf,
+                                                       const int64_t *__restrict__ ocolptr, const int32_t *__restrict__ rownew,
+                                                       const double *__restrict__ gmean, const int32_t *__restrict__ bins, int mode,
+                                                       int32_t *__restrict__ orow, int32_t *__restrict__ oi, float *__restrict__ of)
+{
+    const int lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= pf) return;
+    const long long a = colptr[fcols[f]], dst = ocolptr[f];
+    const int m = (int)(ocolptr[f + 1] - dst);
+    for (int k = lane; k < m; k += 64) {
+        const int r = rownew[rowval[a + k]];
+        orow[dst + k] = r;
+        if (mode == 0)
+            oi[dst + k] = 1;
+        else if (mode == 1)
+            oi[dst + k] = bins[a + k];
+        else
+            of[dst + k] = (float)log((double)nzval[a + k] / gmean[r]);
+    }
+}
+
+// FW_FZ (clr_adapt), dense nk x pk output: every cell as an absent one (norm_clr_out_kernel's mode 0 with x == 0) ...
+__global__ __launch_bounds__(256) void csc_adapt_fill_kernel(int nk, int pk, const double *__restrict__ pseudo, const double *__restrict__ gmean,
+                                                             float *__restrict__ out)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nk) return;
+    const float o = (float)log(pseudo[r] / gmean[r]);
+    for (int q = blockIdx.y; q < pk; q += gridDim.y) out[(size_t)q * nk + r] = o;
+}
+
+// ... then the stored entries of the kept columns over them, one wavefront per kept column (entries of dropped rows are skipped)
+__global__ __launch_bounds__(256) void csc_adapt_scatter_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                                const int32_t *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
+                                                                const int32_t *__restrict__ rownew, int nk, const double *__restrict__ gmean,
+                                                                float *__restrict__ out)
+{
+    const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= pk) return;
+    const long long a = colptr[cols[q]], b = colptr[cols[q] + 1];
+    for (long long e = a + lane; e < b; e += 64) {
+        const int r = rownew[rowval[e]];
+        if (r >= 0) out[(size_t)q * nk + r] = (float)log((double)nzval[e] / gmean[r]);
+    }
+}
+
+}  // namespace
+
+extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                                       const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                                       uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
+{
+    const char *fn = "fw_normalize_counts_csc";
+    if (!colptr || !row_mask || !col_mask || !n_out || !p_out || !nnz_out || n <= 0 || p <= 0)
+        return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
+    if (kind != FW_FZ && kind != FW_FZ_NZ && kind != FW_MI && kind != FW_MI_NZ) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
+    const bool discrete = kind == FW_MI || kind == FW_MI_NZ;
+    if ((discrete ? !out_i32 : !out_f32) || (kind != FW_FZ && (!out_colptr || !out_rowval)))
+        return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
+    const long long nnz = colptr[p];
+    if (colptr[0] != 0 || nnz < 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: colptr must run from 0 to nnz (column 0)", fn);
+    if (nnz > 0x7fffffffll) return fw_fail(nullptr, FW_ERR_LIMIT, "%s: %lld stored entries exceed the 32-bit entry index", fn, nnz);
+    if (nnz > 0 && (!rowval || !nzval)) return fw_fail(nullptr, FW_ERR_ARG, "%s: NULL array", fn);
+    if (nnz == 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
+    int rc = FW_OK;
+    int64_t *d_colptr = nullptr, *d_ocolptr = nullptr;
+    int32_t *d_rowval = nullptr, *d_nzval = nullptr, *d_colstat = nullptr, *d_colq = nullptr, *d_cols = nullptr, *d_cnt = nullptr, *d_mn = nullptr,
+            *d_rownew = nullptr, *d_bins = nullptr, *d_two = nullptr, *d_orow = nullptr, *d_oi = nullptr;
+    uint32_t *d_krow = nullptr;
+    unsigned long long *d_pay = nullptr, *d_pay2 = nullptr;
+    double *d_S = nullptr, *d_SL = nullptr, *d_pseudo = nullptr, *d_g = nullptr, *d_keys = nullptr;
+    float *d_of = nullptr;
+    void *d_tmp = nullptr;
+    const unsigned wgrid_p = (unsigned)((p + 3) / 4);
+    {
+        NHIP(hipSetDevice(device));
+        NHIP(hipMalloc((void **)&d_colptr, sizeof(int64_t) * ((size_t)p + 1)));
+        NHIP(hipMalloc((void **)&d_rowval, sizeof(int32_t) * (size_t)nnz));
+        NHIP(hipMalloc((void **)&d_nzval, sizeof(int32_t) * (size_t)nnz));
+        NHIP(hipMalloc((void **)&d_colstat, sizeof(int32_t) * (size_t)p));
+        NHIP(hipMalloc((void **)&d_pay, sizeof(unsigned long long) * (size_t)nnz));
+        NHIP(hipMemcpy(d_colptr, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice));
+        NHIP(hipMemcpy(d_rowval, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+        NHIP(hipMemcpy(d_nzval, nzval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(csc_col_scan_kernel, dim3(wgrid_p), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, n, p, nnz, d_colstat, d_pay);
+        NHIP(hipGetLastError());
+        std::vector<int32_t> colstat((size_t)p), cols, colq((size_t)p, -1);
+        NHIP(hipMemcpy(colstat.data(), d_colstat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost));
+        for (int j = 0; j < p; ++j) {
+            if (colstat[j] < 0) {
+                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: column %d: %s", fn, j, fw_csc_reason(-colstat[j]));
+                goto done;
+            }
+            col_mask[j] = colstat[j] != 0;  // var(data, dims=1) .> 0
+            if (col_mask[j]) {
+                colq[j] = (int32_t)cols.size();
+                cols.push_back(j);
+            }
+        }
+        int pk = (int)cols.size();
+        if (pk == 0) {
+            rc = fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
+            goto done;
+        }
+        // CSR view: stable sort of the entries by row (the payload carries column and count)
+        int bits = 1;
+        while ((1ll << bits) < (long long)n) ++bits;
+        size_t tb = 0;
+        NHIP(hipMalloc((void **)&d_krow, sizeof(uint32_t) * (size_t)nnz));
+        NHIP(hipMalloc((void **)&d_pay2, sizeof(unsigned long long) * (size_t)nnz));
+        NHIP((rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)d_rowval, d_krow, (const unsigned long long *)d_pay, d_pay2, (size_t)nnz, 0u,
+                                        (unsigned int)bits, (hipStream_t)0)));
+        NHIP(hipMalloc(&d_tmp, tb ? tb : 1));
+        NHIP((rocprim::radix_sort_pairs(d_tmp, tb, (const uint32_t *)d_rowval, d_krow, (const unsigned long long *)d_pay, d_pay2, (size_t)nnz, 0u,
+                                        (unsigned int)bits, (hipStream_t)0)));
+        NHIP(hipMalloc((void **)&d_colq, sizeof(int32_t) * (size_t)p));
+        NHIP(hipMemcpy(d_colq, colq.data(), sizeof(int32_t) * (size_t)p, hipMemcpyHostToDevice));
+        NHIP(hipMalloc((void **)&d_S, sizeof(double) * (size_t)n));
+        NHIP(hipMalloc((void **)&d_SL, sizeof(double) * (size_t)n));
+        NHIP(hipMalloc((void **)&d_cnt, sizeof(int32_t) * (size_t)n));
+        NHIP(hipMalloc((void **)&d_mn, sizeof(int32_t) * (size_t)n));
+        hipLaunchKernelGGL(csc_row_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow, d_pay2, nnz, n, d_colq, pk, d_S, d_SL, d_cnt, d_mn);
+        NHIP(hipGetLastError());
+        std::vector<double> S((size_t)n), SL((size_t)n), pseudo, g;
+        std::vector<int32_t> CNT((size_t)n), RMIN((size_t)n), rows;
+        NHIP(hipMemcpy(S.data(), d_S, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        NHIP(hipMemcpy(SL.data(), d_SL, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        NHIP(hipMemcpy(CNT.data(), d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        NHIP(hipMemcpy(RMIN.data(), d_mn, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        std::vector<int64_t> NZ((size_t)n);
+        for (int i = 0; i < n; ++i) NZ[i] = (int64_t)pk - CNT[i];
+        if ((rc = norm_row_params(fn, kind, n, pk, S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
+        const int nk = (int)rows.size();
+        std::vector<int32_t> rownew((size_t)n, -1);  // row renumbering: the prefix sum over the row mask, on the host (n entries, uploaded)
+        for (int r = 0; r < nk; ++r) rownew[rows[r]] = r;
+        NHIP(hipMalloc((void **)&d_rownew, sizeof(int32_t) * (size_t)n));
+        NHIP(hipMemcpy(d_rownew, rownew.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        NHIP(hipMalloc((void **)&d_cols, sizeof(int32_t) * (size_t)pk));
+        NHIP(hipMemcpy(d_cols, cols.data(), sizeof(int32_t) * (size_t)pk, hipMemcpyHostToDevice));
+        NHIP(hipMalloc((void **)&d_g, sizeof(double) * (size_t)std::max(nk, 1)));
+        NHIP(hipMemcpy(d_g, g.data(), sizeof(double) * (size_t)nk, hipMemcpyHostToDevice));
+        if (kind == FW_FZ) {
+            if ((long long)nk * pk == 0) {
+                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no sample is left after the pseudo-counts", fn);
+                goto done;
+            }
+            NHIP(hipMalloc((void **)&d_pseudo, sizeof(double) * (size_t)nk));
+            NHIP(hipMemcpy(d_pseudo, pseudo.data(), sizeof(double) * (size_t)nk, hipMemcpyHostToDevice));
+            NHIP(hipMalloc((void **)&d_of, sizeof(float) * (size_t)nk * pk));
+            hipLaunchKernelGGL(csc_adapt_fill_kernel, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, nk, pk, d_pseudo, d_g, d_of);
+            hipLaunchKernelGGL(csc_adapt_scatter_kernel, dim3((unsigned)((pk + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pk, d_rownew,
+                               nk, d_g, d_of);
+            NHIP(hipGetLastError());
+            NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * (size_t)nk * pk, hipMemcpyDeviceToHost));
+            *n_out = nk;
+            *p_out = pk;
+            *nnz_out = (int64_t)nk * pk;
+            goto done;
+        }
+        // the sparse kinds: every entry of a kept column lies in a kept row, so a column keeps its stored length
+        std::vector<int32_t> fcols;  // output columns, as input column ids
+        if (kind == FW_FZ_NZ) {
+            fcols = cols;
+        } else if (kind == FW_MI) {  // presabs_norm!: two levels among the kept samples <=> an absence among them
+            for (int j : cols) {
+                if (colptr[j + 1] - colptr[j] < (int64_t)nk)
+                    fcols.push_back(j);
+                else
+                    col_mask[j] = 0;
+            }
+            if (fcols.empty()) {
+                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column with two levels", fn);
+                goto done;
+            }
+        } else {
+            int64_t mmax = 0;
+            for (int j : cols) mmax = std::max(mmax, colptr[j + 1] - colptr[j]);
+            int M = 2;
+            while (M < mmax) M <<= 1;
+            const bool keys_in_lds = M <= NORM_BIN_MAX;  // beyond: one slice of device memory per workgroup
+            const int bgrid = keys_in_lds ? pk : std::min(pk, 1024);
+            const int bthreads = M <= 2048 ? 256 : 1024;  // short columns (the HE case): more workgroups per CU instead of idle lanes
+            if (!keys_in_lds) NHIP(hipMalloc((void **)&d_keys, sizeof(double) * (size_t)M * (size_t)bgrid));
+            NHIP(hipMalloc((void **)&d_bins, sizeof(int32_t) * (size_t)nnz));
+            NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * (size_t)pk));
+            NHIP(hipFuncSetAttribute((const void *)csc_binned_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
+            hipLaunchKernelGGL(csc_binned_kernel, dim3(bgrid), dim3(bthreads), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_colptr, d_rowval, d_nzval,
+                               d_cols, pk, d_rownew, d_g, d_bins, d_two, M, d_keys);
+            NHIP(hipGetLastError());
+            std::vector<int32_t> two((size_t)pk);
+            NHIP(hipMemcpy(two.data(), d_two, sizeof(int32_t) * (size_t)pk, hipMemcpyDeviceToHost));
+            for (int q = 0; q < pk; ++q) {
+                if (two[q])
+                    fcols.push_back(cols[q]);
+                else
+                    col_mask[cols[q]] = 0;
+            }
+            if (fcols.empty()) {
+                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column whose non-zero abundances fall into two bins", fn);
+                goto done;
+            }
+        }
+        const int pf = (int)fcols.size();
+        std::vector<int64_t> ocolptr((size_t)pf + 1, 0);  // column compaction: the scan over the kept columns' lengths, on the host (p entries)
+        for (int f = 0; f < pf; ++f) ocolptr[f + 1] = ocolptr[f] + (colptr[fcols[f] + 1] - colptr[fcols[f]]);
+        const size_t onnz = (size_t)ocolptr[pf];
+        NHIP(hipMemcpy(d_cols, fcols.data(), sizeof(int32_t) * (size_t)pf, hipMemcpyHostToDevice));
+        NHIP(hipMalloc((void **)&d_ocolptr, sizeof(int64_t) * ((size_t)pf + 1)));
+        NHIP(hipMemcpy(d_ocolptr, ocolptr.data(), sizeof(int64_t) * ((size_t)pf + 1), hipMemcpyHostToDevice));
+        NHIP(hipMalloc((void **)&d_orow, sizeof(int32_t) * onnz));
+        if (discrete)
+            NHIP(hipMalloc((void **)&d_oi, sizeof(int32_t) * onnz));
+        else
+            NHIP(hipMalloc((void **)&d_of, sizeof(float) * onnz));
+        hipLaunchKernelGGL(csc_emit_kernel, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pf, d_ocolptr, d_rownew, d_g,
+                           d_bins, kind == FW_MI ? 0 : kind == FW_MI_NZ ? 1 : 2, d_orow, d_oi, d_of);
+        NHIP(hipGetLastError());
+        NHIP(hipMemcpy(out_rowval, d_orow, sizeof(int32_t) * onnz, hipMemcpyDeviceToHost));
+        if (discrete)
+            NHIP(hipMemcpy(out_i32, d_oi, sizeof(int32_t) * onnz, hipMemcpyDeviceToHost));
+        else
+            NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * onnz, hipMemcpyDeviceToHost));
+        std::copy(ocolptr.begin(), ocolptr.end(), out_colptr);
+        *n_out = nk;
+        *p_out = pf;
+        *nnz_out = (int64_t)onnz;
+    }
+done:
+    void *ptrs[] = {d_colptr, d_ocolptr, d_rowval, d_nzval, d_colstat, d_colq, d_cols, d_cnt, d_mn, d_rownew, d_bins, d_two, d_orow, d_oi,
+                    d_krow, d_pay, d_pay2, d_S, d_SL, d_pseudo, d_g, d_keys, d_of, d_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     return rc;

@@ -143,6 +143,10 @@ def load_library():
     L.fw_rejections_get.argtypes = [vp, vp]
     L.fw_normalize_counts.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32)]
+    if hasattr(L, "fw_normalize_counts_csc"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        L.fw_normalize_counts_csc.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.fw_set_data_csc_f32.argtypes = [vp, vp, vp, vp]
     L.fw_level0_sharded.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int64)]
     L.fw_level0_sharded_dev.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(_DevExchange), C.POINTER(C.c_int64)]
     L.fw_use_cor_buffer.argtypes = [vp, vp, C.c_int64]
@@ -176,10 +180,92 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def is_sparse(data):
+    """True for a scipy.sparse matrix / array (scipy is only imported when the object looks like one)."""
+    if not (hasattr(data, "tocsc") and hasattr(data, "nnz")):
+        return False
+    import scipy.sparse as sp
+    return bool(sp.issparse(data))
+
+
+class CSC(namedtuple("CSC", "colptr rowval nzval shape")):
+    """The canonical triple as_csc returns; handing it to as_csc / normalize_counts / Engine.set_data again costs nothing."""
+    __slots__ = ()
+
+
+def as_csc(data, dtype):
+    """Any scipy.sparse matrix / array, or a (colptr, rowval, nzval, (n, p)) tuple with 0-based indices -> the canonical CSC
+    triple (colptr int64, rowval int32, nzval dtype, (n, p)): duplicates summed, explicit zeros dropped, rows ascending within a
+    column -- the triple scipy.sparse.csc_matrix(dense) gives.  With an integer dtype the values must be integral and lie in
+    0 .. 2^31 - 1 (what the device front-end takes, as api._integral asks of a dense table), else ValueError.  Pure host code, O(nnz)."""
+    dtype = np.dtype(dtype)
+    if isinstance(data, CSC) and data.nzval.dtype == dtype:
+        return data  # already canonical
+    import scipy.sparse as sp
+    if isinstance(data, CSC):
+        data = tuple(data)
+    if isinstance(data, tuple):
+        if len(data) != 4:
+            raise ValueError("as_csc: a tuple must be (colptr, rowval, nzval, (n, p))")
+        m = sp.csc_matrix((np.asarray(data[2]), np.asarray(data[1]), np.asarray(data[0])), shape=tuple(int(v) for v in data[3]))
+    elif sp.issparse(data):
+        m = sp.csc_matrix(data)
+    else:
+        raise ValueError("as_csc: expected a scipy.sparse matrix or a (colptr, rowval, nzval, (n, p)) tuple, got %s" % type(data).__name__)
+    if m.data.dtype.kind not in "iuf":
+        raise ValueError("as_csc: values must be real numbers (got %s)" % m.data.dtype)
+    # sums of duplicates in a type that cannot wrap before the range check
+    m = m.astype(np.float64 if m.data.dtype.kind == "f" else np.int64 if m.data.dtype.kind == "i" else np.uint64, copy=True)
+    m.sum_duplicates()
+    m.eliminate_zeros()
+    m.sort_indices()
+    v = m.data
+    if dtype.kind in "iu":
+        if v.size and v.dtype.kind == "f" and (not np.all(np.isfinite(v)) or np.any(v != np.floor(v))):
+            raise ValueError("as_csc: non-integral values where integer counts are expected")
+        if v.size and (v.min() < 0 or v.max() > np.iinfo(np.int32).max):
+            raise ValueError("as_csc: counts must lie in 0 .. 2^31 - 1")
+    n, p = m.shape
+    if n >= 2**31 or p >= 2**31:
+        raise ValueError("as_csc: the shape exceeds the 32-bit row / column index")
+    return CSC(np.ascontiguousarray(m.indptr, dtype=np.int64), np.ascontiguousarray(m.indices, dtype=np.int32),
+               np.ascontiguousarray(v, dtype=dtype), (int(n), int(p)))
+
+
+def _normalize_counts_csc(L, counts, test_name, device):
+    import scipy.sparse as sp
+    colptr, rowval, nzval, (n, p) = as_csc(counts, np.int32)
+    if n <= 0 or p <= 0:
+        raise ValueError("normalize_counts: counts must be a samples x OTUs matrix")
+    kind = _KINDS[test_name]
+    nnz = int(colptr[-1])
+    rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
+    no, po, nz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    ocp, orow = np.zeros(p + 1, np.int64), np.zeros(max(nnz, 1), np.int32)
+    of = np.zeros(n * p if kind == FW_FZ else max(nnz, 1), np.float32) if kind in (FW_FZ, FW_FZ_NZ) else None
+    oi = np.zeros(max(nnz, 1), np.int32) if kind in (FW_MI, FW_MI_NZ) else None
+    rc = L.fw_normalize_counts_csc(device, kind, n, p, _ptr(colptr), _ptr(rowval), _ptr(nzval), _ptr(ocp), _ptr(orow), _ptr(oi), _ptr(of),
+                                   _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), C.byref(nz))
+    if rc != 0:
+        raise FlashWeaveError(rc, L.fw_last_error(None).decode())
+    if kind == FW_FZ:
+        out = of[:no.value * po.value].reshape((no.value, po.value), order="F")
+    else:  # (assembled field by field: the constructor would re-check and could drop the stored 0.0f of clr_nz)
+        out = sp.csc_matrix((no.value, po.value), dtype=np.float32 if of is not None else np.int32)
+        out.indptr, out.indices = ocp[:po.value + 1].astype(np.int32), orow[:nz.value].copy()  # (one index type, as scipy keeps it)
+        out.data = (of if of is not None else oi)[:nz.value].copy()
+    return out, rm.astype(bool), cm.astype(bool)
+
+
 def normalize_counts(counts, test_name, device=0):
     """Normalisation front-end on the device (fw_normalize_counts): -> (data, row_mask, col_mask) like preprocess.normalize,
-    for every test_name ("fz": clr_adapt, "fz_nz": clr_nz, "mi": binary, "mi_nz": binned_nz_clr)."""
+    for every test_name ("fz": clr_adapt, "fz_nz": clr_nz, "mi": binary, "mi_nz": binned_nz_clr).
+    A scipy.sparse count table (or what as_csc returned) takes fw_normalize_counts_csc and stays sparse: data is then a
+    scipy.sparse.csc_matrix (Int32 for "mi" / "mi_nz", Float32 for "fz_nz", where a stored 0.0 is a present count whose clr_nz value
+    is 0) and a dense array for "fz"; the values are the bits the dense table gives."""
     L = load_library()
+    if is_sparse(counts) or isinstance(counts, CSC):  # (any other tuple is a dense table, as before)
+        return _normalize_counts_csc(L, counts, test_name, device)
     raw = np.asarray(counts)
     if raw.ndim != 2:
         raise ValueError("normalize_counts: counts must be a samples x OTUs matrix")
@@ -254,9 +340,24 @@ class Engine:
 
     # -- data ----------------------------------------------------------------------------------------
     def set_data(self, data):
-        """fz: dense Float32 n x p; mi / mi_nz: integer n x p (dense ndarray) or a (colptr, rowval, nzval) CSC triple
-        with 0-based rows."""
-        if self.test_name in ("fz", "fz_nz"):
+        """fz: dense Float32 n x p; fz_nz: the same, a scipy.sparse matrix or a (colptr, rowval, nzval) CSC triple with float
+        values (fw_set_data_csc_f32: zeros = absences, nothing is densified on the host); mi / mi_nz: integer n x p (dense
+        ndarray), a scipy.sparse matrix or a (colptr, rowval, nzval) CSC triple with 0-based rows."""
+        if is_sparse(data) or isinstance(data, CSC):
+            if self.test_name == "fz":
+                raise ValueError("Engine.set_data: the plain \"fz\" test takes a dense matrix (sparse input is served for mi, mi_nz and fz_nz)")
+            if self.prec == 64:
+                raise ValueError("Engine.set_data: prec=64 takes a dense matrix")
+            colptr, rowval, nzval, shape = as_csc(data, np.float32 if self.test_name == "fz_nz" else np.int32)
+            assert shape == (self.n, self.p)
+            data = (colptr, rowval, nzval)
+        if self.test_name == "fz_nz" and isinstance(data, tuple):
+            colptr, rowval, nzval = (np.ascontiguousarray(data[0], dtype=np.int64),
+                                     np.ascontiguousarray(data[1], dtype=np.int32),
+                                     np.ascontiguousarray(data[2], dtype=np.float32))
+            assert colptr.shape == (self.p + 1,)
+            self._ck(self.L.fw_set_data_csc_f32(self.h, _ptr(colptr), _ptr(rowval), _ptr(nzval)))
+        elif self.test_name in ("fz", "fz_nz"):
             d = np.asfortranarray(np.asarray(data, dtype=np.float64 if self.prec == 64 else np.float32))
             assert d.shape == (self.n, self.p)
             self._ck((self.L.fw_set_data_dense_f64 if self.prec == 64 else self.L.fw_set_data_dense_f32)(self.h, _ptr(d)))

@@ -154,8 +154,16 @@ int fw_abi_version(void);
 
 /* FW_FZ: the normalised dense matrix (Matrix{Float32}, n x p column-major) the reference hands to
  * cor() in prepare_lgl (src/learning.jl:42-45).  FW_FZ_NZ: the clr_nz matrix with zeros = absences (the reference
- * holds it as SparseMatrixCSC{Float32}; the Julia shim densifies it once). */
+ * holds it as SparseMatrixCSC{Float32}; fw_set_data_csc_f32 takes it in that form). */
 int fw_set_data_dense_f32(fw_ctx *ctx, const float *data);
+
+/* FW_FZ_NZ only (FW_ERR_ARG on any other kind): the clr_nz matrix as SparseMatrixCSC{Float32,Int64} with 0-based colptr / rowval.  The
+ * triple is copied to the device and scattered there into the resident layout of fw_set_data_dense_f32 (values [p][n] and the plane
+ * of values != 0): the host never holds n x p floats, and the two uploads of one matrix leave identical device bytes.  A stored
+ * 0.0f means what a 0.0f cell means to the dense upload: an absence.  colptr must be monotone from 0 to nnz and the rows of a
+ * column strictly ascending in 0 .. n-1 (checked on the device, one pass): otherwise FW_ERR_ARG, the message names the first bad
+ * column, and the context holds no data until the next successful upload. */
+int fw_set_data_csc_f32(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);
 
 /* FW_MI / FW_MI_NZ: SparseMatrixCSC{Int32,Int64} as produced by normalize_data (make_sparse = true).
  * colptr has p+1 entries; rowval is 0-based and sorted within each column; values are 1..61, stored
@@ -354,6 +362,20 @@ int fw_rejections_get(const fw_ctx *ctx, fw_rejection *out);
  * (one-hot, discretisation: preprocess.py) and appended. */
 int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *counts, float *out_f32, int32_t *out_i32,
                         uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out);
+
+/* The same front-end on a sparse count table (SparseMatrixCSC{Int32,Int64}, 0-based colptr[p+1] / rowval, counts 1 .. 2^31-1), as the
+ * reference keeps heterogeneous data (make_sparse, src/learning.jl:470): O(nnz) work and memory on host and device, results bit-identical
+ * to fw_normalize_counts on the dense form of the same table.  Checked on the device in one pass: a non-monotone colptr, a row
+ * outside 0 .. n-1, unsorted or duplicate rows, a stored zero or a negative count give FW_ERR_ARG and the message names the first
+ * bad column.  At most 2^31-1 stored entries (FW_ERR_LIMIT).
+ * Outputs (host buffers): FW_MI / FW_MI_NZ: CSC Int32 out_colptr / out_rowval / out_i32 over the kept samples (renumbered) and
+ * kept variables -- what fw_set_data_csc_i32 takes; FW_FZ_NZ: CSC Float32 with out_f32 as values -- what fw_set_data_csc_f32
+ * takes; a kept entry whose clr_nz value is exactly 0 is a stored 0.0f; FW_FZ (clr_adapt, no cell is zero): dense *n_out x *p_out
+ * column-major in out_f32, out_colptr / out_rowval unused.  out_colptr holds p+1 entries, out_rowval and the value buffer the
+ * input's nnz (FW_FZ: n x p floats); the buffer of the other value type may be NULL.  *nnz_out = entries written. */
+int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                            const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                            uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out);
 
 /* Device self-test of hand-written arithmetic sequences that replace a compiler-generated IEEE sequence and must return the
  * same bits.  which = FW_SELFTEST_DIV: the unscaled Float64 division of the NaN-free partial-correlation path (statfuns.jl:44-62
