@@ -48,7 +48,7 @@ def _integral(a):
 def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
                   meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
-                  no_red_tests=True, track_rejections=False, **unsupported):
+                  no_red_tests=True, track_rejections=False, csc_resident=False, **unsupported):
     """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False); a numpy array or a scipy.sparse
     matrix.  A sparse table stays sparse end to end (what the reference does with make_sparse, learning.jl:470): normalize=True runs
     the device CSC front-end (integer counts only) and the sparse upload, normalize=False uploads the matrix as it is (Int32 levels
@@ -79,7 +79,12 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     prec (learning.jl:42-45, cont_type): 32 or 64 (16 and 128 are not served).  With the plain "fz" test, prec=64 runs the whole
     continuous pipeline in Float64 on the device: the Pearson matrix, level 0 and pcor_rec with its five-digit rounding (what the
     reference's golden networks were generated with); it needs recursive_pcor=True and dense_cor=True.  "fz_nz" keeps Float32 values
-    with Float64 arithmetic whatever prec says, and the discrete tests have no element type: parameters["prec"] records what ran."""
+    with Float64 arithmetic whatever prec says, and the discrete tests have no element type: parameters["prec"] records what ran.
+    csc_resident (default False): True keeps a sparse fz_nz table sparse on the device as well -- the bit plane, one 32-bit position
+    per plane word and the values != 0 (12 p ceil(n / 64) + 4 nnz bytes) instead of the n x p Float32 matrix -- for tables whose dense
+    form does not fit; the network is the same to the bit, the tests read each value through two more loads.  It needs sparse data,
+    sensitive=True, heterogeneous=True and recursive_pcor=True; anything else is refused (ValueError) before any device call.
+    counters["csc_resident"] and counters["data_resident_bytes"] (fz_nz only, else None) record what ran."""
     if unsupported:
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
     if prec not in (32, 64):
@@ -87,6 +92,17 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     import time
     test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
     eng_prec = 64 if (prec == 64 and test_name == "fz") else 32  # the element type of the device pipeline
+    csc_resident = bool(csc_resident)
+    if csc_resident:  # what the CSC-resident layout does not serve is refused by name, never densified
+        if test_name != "fz_nz":
+            raise ValueError("learn_network: csc_resident=True is served for sensitive=True, heterogeneous=True (fz_nz) only; the discrete "
+                             "kinds are bit-packed already and the plain fz test needs the dense matrix")
+        if not is_sparse(data):
+            raise ValueError("learn_network: csc_resident=True needs sparse data (a scipy.sparse matrix); a dense table is not "
+                             "converted silently")
+        if not recursive_pcor:
+            raise ValueError("learn_network: csc_resident=True with recursive_pcor=False is not supported: those conditional tests "
+                             "stream whole dense columns")
     if eng_prec == 64 and not (recursive_pcor and dense_cor):
         raise ValueError("learn_network: prec=64 with %s is not supported: the Float64 path conditions on the resident Float64 "
                          "Pearson matrix (recursive_pcor=True, dense_cor=True)"
@@ -153,22 +169,25 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
                  device=device, recursive_pcor=recursive_pcor, dense_cor=dense_cor, prec=eng_prec)
     try:
         # (what the device front-end returned is canonical already: its triple goes up as it is, stored 0.0f of clr_nz included)
-        eng.set_data((mat.indptr, mat.indices, mat.data) if (sparse and normalize and is_sparse(mat)) else mat)
+        eng.set_data((mat.indptr, mat.indices, mat.data) if (sparse and normalize and is_sparse(mat)) else mat, csc_resident=csc_resident)
         if test_name == "fz" and dense_cor:
             eng.compute_cor()
         net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests,
                       track_rejections=track_rejections)
         counters = eng.counters()
+        counters["data_resident_bytes"] = eng.data_resident_bytes() if (test_name == "fz_nz" and hasattr(eng.L, "fw_data_resident_bytes")) else None
     finally:
         eng.close()
     counters["t_normalize_s"] = t_norm
     counters["normalized_on_device"] = on_device
     counters["sparse_input"] = sparse
+    counters["csc_resident"] = csc_resident
     return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header),
                     parameters=dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha,
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,
                                     recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
                                     no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections), prec=eng_prec,
+                                    csc_resident=csc_resident,
                                     schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
                                               else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
                                               else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),

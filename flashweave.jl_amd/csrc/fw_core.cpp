@@ -159,7 +159,7 @@ int fw_ctx_destroy(fw_ctx *c)
     fwi_fz_fastdbg_print();
 #endif
     if (c->cor_external) c->d_cor = nullptr;  // caller-owned (fw_use_cor_buffer)
-    void *ptrs[] = {c->d_data64, c->d_xc64, c->d_sd64, c->d_cor64, c->d_data, c->d_xc, c->d_sd, c->d_cor, c->d_thr, c->d_fzs_stat, c->d_nzbits, c->d_hibits, c->d_levels, c->d_maxvals, c->d_firstnz, c->d_xlnx, c->d_gthr, c->d_vals};
+    void *ptrs[] = {c->d_data64, c->d_xc64, c->d_sd64, c->d_cor64, c->d_data, c->d_xc, c->d_sd, c->d_cor, c->d_thr, c->d_fzs_stat, c->d_nzbits, c->d_hibits, c->d_levels, c->d_maxvals, c->d_firstnz, c->d_xlnx, c->d_gthr, c->d_vals, c->d_cbase, c->d_cvals};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     free_dev(c->d_jobs);
@@ -378,6 +378,40 @@ int fw_set_data_csc_f32(fw_ctx *c, const int64_t *colptr, const int32_t *rowval,
     int rc = fwi_fznz_upload_csc(c, colptr, rowval, nzval);
     if (rc) return rc;
     c->have_data = true;
+    return FW_OK;
+}
+
+// A refused triple leaves the data, the level-0 lists and the network of the context as they were.  The upload stages the triple in
+// d_tmp1 and the scan's scratch in d_tmp2 before it knows whether the triple is good, so this rests on the rule that d_tmp0..2 are
+// scratch of the call that fills them and hold nothing that outlives it (level-0 results live in d_bh and on the host).
+int fw_set_data_csc_f32_resident(fw_ctx *c, const int64_t *colptr, const int32_t *rowval, const float *nzval)
+{
+    CHECK_CTX(c);
+    if (c->P.kind != FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_csc_f32_resident: context is not FW_FZ_NZ");
+    if (!c->P.recursive_pcor)
+        return fw_fail(c, FW_ERR_LIMIT, "fw_set_data_csc_f32_resident: recursive_pcor = 0 is not served on the CSC-resident layout (its kernels "
+                                        "stream whole dense columns); use fw_set_data_csc_f32");
+    if (!colptr || (colptr[c->P.p] > 0 && (!rowval || !nzval))) return fw_fail(c, FW_ERR_ARG, "fw_set_data_csc_f32_resident: NULL array");
+    int rc = fwi_fznz_upload_csc_resident(c, colptr, rowval, nzval);  // (a refused triple leaves the context as it was)
+    if (rc) return rc;
+    c->have_data = true;
+    c->have_level0 = false;
+    c->have_network = false;
+    return FW_OK;
+}
+
+int fw_data_resident_bytes(const fw_ctx *c, int64_t *bytes)
+{
+    CHECK_CTX(c);
+    if (c->P.kind != FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_data_resident_bytes: context is not FW_FZ_NZ");
+    if (!bytes) return fw_fail(c, FW_ERR_ARG, "fw_data_resident_bytes: NULL output");
+    if (!c->have_data) return fw_fail(c, FW_ERR_STATE, "fw_data_resident_bytes: no data uploaded");
+    const int64_t cells = (int64_t)c->P.p * c->W;
+    // the sizes asked of the allocator: values (matrix, or vals with its one-float minimum), plane, base
+    if (c->csc_resident)
+        *bytes = 4 * std::max<int64_t>(c->cvals_n, 1) + 8 * cells + 4 * cells;
+    else
+        *bytes = 4 * (int64_t)c->P.n * c->P.p + 8 * cells;
     return FW_OK;
 }
 

@@ -9,10 +9,12 @@
 // Compiled with -ffp-contract=off: the reference never fuses a*b+c and the partial-correlation value must be
 // reproducible to the bit (only +,-,*,/,sqrt,rint are involved).
 #include "fw_csc.h"
+#include "fw_cscres.h"
 #include "fw_internal.h"
 #include "fw_unrank.h"
 
 #include <algorithm>
+#include <rocprim/device/device_scan.hpp>
 #include <cmath>
 
 // ------------------------------------------------------------------------------------------------
@@ -989,29 +991,71 @@ int fwi_fz_segments(fw_ctx *ctx, int64_t nseg, int64_t nseg_tab, const FwSeg *d_
 // (T, candidate) job), hiton.jl:41-50,85 (row views).  Data layout: dense Float32 [p][n] column-major exactly as
 // uploaded (zeros = absences) + one nz bit plane [p][W].  All sums run sequentially over the rows in Float64 in row
 // order -- the same operation sequence as the oracle -- so correlations are reproducible to the bit.
+// CSC-resident layout (fw_set_data_csc_f32_resident, fw_cscres.h): the same plane, base[p][W] and the values != 0 instead of the
+// [p][n] matrix.  The kernels take the layout as a template parameter and read every value through FznzCol: the rows visited, their
+// order, the Float64 sums and the reduction trees are the same code, only the load of one value differs, so the two layouts give
+// the same bits.
 // ================================================================================================
 
+// One column of the resident data.  word(w) fetches what the layout keeps per plane word (nothing for the dense matrix; the plane
+// word and its base for the CSC form -- the two share an index and are loaded together, once per word instead of once per row);
+// at(word, row) is the value of a row inside that word, at_set the same for a row whose plane bit is known set.
+template <bool CSC>
+struct FznzCol;
+template <>
+struct FznzCol<false> {
+    const float *c;
+    struct Word {};
+    __device__ __forceinline__ FznzCol(const float *data, const unsigned long long *, const uint32_t *, int n, int, int v) : c(data + (size_t)v * n) {}
+    __device__ __forceinline__ Word word(int) const { return Word{}; }
+    __device__ __forceinline__ float at(Word, int row) const { return c[row]; }
+    __device__ __forceinline__ float at_set(Word, int row) const { return c[row]; }
+    __device__ __forceinline__ float at(int row) const { return c[row]; }
+};
+template <>
+struct FznzCol<true> {
+    const unsigned long long *m;
+    const uint32_t *b;
+    const float *vals;
+    struct Word {
+        unsigned long long m;
+        uint32_t b;
+    };
+    __device__ __forceinline__ FznzCol(const float *vals_, const unsigned long long *nz, const uint32_t *cbase, int, int W, int v)
+        : m(nz + (size_t)v * W), b(cbase + (size_t)v * W), vals(vals_)
+    {
+    }
+    __device__ __forceinline__ Word word(int w) const { return Word{m[w], b[w]}; }
+    __device__ __forceinline__ float at(Word wd, int row) const { return fw_cscres_word_value(wd.m, wd.b, vals, row & 63); }
+    __device__ __forceinline__ float at_set(Word wd, int row) const { return vals[fw_cscres_pos(wd.m, wd.b, row & 63)]; }
+    __device__ __forceinline__ float at(int row) const { return fw_cscres_value(m, b, vals, row); }
+};
+
 // ---- level 0: one thread per pair (16 x 16 pair tiles), two passes over the samples ----
+// (CSC: `data` is vals; both plane bits of a visited row are set, so a value's position needs no bit test, and the two base words are
+// loaded once per plane word)
+template <bool CSC>
 __global__ __launch_bounds__(256) void fznz_level0_kernel(const float *__restrict__ data, const unsigned long long *__restrict__ nz,
-                                                          int n, int p, int W, double alpha, long long n_obs_min,
+                                                          const uint32_t *__restrict__ cbase, int n, int p, int W, double alpha, long long n_obs_min,
                                                           FzL0Counters *cnt, unsigned long long cap, int32_t *out_i,
                                                           int32_t *out_j, double *out_s, double *out_p)
 {
     const int X = blockIdx.y * 16 + (threadIdx.x >> 4), Y = blockIdx.x * 16 + (threadIdx.x & 15);
     if (blockIdx.x * 16 + 15 <= blockIdx.y * 16) return;  // tile entirely on/below the diagonal
     const bool valid = X < Y && Y < p;
-    const float *cx = data + (size_t)(valid ? X : 0) * n, *cy = data + (size_t)(valid ? Y : 0) * n;
+    const FznzCol<CSC> cx(data, nz, cbase, n, W, valid ? X : 0), cy(data, nz, cbase, n, W, valid ? Y : 0);
     const unsigned long long *mx = nz + (size_t)(valid ? X : 0) * W, *my = nz + (size_t)(valid ? Y : 0) * W;
     double sum_x = 0.0, sum_y = 0.0;
     long long nn = 0;
     for (int w = 0; w < W; ++w) {
         unsigned long long m = valid ? (mx[w] & my[w]) : 0ull;
         nn += __popcll(m);
+        const typename FznzCol<CSC>::Word wx = cx.word(w), wy = cy.word(w);
         while (m) {
             const int row = w * 64 + __builtin_ctzll(m);
             m &= m - 1;
-            sum_x += (double)cx[row];
-            sum_y += (double)cy[row];
+            sum_x += (double)cx.at_set(wx, row);
+            sum_y += (double)cy.at_set(wy, row);
         }
     }
     double stat = 0.0, pval = 1.0;
@@ -1023,10 +1067,11 @@ __global__ __launch_bounds__(256) void fznz_level0_kernel(const float *__restric
             double cov = 0.0, vx = 0.0, vy = 0.0;
             for (int w = 0; w < W; ++w) {
                 unsigned long long m = mx[w] & my[w];
+                const typename FznzCol<CSC>::Word wx = cx.word(w), wy = cy.word(w);
                 while (m) {
                     const int row = w * 64 + __builtin_ctzll(m);
                     m &= m - 1;
-                    const double dx = (double)cx[row] - mean_x, dy = (double)cy[row] - mean_y;
+                    const double dx = (double)cx.at_set(wx, row) - mean_x, dy = (double)cy.at_set(wy, row) - mean_y;
                     cov += dx * dy;
                     vx += dx * dx;
                     vy += dy * dy;
@@ -1133,8 +1178,12 @@ static inline size_t fznz_lds_bytes(int m_cap, int n)
     return sizeof(double) * FZNZ_NW * FZNZ_RED_STRIDE + (size_t)m_cap * (2 * sizeof(double) + sizeof(int)) + 264 * sizeof(int) + rows;
 }
 
+// (CSC: `data` is vals.  A conditioning column may be zero at a row of the view, so its reads test the plane bit; the tree branch
+// reads whole rows of the LDS list through at(row) -- plane word and base fetched together, then the value -- and the sequential
+// branch fetches the column's word once per plane word of the view)
+template <bool CSC>
 __global__ __launch_bounds__(FZNZ_NT) void fznz_submat_kernel(const float *__restrict__ data, const unsigned long long *__restrict__ nz,
-                                                              int n, int W, FwNzJob *__restrict__ recs,
+                                                              const uint32_t *__restrict__ cbase, int n, int W, FwNzJob *__restrict__ recs,
                                                               const int32_t *__restrict__ accflat, float *__restrict__ arena,
                                                               double alpha, int m_cap, double xcrit,
                                                               double *__restrict__ arena64 /* recursive_pcor = 0: the UNROUNDED Float64
@@ -1184,15 +1233,15 @@ __global__ __launch_bounds__(FZNZ_NT) void fznz_submat_kernel(const float *__res
         __syncthreads();
         const int nr = (int)nR;
         for (int t = wave; t < m; t += FZNZ_NW) {  // column means and norms
-            const float *col = data + (size_t)s_var[t] * n;
+            const FznzCol<CSC> col(data, nz, cbase, n, W, s_var[t]);
             double sacc = 0.0;
 #pragma unroll 4
-            for (int q = lane; q < nr; q += 64) sacc += (double)col[s_rows[q]];
+            for (int q = lane; q < nr; q += 64) sacc += (double)col.at(s_rows[q]);
             const double mean = fznz_tree64(sacc) / (double)nR;
             double ss = 0.0;
 #pragma unroll 4
             for (int q = lane; q < nr; q += 64) {
-                const double d = (double)col[s_rows[q]] - mean;
+                const double d = (double)col.at(s_rows[q]) - mean;
                 ss += d * d;
             }
             ss = fznz_tree64(ss);
@@ -1218,16 +1267,20 @@ __global__ __launch_bounds__(FZNZ_NT) void fznz_submat_kernel(const float *__res
             while (A > 0 && A * (2 * nb - A + 1) / 2 > t) --A;
             while ((A + 1) * (2 * nb - A) / 2 <= t) ++A;
             const int B = A + (t - A * (2 * nb - A + 1) / 2);
-            const float *ca[4], *cb[4];
+            int va[4], vb[4];
             double ma[4], mb[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int ia = 4 * A + i < m ? 4 * A + i : m - 1, ib = 4 * B + i < m ? 4 * B + i : m - 1;
-                ca[i] = data + (size_t)s_var[ia] * n;
-                cb[i] = data + (size_t)s_var[ib] * n;
+                va[i] = s_var[ia];
+                vb[i] = s_var[ib];
                 ma[i] = s_mean[ia];
                 mb[i] = s_mean[ib];
             }
+            const FznzCol<CSC> ca[4] = {FznzCol<CSC>(data, nz, cbase, n, W, va[0]), FznzCol<CSC>(data, nz, cbase, n, W, va[1]),
+                                        FznzCol<CSC>(data, nz, cbase, n, W, va[2]), FznzCol<CSC>(data, nz, cbase, n, W, va[3])};
+            const FznzCol<CSC> cb[4] = {FznzCol<CSC>(data, nz, cbase, n, W, vb[0]), FznzCol<CSC>(data, nz, cbase, n, W, vb[1]),
+                                        FznzCol<CSC>(data, nz, cbase, n, W, vb[2]), FznzCol<CSC>(data, nz, cbase, n, W, vb[3])};
             double acc[16];
 #pragma unroll
             for (int c = 0; c < 16; ++c) acc[c] = 0.0;
@@ -1236,8 +1289,8 @@ __global__ __launch_bounds__(FZNZ_NT) void fznz_submat_kernel(const float *__res
                 double xa[4], xb[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    xa[i] = (double)ca[i][row] - ma[i];
-                    xb[i] = (double)cb[i][row] - mb[i];
+                    xa[i] = (double)ca[i].at(row) - ma[i];
+                    xb[i] = (double)cb[i].at(row) - mb[i];
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
@@ -1305,24 +1358,26 @@ __global__ __launch_bounds__(FZNZ_NT) void fznz_submat_kernel(const float *__res
     // sequential form (univariate jobs -- their pair statistic must equal level 0's, statfuns.jl:91-123 in row order -- and
     // views beyond the LDS row list): column means and norms over R, sequential Float64 sums in row order
     for (int t = tid; t < m; t += FZNZ_NT) {
-        const float *col = data + (size_t)s_var[t] * n;
+        const FznzCol<CSC> col(data, nz, cbase, n, W, s_var[t]);
         double sacc = 0.0;
         for (int w = 0; w < W; ++w) {
             unsigned long long mk = mx[w] & my[w];
+            const typename FznzCol<CSC>::Word cw = col.word(w);
             while (mk) {
                 const int row = w * 64 + __builtin_ctzll(mk);
                 mk &= mk - 1;
-                sacc += (double)col[row];
+                sacc += (double)col.at(cw, row);
             }
         }
         const double mean = sacc / (double)nR;
         double ss = 0.0;
         for (int w = 0; w < W; ++w) {
             unsigned long long mk = mx[w] & my[w];
+            const typename FznzCol<CSC>::Word cw = col.word(w);
             while (mk) {
                 const int row = w * 64 + __builtin_ctzll(mk);
                 mk &= mk - 1;
-                const double d = (double)col[row] - mean;
+                const double d = (double)col.at(cw, row) - mean;
                 ss += d * d;
             }
         }
@@ -1337,15 +1392,16 @@ __global__ __launch_bounds__(FZNZ_NT) void fznz_submat_kernel(const float *__res
         while (a > 0 && (long long)a * (2 * m - a - 1) / 2 > q) --a;
         while ((long long)(a + 1) * (2 * m - a - 2) / 2 <= q) ++a;
         const int b = a + 1 + (int)(q - (long long)a * (2 * m - a - 1) / 2);
-        const float *ca = data + (size_t)s_var[a] * n, *cb = data + (size_t)s_var[b] * n;
+        const FznzCol<CSC> ca(data, nz, cbase, n, W, s_var[a]), cb(data, nz, cbase, n, W, s_var[b]);
         const double ma = s_mean[a], mb = s_mean[b];
         double sacc = 0.0;
         for (int w = 0; w < W; ++w) {
             unsigned long long mk = mx[w] & my[w];
+            const typename FznzCol<CSC>::Word wa = ca.word(w), wb = cb.word(w);
             while (mk) {
                 const int row = w * 64 + __builtin_ctzll(mk);
                 mk &= mk - 1;
-                sacc += ((double)ca[row] - ma) * ((double)cb[row] - mb);
+                sacc += ((double)ca.at(wa, row) - ma) * ((double)cb.at(wb, row) - mb);
             }
         }
         if (q == 0) {  // (a, b) = (0, 1): the pair statistic of statfuns.jl:114-120, unrounded
@@ -1439,10 +1495,22 @@ __global__ __launch_bounds__(64) void fznz_single_kernel(const FwNzJob *__restri
     out[t] = o;
 }
 
+// a dense-resident upload replaces a CSC-resident one: base and vals go, the [p][n] matrix is allocated afresh below
+static void fznz_drop_cscres(fw_ctx *ctx)
+{
+    if (ctx->d_cbase) (void)hipFree(ctx->d_cbase);
+    if (ctx->d_cvals) (void)hipFree(ctx->d_cvals);
+    ctx->d_cbase = nullptr;
+    ctx->d_cvals = nullptr;
+    ctx->cvals_n = 0;
+    ctx->csc_resident = false;
+}
+
 int fwi_fznz_upload(fw_ctx *ctx, const float *data)
 {
     const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
     const size_t bytes = sizeof(float) * (size_t)n * p;
+    fznz_drop_cscres(ctx);
     if (!ctx->d_data) FW_HIP(ctx, hipMalloc(&ctx->d_data, bytes));
     FW_HIP(ctx, hipMemcpy(ctx->d_data, data, bytes, hipMemcpyHostToDevice));
     std::vector<uint64_t> nzb((size_t)p * W, 0);
@@ -1495,6 +1563,7 @@ int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowva
     const long long nnz = colptr[p];
     if (colptr[0] != 0 || nnz < 0) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32: colptr must run from 0 to nnz (column 0)");
     const size_t bytes = sizeof(float) * (size_t)n * p;
+    fznz_drop_cscres(ctx);
     if (!ctx->d_data) FW_HIP(ctx, hipMalloc(&ctx->d_data, bytes));
     if (ctx->d_nzbits) (void)hipFree(ctx->d_nzbits);
     ctx->d_nzbits = nullptr;
@@ -1523,6 +1592,148 @@ int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowva
     return FW_OK;
 }
 
+// fw_set_data_csc_f32_resident: the CSC-resident layout of fw_cscres.h built on the device from the staged triple, in three steps.
+//   plane     one wavefront per column: the column is checked (fw_csc.h) and its plane words are built as fznz_csc_scatter_kernel
+//             builds them; the popcount of every word goes to base[c][w], the column's count of values != 0 to a 64-bit total
+//   scan      rocPRIM exclusive scan of the popcounts over [p][W], in place: base
+//   compact   one thread per stored entry: a value != 0.0f goes to the position fw_cscres_pos gives its row
+// The plane kernel of a bad column writes zero words, so the later steps never see undefined counts; the host stops after it anyway.
+__global__ __launch_bounds__(256) void fznz_cscres_plane_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                                const float *__restrict__ nzval, int n, int p, int W, long long nnz,
+                                                                unsigned long long *__restrict__ nzb, uint32_t *__restrict__ cnt,
+                                                                int32_t *__restrict__ colstat, unsigned long long *__restrict__ total)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= p) return;
+    long long a, b;
+    const int bad = fw_csc_check_column(colptr, rowval, j, n, nnz, lane, &a, &b);
+    if (lane == 0) colstat[j] = bad;
+    unsigned long long mine = 0;
+    for (int w = lane; w < W; w += 64) {
+        unsigned long long word = 0;
+        if (!bad) {
+            long long lo = a, hi = b;  // first entry with row >= 64 w
+            while (lo < hi) {
+                const long long mid = (lo + hi) >> 1;
+                if (rowval[mid] < w * 64)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            for (long long e = lo; e < b && rowval[e] < w * 64 + 64; ++e)
+                if (nzval[e] != 0.0f) word |= 1ull << (rowval[e] & 63);
+        }
+        nzb[(size_t)j * W + w] = word;
+        cnt[(size_t)j * W + w] = (uint32_t)__popcll(word);
+        mine += (unsigned long long)__popcll(word);
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if (lane == 0 && mine) atomicAdd(total, mine);
+}
+
+// (rows are in 0 .. n-1 and ascending in every column: the plane kernel found no bad column before this one is launched)
+__global__ __launch_bounds__(256) void fznz_cscres_compact_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                                  const float *__restrict__ nzval, int p, int W,
+                                                                  const unsigned long long *__restrict__ nzb, const uint32_t *__restrict__ cbase,
+                                                                  float *__restrict__ vals, unsigned long long nvals)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= p) return;
+    const long long a = colptr[j], b = colptr[j + 1];
+    for (long long e = a + lane; e < b; e += 64) {
+        const float v = nzval[e];
+        if (v == 0.0f) continue;  // a stored zero (and -0.0f) is an absence: no plane bit, no entry
+        const int row = rowval[e];
+        const size_t k = (size_t)j * W + (row >> 6);
+        const uint32_t pos = fw_cscres_pos(nzb[k], cbase[k], row & 63);
+        if (pos < nvals) vals[pos] = v;
+    }
+}
+
+int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval)
+{
+    const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
+    const long long nnz = colptr[p];
+    if (colptr[0] != 0 || nnz < 0) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32_resident: colptr must run from 0 to nnz (column 0)");
+    const size_t cells = (size_t)p * W;
+    int rc;
+    // staging: the triple, the column flags and the 64-bit total (d_tmp1); the scan's scratch (d_tmp2)
+    const size_t o_row = ((sizeof(int64_t) * ((size_t)p + 1)) + 255) & ~(size_t)255, o_val = o_row + ((sizeof(int32_t) * (size_t)nnz + 255) & ~(size_t)255),
+                 o_stat = o_val + ((sizeof(float) * (size_t)nnz + 255) & ~(size_t)255), o_tot = o_stat + ((sizeof(int32_t) * (size_t)p + 255) & ~(size_t)255);
+    if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, o_tot + sizeof(unsigned long long)))) return rc;
+    size_t scan_bytes = 0;
+    FW_HIP(ctx, (rocprim::exclusive_scan(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, cells, rocprim::plus<uint32_t>(), ctx->stream)));
+    if ((rc = fw_dev_reserve(ctx, ctx->d_tmp2, std::max<size_t>(scan_bytes, 1)))) return rc;
+    // the new layout is built beside whatever the context holds and takes its place only when the triple is good
+    unsigned long long *plane = nullptr;
+    uint32_t *base = nullptr;
+    float *vals = nullptr;
+    auto drop = [&]() {
+        if (plane) (void)hipFree(plane);
+        if (base) (void)hipFree(base);
+        if (vals) (void)hipFree(vals);
+    };
+#define FZNZ_RES_HIP(call)                                                                                                         \
+    do {                                                                                                                           \
+        hipError_t e__ = (call);                                                                                                   \
+        if (e__ != hipSuccess) {                                                                                                   \
+            drop();                                                                                                                \
+            return fw_fail(ctx, e__ == hipErrorOutOfMemory ? FW_ERR_NOMEM : FW_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), \
+                           __FILE__, __LINE__);                                                                                    \
+        }                                                                                                                          \
+    } while (0)
+    FZNZ_RES_HIP(hipMalloc((void **)&plane, sizeof(unsigned long long) * cells));
+    FZNZ_RES_HIP(hipMalloc((void **)&base, sizeof(uint32_t) * cells));
+    char *B = (char *)ctx->d_tmp1.ptr;
+    FZNZ_RES_HIP(hipMemcpyAsync(B, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz > 0) {
+        FZNZ_RES_HIP(hipMemcpyAsync(B + o_row, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        FZNZ_RES_HIP(hipMemcpyAsync(B + o_val, nzval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    }
+    FZNZ_RES_HIP(hipMemsetAsync(B + o_tot, 0, sizeof(unsigned long long), ctx->stream));
+    const dim3 grid((unsigned)((p + 3) / 4));
+    hipLaunchKernelGGL(fznz_cscres_plane_kernel, grid, dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val),
+                       n, p, W, nnz, plane, base, (int32_t *)(B + o_stat), (unsigned long long *)(B + o_tot));
+    FZNZ_RES_HIP(hipGetLastError());
+    std::vector<int32_t> colstat((size_t)p);
+    unsigned long long nvals = 0;
+    FZNZ_RES_HIP(hipMemcpyAsync(colstat.data(), B + o_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+    FZNZ_RES_HIP(hipMemcpyAsync(&nvals, B + o_tot, sizeof(nvals), hipMemcpyDeviceToHost, ctx->stream));
+    FZNZ_RES_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->cnt.kernel_launches += 1;
+    for (int j = 0; j < p; ++j)
+        if (colstat[j]) {
+            drop();
+            return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32_resident: column %d: %s", j, fw_csc_reason(colstat[j]));
+        }
+    if (nvals >= (1ull << 32)) {
+        drop();
+        return fw_fail(ctx, FW_ERR_LIMIT, "fw_set_data_csc_f32_resident: %llu values != 0 exceed the 32-bit positions of the CSC-resident layout", nvals);
+    }
+    // (vals holds at least one float: position 0 stands in for an absent entry in fw_cscres_word_value)
+    FZNZ_RES_HIP(hipMalloc((void **)&vals, sizeof(float) * (size_t)std::max<unsigned long long>(nvals, 1)));
+    if (nvals == 0) FZNZ_RES_HIP(hipMemsetAsync(vals, 0, sizeof(float), ctx->stream));
+    FZNZ_RES_HIP((rocprim::exclusive_scan(ctx->d_tmp2.ptr, scan_bytes, (const uint32_t *)base, base, 0u, cells, rocprim::plus<uint32_t>(), ctx->stream)));
+    hipLaunchKernelGGL(fznz_cscres_compact_kernel, grid, dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val), p,
+                       W, (const unsigned long long *)plane, (const uint32_t *)base, vals, nvals);
+    FZNZ_RES_HIP(hipGetLastError());
+    FZNZ_RES_HIP(hipStreamSynchronize(ctx->stream));
+#undef FZNZ_RES_HIP
+    ctx->cnt.kernel_launches += 2;
+    // install: whatever either layout held before goes
+    fznz_drop_cscres(ctx);
+    if (ctx->d_data) (void)hipFree(ctx->d_data);
+    ctx->d_data = nullptr;
+    if (ctx->d_nzbits) (void)hipFree(ctx->d_nzbits);
+    ctx->d_nzbits = (uint64_t *)plane;
+    ctx->d_cbase = base;
+    ctx->d_cvals = vals;
+    ctx->cvals_n = (int64_t)nvals;
+    ctx->csc_resident = true;
+    ctx->W = W;
+    return FW_OK;
+}
+
 int fwi_fznz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                     std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev)
 {
@@ -1542,9 +1753,14 @@ int fwi_fznz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> 
         int32_t *oi = (int32_t *)ctx->d_tmp1.ptr, *oj = oi + cap;
         double *os = (double *)ctx->d_tmp2.ptr, *op = os + cap;
         dim3 grid((p + 15) / 16, (p + 15) / 16);
-        hipLaunchKernelGGL(fznz_level0_kernel, grid, dim3(256), 0, ctx->stream, ctx->d_data,
-                           (const unsigned long long *)ctx->d_nzbits, ctx->P.n, p, ctx->W, ctx->P.alpha,
-                           (long long)ctx->n_obs_min_eff, (FzL0Counters *)ctx->d_tmp0.ptr, cap, oi, oj, os, op);
+        if (ctx->csc_resident)
+            hipLaunchKernelGGL(fznz_level0_kernel<true>, grid, dim3(256), 0, ctx->stream, (const float *)ctx->d_cvals,
+                               (const unsigned long long *)ctx->d_nzbits, (const uint32_t *)ctx->d_cbase, ctx->P.n, p, ctx->W, ctx->P.alpha,
+                               (long long)ctx->n_obs_min_eff, (FzL0Counters *)ctx->d_tmp0.ptr, cap, oi, oj, os, op);
+        else
+            hipLaunchKernelGGL(fznz_level0_kernel<false>, grid, dim3(256), 0, ctx->stream, (const float *)ctx->d_data,
+                               (const unsigned long long *)ctx->d_nzbits, (const uint32_t *)nullptr, ctx->P.n, p, ctx->W, ctx->P.alpha,
+                               (long long)ctx->n_obs_min_eff, (FzL0Counters *)ctx->d_tmp0.ptr, cap, oi, oj, os, op);
         FW_HIP(ctx, hipGetLastError());
         FW_HIP(ctx, hipMemcpyAsync(&h, ctx->d_tmp0.ptr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1594,11 +1810,35 @@ static double fznz_xcrit(double alpha)
     return 0.5 * (lo + hi);
 }
 
+// The sub-matrix kernel of the context's layout: raises the instantiation's dynamic-LDS limit (above the 64 KB default) once per
+// context, i.e. per device, and launches it.  All three launch sites (host job pool, the two launches of the device rounds) go through here.
+static int fznz_submat_launch(fw_ctx *ctx, unsigned nblocks, size_t lds, hipStream_t stream, FwNzJob *d_recs, const int32_t *d_acc, float *d_arena, int m_cap,
+                              double *d_arena64, int m_lo)
+{
+    bool &raised = ctx->csc_resident ? ctx->fznz_lds_raised_csc : ctx->fznz_lds_raised;
+    if (!raised) {
+        FW_HIP(ctx, hipFuncSetAttribute(ctx->csc_resident ? (const void *)fznz_submat_kernel<true> : (const void *)fznz_submat_kernel<false>,
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160u * 1024u - 64u)));
+        raised = true;
+    }
+    if (ctx->csc_resident)
+        hipLaunchKernelGGL(fznz_submat_kernel<true>, dim3(nblocks), dim3(FZNZ_NT), lds, stream, (const float *)ctx->d_cvals,
+                           (const unsigned long long *)ctx->d_nzbits, (const uint32_t *)ctx->d_cbase, ctx->P.n, ctx->W, d_recs, d_acc, d_arena, ctx->P.alpha,
+                           m_cap, fznz_xcrit(ctx->P.alpha), d_arena64, m_lo);
+    else
+        hipLaunchKernelGGL(fznz_submat_kernel<false>, dim3(nblocks), dim3(FZNZ_NT), lds, stream, (const float *)ctx->d_data,
+                           (const unsigned long long *)ctx->d_nzbits, (const uint32_t *)nullptr, ctx->P.n, ctx->W, d_recs, d_acc, d_arena, ctx->P.alpha,
+                           m_cap, fznz_xcrit(ctx->P.alpha), d_arena64, m_lo);
+    return FW_OK;
+}
+
 // recs_host: one record per job of this launch (X, Y, acc_off, acc_len, m, cor_off filled); d_acc: flat accepted ints
 int fwi_fznz_submatrices(fw_ctx *ctx, int64_t njobs, const FwNzJob *recs_host, size_t arena_floats, const int32_t *d_acc,
                          hipStream_t stream, bool f64)
 {
     int rc;
+    if (f64 && ctx->csc_resident)
+        return fw_fail(ctx, FW_ERR_LIMIT, "fz_nz: recursive_pcor = 0 is not served on the CSC-resident layout (fw_set_data_csc_f32_resident)");
     static const bool nz_trace = fw_knob_set(knob::FW_NZ_TRACE);  // profiling: shape of every sub-matrix launch
     if (nz_trace) {
         long long mmax = 0, pairs = 0, uni = 0;
@@ -1618,13 +1858,9 @@ int fwi_fznz_submatrices(fw_ctx *ctx, int64_t njobs, const FwNzJob *recs_host, s
     const size_t lds = fznz_lds_bytes(m_cap, ctx->P.n);
     if (lds > 160u * 1024u - 64u)
         return fw_fail(ctx, FW_ERR_LIMIT, "fz_nz: a job with %d variables does not fit the LDS of one workgroup", m_cap);
-    if (!ctx->fznz_lds_raised) {  // raise the kernel's dynamic-LDS limit (above the 64 KB default) once per context, i.e. per device
-        FW_HIP(ctx, hipFuncSetAttribute((const void *)fznz_submat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160u * 1024u - 64u)));
-        ctx->fznz_lds_raised = true;
-    }
-    hipLaunchKernelGGL(fznz_submat_kernel, dim3((unsigned)njobs), dim3(FZNZ_NT), lds, stream, ctx->d_data,
-                       (const unsigned long long *)ctx->d_nzbits, ctx->P.n, ctx->W, (FwNzJob *)ctx->d_nzrecs.ptr, d_acc,
-                       (float *)ctx->d_arena.ptr, ctx->P.alpha, m_cap, fznz_xcrit(ctx->P.alpha), f64 ? (double *)ctx->d_arena.ptr : (double *)nullptr, 0);
+    if ((rc = fznz_submat_launch(ctx, (unsigned)njobs, lds, stream, (FwNzJob *)ctx->d_nzrecs.ptr, d_acc, (float *)ctx->d_arena.ptr, m_cap,
+                                 f64 ? (double *)ctx->d_arena.ptr : (double *)nullptr, 0)))
+        return rc;
     FW_HIP(ctx, hipGetLastError());
     ctx->cnt.kernel_launches += 1;
     return FW_OK;
@@ -1641,19 +1877,13 @@ int fwi_fznz_dev_limits(fw_ctx *ctx, int m_max)
 }
 int fwi_fznz_submatrices_dev(fw_ctx *ctx, int nslots, FwNzJob *d_recs, const int32_t *d_acc, float *d_arena, int m_max, bool any_long, hipStream_t stream)
 {
-    if (!ctx->fznz_lds_raised) {
-        FW_HIP(ctx, hipFuncSetAttribute((const void *)fznz_submat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160u * 1024u - 64u)));
-        ctx->fznz_lds_raised = true;
-    }
+    int rc;
     const int m_small = std::min(FZNZ_DEV_SMALL, (std::max(m_max, 4) + 15) & ~15);
-    hipLaunchKernelGGL(fznz_submat_kernel, dim3((unsigned)nslots), dim3(FZNZ_NT), fznz_lds_bytes(m_small, ctx->P.n), stream, ctx->d_data,
-                       (const unsigned long long *)ctx->d_nzbits, ctx->P.n, ctx->W, d_recs, d_acc, d_arena, ctx->P.alpha, m_small,
-                       fznz_xcrit(ctx->P.alpha), (double *)nullptr, 0);
+    if ((rc = fznz_submat_launch(ctx, (unsigned)nslots, fznz_lds_bytes(m_small, ctx->P.n), stream, d_recs, d_acc, d_arena, m_small, (double *)nullptr, 0))) return rc;
     if (any_long && m_max > m_small) {
         const int m_cap = (m_max + 15) & ~15;
-        hipLaunchKernelGGL(fznz_submat_kernel, dim3((unsigned)nslots), dim3(FZNZ_NT), fznz_lds_bytes(m_cap, ctx->P.n), stream, ctx->d_data,
-                           (const unsigned long long *)ctx->d_nzbits, ctx->P.n, ctx->W, d_recs, d_acc, d_arena, ctx->P.alpha, m_cap,
-                           fznz_xcrit(ctx->P.alpha), (double *)nullptr, m_small);
+        if ((rc = fznz_submat_launch(ctx, (unsigned)nslots, fznz_lds_bytes(m_cap, ctx->P.n), stream, d_recs, d_acc, d_arena, m_cap, (double *)nullptr, m_small)))
+            return rc;
     }
     FW_HIP(ctx, hipGetLastError());
     return FW_OK;

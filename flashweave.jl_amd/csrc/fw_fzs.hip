@@ -759,6 +759,7 @@ int fwi_fzs_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *
                        fw_test_result *out)
 {
     if (m == 0) return FW_OK;
+    if (ctx->csc_resident) return fw_fail(ctx, FW_ERR_LIMIT, "recursive_pcor = 0 is not served on the CSC-resident layout (fw_set_data_csc_f32_resident)");
     if (!ctx->d_data) return fw_fail(ctx, FW_ERR_STATE, "recursive_pcor = 0 needs the data matrix on the device (fw_set_data_dense_f32)");
     const int64_t nz = zoff[m];
     int kmax = 0;
@@ -796,6 +797,7 @@ int fwi_fzs_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32
                      const FwNzJob *recs_host, int64_t njobs, size_t arena_doubles)
 {
     if (nseg == 0) return FW_OK;
+    if (ctx->csc_resident) return fw_fail(ctx, FW_ERR_LIMIT, "recursive_pcor = 0 is not served on the CSC-resident layout (fw_set_data_csc_f32_resident)");
     if (!ctx->d_data) return fw_fail(ctx, FW_ERR_STATE, "recursive_pcor = 0 needs the data matrix on the device (fw_set_data_dense_f32)");
     if (int rc = fzs_ensure_stat(ctx, pb.launch_stream)) return rc;
     // job-local correlation matrices (fzs_gram_kernel) unless FW_FZS_GRAM=0 (profiling / parity knob: every test streams its columns)
@@ -843,6 +845,7 @@ int fwi_fzs_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32
 int fwi_fzs_segments_nz(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, FwPoolBuf &pb, int m_max)
 {
     if (nseg == 0) return FW_OK;
+    if (ctx->csc_resident) return fw_fail(ctx, FW_ERR_LIMIT, "recursive_pcor = 0 is not served on the CSC-resident layout (fw_set_data_csc_f32_resident)");
     FW_HIP(ctx, hipEventRecord(pb.ev0, pb.launch_stream));
     FzsDev P;
     P.data = (const float *)ctx->d_data;

@@ -177,6 +177,12 @@ struct fw_ctx {
     // one table per wavefront of a launch in device memory, launches cut so that the tables of one fit mig_gtab_bytes_max
     long long mig_gtab_words = 0;  // words of one table (0: the table lives in LDS)
     FwDevBuf d_mig_tab[3];  // [the engine's own stream, pool 0, pool 1]: two pools can be in flight
+    // fz_nz, CSC-resident layout (fw_set_data_csc_f32_resident, fw_cscres.h): d_nzbits is the plane, d_data stays null
+    bool csc_resident = false;
+    uint32_t *d_cbase = nullptr;  // [p][W] position in d_cvals of the column's first entry at or after row 64 w
+    float *d_cvals = nullptr;     // values != 0.0f, column after column, rows ascending (max(cvals_n, 1) floats)
+    int64_t cvals_n = 0;
+    bool fznz_lds_raised_csc = false;  // as fznz_lds_raised, for the kernel's CSC instantiation
     bool fznz_lds_raised = false;  // fznz_submat_kernel's dynamic-LDS limit was raised on this context's device (a property of (function, device): one flag per context, set under the context's own launches)
     float *d_xlnx = nullptr;       // [x ln x | ln x] for x = 0..n (Float32 tables of the discrete level-0 screen)
     int32_t *d_firstnz = nullptr;  // per column: index of the first non-zero sample (n if none)
@@ -274,6 +280,7 @@ int fwi_fzs_segments_nz(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const in
 // ---- HE-S / fz_nz (fw_fz.hip) ----
 int fwi_fznz_upload(fw_ctx *ctx, const float *data);
 int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);  // the same layout from a CSC triple
+int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);  // plane + base + values != 0 (fw_cscres.h)
 int fwi_fznz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                     std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev);
 int fwi_fznz_submatrices(fw_ctx *ctx, int64_t njobs, const FwNzJob *recs_host, size_t arena_floats, const int32_t *d_acc,

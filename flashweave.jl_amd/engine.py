@@ -147,6 +147,9 @@ def load_library():
         L.fw_normalize_counts_csc.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.fw_set_data_csc_f32.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "fw_set_data_csc_f32_resident"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        L.fw_set_data_csc_f32_resident.argtypes = [vp, vp, vp, vp]
+        L.fw_data_resident_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
     L.fw_level0_sharded.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int64)]
     L.fw_level0_sharded_dev.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(_DevExchange), C.POINTER(C.c_int64)]
     L.fw_use_cor_buffer.argtypes = [vp, vp, C.c_int64]
@@ -327,6 +330,11 @@ class Engine:
         if rc != 0:
             raise FlashWeaveError(rc, self.L.fw_last_error(self.h).decode())
 
+    def _need(self, symbol, what):
+        # (an older build loaded through FW_LIB_PATH for A/B profiling may lack the newer entry points: refused by name)
+        if not hasattr(self.L, symbol):
+            raise FlashWeaveError(-5, "%s is not served by this build of libflashweave_amd.so (%s is missing from %s)" % (what, symbol, lib_path()))
+
     def close(self):
         if getattr(self, "h", None):
             self.L.fw_ctx_destroy(self.h)
@@ -339,10 +347,19 @@ class Engine:
             pass
 
     # -- data ----------------------------------------------------------------------------------------
-    def set_data(self, data):
+    def set_data(self, data, csc_resident=False):
         """fz: dense Float32 n x p; fz_nz: the same, a scipy.sparse matrix or a (colptr, rowval, nzval) CSC triple with float
         values (fw_set_data_csc_f32: zeros = absences, nothing is densified on the host); mi / mi_nz: integer n x p (dense
-        ndarray), a scipy.sparse matrix or a (colptr, rowval, nzval) CSC triple with 0-based rows."""
+        ndarray), a scipy.sparse matrix or a (colptr, rowval, nzval) CSC triple with 0-based rows.
+        csc_resident=True (fz_nz with sparse input or a triple only, else ValueError): the data stays sparse on the device as well
+        (fw_set_data_csc_f32_resident: plane + base + the values != 0 instead of the n x p matrix); results are the same bits."""
+        if csc_resident:
+            if self.test_name != "fz_nz":
+                raise ValueError("Engine.set_data: csc_resident=True is served for test_name \"fz_nz\" only (got %r)" % (self.test_name,))
+            if not (is_sparse(data) or isinstance(data, tuple)):
+                raise ValueError("Engine.set_data: csc_resident=True takes a scipy.sparse matrix or a (colptr, rowval, nzval) CSC triple, "
+                                 "not a dense matrix")
+            self._need("fw_set_data_csc_f32_resident", "csc_resident=True")
         if is_sparse(data) or isinstance(data, CSC):
             if self.test_name == "fz":
                 raise ValueError("Engine.set_data: the plain \"fz\" test takes a dense matrix (sparse input is served for mi, mi_nz and fz_nz)")
@@ -356,7 +373,8 @@ class Engine:
                                      np.ascontiguousarray(data[1], dtype=np.int32),
                                      np.ascontiguousarray(data[2], dtype=np.float32))
             assert colptr.shape == (self.p + 1,)
-            self._ck(self.L.fw_set_data_csc_f32(self.h, _ptr(colptr), _ptr(rowval), _ptr(nzval)))
+            upload = self.L.fw_set_data_csc_f32_resident if csc_resident else self.L.fw_set_data_csc_f32
+            self._ck(upload(self.h, _ptr(colptr), _ptr(rowval), _ptr(nzval)))
         elif self.test_name in ("fz", "fz_nz"):
             d = np.asfortranarray(np.asarray(data, dtype=np.float64 if self.prec == 64 else np.float32))
             assert d.shape == (self.n, self.p)
@@ -370,6 +388,14 @@ class Engine:
             d = np.asfortranarray(np.asarray(data, dtype=np.int32))
             assert d.shape == (self.n, self.p)
             self._ck(self.L.fw_set_data_dense_i32(self.h, _ptr(d)))
+
+    def data_resident_bytes(self):
+        """fz_nz: bytes of device memory the context holds for the data (fw_data_resident_bytes) -- 4 n p + 8 p W dense-resident,
+        12 p W + 4 nnz' CSC-resident (W = ceil(n / 64), nnz' = values != 0)."""
+        self._need("fw_data_resident_bytes", "data_resident_bytes()")
+        b = C.c_int64(0)
+        self._ck(self.L.fw_data_resident_bytes(self.h, C.byref(b)))
+        return b.value
 
     def set_cor_mat(self, cor_mat):
         cm = np.asfortranarray(np.asarray(cor_mat, dtype=np.float64 if self.prec == 64 else np.float32))

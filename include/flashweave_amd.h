@@ -165,6 +165,21 @@ int fw_set_data_dense_f32(fw_ctx *ctx, const float *data);
  * column, and the context holds no data until the next successful upload. */
 int fw_set_data_csc_f32(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);
 
+/* FW_FZ_NZ only (FW_ERR_ARG on any other kind): the same triple, kept sparse on the device -- the CSC-resident layout.  Resident are
+ * the plane of values != 0 ([p][W] 64-bit words, W = ceil(n / 64)), base[p][W] (uint32: the position in `vals` of the column's first
+ * entry at or after row 64 w) and vals (the values != 0.0f, column after column, rows ascending): 12 p W + 4 nnz' bytes instead of
+ * 4 n p + 8 p W, nnz' = the number of values != 0; the n x p matrix is never allocated, and neither rowval nor colptr stays resident.
+ * A stored 0.0f (and -0.0f) is an absence and is dropped while the layout is built.  Level 0, fw_test_batch, fw_test_subsets_batch
+ * and fw_learn_network* run the same kernels with another load of each value: results are the bits of the dense-resident layout.
+ * The triple is checked as fw_set_data_csc_f32 checks it (same messages); a refused triple leaves the context as it was.  An upload
+ * of either layout replaces what the other held.  FW_ERR_LIMIT: nnz' >= 2^32, and recursive_pcor = 0 (the message names it; its
+ * kernels stream whole dense columns). */
+int fw_set_data_csc_f32_resident(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);
+
+/* FW_FZ_NZ: bytes of device memory the context holds for the data, as asked of the allocator -- dense-resident: 4 n p (values) +
+ * 8 p W (plane); CSC-resident: 4 max(nnz', 1) (vals) + 8 p W (plane) + 4 p W (base).  FW_ERR_STATE before the first upload. */
+int fw_data_resident_bytes(const fw_ctx *ctx, int64_t *bytes);
+
 /* FW_MI / FW_MI_NZ: SparseMatrixCSC{Int32,Int64} as produced by normalize_data (make_sparse = true).
  * colptr has p+1 entries; rowval is 0-based and sorted within each column; values are 1..61, stored
  * zeros are not allowed.  Values 1..2 everywhere (presence / absence, the two bins of binned_nz_clr): two bit planes per variable, the
