@@ -1,11 +1,13 @@
 """`learn_network`: the reference's user entry point (src/learning.jl:466-598) for the modes this engine covers, as a thin
 composition of the normalisation front-end, the device engine and the host driver.  Keyword names and defaults
 follow the reference; unsupported options raise instead of being silently ignored."""
+import os
+
 import numpy as np
 
 from . import io as fio
 from . import preprocess as pre
-from .engine import Engine, as_csc, is_sparse, normalize_counts
+from .engine import CSC, Engine, as_csc, is_sparse, normalize_counts
 
 
 class FWResult(dict):
@@ -44,11 +46,147 @@ def _integral(a):
     return bool(np.issubdtype(a.dtype, np.floating) and np.all(np.isfinite(a)) and np.all(a == np.floor(a)) and
                 a.max() < 2**31 and a.min() >= 0)
 
+_TEST_NAMES = ("fz", "fz_nz", "mi", "mi_nz")
 
-def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
+
+def _is_path(x):
+    return isinstance(x, (str, os.PathLike))
+
+
+def _load_paths(paths, meta_data_path, transposed):
+    """learn_network(data_path | all_data_paths, meta_data_path) (learning.jl:354-401): the first path is the main table, the others
+    become extra_data with their file headers; only the main table has meta data.  io.load_data decides what is readable."""
+    meta_path = None if meta_data_path is None else os.fspath(meta_data_path)
+    data, header, meta_data, meta_header = fio.load_data(os.fspath(paths[0]), meta_path, transposed=transposed)
+    extra = [fio.load_data(os.fspath(q), None, transposed=transposed)[:2] for q in paths[1:]]
+    return data, header, meta_data, meta_header, extra
+
+
+def _sparse_refusals(who, test_name, normalize, prec, device_normalize, meta_data):
+    """What a sparse table is not served with: each would need the dense matrix, and densifying silently would defeat the point."""
+    if not device_normalize:
+        raise ValueError("%s: sparse data with device_normalize=False is not supported: the host front-end "
+                         "(preprocess.py) is dense; pass data.toarray() or leave device_normalize=True" % who)
+    if prec == 64:
+        raise ValueError("%s: sparse data with prec=64 is not supported: the Float64 path takes a dense matrix" % who)
+    if meta_data is not None:
+        raise ValueError("%s: sparse data with meta_data is not supported: append the prepared meta columns to "
+                         "`data` yourself (preprocess.normalize_with_meta)" % who)
+    if test_name == "fz" and not normalize:
+        raise ValueError("%s: sparse data with sensitive=True, heterogeneous=False, normalize=False is not supported: "
+                         "the plain fz test needs the dense matrix, pass one" % who)
+
+
+def _canonical_csc(who, data, test_name, normalize):
+    try:
+        return as_csc(data, np.int32 if (normalize or test_name in ("mi", "mi_nz")) else np.float32)
+    except ValueError as e:
+        raise ValueError("%s: sparse data with normalize=%s needs %s (%s)"
+                         % (who, normalize, "integer counts in 0 .. 2^31 - 1: the device front-end takes nothing else" if normalize
+                            else "integer levels", e)) from None
+
+
+def _shape(t):
+    return tuple(t[3]) if isinstance(t, CSC) else tuple(t.shape)
+
+
+def _extra_tables(who, data, extra_data, test_name, normalize):
+    """Checks learn_network's / normalize_data's extra_data against the main table (an array or what as_csc returned) before anything
+    reaches a device -> [(table, header)] in the caller's order, sparse tables canonical.  A missing header is numbered on from the
+    main table's columns, as the reference does (learning.jl:506-520)."""
+    if extra_data is None:
+        return []
+    sparse, (n, n_named) = isinstance(data, CSC), _shape(data)
+    if not isinstance(extra_data, (list, tuple)):
+        raise ValueError("%s: extra_data must be a list of (table, header) pairs, got %s" % (who, type(extra_data).__name__))
+    out = []
+    for i, entry in enumerate(extra_data):
+        if not (isinstance(entry, (list, tuple)) and len(entry) == 2):
+            raise ValueError("%s: extra_data[%d] is not a (table, header) pair" % (who, i))
+        tab, hdr = entry
+        if not (is_sparse(tab) or isinstance(tab, CSC)):
+            tab = np.asarray(tab)
+            if tab.ndim != 2 or tab.dtype.kind not in "biuf":
+                raise ValueError("%s: extra_data[%d] is not a (table, header) pair: the table must be a samples x OTUs matrix of "
+                                 "numbers" % (who, i))
+        if hdr is not None and (isinstance(hdr, (str, bytes)) or not hasattr(hdr, "__len__")):
+            raise ValueError("%s: extra_data[%d] is not a (table, header) pair: the header must be a list of names or None" % (who, i))
+        if (is_sparse(tab) or isinstance(tab, CSC)) != sparse:
+            raise ValueError("%s: extra_data[%d] is %s while data is %s: a mix of sparse and dense tables is not supported, pass all "
+                             "of them in one form" % (who, i, "dense" if sparse else "sparse", "sparse" if sparse else "dense"))
+        rows, cols = _shape(tab)
+        if rows != n:
+            raise ValueError("%s: extra_data[%d] has %d rows, data has %d: every table holds the same samples in the same order"
+                             % (who, i, rows, n))
+        if hdr is None:
+            hdr = ["X%d" % (n_named + j + 1) for j in range(cols)]
+            n_named += cols
+        elif len(hdr) != cols:
+            raise ValueError("%s: extra_data[%d] has a header of %d names for %d columns" % (who, i, len(hdr), cols))
+        out.append((tab, [str(h) for h in hdr]))
+    return [(_canonical_csc(who, t, test_name, normalize), h) for t, h in out] if sparse else out
+
+
+def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device):
+    """Every table through ONE front-end -- the device one when all of them are count tables it takes (sparse, or _integral) and
+    prec == 32 and device_normalize, else the host one -- each on its own (its own row sums, geometric means, pseudo-counts and
+    filters), then preprocess.combine_data.  -> (dict(data, header, meta_mask, row_mask), on_device)"""
+    on_device = bool(device_normalize and prec == 32 and all(isinstance(t, CSC) or _integral(t) for t in [data] + [t for t, _ in extra]))
+    dev_norm = (lambda c, t: normalize_counts(c, t, device=device)) if on_device else None
+    if meta_data is not None:
+        r = pre.normalize_with_meta(data, test_name, meta_data, prec=prec, header=header, meta_header=meta_header,
+                                    make_onehot=make_onehot, normalizer=dev_norm)
+        main = dict(data=r["data"], header=r["header"], meta_mask=np.asarray(r["meta_mask"], dtype=bool), row_mask=r["row_mask"])
+    else:
+        mat, row_mask, col_mask = dev_norm(data, test_name) if on_device else pre.normalize(data, test_name, prec=prec)
+        hdr = [h for h, k in zip(header, col_mask) if k]
+        main = dict(data=mat, header=hdr, meta_mask=np.zeros(len(hdr), dtype=bool), row_mask=row_mask)
+    if not extra:
+        return main, on_device
+    tabs, hdrs, masks = [], [], []
+    for tab, hdr in extra:
+        mat, row_mask, col_mask = dev_norm(tab, test_name) if on_device else pre.normalize(tab, test_name, prec=prec)
+        tabs.append(mat)
+        hdrs.append([h for h, k in zip(hdr, col_mask) if k])
+        masks.append(row_mask)
+    mat, hdr, meta_mask, row_mask = pre.combine_data(tabs + [main["data"]], hdrs + [main["header"]],
+                                                     [None] * len(extra) + [main["meta_mask"]], masks + [main["row_mask"]])
+    return dict(data=mat, header=hdr, meta_mask=meta_mask, row_mask=row_mask), on_device
+
+
+def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
+                   device_normalize=True, device=0):
+    """normalize_data (preprocessing.jl:660-701), both forms: what learn_network(normalize=True) does to its tables, as a function of
+    its own.  data: samples x OTUs counts (array or scipy.sparse); extra_data: a list of (table, header) pairs, count tables of further
+    sequencing experiments on the same samples.  Every table is normalised on its own for `test_name` ("fz" clr_adapt, "fz_nz" clr_nz,
+    "mi" presence / absence, "mi_nz" binned_nz_clr) with its own filters; then the samples every table kept are gathered and the
+    columns laid out as [last extra, ..., first extra, data (+ meta columns)] (preprocess.combine_data).  All tables take one
+    front-end: the device one (integral counts, prec == 32, device_normalize) or, if any table is not integral, the host one.  Sparse
+    tables need the device front-end and are refused with what learn_network refuses them with; sparse and dense do not mix.
+    -> dict(data, header, meta_mask, row_mask): row_mask over the input samples, data a scipy.sparse.csc_matrix for sparse tables
+    (dense for "fz")."""
+    who = "normalize_data"
+    if test_name not in _TEST_NAMES:
+        raise ValueError("%s: unsupported test_name %r" % (who, test_name))
+    if prec not in (32, 64):
+        raise ValueError("%s: prec=%r is not supported (32 or 64)" % (who, prec))
+    if is_sparse(data) or isinstance(data, CSC):
+        _sparse_refusals(who, test_name, True, prec, device_normalize, meta_data)
+        data = _canonical_csc(who, data, test_name, True)
+    else:
+        data = np.asarray(data)
+    extra = _extra_tables(who, data, extra_data, test_name, True)
+    if header is None:
+        header = ["X%d" % (i + 1) for i in range(_shape(data)[1])]
+    elif len(header) != _shape(data)[1]:
+        raise ValueError("%s: a header of %d names for %d columns" % (who, len(header), _shape(data)[1]))
+    return _normalize_tables(data, list(header), extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device)[0]
+
+
+def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
                   meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
-                  no_red_tests=True, track_rejections=False, csc_resident=False, **unsupported):
+                  no_red_tests=True, track_rejections=False, csc_resident=False, extra_data=None, transposed=False, **unsupported):
     """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False); a numpy array or a scipy.sparse
     matrix.  A sparse table stays sparse end to end (what the reference does with make_sparse, learning.jl:470): normalize=True runs
     the device CSC front-end (integer counts only) and the sparse upload, normalize=False uploads the matrix as it is (Int32 levels
@@ -84,12 +222,40 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     per plane word and the values != 0 (12 p ceil(n / 64) + 4 nnz bytes) instead of the n x p Float32 matrix -- for tables whose dense
     form does not fit; the network is the same to the bit, the tests read each value through two more loads.  It needs sparse data,
     sensitive=True, heterogeneous=True and recursive_pcor=True; anything else is refused (ValueError) before any device call.
-    counters["csc_resident"] and counters["data_resident_bytes"] (fz_nz only, else None) record what ran."""
+    counters["csc_resident"] and counters["data_resident_bytes"] (fz_nz only, else None) record what ran.
+    extra_data (learning.jl:460,497-541): a list of (table, header) pairs -- count tables of further sequencing experiments (16S + ITS)
+    on the same samples, same rows in the same order; header None numbers the columns on from the main table's.  normalize=True
+    normalises every table on its own (normalize_data: its own row sums, geometric means, pseudo-counts and filters -- what stacking
+    the tables first would not do), keeps the samples every table kept (a warning says how many were dropped) and lays the columns out
+    as [last extra, ..., first extra, data, meta columns]: that order numbers the variables.  normalize=False only lays the prepared
+    tables side by side in that order.  meta_data belongs to the main table.  All tables are dense or all sparse, and all take one
+    front-end (if any table is not integral, all take the host one).  A table with another number of rows, a header of another length,
+    a sparse / dense mix and an entry that is no pair raise ValueError naming extra_data before any device call.
+    counters["n_tables"] and parameters["extra_data"] record the count; t_normalize_s covers all tables.
+    Path form (learning.jl:354-401): data may be a path (str / os.PathLike) or a list of paths, read with io.load_data (.tsv, .csv,
+    BIOM 1.0 JSON; anything else raises what load_data raises): the first is the main table, the others become extra_data under their
+    file headers; meta_data_path (second positional argument, as in the reference) is the main table's meta data file;
+    transposed=True reads every file as variables x samples.  Every other option is a keyword.  meta_data_path or transposed with an
+    array raise ValueError."""
     if unsupported:
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
     if prec not in (32, 64):
         raise ValueError("learn_network: prec=%r is not supported (32 or 64; the reference's 16 and 128 are not served)" % (prec,))
     import time
+    paths = [data] if _is_path(data) else list(data) if (isinstance(data, (list, tuple)) and len(data) and all(_is_path(q) for q in data)) else None
+    if paths is None:
+        if meta_data_path is not None:
+            raise ValueError("learn_network: meta_data_path goes with a data path (learn_network(data_path, meta_data_path)); with an "
+                             "array pass meta_data")
+        if transposed:
+            raise ValueError("learn_network: transposed=True is served for the path form; pass the transposed array")
+    else:
+        if not (meta_data_path is None or _is_path(meta_data_path)):
+            raise TypeError("learn_network: meta_data_path must be a path, got %s (options are keywords)" % type(meta_data_path).__name__)
+        if header is not None or meta_data is not None or meta_header is not None:
+            raise ValueError("learn_network: header, meta_data and meta_header come from the files in the path form")
+        data, header, meta_data, meta_header, from_files = _load_paths(paths, meta_data_path, transposed)
+        extra_data = from_files + list(extra_data or []) if (from_files or extra_data is not None) else None
     test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
     eng_prec = 64 if (prec == 64 and test_name == "fz") else 32  # the element type of the device pipeline
     csc_resident = bool(csc_resident)
@@ -118,29 +284,13 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     if sparse:
         # a sparse table stays sparse from here to the device (fw_normalize_counts_csc, fw_set_data_csc_*); what would need the dense
         # matrix is refused by name before any device call -- densifying silently would defeat the point
-        if not device_normalize:
-            raise ValueError("learn_network: sparse data with device_normalize=False is not supported: the host front-end "
-                             "(preprocess.py) is dense; pass data.toarray() or leave device_normalize=True")
-        if prec == 64:
-            raise ValueError("learn_network: sparse data with prec=64 is not supported: the Float64 path takes a dense matrix")
-        if meta_data is not None:
-            raise ValueError("learn_network: sparse data with meta_data is not supported: append the prepared meta columns to "
-                             "`data` yourself (preprocess.normalize_with_meta)")
-        if test_name == "fz" and not normalize:
-            raise ValueError("learn_network: sparse data with sensitive=True, heterogeneous=False, normalize=False is not supported: "
-                             "the plain fz test needs the dense matrix, pass one")
-        try:
-            data = as_csc(data, np.int32 if (normalize or test_name in ("mi", "mi_nz")) else np.float32)
-        except ValueError as e:
-            raise ValueError("learn_network: sparse data with normalize=%s needs %s (%s)"
-                             % (normalize, "integer counts in 0 .. 2^31 - 1: the device front-end takes nothing else" if normalize
-                                else "integer levels", e)) from None
-        n_cols = data[3][1]
+        _sparse_refusals("learn_network", test_name, normalize, prec, device_normalize, meta_data)
+        data = _canonical_csc("learn_network", data, test_name, normalize)
     else:
         data = np.asarray(data)
-        n_cols = data.shape[1]
+    extra = _extra_tables("learn_network", data, extra_data, test_name, normalize)  # (refused by name before any device call)
     if header is None:
-        header = ["X%d" % (i + 1) for i in range(n_cols)]
+        header = ["X%d" % (i + 1) for i in range(_shape(data)[1])]
     meta_mask = None
     if meta_data is not None and not normalize:
         # the reference appends the meta columns as they are and keeps their mask (learning.jl:500-520); here an already
@@ -148,28 +298,29 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
         raise ValueError("learn_network: meta_data with normalize=False is not supported: append the prepared meta columns to "
                          "`data` yourself (preprocess.normalize_with_meta) or pass normalize=True")
     t_norm0 = time.perf_counter()
-    on_device = bool(normalize and device_normalize and prec == 32 and (sparse or _integral(data)))
-    dev_norm = (lambda c, t: normalize_counts(c, t, device=device)) if on_device else None
-    if normalize and meta_data is not None:
-        r = pre.normalize_with_meta(data, test_name, meta_data, prec=prec, header=header, meta_header=meta_header,
-                                    make_onehot=make_onehot, normalizer=dev_norm)
-        mat, header, meta_mask = r["data"], r["header"], [bool(v) for v in r["meta_mask"]]
-    elif normalize:
-        mat, row_mask, col_mask = dev_norm(data, test_name) if on_device else pre.normalize(data, test_name, prec=prec)
-        header = [h for h, k in zip(header, col_mask) if k]
+    on_device = False
+    if normalize:
+        r, on_device = _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device)
+        mat, header = r["data"], r["header"]
+        meta_mask = [bool(v) for v in r["meta_mask"]]
+    elif extra:
+        # already normalised tables are only laid side by side (learning.jl:537-541): no filter, no alignment, extra tables first
+        everyone = np.ones(_shape(data)[0], dtype=bool)
+        mat, header, _, _ = pre.combine_data([t for t, _ in extra] + [data], [h for _, h in extra] + [header],
+                                             [None] * (len(extra) + 1), [everyone] * (len(extra) + 1))
     elif sparse:
         mat = tuple(data[:3])  # the prepared matrix as it is: Int32 CSC for mi / mi_nz, Float32 CSC for fz_nz
     else:
         mat = data
     t_norm = time.perf_counter() - t_norm0
-    n, p = data[3] if (sparse and not normalize) else mat.shape
+    n, p = data[3] if isinstance(mat, tuple) else mat.shape
     if round_size is None:
         round_size = default_round_size(p)
     eng = Engine(test_name, n, p, max_k=max_k, alpha=alpha, hps=hps, n_obs_min=n_obs_min, max_tests=max_tests, FDR=FDR,
                  device=device, recursive_pcor=recursive_pcor, dense_cor=dense_cor, prec=eng_prec)
     try:
         # (what the device front-end returned is canonical already: its triple goes up as it is, stored 0.0f of clr_nz included)
-        eng.set_data((mat.indptr, mat.indices, mat.data) if (sparse and normalize and is_sparse(mat)) else mat, csc_resident=csc_resident)
+        eng.set_data((mat.indptr, mat.indices, mat.data) if is_sparse(mat) else mat, csc_resident=csc_resident)
         if test_name == "fz" and dense_cor:
             eng.compute_cor()
         net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests,
@@ -181,13 +332,14 @@ def learn_network(data, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01
     counters["t_normalize_s"] = t_norm
     counters["normalized_on_device"] = on_device
     counters["sparse_input"] = sparse
+    counters["n_tables"] = 1 + len(extra)
     counters["csc_resident"] = csc_resident
     return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header),
                     parameters=dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha,
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,
                                     recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
                                     no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections), prec=eng_prec,
-                                    csc_resident=csc_resident,
+                                    csc_resident=csc_resident, extra_data=len(extra),
                                     schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
                                               else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
                                               else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),

@@ -117,6 +117,21 @@ def load_data(data_path, meta_path=None, transposed=False):
     raise ValueError("load_data: unsupported format .%s (supported: .tsv, .csv, .biom as JSON)" % ext)
 
 
+def write_table(path, data, header=None, row_ids=None):
+    """The delimited table load_dlm reads back (.tsv: tabs, else commas): an empty first header cell, then the variable ids; one row
+    per sample, its id first.  Integral values are written as integers, others with repr (they round-trip)."""
+    data = np.asarray(data)
+    sep = "\t" if path.endswith(".tsv") else ","
+    if header is None:
+        header = ["X%d" % (i + 1) for i in range(data.shape[1])]
+    if row_ids is None:
+        row_ids = ["S%d" % (i + 1) for i in range(data.shape[0])]
+    with open(path, "w") as f:
+        f.write(sep.join([""] + [str(h) for h in header]) + "\n")
+        for rid, row in zip(row_ids, data):
+            f.write(sep.join([str(rid)] + [str(int(v)) if float(v) == int(v) else repr(float(v)) for v in row]) + "\n")
+
+
 # ---- GML networks (src/io.jl:392-482) -------------------------------------------------------------------------------------------
 def write_gml(path, edges, header=None, meta_mask=None, n_vars=None):
     """write_gml (src/io.jl:392-423): undirected graph, 1-based node ids, node attributes `label` and `mv` (meta variable), edge

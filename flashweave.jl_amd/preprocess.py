@@ -179,3 +179,88 @@ def normalize(counts, test_name, prec=32):
         out = clr_nz(data)
         return out.astype(np.float32 if prec == 32 else np.float64), row_mask, col_mask
     raise ValueError("unsupported test_name %r" % (test_name,))
+
+
+# ---- several count tables of the same samples (preprocessing.jl:596-635 combine_data) ------------------------------------------
+def _is_csc(t):
+    """A sparse table: a scipy.sparse matrix, or a (colptr, rowval, nzval[, shape]) CSC triple with 0-based rows (what the device
+    front-end hands back / engine.as_csc returns).  Tables here are outputs of a normalisation, so a tuple is never a dense table."""
+    return isinstance(t, tuple) or (hasattr(t, "tocsc") and hasattr(t, "nnz"))
+
+
+def _csc_parts(t):
+    """-> (colptr, rowval, nzval, number of rows or None when a bare triple does not say)"""
+    if isinstance(t, tuple):
+        return t[0], t[1], t[2], (int(t[3][0]) if len(t) > 3 else None)
+    m = t.tocsc()
+    return m.indptr, m.indices, m.data, int(m.shape[0])
+
+
+def _csc_take_rows(colptr, rowval, nzval, keep):
+    """Rows `keep` (a mask over the table's rows) of a CSC triple, renumbered; O(nnz), stored zeros stay stored (a stored 0.0 of
+    clr_nz is a present count)."""
+    colptr, rowval, nzval = np.asarray(colptr, dtype=np.int64), np.asarray(rowval), np.asarray(nzval)
+    if keep.all():
+        return colptr, rowval, nzval
+    newrow = np.cumsum(keep) - 1  # the prefix sum over the mask renumbers the rows; ascending order inside a column survives
+    sel = keep[rowval]
+    upto = np.concatenate(([0], np.cumsum(sel, dtype=np.int64)))
+    return upto[colptr], newrow[rowval[sel]], nzval[sel]
+
+
+def combine_data(tables, headers, meta_masks, row_masks):
+    """combine_data (preprocessing.jl:596-635): column-wise union of several normalised tables of the same n samples.
+    tables[-1] is the main table (meta columns appended already), tables[:-1] the extra ones in the caller's order; row_masks[i] is
+    the mask over the original n samples that the normalisation of table i kept (its rows, ascending); meta_masks[i] may be None
+    (no meta variables: every extra table).  Every table is cut down to the samples all of them kept (a row gather), then the columns
+    are laid out as the reference's pushfirst! leaves them: last extra, ..., first extra, main.  Nothing is filtered afterwards: a
+    column that is constant on the common samples stays.  Dense arrays or CSC tables (_is_csc), never a mix; the CSC form gathers and
+    stacks in O(nnz) and returns a scipy.sparse.csc_matrix assembled field by field (stored zeros are kept).
+    -> (data, header, meta_mask, common row mask)"""
+    k = len(tables)
+    if k == 0 or not (len(headers) == len(meta_masks) == len(row_masks) == k):
+        raise ValueError("combine_data: one header, meta mask and row mask per table")
+    sparse = [_is_csc(t) for t in tables]
+    if any(sparse) and not all(sparse):
+        raise ValueError("combine_data: extra_data mixes sparse and dense tables; pass all of them in one form")
+    masks = [np.asarray(m, dtype=bool) for m in row_masks]
+    if any(m.shape != masks[0].shape for m in masks):
+        raise ValueError("combine_data: extra_data tables are not over the same samples (row masks of %s entries)"
+                         % sorted({int(m.size) for m in masks}))
+    common = np.logical_and.reduce(masks)
+    if not common.all():
+        import warnings
+        warnings.warn("%d samples had only zero counts in at least one data set and will not be used for inference"
+                      % int((~common).sum()), stacklevel=2)
+    parts, header, meta_mask = [], [], []
+    for i in list(range(k - 2, -1, -1)) + [k - 1]:
+        t, keep = tables[i], common[masks[i]]
+        if sparse[i]:
+            *t, have = _csc_parts(t)
+            rows, cols = int(masks[i].sum()), len(t[0]) - 1
+            if have is not None and have != rows:
+                raise ValueError("combine_data: extra_data table %d has %d rows, its row mask keeps %d" % (i, have, rows))
+            t = _csc_take_rows(*t, keep)
+        else:
+            t = np.asarray(t)
+            rows, cols = int(masks[i].sum()), t.shape[1]
+            if t.shape[0] != rows:
+                raise ValueError("combine_data: extra_data table %d has %d rows, its row mask keeps %d" % (i, t.shape[0], rows))
+            t = t if keep.all() else t[keep]
+        if len(headers[i]) != cols:
+            raise ValueError("combine_data: extra_data header %d names %d columns, its table has %d" % (i, len(headers[i]), cols))
+        parts.append(t)
+        header += list(headers[i])
+        meta_mask.append(np.zeros(cols, bool) if meta_masks[i] is None else np.asarray(meta_masks[i], dtype=bool))
+    meta_mask = np.concatenate(meta_mask)
+    if not sparse[0]:
+        return np.concatenate(parts, axis=1), header, meta_mask, common
+    import scipy.sparse as sp
+    n, nnz = int(common.sum()), [int(c[-1]) for c, _, _ in parts]
+    offs = np.concatenate(([0], np.cumsum(nnz)))
+    colptr = np.concatenate([parts[0][0][:1]] + [c[1:] + o for (c, _, _), o in zip(parts, offs)])
+    nzval = np.concatenate([v for _, _, v in parts])
+    idx = np.int32 if max(n, len(colptr), int(offs[-1])) < 2**31 else np.int64  # (one index type, as scipy keeps it)
+    out = sp.csc_matrix((n, len(colptr) - 1), dtype=nzval.dtype)
+    out.indptr, out.indices, out.data = colptr.astype(idx), np.concatenate([r for _, r, _ in parts]).astype(idx), nzval
+    return out, header, meta_mask, common
