@@ -14,7 +14,9 @@
 #include <algorithm>
 #include <cassert>
 #include <cstring>
+#include <condition_variable>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #include "fw_internal.h"
@@ -2524,12 +2526,86 @@ __global__ __launch_bounds__(256) void dh_wl_append_kernel(const DhTgt *__restri
     }
 }
 
+// ---- the whole feed-forward schedule of Fisher-z on the device (fwi_devhiton_fz_schedule) ----
+// per-target state of every target of the schedule, in slot order (round, chain, index in the chain): what dh_build_targets makes, with
+// the persistent arrays (TPC / PC, accepted lists, whitelist) at the level-0 offset nb_off[T] and the degree as capacity
+__global__ __launch_bounds__(256) void dh_fz_init_kernel(DhTgt *__restrict__ tg, int nt, const int32_t *__restrict__ slot_T,
+                                                         const long long *__restrict__ slot_tm, const long long *__restrict__ nb_off)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= nt) return;
+    DhTgt x;
+    __builtin_memset(&x, 0, sizeof(x));
+    const int T = slot_T[i];
+    const long long o = nb_off[T];
+    const int deg = (int)(nb_off[T + 1] - o);
+    x.T = T;
+    x.nc = x.cap = deg;
+    x.phase = deg == 0 ? 2 : 0;  // hiton.jl:336-338 (no candidate)
+    x.co = x.cand_off = x.wl_off = x.nb_off = o;
+    x.nb_n = deg;
+    x.tm_off = slot_tm[i];
+    tg[i] = x;
+}
+
+// the list of unfinished targets at the start of a round of targets: every target, in order
+__global__ __launch_bounds__(256) void dh_iota_kernel(int32_t *__restrict__ act, int n)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i < n) act[i] = i;
+}
+
+// Start of a chain's round of targets (one workgroup per target): the whitelist that the earlier rounds appended (dh_wl_append_kernel)
+// is sorted in place -- its entries are distinct, so an entry's rank is the number of smaller ones -- which gives dh_in_wl the early
+// exit it has on the host-built lists.  The rank sort is quadratic in the list and stages it in 16 KB of LDS: choose_path keeps runs
+// with a level-0 list beyond 4096 entries on the round loop, so the unsorted flag below is never set by the schedule (it keeps the
+// kernel correct should that gate move); the round's control state is what
+// dh_upload writes: every target on the list, no segment, a zeroed record.  wl_max: the longest whitelist of the chain's round (the
+// host reads this word before it enqueues the round's first batch: DhRounds::enqueue_batch, any_big).
+__global__ __launch_bounds__(256) void dh_fz_round_begin_kernel(DhTgt *__restrict__ tg, int ntg, const unsigned int *__restrict__ wl_cnt,
+                                                                int32_t *__restrict__ wl, DhGlobal *__restrict__ g, long long *__restrict__ seg0,
+                                                                int32_t *__restrict__ act, unsigned int *__restrict__ wl_max)
+{
+    __shared__ int32_t s_w[4096];
+    const int t = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (t >= ntg) return;
+    DhTgt &x = tg[t];
+    const int n = (int)wl_cnt[x.T];  // (workgroup-uniform; at most the degree: dh_wl_append_kernel)
+    if (n > 1 && n <= 4096) {
+        int32_t *w = wl + x.wl_off;
+        for (int i = tid; i < n; i += 256) s_w[i] = w[i];
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            const int32_t e = s_w[i];
+            int r = 0;
+            for (int j = 0; j < n; ++j) r += s_w[j] < e;
+            w[r] = e;
+        }
+    }
+    if (tid == 0) {
+        x.wl_n = n;
+        x.wl_unsorted = n > 4096;
+        act[t] = t;
+        seg0[t] = 0;
+        if (n > 0) atomicMax(wl_max, (unsigned int)n);
+    }
+    if (t == 0) {
+        unsigned int *gw = (unsigned int *)g;
+        for (int i = tid; i < (int)(sizeof(DhGlobal) / 4); i += 256) gw[i] = 0u;
+        __syncthreads();
+        if (tid == 0) {
+            g->n_act = (unsigned int)ntg;
+            seg0[ntg] = 0;
+        }
+    }
+}
+
 // results of the whole schedule, packed for ONE small download: every target's PC entries (target, neighbour, statistic, p) as a block
 // of consecutive records in insertion order -- the blocks land where an atomic ticket puts them: the host's CSR over targets
 // (fw_hiton.cpp: a stable counting sort by target) does not depend on the order of the blocks -- and the per-target counters summed
 // (integers and multiples of 1/8: every order gives the same sums).  tot[0] entries, [1] tests in reference order, [2] jobs,
 // [3] executed tests, [4] unfinished targets (must stay 0); alg: algorithmic bytes
-__global__ __launch_bounds__(256) void dh_mi_pack_kernel(const DhTgt *__restrict__ tg, int nt, const int32_t *__restrict__ pc_key,
+__global__ __launch_bounds__(256) void dh_sched_pack_kernel(const DhTgt *__restrict__ tg, int nt, const int32_t *__restrict__ pc_key,
                                                          const double *__restrict__ pc_stat, const double *__restrict__ pc_p,
                                                          int32_t *__restrict__ o_t, int32_t *__restrict__ o_u, double *__restrict__ o_s,
                                                          double *__restrict__ o_p, unsigned long long *__restrict__ tot, double *__restrict__ alg)
@@ -2949,6 +3025,7 @@ struct DhRun {
     std::vector<float> log_ms;  // FW_DH_LOG: segment-kernel time of launch i (planned by plan #i)
     unsigned max_a_seen = 0;    // longest accepted list reported so far (lags by up to two batches)
     unsigned max_ab_seen = 0;   // ... and the largest accepted + whitelisted-to-come
+    bool dev_wl = false;        // fwi_devhiton_fz_schedule: the whitelists were built on the device (R.wl stays empty), the longest holds max_wl entries
 };
 
 // targets, candidate lists and whitelists in one flat layout each; offsets of the local matrices
@@ -3025,11 +3102,7 @@ static int dh_upload(DhRun &R)
     FW_HIP(c, hipMemcpyAsync(D.tg, R.tg.data(), sizeof(DhTgt) * ntg, hipMemcpyHostToDevice, st));
     hg[0].n_act = (unsigned int)ntg;  // every target starts on the list (the pinned page is the staging copy: stream-ordered)
     FW_HIP(c, hipMemcpyAsync(D.g, hg, sizeof(DhGlobal), hipMemcpyHostToDevice, st));
-    {
-        std::vector<int32_t> iota((size_t)ntg);
-        for (int t = 0; t < ntg; ++t) iota[t] = t;
-        FW_HIP(c, hipMemcpy(D.act, iota.data(), sizeof(int32_t) * (size_t)ntg, hipMemcpyHostToDevice));
-    }
+    hipLaunchKernelGGL(dh_iota_kernel, dim3((unsigned)((ntg + 255) / 256)), dim3(256), 0, st, D.act, ntg);  // (was a blocking copy of a host list)
     FW_HIP(c, hipMemsetAsync(D.seg0, 0, sizeof(long long) * ((size_t)ntg + 1), st));
     if (tot && !R.use_devc) FW_HIP(c, hipMemcpyAsync(D.cand0, R.cand0.data(), 4 * tot, hipMemcpyHostToDevice, st));
     if (!R.wl.empty()) FW_HIP(c, hipMemcpyAsync(D.wl, R.wl.data(), 4 * R.wl.size(), hipMemcpyHostToDevice, st));
@@ -3119,7 +3192,7 @@ struct DhRounds {
     // The in-lane kernel (accepted lists beyond FW_TAB_A) is only launched when such a list can exist in the coming batch:
     // without whitelists an accepted list grows by at most one entry per round, so max_a (longest list so far, read
     // back once per batch) + BATCH bounds it; with whitelists a round can append several entries -> static bound.
-    const bool any_wl = !R.wl.empty();
+    const bool any_wl = !R.wl.empty() || (R.dev_wl && R.max_wl > 0);
     const bool any_big_static = (any_wl ? 2 * R.max_cap : R.max_cap) > FW_TAB_A;
     const unsigned g_fill = (R.max_ns + 255) / 256;
     unsigned n_act_bound = (unsigned)R.ntg;  // unfinished targets as of the last record read (only ever shrinks)
@@ -3301,17 +3374,21 @@ static int dh_download(DhRun &R, std::vector<FwDhResult> &out, FwDhFlat &flat)
 {
     fw_ctx *c = R.c;
     const size_t tot = R.tot;
-    FW_HIP(c, hipMemcpy(R.tg.data(), R.D.tg, sizeof(DhTgt) * R.ntg, hipMemcpyDeviceToHost));
-    if (R.D.log)
-        if (int rc = dh_write_log(R)) return rc;
     flat.key.resize(tot);
     flat.stat.resize(tot);
     flat.pval.resize(tot);
+    // four copies enqueued on the chain's stream and one wait, instead of four blocking copies on the null stream.  The destinations
+    // are pageable vectors: HIP stages such a copy and may block the host in the call, so this only takes the four synchronisations of
+    // the null stream out; it was not measured alone (pinned destinations would be the next step)
+    FW_HIP(c, hipMemcpyAsync(R.tg.data(), R.D.tg, sizeof(DhTgt) * R.ntg, hipMemcpyDeviceToHost, R.st));
     if (tot) {
-        FW_HIP(c, hipMemcpy(flat.key.data(), R.A.pc_key, 4 * tot, hipMemcpyDeviceToHost));
-        FW_HIP(c, hipMemcpy(flat.stat.data(), R.A.pc_stat, 8 * tot, hipMemcpyDeviceToHost));
-        FW_HIP(c, hipMemcpy(flat.pval.data(), R.A.pc_p, 8 * tot, hipMemcpyDeviceToHost));
+        FW_HIP(c, hipMemcpyAsync(flat.key.data(), R.A.pc_key, 4 * tot, hipMemcpyDeviceToHost, R.st));
+        FW_HIP(c, hipMemcpyAsync(flat.stat.data(), R.A.pc_stat, 8 * tot, hipMemcpyDeviceToHost, R.st));
+        FW_HIP(c, hipMemcpyAsync(flat.pval.data(), R.A.pc_p, 8 * tot, hipMemcpyDeviceToHost, R.st));
     }
+    FW_HIP(c, hipStreamSynchronize(R.st));
+    if (R.D.log)
+        if (int rc = dh_write_log(R)) return rc;
     for (int t = 0; t < R.ntg; ++t) {
         const DhTgt &x = R.tg[t];
         if (x.phase != 2) return fw_fail(c, FW_ERR_DEVICE, "device HITON: target %d did not finish (phase %d)", x.T, x.phase);
@@ -3534,7 +3611,7 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     FW_HIP(c, hipGetLastError());
     FW_HIP(c, hipEventRecord(E.ev[1], st));
     // ---- results: packed on the device, one small download ----
-    hipLaunchKernelGGL(dh_mi_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)D.tg, nt, (const int32_t *)A.pc_key,
+    hipLaunchKernelGGL(dh_sched_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)D.tg, nt, (const int32_t *)A.pc_key,
                        (const double *)A.pc_stat, (const double *)A.pc_p, D.ot, D.ou, D.os, D.op, D.tot, (double *)(D.tot + 5));
     FW_HIP(c, hipGetLastError());
     std::vector<MiQueue> hq((size_t)nrounds);
@@ -3572,5 +3649,339 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     if (trace_host)
         fprintf(stderr, "[fw] device schedule: %d targets in %d rounds, set-up %.2f ms, launches + download %.2f ms (kernels %.2f ms), results %.2f ms\n", nt, nrounds,
                 1e3 * (th1 - th0), 1e3 * (th2 - th1), (double)ms, 1e3 * (fwi_now_s() - th2));
+    return FW_OK;
+}
+
+// ---- the whole feed-forward schedule of Fisher-z (fwi_devhiton_fz_schedule) ----
+
+struct DhFzChainSizes {
+    size_t ntg, max_ns, tm_floats;  // the largest round of the chain, each
+};
+struct DhFzSizes {
+    size_t nt, p, nnz, d1, nslots;
+    int K;
+    DhFzChainSizes ch[FW_DH_MAX_CHAINS];
+};
+struct DhFzChainBufs {  // a chain's scratch: reserved once, for its largest round
+    DhGlobal *g;
+    long long *seg0;
+    unsigned long long *win, *win2;
+    unsigned int *sp;
+    int32_t *act;
+    FwSeg *segs;
+    FwSegOut *so;
+    float *tmat;
+};
+struct DhFzBufs {
+    DhTgt *tg;  // every target of the schedule, in slot order
+    int32_t *slot_T, *round_of;
+    long long *slot_tm;
+    unsigned int *wl_cnt, *wl_max;  // wl_max: one word per (round, chain)
+    int32_t *tpc_key, *pc_key, *wl, *acc;  // at level-0 offsets
+    double *tpc_stat, *tpc_p, *pc_stat, *pc_p;
+    int32_t *ot, *ou;  // packed results
+    double *os, *op;
+    unsigned long long *tot;
+    DhFzChainBufs ch[FW_DH_MAX_CHAINS];
+};
+static DhFzBufs dh_fz_layout(DhArena &a, const DhFzSizes &z)
+{
+    DhFzBufs b{};
+    b.tg = a.take<DhTgt>(z.nt);
+    b.slot_T = a.take<int32_t>(z.nt);
+    b.slot_tm = a.take<long long>(z.nt);
+    b.round_of = a.take<int32_t>(z.p);
+    b.wl_cnt = a.take<unsigned int>(z.p);
+    b.wl_max = a.take<unsigned int>(z.nslots);
+    b.tpc_key = a.take<int32_t>(z.nnz, 4);
+    b.pc_key = a.take<int32_t>(z.nnz, 4);
+    b.wl = a.take<int32_t>(z.nnz, 4);
+    b.acc = a.take<int32_t>(2 * z.nnz * z.d1, 4);
+    b.tpc_stat = a.take<double>(z.nnz, 8);
+    b.tpc_p = a.take<double>(z.nnz, 8);
+    b.pc_stat = a.take<double>(z.nnz, 8);
+    b.pc_p = a.take<double>(z.nnz, 8);
+    b.ot = a.take<int32_t>(z.nnz, 4);
+    b.ou = a.take<int32_t>(z.nnz, 4);
+    b.os = a.take<double>(z.nnz, 8);
+    b.op = a.take<double>(z.nnz, 8);
+    b.tot = a.take<unsigned long long>(8);
+    for (int q = 0; q < z.K; ++q) {
+        const DhFzChainSizes &s = z.ch[q];
+        DhFzChainBufs &cb = b.ch[q];
+        cb.g = a.take<DhGlobal>(1);
+        cb.seg0 = a.take<long long>(s.ntg + 1);
+        cb.win = a.take<unsigned long long>(s.ntg + 1);
+        cb.sp = a.take<unsigned int>(s.ntg + 1);
+        cb.win2 = a.take<unsigned long long>(s.ntg + 1);
+        cb.act = a.take<int32_t>(2 * s.ntg);
+        cb.segs = a.take<FwSeg>(s.max_ns);
+        cb.so = a.take<FwSegOut>(s.max_ns);
+        if (s.tm_floats) cb.tmat = a.take<float>(s.tm_floats, 4);
+    }
+    return b;
+}
+
+// where the host threads of the chains meet between two rounds of targets; an error of any chain ends the schedule for all of them
+struct DhFzBarrier {
+    std::mutex m;
+    std::condition_variable cv;
+    int n, waiting = 0, rc = FW_OK;
+    unsigned gen = 0;
+    explicit DhFzBarrier(int k) : n(k) {}
+    int arrive(int my_rc)
+    {
+        std::unique_lock<std::mutex> lk(m);
+        if (my_rc && !rc) rc = my_rc;
+        const unsigned g = gen;
+        if (++waiting == n) {
+            waiting = 0;
+            ++gen;
+            cv.notify_all();
+        } else {
+            cv.wait(lk, [&] { return gen != g; });
+        }
+        return rc;
+    }
+};
+
+// a chain's share of one round of the schedule
+struct DhFzSlot {
+    int base = 0, ntg = 0, max_cap = 0;
+    unsigned max_ns = 0;
+    size_t tm_floats = 0;
+};
+
+// The WHOLE feed-forward schedule of Fisher-z on the device (one GPU, no exchange between the rounds): what fwi_devhiton_mi_schedule
+// does for the discrete kinds.  The round loop (fw_hiton.cpp: run_rounds) paid per round of targets: whitelists from the host's running
+// graph, one FwDhTarget per target, a thread per chain, dh_build_targets + dh_upload, 66 events made and destroyed, four downloads, one
+// push per result entry and the running graph's update -- 0.8 ms of host time around ~1.1 ms of device rounds in each of cfg3's nine
+// light rounds (profiles/r14_fz_device_schedule.txt).  Here the host computes the layout of every round once (slots: round, chain, index
+// in the chain; same deal and same per-chain policy as the round loop), the state of every target is built on the device
+// (dh_fz_init_kernel), the whitelists grow on the device (dh_wl_append_kernel, sorted at the start of the round that reads them:
+// dh_fz_round_begin_kernel), and the chains' host threads live for the whole schedule.  Level-synchronous as before: a chain starts
+// round r + 1 when every chain has retired round r (DhFzBarrier) and its stream has waited for the other chains' appends (events).
+// Per round and chain the host reads ONE word (the longest whitelist: DhRounds needs the exact bound, see enqueue_batch) besides the
+// batch records.  Results: packed on the device, one download.  sched[0 .. nt): the targets in schedule order, rounds of R.
+int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, bool feed_forward, FwDirected &all)
+{
+    if (nt == 0) return FW_OK;
+    if (!c->d_cand || !c->d_nb_idx || !c->d_nb_off) return fw_fail(c, FW_ERR_STATE, "device schedule: the level-0 lists are not on the device");
+    static const bool trace_host = fw_trace_host();
+    const double th0 = fwi_now_s();
+    const int p = c->P.p;
+    const size_t nnz = (size_t)c->nb_off[p];
+    if (R <= 0 || R > nt) R = nt;
+    const int nrounds = (nt + R - 1) / R;
+    // ---- host, once: the slots of every round (deal_chains order), their DhTgt offsets and sizes ----
+    int K = 1;
+    for (int r = 0; r < nrounds; ++r) K = std::max(K, fwi_chain_count(c, (size_t)(std::min(nt, r * R + R) - r * R)));
+    std::vector<DhFzSlot> slots((size_t)nrounds * (size_t)K);
+    std::vector<int32_t> slot_T((size_t)nt), round_of((size_t)p, 0x7fffffff);
+    std::vector<long long> slot_tm((size_t)nt, -1);
+    DhFzSizes z{(size_t)nt, (size_t)p, nnz, 0, (size_t)nrounds * (size_t)K, K, {}};
+    const bool tm_on = c->P.max_k <= 5 && c->d_cor != nullptr;
+    {
+        std::vector<int> chain_of;
+        std::vector<size_t> chain_idx;
+        for (int r = 0; r < nrounds; ++r) {
+            const int r0 = r * R, n = std::min(nt, r0 + R) - r0;
+            const int Kr = fwi_chain_count(c, (size_t)n);
+            fwi_deal_chains((size_t)n, Kr, chain_of, chain_idx);
+            DhFzSlot *s = &slots[(size_t)r * (size_t)K];
+            for (int i = 0; i < n; ++i) ++s[chain_of[i]].ntg;
+            for (int q = 0, base = r0; q < K; ++q) {
+                s[q].base = base;
+                base += s[q].ntg;
+            }
+            for (int i = 0; i < n; ++i) {
+                slot_T[(size_t)s[chain_of[i]].base + chain_idx[i]] = sched[r0 + i];
+                round_of[sched[r0 + i]] = r;
+            }
+            for (int q = 0; q < K; ++q) {
+                if (s[q].ntg == 0) continue;
+                const DhPolicy y = dh_policy(c, s[q].ntg);
+                z.d1 = (size_t)y.spec_depth + 1;
+                for (int t = 0; t < s[q].ntg; ++t) {  // (dh_build_targets)
+                    const int T = slot_T[(size_t)(s[q].base + t)];
+                    const int deg = (int)(c->nb_off[T + 1] - c->nb_off[T]);
+                    s[q].max_cap = std::max(s[q].max_cap, deg);
+                    const size_t m = (size_t)deg + 1;
+                    if (!tm_on || y.tm_min <= 0 || deg < y.tm_min || m > 4096 || s[q].tm_floats + m * m > (size_t)1 << 32) continue;
+                    slot_tm[(size_t)(s[q].base + t)] = (long long)s[q].tm_floats;
+                    s[q].tm_floats += m * m;
+                }
+                s[q].max_ns = y.seg_target + (unsigned)s[q].ntg * (unsigned)(1 + DH_MAX_SPEC) + 256u;
+                z.ch[q].ntg = std::max(z.ch[q].ntg, (size_t)s[q].ntg);
+                z.ch[q].max_ns = std::max(z.ch[q].max_ns, (size_t)s[q].max_ns);
+                z.ch[q].tm_floats = std::max(z.ch[q].tm_floats, s[q].tm_floats);
+            }
+        }
+    }
+    // ---- device arena (reserved once: growing it mid-schedule would synchronise the device under the other chain), streams, events ----
+    DhFzBufs D;
+    if (int rc = dh_arena_reserve(c, c->d_dh[0], dh_fz_layout, z, &D)) return rc;
+    hipStream_t sts[FW_DH_MAX_CHAINS];
+    for (int q = 0; q < K; ++q) {
+        if (q > 0 && !c->dh_stream[q]) FW_HIP(c, hipStreamCreateWithFlags(&c->dh_stream[q], hipStreamNonBlocking));
+        sts[q] = q == 0 ? c->pb[0].stream : c->dh_stream[q];
+        if (int rc = fw_pin_reserve(c, c->h_dh[q], 4096)) return rc;
+    }
+    static_assert(2 * sizeof(DhGlobal) <= 3072, "the pinned page holds two batch records and, at byte 3072, the whitelist word");
+    hipStream_t st = sts[0];
+    DhEvents X(st, 0, 3 * K);  // ev_end[q * 3 + 0 / 1]: chain q's round r (r & 1) and its appends are done; [q * 3 + 2]: the whitelist word
+    if (!X.ok) return fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventCreate failed");
+    DhArrays A{};
+    A.cand0 = c->d_cand;
+    A.tpc_key = D.tpc_key;
+    A.pc_key = D.pc_key;
+    A.acc = D.acc;
+    A.tpc_stat = D.tpc_stat;
+    A.tpc_p = D.tpc_p;
+    A.pc_stat = D.pc_stat;
+    A.pc_p = D.pc_p;
+    A.wl = D.wl;
+    A.nb_off = c->d_nb_off;
+    A.nb_idx = c->d_nb_idx;
+    A.nb_stat = c->d_nb_stat;
+    A.nb_p = c->d_nb_p;
+    A.rej = c->d_rej_run;
+    FW_HIP(c, hipMemsetAsync(D.tot, 0, 64, st));
+    FW_HIP(c, hipMemsetAsync(D.wl_cnt, 0, 4 * (size_t)p, st));
+    FW_HIP(c, hipMemsetAsync(D.wl_max, 0, 4 * z.nslots, st));
+    FW_HIP(c, hipMemcpyAsync(D.slot_T, slot_T.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemcpyAsync(D.slot_tm, slot_tm.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, st));
+    FW_HIP(c, hipMemcpyAsync(D.round_of, round_of.data(), 4 * (size_t)p, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dh_fz_init_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, D.tg, nt, (const int32_t *)D.slot_T,
+                       (const long long *)D.slot_tm, c->d_nb_off);
+    FW_HIP(c, hipGetLastError());
+    for (int q = 1; q < K; ++q) {  // the other chains' streams start behind the set-up
+        FW_HIP(c, hipEventRecord(X.ev_end[(size_t)q * 3], st));
+        FW_HIP(c, hipStreamWaitEvent(sts[q], X.ev_end[(size_t)q * 3], 0));
+    }
+    const double th1 = fwi_now_s();
+    // ---- the rounds: one host thread per chain for the whole schedule ----
+    DhFzBarrier bar(K);
+    std::vector<double> t_start((size_t)nrounds, 0.0);
+    auto chain_round = [&](int q, int r, DhEvents &E) -> int {
+        const DhFzSlot &s = slots[(size_t)r * (size_t)K + (size_t)q];
+        hipStream_t sq = sts[q];
+        if (r > 0)
+            for (int o = 0; o < K; ++o)
+                if (o != q) FW_HIP(c, hipStreamWaitEvent(sq, X.ev_end[(size_t)o * 3 + (size_t)((r - 1) & 1)], 0));
+        if (q == 0) t_start[(size_t)r] = fwi_now_s() - th0;
+        DhRun Rn{c, q, s.ntg, sq, trace_host, dh_policy(c, s.ntg)};
+        Rn.use_devc = true;
+        Rn.dev_wl = true;
+        Rn.max_cap = s.max_cap;
+        Rn.max_ns = s.max_ns;
+        Rn.tm_floats = s.tm_floats;
+        const DhFzChainBufs &cb = D.ch[q];
+        Rn.D.tg = D.tg + s.base;
+        Rn.D.g = cb.g;
+        Rn.D.seg0 = cb.seg0;
+        Rn.D.win = cb.win;
+        Rn.D.win2 = cb.win2;
+        Rn.D.sp = cb.sp;
+        Rn.D.act = cb.act;
+        Rn.D.segs = cb.segs;
+        Rn.D.so = cb.so;
+        Rn.D.tmat = s.tm_floats ? cb.tmat : nullptr;
+        Rn.A = A;
+        Rn.A.tmat = Rn.D.tmat;
+        Rn.hg = (DhGlobal *)c->h_dh[q].ptr;
+        memset(Rn.hg, 0, 2 * sizeof(DhGlobal));
+        unsigned int *h_wl_max = (unsigned int *)((char *)c->h_dh[q].ptr + 3072);
+        unsigned int *d_wl_max = D.wl_max + (size_t)r * (size_t)K + (size_t)q;
+        hipLaunchKernelGGL(dh_fz_round_begin_kernel, dim3((unsigned)s.ntg), dim3(256), 0, sq, Rn.D.tg, s.ntg, (const unsigned int *)D.wl_cnt, D.wl,
+                           cb.g, cb.seg0, cb.act, d_wl_max);
+        FW_HIP(c, hipGetLastError());
+        if (feed_forward && r > 0) {
+            FW_HIP(c, hipMemcpyAsync(h_wl_max, d_wl_max, sizeof(unsigned int), hipMemcpyDeviceToHost, sq));
+            FW_HIP(c, hipEventRecord(X.ev_end[(size_t)q * 3 + 2], sq));
+        }
+        if (Rn.D.tmat) {
+            hipLaunchKernelGGL(dh_tmat_build_kernel, dim3((unsigned)s.ntg, 8u), dim3(256), 0, sq, (const DhTgt *)Rn.D.tg, s.ntg, A.nb_idx,
+                               (const float *)c->d_cor, p, Rn.D.tmat);
+            FW_HIP(c, hipGetLastError());
+        }
+        Rn.P = dh_make_params(c, s.ntg, Rn.y.spec_depth, Rn.y.spec0_depth);
+        if (feed_forward && r > 0) {  // the exact longest whitelist, before the round's first batch is enqueued
+            FW_HIP(c, hipEventSynchronize(X.ev_end[(size_t)q * 3 + 2]));
+            Rn.max_wl = (int)*h_wl_max;
+        }
+        int rc = DhRounds(Rn, E).run();
+        const bool append = !rc && feed_forward && r + 1 < nrounds;
+        {
+            std::lock_guard<std::mutex> lk(dh_cnt_mu);
+            if (Rn.timed_n > 0) c->cnt.t_dev_subsets_s += Rn.timed_s * (double)Rn.launches_n / (double)Rn.timed_n;
+            c->cnt.subsets_launches += Rn.launches_n;
+            // the four kernels of every round of the segment kernel, as in fwi_devhiton_run, and what this round of targets launched
+            // besides: the round-begin kernel, the local matrices and the append where they run
+            c->cnt.kernel_launches += 4 * Rn.launches_n + 1 + (Rn.D.tmat ? 1 : 0) + (append ? 1 : 0);
+        }
+        if (rc) return rc;
+        if (append) {  // interleaved.jl:136-140, kept where a later round reads it
+            hipLaunchKernelGGL(dh_wl_append_kernel, dim3((unsigned)((s.ntg + 3) / 4)), dim3(256), 0, sq, (const DhTgt *)Rn.D.tg, s.ntg,
+                               (const int32_t *)A.pc_key, (const int32_t *)D.round_of, r, D.wl, c->d_nb_off, D.wl_cnt);
+            FW_HIP(c, hipGetLastError());
+        }
+        return FW_OK;
+    };
+    auto chain_body = [&](int q) {
+        DhEvents E(sts[q], 2 * 2 * DH_BATCH, 2);  // once per chain and schedule (its destructor synchronises the chain's stream)
+        int rc = E.ok ? FW_OK : fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventCreate failed");
+        for (int r = 0; r < nrounds; ++r) {
+            if (!rc && slots[(size_t)r * (size_t)K + (size_t)q].ntg > 0) rc = chain_round(q, r, E);
+            if (!rc && hipEventRecord(X.ev_end[(size_t)q * 3 + (size_t)(r & 1)], sts[q]) != hipSuccess)
+                rc = fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventRecord failed");
+            if ((rc = bar.arrive(rc))) break;  // (every chain leaves at the same barrier)
+        }
+    };
+    {
+        std::vector<std::thread> th;
+        for (int q = 1; q < K; ++q)
+            th.emplace_back([&, q] {
+                (void)hipSetDevice(c->P.device);
+                chain_body(q);
+            });
+        chain_body(0);
+        for (std::thread &t : th) t.join();
+    }
+    if (bar.rc) return bar.rc;
+    const double th2 = fwi_now_s();
+    // ---- results: packed on the device, one small download (every chain has retired its last batch: the device is idle) ----
+    hipLaunchKernelGGL(dh_sched_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)D.tg, nt, (const int32_t *)A.pc_key,
+                       (const double *)A.pc_stat, (const double *)A.pc_p, D.ot, D.ou, D.os, D.op, D.tot, (double *)(D.tot + 5));
+    FW_HIP(c, hipGetLastError());
+    unsigned long long htot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    FW_HIP(c, hipMemcpyAsync(htot, D.tot, 64, hipMemcpyDeviceToHost, st));
+    FW_HIP(c, hipStreamSynchronize(st));
+    if (htot[4]) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %llu targets did not finish", htot[4]);
+    const size_t nres = (size_t)htot[0], at0 = all.size();
+    if (nres > nnz) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %zu result entries for %zu level-0 entries", nres, nnz);
+    all.resize(at0 + nres);
+    if (nres) {  // (pageable destinations: staged copies that may block in the call -- 0.9 ms for cfg3's 3.6 MB, as in fwi_devhiton_mi_schedule)
+        FW_HIP(c, hipMemcpyAsync(all.t.data() + at0, D.ot, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.u.data() + at0, D.ou, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.s.data() + at0, D.os, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.p.data() + at0, D.op, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipStreamSynchronize(st));
+    }
+    c->cnt.cond_tests_ref += (int64_t)htot[1];
+    c->cnt.subsets_calls += (int64_t)htot[2];
+    c->cnt.cond_tests_evaluated += (int64_t)htot[3];
+    {
+        double alg;
+        memcpy(&alg, &htot[5], sizeof(double));
+        c->cnt.alg_bytes_subsets += alg;
+    }
+    c->cnt.kernel_launches += 2;  // dh_fz_init_kernel, dh_sched_pack_kernel
+    if (trace_host) {
+        fprintf(stderr, "[fw] fz device schedule: %d targets in %d rounds on %d chains, set-up %.2f ms, rounds %.2f ms, results %.2f ms; rounds start at", nt,
+                nrounds, K, 1e3 * (th1 - th0), 1e3 * (th2 - th1), 1e3 * (fwi_now_s() - th2));
+        for (int r = 0; r < nrounds; ++r) fprintf(stderr, " %.2f", 1e3 * t_start[(size_t)r]);
+        fprintf(stderr, " ms\n");
+    }
     return FW_OK;
 }

@@ -190,7 +190,8 @@ struct PathChoice {
 };
 
 // round == nullptr asks for the whole run: PATH_DEV_SCHEDULE (fwi_devhiton_mi_schedule: discrete kinds on bit planes, one rank, no
-// exchange callback, level-0 lists and candidate order on the device, rounds the persistent kernel is worth launching for), else the
+// exchange callback, level-0 lists and candidate order on the device, rounds the persistent kernel is worth launching for;
+// fwi_devhiton_fz_schedule: fz under the same conditions, when EVERY round of the schedule would take the device rounds), else the
 // rounds are asked one by one (`why` then says what kept the schedule off): order[r0 .. r1), n_my of them this rank's.
 // Knobs are read per call: the tests and bench.py switch them inside a live process.
 PathChoice choose_path(fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, const int32_t *order, int nt, const int *round, size_t n_my)
@@ -209,9 +210,28 @@ PathChoice choose_path(fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, c
     // worth it from a few hundred targets on.  (a negative value: every round of the schedule, no round of the per-round paths)
     const long long min_targets = (long long)fw_knob_u64(knob::FW_DEV_MIN_TARGETS, discrete ? 256 : 64);
     if (!round) {
-        if (!discrete) return host("device schedule: discrete kinds only");
+        if (!discrete && kind != FW_FZ) return host("device schedule: not for fz_nz");
         if (has_exchange || opt.world_size > 1) return host("device schedule: exchange callback present");
         if (!c->d_cand || !c->d_nb_idx || !c->d_nb_off) return host("device schedule: level-0 lists not on the device (FW_HOST_BH)");
+        if (!discrete) {  // fwi_devhiton_fz_schedule
+            if (!fw_knob_on(knob::FW_FZ_SCHED)) return host("device schedule: FW_FZ_SCHED=0");  // (A/B runs, tests/test_gpu_fz_sched.py compares the two)
+            if (c->track_rej != 0) return host("device schedule: track_rejections runs on the round loop");
+            if (fw_knob_str(knob::FW_DH_LOG)) return host("device schedule: FW_DH_LOG is written by the round loop");
+            // (accepted-list buffers of every target at its level-0 offset: 8 * (look-ahead + 1) bytes per level-0 entry)
+            if ((unsigned long long)c->nb_off[c->P.p] > (1ull << 27)) return host("device schedule: level-0 lists too long for buffers at level-0 offsets");
+            // every round must be one the round loop would give to the device: a round for the host pool keeps the whole run on the loop
+            for (int r0 = 0, r1 = 0; r0 < nt; r0 = r1) {
+                r1 = fw_round_end(r0, opt.round_size, nt);
+                if (r1 - r0 < min_targets) return host("device schedule: a round of fewer targets than FW_DEV_MIN_TARGETS");
+            }
+            const int R = (opt.round_size <= 0 || opt.round_size > nt) ? nt : opt.round_size;
+            if (R < 2) return host("device schedule: single_il");
+            // (dh_fz_round_begin_kernel sorts a device-built whitelist, at most the degree long, in 16 KB of LDS by a quadratic rank sort)
+            if (opt.feed_forward)
+                for (int i = 0; i < nt; ++i)
+                    if (c->nb_off[order[i] + 1] - c->nb_off[order[i]] > 4096) return host("device schedule: a level-0 list beyond 4096 entries (whitelist sort)");
+            return PathChoice{PATH_DEV_SCHEDULE, true, ""};
+        }
         if (fw_mi_rounds()) return host("device schedule: FW_MI_ROUNDS=1");
         if (!fw_knob_on(knob::FW_MI_SCHED)) return host("device schedule: FW_MI_SCHED=0");  // (A/B runs, tests/test_gpu_mi.py compares the two)
         const int R = (opt.round_size <= 0 || opt.round_size > nt) ? nt : opt.round_size;
@@ -328,7 +348,7 @@ void deal_chains(size_t n, int K, std::vector<int> &chain_of, std::vector<size_t
     }
 }
 
-// chain q runs the targets dealt to it, chains 1.. on threads of their own
+// chain q runs the targets dealt to it, chains 1.. on threads of their own (the round loop; fwi_devhiton_fz_schedule keeps its own)
 int run_chains(fw_ctx *c, std::vector<FwDhTarget> &din, const std::vector<int> &chain_of, std::vector<std::vector<FwDhResult>> &pres,
                std::vector<FwDhFlat> &pflat)
 {
@@ -591,12 +611,14 @@ int conditional_stage(Learn &L)
     if (c->P.max_k == 0) return level0_as_directed(c, L.all);
     const PathChoice whole = choose_path(c, L.opt, L.allgather != nullptr, L.order.data(), L.nt, nullptr, 0);
     if (whole.path != PATH_DEV_SCHEDULE) {
-        if (fw_trace_host() && L.discrete) fprintf(stderr, "[fw] no %s\n", whole.why);
+        if (fw_trace_host()) fprintf(stderr, "[fw] no %s\n", whole.why);
         return run_rounds(L);
     }
     // the whole schedule stays on the device (whitelists built between the launches, one download at the end) -- same kernel, order
     // and team sizes per round as the round loop
-    return fwi_devhiton_mi_schedule(c, L.order.data(), L.nt, L.opt.round_size <= 0 ? L.nt : L.opt.round_size, L.opt.feed_forward != 0, L.all);
+    const int R = L.opt.round_size <= 0 ? L.nt : L.opt.round_size;
+    return L.discrete ? fwi_devhiton_mi_schedule(c, L.order.data(), L.nt, R, L.opt.feed_forward != 0, L.all)
+                      : fwi_devhiton_fz_schedule(c, L.order.data(), L.nt, R, L.opt.feed_forward != 0, L.all);
 }
 
 // make_weights / make_symmetric_graph (fw_graph.h) on the host threads of the context
@@ -695,6 +717,9 @@ struct ElimGuard {  // the device rounds read the mode from the context (fw_devh
 };
 
 }  // namespace
+
+int fwi_chain_count(const fw_ctx *c, size_t n_targets) { return chain_count(c, n_targets); }
+void fwi_deal_chains(size_t n, int K, std::vector<int> &chain_of, std::vector<size_t> &chain_idx) { deal_chains(n, K, chain_of, chain_idx); }
 
 void fwi_host_workers_free(fw_ctx *c)
 {

@@ -378,6 +378,11 @@ struct FwDhFlat {  // (one allocation per run instead of three per target: 150 0
 int fwi_devhiton_run(fw_ctx *ctx, const std::vector<FwDhTarget> &in, std::vector<FwDhResult> &out, FwDhFlat &flat, int chain = 0);
 // the whole feed-forward schedule of the discrete kinds on the device: whitelists built between the launches, one download (r05)
 int fwi_devhiton_mi_schedule(fw_ctx *ctx, const int32_t *sched, int nt, int R, bool feed_forward, FwDirected &all);
+// the same for Fisher-z (device rounds on concurrent chains, the host between the rounds of targets gone)
+int fwi_devhiton_fz_schedule(fw_ctx *ctx, const int32_t *sched, int nt, int R, bool feed_forward, FwDirected &all);
+// fw_hiton.cpp: chains of a round of n targets, and which chain target i goes to (and its index there)
+int fwi_chain_count(const fw_ctx *ctx, size_t n_targets);
+void fwi_deal_chains(size_t n, int K, std::vector<int> &chain_of, std::vector<size_t> &chain_idx);
 int fwi_mi_segments_dev(fw_ctx *ctx, unsigned grid, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns,
                         hipStream_t stream);
 int fwi_fz_thresholds(fw_ctx *ctx, hipStream_t stream, double *zscale);  // ensures ctx->d_thr (fz_thresholds_kernel)

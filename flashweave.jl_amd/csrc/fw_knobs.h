@@ -20,6 +20,7 @@
     X(FW_DEV_MIN_TARGETS, "fewest targets of a round that take the device path; default 64 (fz, fz_nz) / 256 (discrete)")                                                 \
     X(FW_NZ_DEV, "0: fz_nz rounds through the host pool; default on")                                                                                                     \
     X(FW_MI_SCHED, "0: discrete kinds as one launch per round with the host in between instead of the device schedule; default on")                                       \
+    X(FW_FZ_SCHED, "0: fz feed-forward rounds one by one with the host in between instead of the device schedule; default on")                                            \
     X(FW_MI_ROUNDS, "non-zero: discrete kinds as level-synchronous rounds over the segment kernels instead of the persistent kernel; default 0")                          \
     X(FW_DH_CHAINS, "concurrent chains of device rounds (fz), clamped to 1..4; default 2")                                                                                \
     X(FW_DH_CHAINS_DISC, "the same for the discrete kinds under FW_MI_ROUNDS, clamped to 1..4; default 2")                                                                \
