@@ -2487,25 +2487,32 @@ __global__ __launch_bounds__(256) void dh_nz_recs_kernel(const DhTgt *__restrict
     }
 }
 
-// ---- the whole feed-forward schedule of the discrete kinds on the device (fwi_devhiton_mi_schedule) ------------------------------
+// ---- the whole feed-forward schedule on the device (fwi_devhiton_mi_schedule, fwi_devhiton_fz_schedule) ------------------------------
 // per-target state of EVERY target of the schedule, built on the device from the level-0 CSR: a target's arrays (candidates in
-// hiton.jl:211-217 order, TPC / PC, accepted list, whitelist) all sit at its level-0 offset nb_off[T] with its degree as capacity
-__global__ __launch_bounds__(256) void dh_mi_init_kernel(DhTgt *__restrict__ tg, int nt, const int32_t *__restrict__ sched,
-                                                         const long long *__restrict__ nb_off, const int32_t *__restrict__ levels)
+// hiton.jl:211-217 order, TPC / PC, accepted lists, whitelist) all sit at its level-0 offset nb_off[T] with its degree as capacity --
+// what dh_build_targets makes on the host.  tgt_T: the targets in the order of tg (discrete: schedule order; Fisher-z: slot order =
+// round, chain, index in the chain).  levels (discrete kinds, else null): a constant variable has nothing to test.  slot_tm (Fisher-z,
+// else null): the offsets of the local correlation matrices (dh_tm_off); absent, tm_off stays what the memset gives.  wl_unsorted:
+// 1 where the whitelists are read as the appends left them (discrete), 0 where the round that reads them sorts them first
+// (dh_fz_round_begin_kernel)
+__global__ __launch_bounds__(256) void dh_sched_init_kernel(DhTgt *__restrict__ tg, int nt, const int32_t *__restrict__ tgt_T,
+                                                            const long long *__restrict__ nb_off, const int32_t *__restrict__ levels,
+                                                            const long long *__restrict__ slot_tm, int wl_unsorted)
 {
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= nt) return;
     DhTgt x;
     __builtin_memset(&x, 0, sizeof(x));
-    const int T = sched[i];
+    const int T = tgt_T[i];
     const long long o = nb_off[T];
     const int deg = (int)(nb_off[T + 1] - o);
     x.T = T;
     x.nc = x.cap = deg;
-    x.phase = (deg == 0 || levels[T] < 2) ? 2 : 0;  // hiton.jl:182-184 (a constant variable), :336-338 (no candidate)
+    x.phase = (deg == 0 || (levels && levels[T] < 2)) ? 2 : 0;  // hiton.jl:182-184 (a constant variable), :336-338 (no candidate)
     x.co = x.cand_off = x.wl_off = x.nb_off = o;
     x.nb_n = deg;
-    x.wl_unsorted = 1;
+    x.wl_unsorted = wl_unsorted;
+    if (slot_tm) x.tm_off = slot_tm[i];
     tg[i] = x;
 }
 
@@ -2524,28 +2531,6 @@ __global__ __launch_bounds__(256) void dh_wl_append_kernel(const DhTgt *__restri
         const int32_t u = pc_key[co + i];
         if (round_of[u] > round) wl[nb_off[u] + (long long)atomicAdd(&wl_cnt[u], 1u)] = T;
     }
-}
-
-// ---- the whole feed-forward schedule of Fisher-z on the device (fwi_devhiton_fz_schedule) ----
-// per-target state of every target of the schedule, in slot order (round, chain, index in the chain): what dh_build_targets makes, with
-// the persistent arrays (TPC / PC, accepted lists, whitelist) at the level-0 offset nb_off[T] and the degree as capacity
-__global__ __launch_bounds__(256) void dh_fz_init_kernel(DhTgt *__restrict__ tg, int nt, const int32_t *__restrict__ slot_T,
-                                                         const long long *__restrict__ slot_tm, const long long *__restrict__ nb_off)
-{
-    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
-    if (i >= nt) return;
-    DhTgt x;
-    __builtin_memset(&x, 0, sizeof(x));
-    const int T = slot_T[i];
-    const long long o = nb_off[T];
-    const int deg = (int)(nb_off[T + 1] - o);
-    x.T = T;
-    x.nc = x.cap = deg;
-    x.phase = deg == 0 ? 2 : 0;  // hiton.jl:336-338 (no candidate)
-    x.co = x.cand_off = x.wl_off = x.nb_off = o;
-    x.nb_n = deg;
-    x.tm_off = slot_tm[i];
-    tg[i] = x;
 }
 
 // the list of unfinished targets at the start of a round of targets: every target, in order
@@ -2830,11 +2815,13 @@ static DhPolicy dh_policy(const fw_ctx *c, int ntg)
 
 static unsigned dh_team_min() { static const unsigned v = (unsigned)fw_knob_int(knob::FW_MI_TEAM_MIN, 96); return v; }
 static unsigned dh_team_max() { static const unsigned v = (unsigned)fw_knob_int(knob::FW_MI_TEAM_MAX, 192); return v; }  // (64 / 256: cfg2 10.5 ms, cfg4 161.7; 128 / 128: 9.4, 162.7; 96 / 192: 9.3, 159.6)
-// the first targets of `order` (heaviest first; deg(t) = candidates of target t) with at least FW_MI_TEAM_MIN candidates, at most
-// FW_MI_TEAM_MAX of them: a workgroup each
+// order of a discrete round's n targets: heaviest first, stable (deg(t) = candidates of target t).  Returns the team size: the first
+// targets of the order with at least FW_MI_TEAM_MIN candidates, at most FW_MI_TEAM_MAX of them, get a workgroup each
 template <class Deg>
-static unsigned dh_team_size(const int32_t *order, Deg deg, int n)
+static unsigned dh_heaviest_first(int32_t *order, int n, Deg deg)
 {
+    for (int t = 0; t < n; ++t) order[t] = t;
+    std::stable_sort(order, order + n, [&](int32_t u, int32_t v) { return deg(u) > deg(v); });
     const unsigned team_min = dh_team_min(), team_max = dh_team_max();
     unsigned team = 0u;
     while (team_min > 0u && team < team_max && (int)team < n && (unsigned)deg(order[team]) >= team_min) ++team;
@@ -2926,6 +2913,85 @@ static int dh_mi_check(fw_ctx *c, const MiQueue &hq, unsigned grid, int round, i
     return FW_OK;
 }
 
+// ---- device buffers that the drivers share ----
+
+// a target's persistent lists (TPC / PC with statistics and p-values, accepted lists, whitelist), n entries in all; the accepted lists
+// take 2 * n entries in each of acc_d1 buffers (DH_ACC_OFF)
+struct DhLists {
+    int32_t *tpc_key, *pc_key, *acc, *wl;
+    double *tpc_stat, *tpc_p, *pc_stat, *pc_p;
+};
+static DhLists dh_lists_layout(DhArena &a, size_t n, size_t acc_d1, size_t n_wl)
+{
+    DhLists b{};
+    b.tpc_key = a.take<int32_t>(n, 4);
+    b.pc_key = a.take<int32_t>(n, 4);
+    b.acc = a.take<int32_t>(2 * n * acc_d1, 4);
+    b.tpc_stat = a.take<double>(n, 8);
+    b.tpc_p = a.take<double>(n, 8);
+    b.pc_stat = a.take<double>(n, 8);
+    b.pc_p = a.take<double>(n, 8);
+    b.wl = a.take<int32_t>(n_wl, 4);
+    return b;
+}
+
+// what the rounds of the segment kernel over ntg targets work in (DhRounds): a round of fwi_devhiton_run has its own, a chain of
+// fwi_devhiton_fz_schedule reserves one for its largest round
+struct DhRoundScratch {
+    DhGlobal *g;
+    long long *seg0;
+    unsigned long long *win, *win2;
+    unsigned int *sp;
+    int32_t *act;  // ping-pong list of the unfinished targets
+    FwSeg *segs;
+    FwSegOut *so;
+    float *tmat;
+};
+static DhRoundScratch dh_scratch_layout(DhArena &a, size_t ntg, size_t max_ns, size_t tm_floats)
+{
+    DhRoundScratch b{};
+    b.g = a.take<DhGlobal>(1);
+    b.seg0 = a.take<long long>(ntg + 1);
+    b.win = a.take<unsigned long long>(ntg + 1);
+    b.sp = a.take<unsigned int>(ntg + 1);
+    b.win2 = a.take<unsigned long long>(ntg + 1);
+    b.act = a.take<int32_t>(2 * ntg);
+    b.segs = a.take<FwSeg>(max_ns);
+    b.so = a.take<FwSegOut>(max_ns);
+    if (tm_floats) b.tmat = a.take<float>(tm_floats, 4);
+    return b;
+}
+
+// a copy of the level-0 lists
+struct DhLevel0 {
+    long long *off;
+    int32_t *idx;
+    double *stat, *p;
+};
+
+// The arrays the kernels work on: the interleaving candidates, a driver's state and the level-0 lists -- the context's where it holds
+// them on the device, else the run's own copy.  wl_cnt and tmat stay null: the drivers that have them set them.
+static DhArrays dh_arrays(const fw_ctx *c, const int32_t *cand0, const DhLists &s, const DhLevel0 &own)
+{
+    const bool nb_on_dev = c->d_nb_idx != nullptr;
+    DhArrays A{};
+    A.cand0 = cand0;
+    A.tpc_key = s.tpc_key;
+    A.pc_key = s.pc_key;
+    A.acc = s.acc;
+    A.tpc_stat = s.tpc_stat;
+    A.tpc_p = s.tpc_p;
+    A.pc_stat = s.pc_stat;
+    A.pc_p = s.pc_p;
+    A.wl = s.wl;
+    A.nb_off = nb_on_dev ? c->d_nb_off : own.off;
+    A.nb_idx = nb_on_dev ? c->d_nb_idx : own.idx;
+    A.nb_stat = nb_on_dev ? c->d_nb_stat : own.stat;
+    A.nb_p = nb_on_dev ? c->d_nb_p : own.p;
+    A.rej = c->d_rej_run;
+    return A;
+}
+
 // ---- one round of targets (fwi_devhiton_run) ----
 
 // what sizes the arena of a round
@@ -2935,16 +3001,9 @@ struct DhRunSizes {
 };
 struct DhRunBufs {
     DhTgt *tg;
-    DhGlobal *g;
-    long long *seg0;
-    unsigned long long *win, *win2;
-    unsigned int *sp;
-    int32_t *act;  // ping-pong list of the unfinished targets
-    int32_t *cand0, *tpc_key, *pc_key, *acc, *wl;
-    double *tpc_stat, *tpc_p, *pc_stat, *pc_p;
-    FwSeg *segs;
-    FwSegOut *so;
-    float *tmat;
+    DhRoundScratch s;
+    int32_t *cand0;
+    DhLists lists;
     ulonglong2 *log;
     MiQueue *mq;  // persistent kernel only
     MiBoard *boards;
@@ -2953,32 +3012,15 @@ struct DhRunBufs {
     FwNzJob *nzrecs;  // fz_nz only
     long long *nzaoff;
     float *nzarena;
-    long long *nb_off;  // own copy of the level-0 lists: only when the context holds none on the device
-    int32_t *nb_idx;
-    double *nb_stat, *nb_p;
+    DhLevel0 nb;  // own copy of the level-0 lists: only when the context holds none on the device
 };
 static DhRunBufs dh_run_layout(DhArena &a, const DhRunSizes &z)
 {
     DhRunBufs b{};
     b.tg = a.take<DhTgt>(z.ntg);
-    b.g = a.take<DhGlobal>(1);
-    b.seg0 = a.take<long long>(z.ntg + 1);
-    b.win = a.take<unsigned long long>(z.ntg + 1);
-    b.sp = a.take<unsigned int>(z.ntg + 1);
-    b.win2 = a.take<unsigned long long>(z.ntg + 1);
-    b.act = a.take<int32_t>(2 * z.ntg);
+    b.s = dh_scratch_layout(a, z.ntg, z.max_ns, z.tm_floats);
     b.cand0 = a.take<int32_t>(z.tot, 4);
-    b.tpc_key = a.take<int32_t>(z.tot, 4);
-    b.pc_key = a.take<int32_t>(z.tot, 4);
-    b.acc = a.take<int32_t>(2 * z.tot * z.d1, 4);
-    b.tpc_stat = a.take<double>(z.tot, 8);
-    b.tpc_p = a.take<double>(z.tot, 8);
-    b.pc_stat = a.take<double>(z.tot, 8);
-    b.pc_p = a.take<double>(z.tot, 8);
-    b.wl = a.take<int32_t>(z.n_wl, 4);
-    b.segs = a.take<FwSeg>(z.max_ns);
-    b.so = a.take<FwSegOut>(z.max_ns);
-    if (z.tm_floats) b.tmat = a.take<float>(z.tm_floats, 4);
+    b.lists = dh_lists_layout(a, z.tot, z.d1, z.n_wl);
     if (z.log) b.log = a.take<ulonglong2>(DH_LOG_CAP);
     if (z.per_target) {
         b.mq = a.take<MiQueue>(1);
@@ -2992,10 +3034,10 @@ static DhRunBufs dh_run_layout(DhArena &a, const DhRunSizes &z)
         b.nzarena = a.take<float>(z.nz_arena, 4);
     }
     if (z.own_nb) {
-        b.nb_off = a.take<long long>(z.p + 1);
-        b.nb_idx = a.take<int32_t>(z.nnz, 4);
-        b.nb_stat = a.take<double>(z.nnz, 8);
-        b.nb_p = a.take<double>(z.nnz, 8);
+        b.nb.off = a.take<long long>(z.p + 1);
+        b.nb.idx = a.take<int32_t>(z.nnz, 4);
+        b.nb.stat = a.take<double>(z.nnz, 8);
+        b.nb.p = a.take<double>(z.nnz, 8);
     }
     return b;
 }
@@ -3013,7 +3055,7 @@ struct DhRun {
     std::vector<long long> nz_aoff;
     size_t tot = 0, tm_floats = 0, nz_arena = 0;
     int max_cap = 0, max_wl = 0;  // most candidates / most whitelisted neighbours of one target
-    unsigned max_ns = 0;          // capacity of the segment list (a job + its look-ahead jobs each round up)
+    unsigned max_ns = 0;          // capacity of the segment list (dh_max_ns)
     // device side (dh_upload)
     DhRunBufs D{};
     DhGlobal *hg = nullptr;  // two pinned copies of the device record (one per batch in flight)
@@ -3027,6 +3069,21 @@ struct DhRun {
     unsigned max_ab_seen = 0;   // ... and the largest accepted + whitelisted-to-come
     bool dev_wl = false;        // fwi_devhiton_fz_schedule: the whitelists were built on the device (R.wl stays empty), the longest holds max_wl entries
 };
+
+// The layout rule of a round of targets, for the host-built rounds (dh_build_targets) and the slots of fwi_devhiton_fz_schedule alike.
+// dh_tm_off: the offset (floats) of the local correlation matrix of a target with deg level-0 neighbours in its round's block, which
+// holds tm_floats so far and grows by the matrix; -1: the target gets none (dh_tmat_build_kernel fills the others)
+static long long dh_tm_off(const fw_ctx *c, const DhPolicy &y, int deg, size_t &tm_floats)
+{
+    const bool tm_on = c->P.kind == FW_FZ && c->P.max_k <= 5 && c->d_cor != nullptr && y.tm_min > 0;  // (max_k 6-7: the general-form kernel reads the p x p matrix)
+    const size_t m = (size_t)deg + 1;
+    if (!tm_on || deg < y.tm_min || m > 4096 || tm_floats + m * m > (size_t)1 << 32) return -1;  // (<= 16 GB per chain; ids of a target staged in 16 KB of LDS)
+    const long long off = (long long)tm_floats;
+    tm_floats += m * m;
+    return off;
+}
+// capacity of the segment list of a round of ntg targets (a job + its look-ahead jobs each round up)
+static unsigned dh_max_ns(const DhPolicy &y, int ntg) { return y.seg_target + (unsigned)ntg * (unsigned)(1 + DH_MAX_SPEC) + 256u; }
 
 // targets, candidate lists and whitelists in one flat layout each; offsets of the local matrices
 static void dh_build_targets(DhRun &R, const std::vector<FwDhTarget> &in)
@@ -3057,14 +3114,7 @@ static void dh_build_targets(DhRun &R, const std::vector<FwDhTarget> &in)
         R.tg[t] = x;
     }
     R.tot = (size_t)co;
-    const bool tm_on = c->P.kind == FW_FZ && c->P.max_k <= 5 && c->d_cor != nullptr && R.y.tm_min > 0;  // (max_k 6-7: the general-form kernel reads the p x p matrix)
-    for (int t = 0; t < ntg; ++t) {
-        R.tg[t].tm_off = -1;
-        const size_t m = (size_t)R.tg[t].nb_n + 1;
-        if (!tm_on || R.tg[t].nb_n < R.y.tm_min || m > 4096 || R.tm_floats + m * m > (size_t)1 << 32) continue;  // (<= 16 GB per chain; ids of a target staged in 16 KB of LDS)
-        R.tg[t].tm_off = (long long)R.tm_floats;
-        R.tm_floats += m * m;
-    }
+    for (int t = 0; t < ntg; ++t) R.tg[t].tm_off = dh_tm_off(c, R.y, R.tg[t].nb_n, R.tm_floats);
     // fz_nz: a record and an arena slice of (longest list + 2)^2 floats per target.  Without whitelists an accepted list never outgrows
     // the candidate list; with whitelists (feed-forward) a whitelisted member of the elimination pool is pushed a second time
     // (hiton.jl:24-26), so a list can reach twice the candidates -- the capacity of the accepted buffers (DH_ACC_OFF: 2 x cap)
@@ -3076,7 +3126,7 @@ static void dh_build_targets(DhRun &R, const std::vector<FwDhTarget> &in)
             R.nz_arena += mt * mt;
         }
     }
-    R.max_ns = R.y.seg_target + (unsigned)ntg * (unsigned)(1 + DH_MAX_SPEC) + 256u;
+    R.max_ns = dh_max_ns(R.y, ntg);
 }
 
 // device buffers (one arena), the round's inputs, the local correlation matrices, the run's parameters
@@ -3086,7 +3136,7 @@ static int dh_upload(DhRun &R)
     hipStream_t st = R.st;
     const int ntg = R.ntg, p = c->P.p;
     const size_t tot = R.tot, nnz = (size_t)c->nb_off[p];
-    const bool nb_on_dev = c->d_nb_idx != nullptr;
+    const bool nb_on_dev = c->d_nb_idx != nullptr;  // (else the run carries its own copy: dh_arrays)
     const DhRunSizes z{(size_t)ntg, tot, (size_t)R.y.spec_depth + 1, R.wl.size(), R.max_ns, R.tm_floats, R.nz_arena, (size_t)p, nnz,
                        R.y.log_path != nullptr, R.y.per_target, R.y.nzk, !nb_on_dev};
     int rc;
@@ -3101,37 +3151,23 @@ static int dh_upload(DhRun &R)
     }
     FW_HIP(c, hipMemcpyAsync(D.tg, R.tg.data(), sizeof(DhTgt) * ntg, hipMemcpyHostToDevice, st));
     hg[0].n_act = (unsigned int)ntg;  // every target starts on the list (the pinned page is the staging copy: stream-ordered)
-    FW_HIP(c, hipMemcpyAsync(D.g, hg, sizeof(DhGlobal), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(dh_iota_kernel, dim3((unsigned)((ntg + 255) / 256)), dim3(256), 0, st, D.act, ntg);  // (was a blocking copy of a host list)
-    FW_HIP(c, hipMemsetAsync(D.seg0, 0, sizeof(long long) * ((size_t)ntg + 1), st));
+    FW_HIP(c, hipMemcpyAsync(D.s.g, hg, sizeof(DhGlobal), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dh_iota_kernel, dim3((unsigned)((ntg + 255) / 256)), dim3(256), 0, st, D.s.act, ntg);  // (was a blocking copy of a host list)
+    FW_HIP(c, hipMemsetAsync(D.s.seg0, 0, sizeof(long long) * ((size_t)ntg + 1), st));
     if (tot && !R.use_devc) FW_HIP(c, hipMemcpyAsync(D.cand0, R.cand0.data(), 4 * tot, hipMemcpyHostToDevice, st));
-    if (!R.wl.empty()) FW_HIP(c, hipMemcpyAsync(D.wl, R.wl.data(), 4 * R.wl.size(), hipMemcpyHostToDevice, st));
+    if (!R.wl.empty()) FW_HIP(c, hipMemcpyAsync(D.lists.wl, R.wl.data(), 4 * R.wl.size(), hipMemcpyHostToDevice, st));
     if (!nb_on_dev) {
-        FW_HIP(c, hipMemcpyAsync(D.nb_off, c->nb_off.data(), 8 * ((size_t)p + 1), hipMemcpyHostToDevice, st));
+        FW_HIP(c, hipMemcpyAsync(D.nb.off, c->nb_off.data(), 8 * ((size_t)p + 1), hipMemcpyHostToDevice, st));
         if (nnz) {
-            FW_HIP(c, hipMemcpyAsync(D.nb_idx, c->nb_idx.data(), 4 * nnz, hipMemcpyHostToDevice, st));
-            FW_HIP(c, hipMemcpyAsync(D.nb_stat, c->nb_stat.data(), 8 * nnz, hipMemcpyHostToDevice, st));
-            FW_HIP(c, hipMemcpyAsync(D.nb_p, c->nb_p.data(), 8 * nnz, hipMemcpyHostToDevice, st));
+            FW_HIP(c, hipMemcpyAsync(D.nb.idx, c->nb_idx.data(), 4 * nnz, hipMemcpyHostToDevice, st));
+            FW_HIP(c, hipMemcpyAsync(D.nb.stat, c->nb_stat.data(), 8 * nnz, hipMemcpyHostToDevice, st));
+            FW_HIP(c, hipMemcpyAsync(D.nb.p, c->nb_p.data(), 8 * nnz, hipMemcpyHostToDevice, st));
         }
     }
-    DhArrays &A = R.A;
-    A.cand0 = R.use_devc ? c->d_cand : D.cand0;
-    A.tpc_key = D.tpc_key;
-    A.pc_key = D.pc_key;
-    A.acc = D.acc;
-    A.tpc_stat = D.tpc_stat;
-    A.tpc_p = D.tpc_p;
-    A.pc_stat = D.pc_stat;
-    A.pc_p = D.pc_p;
-    A.wl = D.wl;
-    A.nb_off = nb_on_dev ? c->d_nb_off : D.nb_off;
-    A.nb_idx = nb_on_dev ? c->d_nb_idx : D.nb_idx;
-    A.nb_stat = nb_on_dev ? c->d_nb_stat : D.nb_stat;
-    A.nb_p = nb_on_dev ? c->d_nb_p : D.nb_p;
-    A.rej = c->d_rej_run;
-    A.tmat = D.tmat;
-    if (D.tmat) {
-        hipLaunchKernelGGL(dh_tmat_build_kernel, dim3((unsigned)ntg, 8u), dim3(256), 0, st, (const DhTgt *)D.tg, ntg, A.nb_idx, (const float *)c->d_cor, p, D.tmat);
+    DhArrays &A = R.A = dh_arrays(c, R.use_devc ? c->d_cand : D.cand0, D.lists, D.nb);
+    A.tmat = D.s.tmat;
+    if (D.s.tmat) {
+        hipLaunchKernelGGL(dh_tmat_build_kernel, dim3((unsigned)ntg, 8u), dim3(256), 0, st, (const DhTgt *)D.tg, ntg, A.nb_idx, (const float *)c->d_cor, p, D.s.tmat);
         FW_HIP(c, hipGetLastError());
         if (R.trace_host) fprintf(stderr, "[fw] chain %d: local correlation matrices: %.1f MB\n", R.chain, 4e-6 * (double)R.tm_floats);
     }
@@ -3148,10 +3184,8 @@ static int dh_run_persistent(DhRun &R, DhEvents &E)
     const DhRunBufs &D = R.D;
     const std::vector<DhTgt> &tg = R.tg;
     std::vector<int32_t> order((size_t)ntg);
-    for (int t = 0; t < ntg; ++t) order[t] = t;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t u, int32_t v) { return tg[u].nc > tg[v].nc; });  // heaviest first
-    FW_HIP(c, hipMemcpyAsync(D.act, order.data(), sizeof(int32_t) * (size_t)ntg, hipMemcpyHostToDevice, st));
-    const unsigned team = dh_team_size(order.data(), [&](int32_t t) { return tg[t].nc; }, ntg);
+    const unsigned team = dh_heaviest_first(order.data(), ntg, [&](int32_t t) { return tg[t].nc; });
+    FW_HIP(c, hipMemcpyAsync(D.s.act, order.data(), sizeof(int32_t) * (size_t)ntg, hipMemcpyHostToDevice, st));
     if (R.trace_host) {
         int c32 = 0, c64 = 0, c128 = 0, c192 = 0;
         for (int t = 0; t < ntg; ++t) c32 += tg[t].nc >= 32, c64 += tg[t].nc >= 64, c128 += tg[t].nc >= 128, c192 += tg[t].nc >= 192;
@@ -3162,7 +3196,7 @@ static int dh_run_persistent(DhRun &R, DhEvents &E)
     FW_HIP(c, hipMemsetAsync(D.mq, 0, sizeof(MiQueue), st));
     FW_HIP(c, hipMemsetAsync(D.boards, 0, sizeof(MiBoard) * MI_BOARD_CAP, st));  // ready flags, claimed / finished counts
     FW_HIP(c, hipEventRecord(E.ev[0], st));
-    const unsigned grid = dh_mi_launch(c, st, D.tg, ntg, (const int32_t *)D.act, R.A, R.P, team, R.trace_host, D.mq, D.boards, D.mres, D.bacc);
+    const unsigned grid = dh_mi_launch(c, st, D.tg, ntg, (const int32_t *)D.s.act, R.A, R.P, team, R.trace_host, D.mq, D.boards, D.mres, D.bacc);
     FW_HIP(c, hipGetLastError());
     FW_HIP(c, hipEventRecord(E.ev[1], st));
     FW_HIP(c, hipStreamSynchronize(st));
@@ -3185,6 +3219,7 @@ struct DhRounds {
     DhEvents &E;  // E.ev[(q * DH_BATCH + r) * 2 + 0 / 1] around the segment launch of round r of batch slot q; E.ev_end[q]
     fw_ctx *c = R.c;
     const DhRunBufs &D = R.D;
+    const DhRoundScratch &S = R.D.s;
     const DhPolicy &y = R.y;
     const int ntg = R.ntg;
     hipStream_t st = R.st, hs = R.st;  // hs: stream of the small kernels (FW_DH_HP: the chain's high-priority stream)
@@ -3232,21 +3267,21 @@ struct DhRounds {
             FW_HIP(c, hipStreamWaitEvent(hs, c->dh_hp_ev[R.chain][0], 0));
         }
         if (A.rej)  // (the rejection log: its own instantiation, so that the default one keeps its registers)
-            hipLaunchKernelGGL(dh_step_kernel<true>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, D.tg, ntg, D.g, A,
-                               (const FwSegOut *)D.so, (const long long *)D.seg0, D.win, D.sp, D.win2, (const int32_t *)D.act, R.P);
+            hipLaunchKernelGGL(dh_step_kernel<true>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, D.tg, ntg, S.g, A,
+                               (const FwSegOut *)S.so, (const long long *)S.seg0, S.win, S.sp, S.win2, (const int32_t *)S.act, R.P);
         else
-            hipLaunchKernelGGL(dh_step_kernel<false>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, D.tg, ntg, D.g, A,
-                               (const FwSegOut *)D.so, (const long long *)D.seg0, D.win, D.sp, D.win2, (const int32_t *)D.act, R.P);
+            hipLaunchKernelGGL(dh_step_kernel<false>, dim3((n_act_bound + 3u) / 4u), dim3(256), 0, hs, D.tg, ntg, S.g, A,
+                               (const FwSegOut *)S.so, (const long long *)S.seg0, S.win, S.sp, S.win2, (const int32_t *)S.act, R.P);
         if (compact)  // between step and plan: seg0 of the coming launch is built on the new list
-            hipLaunchKernelGGL(dh_compact_kernel, dim3(1), dim3(1024), 0, hs, (const DhTgt *)D.tg, ntg, D.g, D.act);
+            hipLaunchKernelGGL(dh_compact_kernel, dim3(1), dim3(1024), 0, hs, (const DhTgt *)D.tg, ntg, S.g, S.act);
         if (y.plan_small)
-            hipLaunchKernelGGL(dh_plan_small_kernel, dim3(1), dim3(256), 0, hs, ntg, D.g, (const unsigned long long *)D.win,
-                               (const unsigned int *)D.sp, (const unsigned long long *)D.win2, (const int32_t *)D.act, D.seg0, PA);
+            hipLaunchKernelGGL(dh_plan_small_kernel, dim3(1), dim3(256), 0, hs, ntg, S.g, (const unsigned long long *)S.win,
+                               (const unsigned int *)S.sp, (const unsigned long long *)S.win2, (const int32_t *)S.act, S.seg0, PA);
         else
-            hipLaunchKernelGGL(dh_plan_kernel, dim3(1), dim3(1024), 0, hs, ntg, D.g, (const unsigned long long *)D.win,
-                               (const unsigned int *)D.sp, (const unsigned long long *)D.win2, (const int32_t *)D.act, D.seg0, PA);
-        hipLaunchKernelGGL(dh_fill_kernel, dim3(g_fill), dim3(256), 0, hs, (const DhTgt *)D.tg, ntg, D.g,
-                           (const long long *)D.seg0, A, D.segs, y.spec_depth + 1, (const int32_t *)D.act);
+            hipLaunchKernelGGL(dh_plan_kernel, dim3(1), dim3(1024), 0, hs, ntg, S.g, (const unsigned long long *)S.win,
+                               (const unsigned int *)S.sp, (const unsigned long long *)S.win2, (const int32_t *)S.act, S.seg0, PA);
+        hipLaunchKernelGGL(dh_fill_kernel, dim3(g_fill), dim3(256), 0, hs, (const DhTgt *)D.tg, ntg, S.g,
+                           (const long long *)S.seg0, A, S.segs, y.spec_depth + 1, (const int32_t *)S.act);
         if (y.use_hp) {  // ... and in front of the next one
             FW_HIP(c, hipEventRecord(c->dh_hp_ev[R.chain][1], hs));
             FW_HIP(c, hipStreamWaitEvent(st, c->dh_hp_ev[R.chain][1], 0));
@@ -3257,7 +3292,7 @@ struct DhRounds {
     {
         const DhArrays &A = R.A;
         const int q = (int)(b & 1u);
-        const unsigned *d_ns = &D.g->ns;
+        const unsigned *d_ns = &S.g->ns;
         for (int r = 0; r < y.nb; ++r) {
             // lists grow by at most one entry per round: 3 batches cover the lag of the record plus this batch
             // ... and a whitelisted neighbour is appended at most once per target: max_ab (accepted + whitelisted neighbours
@@ -3273,20 +3308,20 @@ struct DhRounds {
             int rc;
             if (y.nzk) {
                 // this round's fresh jobs: records (one thread per unfinished target), their matrices, then the enumeration
-                hipLaunchKernelGGL(dh_nz_recs_kernel, dim3((n_act_bound + 255u) / 256u), dim3(256), 0, st, (const DhTgt *)D.tg, ntg, (const DhGlobal *)D.g,
-                                   (const int32_t *)D.act, A, D.nzrecs, (const long long *)D.nzaoff);
+                hipLaunchKernelGGL(dh_nz_recs_kernel, dim3((n_act_bound + 255u) / 256u), dim3(256), 0, st, (const DhTgt *)D.tg, ntg, (const DhGlobal *)S.g,
+                                   (const int32_t *)S.act, A, D.nzrecs, (const long long *)D.nzaoff);
                 rc = fwi_fznz_submatrices_dev(c, ntg, D.nzrecs, A.acc, D.nzarena, (any_wl ? 2 * R.max_cap : R.max_cap) + 2, true, st);
-                if (!rc) rc = fwi_fznz_segments_dev(c, y.grid_seg, D.segs, A.acc, D.so, d_ns, any_big, &D.g->any_big, D.nzrecs, D.nzarena, st);
+                if (!rc) rc = fwi_fznz_segments_dev(c, y.grid_seg, S.segs, A.acc, S.so, d_ns, any_big, &S.g->any_big, D.nzrecs, D.nzarena, st);
             } else {
-                rc = y.fz ? fwi_fz_segments_dev(c, y.grid_seg, D.segs, A.acc, D.so, d_ns, any_big, &D.g->any_big, st)
-                          : fwi_mi_segments_dev(c, grid_mi, D.segs, A.acc, D.so, d_ns, st);
+                rc = y.fz ? fwi_fz_segments_dev(c, y.grid_seg, S.segs, A.acc, S.so, d_ns, any_big, &S.g->any_big, st)
+                          : fwi_mi_segments_dev(c, grid_mi, S.segs, A.acc, S.so, d_ns, st);
             }
             if (rc) return rc;
             if (timed(b, r)) (void)hipEventRecord(ev(q, 2 * r + 1), st);
             if ((rc = planfill((b * (unsigned)y.nb + (unsigned)r) % 16u == 0u))) return rc;  // the list of unfinished targets is compacted every 16 rounds
         }
         FW_HIP(c, hipGetLastError());
-        FW_HIP(c, hipMemcpyAsync(R.hg + q, D.g, sizeof(DhGlobal), hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(R.hg + q, S.g, sizeof(DhGlobal), hipMemcpyDeviceToHost, st));
         FW_HIP(c, hipEventRecord(E.ev_end[q], st));
         return FW_OK;
     }
@@ -3352,7 +3387,7 @@ static int dh_write_log(const DhRun &R)
     fw_ctx *c = R.c;
     std::vector<ulonglong2> lg(DH_LOG_CAP);
     DhGlobal fin{};
-    FW_HIP(c, hipMemcpy(&fin, R.D.g, sizeof(DhGlobal), hipMemcpyDeviceToHost));
+    FW_HIP(c, hipMemcpy(&fin, R.D.s.g, sizeof(DhGlobal), hipMemcpyDeviceToHost));
     FW_HIP(c, hipMemcpy(lg.data(), R.D.log, sizeof(ulonglong2) * DH_LOG_CAP, hipMemcpyDeviceToHost));
     long long n_tpc = 0, n_pc = 0;  // interleaving survivors / elimination survivors
     for (const DhTgt &x : R.tg) {
@@ -3448,6 +3483,17 @@ static void dh_trace_run(const DhRun &R, double t_setup, double t_rounds, double
             1e3 * t_setup, 1e3 * t_rounds, 1e3 * t_results);
 }
 
+// what the launches of a finished (or failed) run add to the context's counters: the kernels of every round of the segment kernel
+// (the persistent kernel: itself) and `extra_kernels`, what the caller launched around them
+static void dh_count_run(const DhRun &R, long extra_kernels)
+{
+    fw_ctx *c = R.c;
+    std::lock_guard<std::mutex> lk(dh_cnt_mu);
+    if (R.timed_n > 0) c->cnt.t_dev_subsets_s += R.timed_s * (double)R.launches_n / (double)R.timed_n;
+    c->cnt.subsets_launches += R.launches_n;
+    c->cnt.kernel_launches += (R.y.per_target ? R.launches_n : (R.y.nzk ? 7 : 4) * R.launches_n) + extra_kernels;
+}
+
 // One round of targets on the device.  in: T ids, interleaving candidates and (sorted) whitelists per target;
 // out: PC (keys, statistics, p-values) per target in insertion order.
 int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<FwDhResult> &out, FwDhFlat &flat, int chain)
@@ -3467,12 +3513,7 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
     if (!E.ok) return fw_fail(c, FW_ERR_DEVICE, "device HITON: hipEventCreate failed");
     const double th1 = fwi_now_s();
     rc = R.y.per_target ? dh_run_persistent(R, E) : DhRounds(R, E).run();
-    {
-        std::lock_guard<std::mutex> lk(dh_cnt_mu);
-        if (R.timed_n > 0) c->cnt.t_dev_subsets_s += R.timed_s * (double)R.launches_n / (double)R.timed_n;
-        c->cnt.subsets_launches += R.launches_n;
-        c->cnt.kernel_launches += R.y.per_target ? R.launches_n : (R.y.nzk ? 7 : 4) * R.launches_n;
-    }
+    dh_count_run(R, 0);
     if (rc) return rc;
     const double th2 = fwi_now_s();
     if ((rc = dh_download(R, out, flat))) return rc;
@@ -3487,50 +3528,134 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
     return FW_OK;
 }
 
+// ---- what the two whole-schedule drivers share (fwi_devhiton_mi_schedule, fwi_devhiton_fz_schedule) ----
+
+// the schedule: sched[0 .. nt) in rounds of R targets (learning.jl:97-98); round_of[v]: the round of variable v's own target, "never"
+// where it has none
+struct DhSchedPlan {
+    int nt, R, nrounds;
+    std::vector<int32_t> round_of;
+    DhSchedPlan(const int32_t *sched, int nt_, int R_, int p) : nt(nt_), R(R_ <= 0 || R_ > nt_ ? nt_ : R_), nrounds((nt + R - 1) / R), round_of((size_t)p, 0x7fffffff)
+    {
+        for (int i = 0; i < nt; ++i) round_of[sched[i]] = i / R;
+    }
+    int first(int r) const { return r * R; }
+    int count(int r) const { return std::min(nt, r * R + R) - r * R; }
+};
+
+// what lives for the whole schedule: every target's state, its lists at its level-0 offset nb_off[T] with its degree as capacity, the
+// device-built whitelists' counts, the packed results
+struct DhSchedState {
+    DhTgt *tg;
+    int32_t *round_of;
+    unsigned int *wl_cnt;
+    DhLists lists;
+    int32_t *ot, *ou;  // packed results: target, neighbour, statistic, p
+    double *os, *op;
+    unsigned long long *tot;  // [0..4] integers, [5] the Float64 sum of algorithmic bytes
+};
+// acc_d1: accepted-list buffers per target (1 for the discrete kinds, look-ahead + 1 for Fisher-z)
+static DhSchedState dh_sched_state_layout(DhArena &a, size_t nt, size_t p, size_t nnz, size_t acc_d1)
+{
+    DhSchedState b{};
+    b.tg = a.take<DhTgt>(nt);
+    b.round_of = a.take<int32_t>(p);
+    b.wl_cnt = a.take<unsigned int>(p);
+    b.lists = dh_lists_layout(a, nnz, acc_d1, nnz);
+    b.ot = a.take<int32_t>(nnz, 4);
+    b.ou = a.take<int32_t>(nnz, 4);
+    b.os = a.take<double>(nnz, 8);
+    b.op = a.take<double>(nnz, 8);
+    b.tot = a.take<unsigned long long>(8);
+    return b;
+}
+
+// Start of a schedule, on stream st: no result and no whitelist entry yet (a call leaves nothing behind for the next one), the round
+// of every variable, and the state of every target (dh_sched_init_kernel; d_T: the targets in the order of S.tg, uploaded by the
+// caller on the same stream).  The two memsets, the copy and the caller's own uploads are independent operations on one stream in
+// front of the init kernel: since the schedules share this start, each enqueues them in another order than it did on its own.
+static int dh_sched_begin(fw_ctx *c, hipStream_t st, const DhSchedState &S, const DhSchedPlan &pl, const int32_t *d_T, const int32_t *levels,
+                          const long long *slot_tm, int wl_unsorted)
+{
+    const size_t p = pl.round_of.size();
+    FW_HIP(c, hipMemsetAsync(S.tot, 0, 64, st));
+    FW_HIP(c, hipMemsetAsync(S.wl_cnt, 0, 4 * p, st));
+    FW_HIP(c, hipMemcpyAsync(S.round_of, pl.round_of.data(), 4 * p, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dh_sched_init_kernel, dim3((unsigned)((pl.nt + 255) / 256)), dim3(256), 0, st, S.tg, pl.nt, d_T, (const long long *)c->d_nb_off, levels,
+                       slot_tm, wl_unsorted);
+    FW_HIP(c, hipGetLastError());
+    return FW_OK;
+}
+
+// after a round of targets tg[0 .. ntg): interleaved.jl:136-140, kept where a later round reads it (dh_wl_append_kernel)
+static void dh_sched_append(fw_ctx *c, hipStream_t st, const DhSchedState &S, const DhTgt *tg, int ntg, int round)
+{
+    hipLaunchKernelGGL(dh_wl_append_kernel, dim3((unsigned)((ntg + 3) / 4)), dim3(256), 0, st, tg, ntg, (const int32_t *)S.lists.pc_key,
+                       (const int32_t *)S.round_of, round, S.lists.wl, (const long long *)c->d_nb_off, S.wl_cnt);
+}
+
+// results of a schedule: packed on the device (dh_sched_pack_kernel, enqueued behind the last round on st) ...
+static int dh_sched_pack(fw_ctx *c, hipStream_t st, const DhSchedState &S, int nt)
+{
+    hipLaunchKernelGGL(dh_sched_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)S.tg, nt, (const int32_t *)S.lists.pc_key,
+                       (const double *)S.lists.pc_stat, (const double *)S.lists.pc_p, S.ot, S.ou, S.os, S.op, S.tot, (double *)(S.tot + 5));
+    FW_HIP(c, hipGetLastError());
+    return FW_OK;
+}
+// ... the totals read back (with whatever the caller enqueued behind the pack kernel: the stream is idle on return) ...
+static int dh_sched_totals(fw_ctx *c, hipStream_t st, const DhSchedState &S, unsigned long long (&htot)[8])
+{
+    FW_HIP(c, hipMemcpyAsync(htot, S.tot, 64, hipMemcpyDeviceToHost, st));
+    FW_HIP(c, hipStreamSynchronize(st));
+    return FW_OK;
+}
+// ... and, once they are believed, one small download: (target, neighbour, statistic, p) appended to `all`, a target's entries together,
+// in PC insertion order.  The destinations are pageable: staged copies that may block in the call -- 0.9 ms for cfg3's 3.6 MB.
+static int dh_sched_finish(fw_ctx *c, hipStream_t st, const DhSchedState &S, const unsigned long long (&htot)[8], size_t nnz, FwDirected &all)
+{
+    if (htot[4]) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %llu targets did not finish", htot[4]);
+    const size_t nres = (size_t)htot[0], at0 = all.size();
+    if (nres > nnz) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %zu result entries for %zu level-0 entries", nres, nnz);
+    all.resize(at0 + nres);
+    if (nres) {
+        FW_HIP(c, hipMemcpyAsync(all.t.data() + at0, S.ot, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.u.data() + at0, S.ou, 4 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.s.data() + at0, S.os, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipMemcpyAsync(all.p.data() + at0, S.op, 8 * nres, hipMemcpyDeviceToHost, st));
+        FW_HIP(c, hipStreamSynchronize(st));
+    }
+    c->cnt.cond_tests_ref += (int64_t)htot[1];
+    c->cnt.subsets_calls += (int64_t)htot[2];
+    c->cnt.cond_tests_evaluated += (int64_t)htot[3];
+    double alg;
+    memcpy(&alg, &htot[5], sizeof(double));
+    c->cnt.alg_bytes_subsets += alg;
+    return FW_OK;
+}
+
 // ---- the whole feed-forward schedule of the discrete kinds (fwi_devhiton_mi_schedule) ----
 
 struct DhSchedSizes {
     size_t nt, p, nnz, nrounds;
 };
 struct DhSchedBufs {
-    DhTgt *tg;
-    int32_t *sched, *order, *round_of;
-    unsigned int *wl_cnt;
-    int32_t *tpc_key, *pc_key, *wl, *acc;
-    double *tpc_stat, *tpc_p, *pc_stat, *pc_p;
+    DhSchedState S;
+    int32_t *sched, *order;
     MiQueue *mq;  // one per round
     MiBoard *boards;
     FwSegOut *mres;
     int32_t *bacc;
-    int32_t *ot, *ou;  // packed results: target, neighbour, statistic, p
-    double *os, *op;
-    unsigned long long *tot;  // [0..4] integers, [5] the Float64 sum of algorithmic bytes
 };
 static DhSchedBufs dh_sched_layout(DhArena &a, const DhSchedSizes &z)
 {
     DhSchedBufs b{};
-    b.tg = a.take<DhTgt>(z.nt);
+    b.S = dh_sched_state_layout(a, z.nt, z.p, z.nnz, 1);
     b.sched = a.take<int32_t>(z.nt);
     b.order = a.take<int32_t>(z.nt);
-    b.round_of = a.take<int32_t>(z.p);
-    b.wl_cnt = a.take<unsigned int>(z.p);
-    b.tpc_key = a.take<int32_t>(z.nnz, 4);
-    b.pc_key = a.take<int32_t>(z.nnz, 4);
-    b.wl = a.take<int32_t>(z.nnz, 4);
-    b.acc = a.take<int32_t>(2 * z.nnz, 4);
-    b.tpc_stat = a.take<double>(z.nnz, 8);
-    b.tpc_p = a.take<double>(z.nnz, 8);
-    b.pc_stat = a.take<double>(z.nnz, 8);
-    b.pc_p = a.take<double>(z.nnz, 8);
     b.mq = a.take<MiQueue>(z.nrounds);
     b.boards = a.take<MiBoard>(MI_BOARD_CAP);
     b.mres = a.take<FwSegOut>(MI_REC_CAP);
     b.bacc = a.take<int32_t>(MI_BACC_CAP);
-    b.ot = a.take<int32_t>(z.nnz, 4);
-    b.ou = a.take<int32_t>(z.nnz, 4);
-    b.os = a.take<double>(z.nnz, 8);
-    b.op = a.take<double>(z.nnz, 8);
-    b.tot = a.take<unsigned long long>(8);
     return b;
 }
 
@@ -3538,7 +3663,7 @@ static DhSchedBufs dh_sched_layout(DhArena &a, const DhSchedSizes &z)
 // persistent launch per round with the host in between: download the round's PC lists, update the running graph, build the next round's
 // targets and whitelists, upload -- cfg4: ~1.4 ms per round besides the kernel (ten rounds) plus 5 ms before the first one, for nine
 // launches of 1-3 ms each.  Here the state of every target of the schedule is built on the device from the level-0 CSR
-// (dh_mi_init_kernel), the whitelists grow on the device between two launches (dh_wl_append_kernel: interleaved.jl:136-140 kept where a
+// (dh_sched_init_kernel), the whitelists grow on the device between two launches (dh_wl_append_kernel: interleaved.jl:136-140 kept where a
 // later round reads it), and the launches of all rounds are enqueued back to back; the host reads the results once.  Semantics per
 // round are those of fwi_devhiton_run (same kernel, same per-round order and team size).  sched[0 .. nt): the targets in schedule order
 // (learning.jl:97-98); rounds of R targets.  Appends (target, neighbour, statistic, p): a target's entries together, in PC insertion order.
@@ -3551,98 +3676,53 @@ int fwi_devhiton_mi_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     hipStream_t st = c->pb[0].stream;
     const int p = c->P.p;
     const size_t nnz = (size_t)c->nb_off[p];
-    if (R <= 0 || R > nt) R = nt;
-    const int nrounds = (nt + R - 1) / R;
-    // ---- host: per-round order (heaviest first, stable), team sizes, round of every variable ----
-    std::vector<int32_t> order((size_t)nt), round_of((size_t)p, 0x7fffffff);
+    const DhSchedPlan pl(sched, nt, R, p);
+    const int nrounds = pl.nrounds;
+    // ---- host: per-round order and team sizes ----
+    std::vector<int32_t> order((size_t)nt), deg((size_t)nt);
     std::vector<unsigned> team((size_t)nrounds, 0u);
-    std::vector<int32_t> deg((size_t)nt);
-    for (int i = 0; i < nt; ++i) {
-        deg[i] = (int32_t)(c->nb_off[sched[i] + 1] - c->nb_off[sched[i]]);
-        round_of[sched[i]] = i / R;
-    }
+    // (the degrees from an array filled once: read from the level-0 offsets inside the sort's comparison they cost cfg4's 50 020 targets
+    // 0.6 ms of set-up, 0.93 -> 1.56 ms -- the set-up time of FW_TRACE_HOST is where a host regression of this driver shows)
+    for (int i = 0; i < nt; ++i) deg[i] = (int32_t)(c->nb_off[sched[i] + 1] - c->nb_off[sched[i]]);
     for (int r = 0; r < nrounds; ++r) {
-        const int r0 = r * R, r1 = std::min(nt, r0 + R);
-        for (int i = r0; i < r1; ++i) order[i] = i - r0;
-        std::stable_sort(order.begin() + r0, order.begin() + r1, [&](int32_t u, int32_t v) { return deg[r0 + u] > deg[r0 + v]; });
-        team[r] = dh_team_size(order.data() + r0, [&](int32_t i) { return deg[r0 + i]; }, r1 - r0);
+        const int32_t *d = deg.data() + pl.first(r);
+        team[r] = dh_heaviest_first(order.data() + pl.first(r), pl.count(r), [&](int32_t i) { return d[i]; });
     }
     // ---- device arena ----
     DhSchedBufs D;
     if (int rc = dh_arena_reserve(c, c->d_dh[0], dh_sched_layout, DhSchedSizes{(size_t)nt, (size_t)p, nnz, (size_t)nrounds}, &D)) return rc;
-    DhArrays A{};
-    A.cand0 = c->d_cand;
-    A.tpc_key = D.tpc_key;
-    A.pc_key = D.pc_key;
-    A.wl = D.wl;
-    A.wl_cnt = feed_forward ? D.wl_cnt : nullptr;
-    A.acc = D.acc;
-    A.tpc_stat = D.tpc_stat;
-    A.tpc_p = D.tpc_p;
-    A.pc_stat = D.pc_stat;
-    A.pc_p = D.pc_p;
-    A.rej = c->d_rej_run;
-    A.nb_off = c->d_nb_off;
-    A.nb_idx = c->d_nb_idx;
-    A.nb_stat = c->d_nb_stat;
-    A.nb_p = c->d_nb_p;
-    FW_HIP(c, hipMemsetAsync(D.tot, 0, 64, st));
+    DhArrays A = dh_arrays(c, c->d_cand, D.S.lists, DhLevel0{});
+    A.wl_cnt = feed_forward ? D.S.wl_cnt : nullptr;
     FW_HIP(c, hipMemcpyAsync(D.sched, sched, 4 * (size_t)nt, hipMemcpyHostToDevice, st));
     FW_HIP(c, hipMemcpyAsync(D.order, order.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    FW_HIP(c, hipMemcpyAsync(D.round_of, round_of.data(), 4 * (size_t)p, hipMemcpyHostToDevice, st));
-    FW_HIP(c, hipMemsetAsync(D.wl_cnt, 0, 4 * (size_t)p, st));
     FW_HIP(c, hipMemsetAsync(D.mq, 0, sizeof(MiQueue) * (size_t)nrounds, st));
-    hipLaunchKernelGGL(dh_mi_init_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, D.tg, nt, (const int32_t *)D.sched, c->d_nb_off,
-                       (const int32_t *)c->d_levels);
-    const DhParams P = dh_make_params(c, R, 0, 0);
+    if (int rc = dh_sched_begin(c, st, D.S, pl, D.sched, (const int32_t *)c->d_levels, nullptr, 1)) return rc;
+    const DhParams P = dh_make_params(c, pl.R, 0, 0);
     DhEvents E(st, 2, 0);
     if (!E.ok) return fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventCreate failed");
     const double th1 = fwi_now_s();
     FW_HIP(c, hipEventRecord(E.ev[0], st));
     std::vector<unsigned> grids((size_t)nrounds, 0u);
     for (int r = 0; r < nrounds; ++r) {
-        const int r0 = r * R, ntg = std::min(nt, r0 + R) - r0;
+        const int r0 = pl.first(r), ntg = pl.count(r);
         FW_HIP(c, hipMemsetAsync(D.boards, 0, sizeof(MiBoard) * MI_BOARD_CAP, st));  // ready flags, claimed / finished counts
-        grids[r] = dh_mi_launch(c, st, D.tg + r0, ntg, (const int32_t *)(D.order + r0), A, P, team[r], trace_host, D.mq + r, D.boards, D.mres, D.bacc);
-        if (feed_forward && r + 1 < nrounds)
-            hipLaunchKernelGGL(dh_wl_append_kernel, dim3((unsigned)((ntg + 3) / 4)), dim3(256), 0, st, (const DhTgt *)(D.tg + r0), ntg,
-                               (const int32_t *)A.pc_key, (const int32_t *)D.round_of, r, D.wl, c->d_nb_off, D.wl_cnt);
+        grids[r] = dh_mi_launch(c, st, D.S.tg + r0, ntg, (const int32_t *)(D.order + r0), A, P, team[r], trace_host, D.mq + r, D.boards, D.mres, D.bacc);
+        if (feed_forward && r + 1 < nrounds) dh_sched_append(c, st, D.S, D.S.tg + r0, ntg, r);
     }
     FW_HIP(c, hipGetLastError());
     FW_HIP(c, hipEventRecord(E.ev[1], st));
-    // ---- results: packed on the device, one small download ----
-    hipLaunchKernelGGL(dh_sched_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)D.tg, nt, (const int32_t *)A.pc_key,
-                       (const double *)A.pc_stat, (const double *)A.pc_p, D.ot, D.ou, D.os, D.op, D.tot, (double *)(D.tot + 5));
-    FW_HIP(c, hipGetLastError());
+    // ---- results ----
+    if (int rc = dh_sched_pack(c, st, D.S, nt)) return rc;
     std::vector<MiQueue> hq((size_t)nrounds);
-    unsigned long long htot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     FW_HIP(c, hipMemcpyAsync(hq.data(), D.mq, sizeof(MiQueue) * (size_t)nrounds, hipMemcpyDeviceToHost, st));
-    FW_HIP(c, hipMemcpyAsync(htot, D.tot, 64, hipMemcpyDeviceToHost, st));
-    FW_HIP(c, hipStreamSynchronize(st));
+    unsigned long long htot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (int rc = dh_sched_totals(c, st, D.S, htot)) return rc;
     const double th2 = fwi_now_s();
-    for (int r = 0; r < nrounds; ++r)
-        if (int rc = dh_mi_check(c, hq[r], grids[r], r, std::min(nt, r * R + R) - r * R, trace_host)) return rc;
+    for (int r = 0; r < nrounds; ++r)  // (a watchdog leaves targets unfinished: its message first)
+        if (int rc = dh_mi_check(c, hq[r], grids[r], r, pl.count(r), trace_host)) return rc;
     float ms = 0.0f;
     FW_HIP(c, hipEventElapsedTime(&ms, E.ev[0], E.ev[1]));
-    if (htot[4]) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %llu targets did not finish", htot[4]);
-    const size_t nres = (size_t)htot[0], at0 = all.size();
-    if (nres > nnz) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %zu result entries for %zu level-0 entries", nres, nnz);
-    all.resize(at0 + nres);
-    if (nres) {
-        FW_HIP(c, hipMemcpyAsync(all.t.data() + at0, D.ot, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all.u.data() + at0, D.ou, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all.s.data() + at0, D.os, 8 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all.p.data() + at0, D.op, 8 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipStreamSynchronize(st));
-    }
-    c->cnt.cond_tests_ref += (int64_t)htot[1];
-    c->cnt.subsets_calls += (int64_t)htot[2];
-    c->cnt.cond_tests_evaluated += (int64_t)htot[3];
-    {
-        double alg;
-        memcpy(&alg, &htot[5], sizeof(double));
-        c->cnt.alg_bytes_subsets += alg;
-    }
+    if (int rc = dh_sched_finish(c, st, D.S, htot, nnz, all)) return rc;
     c->cnt.t_dev_subsets_s += 1e-3 * (double)ms;
     c->cnt.subsets_launches += nrounds;
     c->cnt.kernel_launches += 2 * nrounds + 1;
@@ -3662,63 +3742,21 @@ struct DhFzSizes {
     int K;
     DhFzChainSizes ch[FW_DH_MAX_CHAINS];
 };
-struct DhFzChainBufs {  // a chain's scratch: reserved once, for its largest round
-    DhGlobal *g;
-    long long *seg0;
-    unsigned long long *win, *win2;
-    unsigned int *sp;
-    int32_t *act;
-    FwSeg *segs;
-    FwSegOut *so;
-    float *tmat;
-};
 struct DhFzBufs {
-    DhTgt *tg;  // every target of the schedule, in slot order
-    int32_t *slot_T, *round_of;
+    DhSchedState S;  // (S.tg: every target of the schedule, in slot order)
+    int32_t *slot_T;
     long long *slot_tm;
-    unsigned int *wl_cnt, *wl_max;  // wl_max: one word per (round, chain)
-    int32_t *tpc_key, *pc_key, *wl, *acc;  // at level-0 offsets
-    double *tpc_stat, *tpc_p, *pc_stat, *pc_p;
-    int32_t *ot, *ou;  // packed results
-    double *os, *op;
-    unsigned long long *tot;
-    DhFzChainBufs ch[FW_DH_MAX_CHAINS];
+    unsigned int *wl_max;                 // one word per (round, chain)
+    DhRoundScratch ch[FW_DH_MAX_CHAINS];  // a chain's scratch: reserved once, for its largest round
 };
 static DhFzBufs dh_fz_layout(DhArena &a, const DhFzSizes &z)
 {
     DhFzBufs b{};
-    b.tg = a.take<DhTgt>(z.nt);
+    b.S = dh_sched_state_layout(a, z.nt, z.p, z.nnz, z.d1);
     b.slot_T = a.take<int32_t>(z.nt);
     b.slot_tm = a.take<long long>(z.nt);
-    b.round_of = a.take<int32_t>(z.p);
-    b.wl_cnt = a.take<unsigned int>(z.p);
     b.wl_max = a.take<unsigned int>(z.nslots);
-    b.tpc_key = a.take<int32_t>(z.nnz, 4);
-    b.pc_key = a.take<int32_t>(z.nnz, 4);
-    b.wl = a.take<int32_t>(z.nnz, 4);
-    b.acc = a.take<int32_t>(2 * z.nnz * z.d1, 4);
-    b.tpc_stat = a.take<double>(z.nnz, 8);
-    b.tpc_p = a.take<double>(z.nnz, 8);
-    b.pc_stat = a.take<double>(z.nnz, 8);
-    b.pc_p = a.take<double>(z.nnz, 8);
-    b.ot = a.take<int32_t>(z.nnz, 4);
-    b.ou = a.take<int32_t>(z.nnz, 4);
-    b.os = a.take<double>(z.nnz, 8);
-    b.op = a.take<double>(z.nnz, 8);
-    b.tot = a.take<unsigned long long>(8);
-    for (int q = 0; q < z.K; ++q) {
-        const DhFzChainSizes &s = z.ch[q];
-        DhFzChainBufs &cb = b.ch[q];
-        cb.g = a.take<DhGlobal>(1);
-        cb.seg0 = a.take<long long>(s.ntg + 1);
-        cb.win = a.take<unsigned long long>(s.ntg + 1);
-        cb.sp = a.take<unsigned int>(s.ntg + 1);
-        cb.win2 = a.take<unsigned long long>(s.ntg + 1);
-        cb.act = a.take<int32_t>(2 * s.ntg);
-        cb.segs = a.take<FwSeg>(s.max_ns);
-        cb.so = a.take<FwSegOut>(s.max_ns);
-        if (s.tm_floats) cb.tmat = a.take<float>(s.tm_floats, 4);
-    }
+    for (int q = 0; q < z.K; ++q) b.ch[q] = dh_scratch_layout(a, z.ch[q].ntg, z.ch[q].max_ns, z.ch[q].tm_floats);
     return b;
 }
 
@@ -3757,12 +3795,12 @@ struct DhFzSlot {
 // graph, one FwDhTarget per target, a thread per chain, dh_build_targets + dh_upload, 66 events made and destroyed, four downloads, one
 // push per result entry and the running graph's update -- 0.8 ms of host time around ~1.1 ms of device rounds in each of cfg3's nine
 // light rounds (profiles/r14_fz_device_schedule.txt).  Here the host computes the layout of every round once (slots: round, chain, index
-// in the chain; same deal and same per-chain policy as the round loop), the state of every target is built on the device
-// (dh_fz_init_kernel), the whitelists grow on the device (dh_wl_append_kernel, sorted at the start of the round that reads them:
-// dh_fz_round_begin_kernel), and the chains' host threads live for the whole schedule.  Level-synchronous as before: a chain starts
-// round r + 1 when every chain has retired round r (DhFzBarrier) and its stream has waited for the other chains' appends (events).
-// Per round and chain the host reads ONE word (the longest whitelist: DhRounds needs the exact bound, see enqueue_batch) besides the
-// batch records.  Results: packed on the device, one download.  sched[0 .. nt): the targets in schedule order, rounds of R.
+// in the chain; the round loop's deal, its per-chain policy and its layout rule: dh_tm_off, dh_max_ns), the state of every target is
+// built on the device (dh_sched_init_kernel), the whitelists grow on the device (dh_wl_append_kernel, sorted at the start of the round
+// that reads them: dh_fz_round_begin_kernel), and the chains' host threads live for the whole schedule.  Level-synchronous as before: a
+// chain starts round r + 1 when every chain has retired round r (DhFzBarrier) and its stream has waited for the other chains' appends
+// (events).  Per round and chain the host reads ONE word (the longest whitelist: DhRounds needs the exact bound, see enqueue_batch)
+// besides the batch records.  Results: packed on the device, one download.  sched[0 .. nt): the targets in schedule order, rounds of R.
 int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, bool feed_forward, FwDirected &all)
 {
     if (nt == 0) return FW_OK;
@@ -3771,21 +3809,20 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     const double th0 = fwi_now_s();
     const int p = c->P.p;
     const size_t nnz = (size_t)c->nb_off[p];
-    if (R <= 0 || R > nt) R = nt;
-    const int nrounds = (nt + R - 1) / R;
+    const DhSchedPlan pl(sched, nt, R, p);
+    const int nrounds = pl.nrounds;
     // ---- host, once: the slots of every round (deal_chains order), their DhTgt offsets and sizes ----
     int K = 1;
-    for (int r = 0; r < nrounds; ++r) K = std::max(K, fwi_chain_count(c, (size_t)(std::min(nt, r * R + R) - r * R)));
+    for (int r = 0; r < nrounds; ++r) K = std::max(K, fwi_chain_count(c, (size_t)pl.count(r)));
     std::vector<DhFzSlot> slots((size_t)nrounds * (size_t)K);
-    std::vector<int32_t> slot_T((size_t)nt), round_of((size_t)p, 0x7fffffff);
-    std::vector<long long> slot_tm((size_t)nt, -1);
+    std::vector<int32_t> slot_T((size_t)nt);
+    std::vector<long long> slot_tm((size_t)nt);
     DhFzSizes z{(size_t)nt, (size_t)p, nnz, 0, (size_t)nrounds * (size_t)K, K, {}};
-    const bool tm_on = c->P.max_k <= 5 && c->d_cor != nullptr;
     {
         std::vector<int> chain_of;
         std::vector<size_t> chain_idx;
         for (int r = 0; r < nrounds; ++r) {
-            const int r0 = r * R, n = std::min(nt, r0 + R) - r0;
+            const int r0 = pl.first(r), n = pl.count(r);
             const int Kr = fwi_chain_count(c, (size_t)n);
             fwi_deal_chains((size_t)n, Kr, chain_of, chain_idx);
             DhFzSlot *s = &slots[(size_t)r * (size_t)K];
@@ -3794,24 +3831,18 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
                 s[q].base = base;
                 base += s[q].ntg;
             }
-            for (int i = 0; i < n; ++i) {
-                slot_T[(size_t)s[chain_of[i]].base + chain_idx[i]] = sched[r0 + i];
-                round_of[sched[r0 + i]] = r;
-            }
+            for (int i = 0; i < n; ++i) slot_T[(size_t)s[chain_of[i]].base + chain_idx[i]] = sched[r0 + i];
             for (int q = 0; q < K; ++q) {
                 if (s[q].ntg == 0) continue;
                 const DhPolicy y = dh_policy(c, s[q].ntg);
                 z.d1 = (size_t)y.spec_depth + 1;
-                for (int t = 0; t < s[q].ntg; ++t) {  // (dh_build_targets)
+                for (int t = 0; t < s[q].ntg; ++t) {
                     const int T = slot_T[(size_t)(s[q].base + t)];
                     const int deg = (int)(c->nb_off[T + 1] - c->nb_off[T]);
                     s[q].max_cap = std::max(s[q].max_cap, deg);
-                    const size_t m = (size_t)deg + 1;
-                    if (!tm_on || y.tm_min <= 0 || deg < y.tm_min || m > 4096 || s[q].tm_floats + m * m > (size_t)1 << 32) continue;
-                    slot_tm[(size_t)(s[q].base + t)] = (long long)s[q].tm_floats;
-                    s[q].tm_floats += m * m;
+                    slot_tm[(size_t)(s[q].base + t)] = dh_tm_off(c, y, deg, s[q].tm_floats);
                 }
-                s[q].max_ns = y.seg_target + (unsigned)s[q].ntg * (unsigned)(1 + DH_MAX_SPEC) + 256u;
+                s[q].max_ns = dh_max_ns(y, s[q].ntg);
                 z.ch[q].ntg = std::max(z.ch[q].ntg, (size_t)s[q].ntg);
                 z.ch[q].max_ns = std::max(z.ch[q].max_ns, (size_t)s[q].max_ns);
                 z.ch[q].tm_floats = std::max(z.ch[q].tm_floats, s[q].tm_floats);
@@ -3831,30 +3862,11 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     hipStream_t st = sts[0];
     DhEvents X(st, 0, 3 * K);  // ev_end[q * 3 + 0 / 1]: chain q's round r (r & 1) and its appends are done; [q * 3 + 2]: the whitelist word
     if (!X.ok) return fw_fail(c, FW_ERR_DEVICE, "device schedule: hipEventCreate failed");
-    DhArrays A{};
-    A.cand0 = c->d_cand;
-    A.tpc_key = D.tpc_key;
-    A.pc_key = D.pc_key;
-    A.acc = D.acc;
-    A.tpc_stat = D.tpc_stat;
-    A.tpc_p = D.tpc_p;
-    A.pc_stat = D.pc_stat;
-    A.pc_p = D.pc_p;
-    A.wl = D.wl;
-    A.nb_off = c->d_nb_off;
-    A.nb_idx = c->d_nb_idx;
-    A.nb_stat = c->d_nb_stat;
-    A.nb_p = c->d_nb_p;
-    A.rej = c->d_rej_run;
-    FW_HIP(c, hipMemsetAsync(D.tot, 0, 64, st));
-    FW_HIP(c, hipMemsetAsync(D.wl_cnt, 0, 4 * (size_t)p, st));
+    const DhArrays A = dh_arrays(c, c->d_cand, D.S.lists, DhLevel0{});  // (tmat: per chain and round)
     FW_HIP(c, hipMemsetAsync(D.wl_max, 0, 4 * z.nslots, st));
     FW_HIP(c, hipMemcpyAsync(D.slot_T, slot_T.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
     FW_HIP(c, hipMemcpyAsync(D.slot_tm, slot_tm.data(), 8 * (size_t)nt, hipMemcpyHostToDevice, st));
-    FW_HIP(c, hipMemcpyAsync(D.round_of, round_of.data(), 4 * (size_t)p, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(dh_fz_init_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, D.tg, nt, (const int32_t *)D.slot_T,
-                       (const long long *)D.slot_tm, c->d_nb_off);
-    FW_HIP(c, hipGetLastError());
+    if (int rc = dh_sched_begin(c, st, D.S, pl, D.slot_T, nullptr, D.slot_tm, 0)) return rc;
     for (int q = 1; q < K; ++q) {  // the other chains' streams start behind the set-up
         FW_HIP(c, hipEventRecord(X.ev_end[(size_t)q * 3], st));
         FW_HIP(c, hipStreamWaitEvent(sts[q], X.ev_end[(size_t)q * 3], 0));
@@ -3876,33 +3888,26 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
         Rn.max_cap = s.max_cap;
         Rn.max_ns = s.max_ns;
         Rn.tm_floats = s.tm_floats;
-        const DhFzChainBufs &cb = D.ch[q];
-        Rn.D.tg = D.tg + s.base;
-        Rn.D.g = cb.g;
-        Rn.D.seg0 = cb.seg0;
-        Rn.D.win = cb.win;
-        Rn.D.win2 = cb.win2;
-        Rn.D.sp = cb.sp;
-        Rn.D.act = cb.act;
-        Rn.D.segs = cb.segs;
-        Rn.D.so = cb.so;
-        Rn.D.tmat = s.tm_floats ? cb.tmat : nullptr;
+        Rn.D.tg = D.S.tg + s.base;
+        Rn.D.s = D.ch[q];
+        if (!s.tm_floats) Rn.D.s.tmat = nullptr;  // (the chain's block is sized for its largest round)
+        const DhRoundScratch &cb = Rn.D.s;
         Rn.A = A;
-        Rn.A.tmat = Rn.D.tmat;
+        Rn.A.tmat = cb.tmat;
         Rn.hg = (DhGlobal *)c->h_dh[q].ptr;
         memset(Rn.hg, 0, 2 * sizeof(DhGlobal));
         unsigned int *h_wl_max = (unsigned int *)((char *)c->h_dh[q].ptr + 3072);
         unsigned int *d_wl_max = D.wl_max + (size_t)r * (size_t)K + (size_t)q;
-        hipLaunchKernelGGL(dh_fz_round_begin_kernel, dim3((unsigned)s.ntg), dim3(256), 0, sq, Rn.D.tg, s.ntg, (const unsigned int *)D.wl_cnt, D.wl,
+        hipLaunchKernelGGL(dh_fz_round_begin_kernel, dim3((unsigned)s.ntg), dim3(256), 0, sq, Rn.D.tg, s.ntg, (const unsigned int *)D.S.wl_cnt, D.S.lists.wl,
                            cb.g, cb.seg0, cb.act, d_wl_max);
         FW_HIP(c, hipGetLastError());
         if (feed_forward && r > 0) {
             FW_HIP(c, hipMemcpyAsync(h_wl_max, d_wl_max, sizeof(unsigned int), hipMemcpyDeviceToHost, sq));
             FW_HIP(c, hipEventRecord(X.ev_end[(size_t)q * 3 + 2], sq));
         }
-        if (Rn.D.tmat) {
+        if (cb.tmat) {
             hipLaunchKernelGGL(dh_tmat_build_kernel, dim3((unsigned)s.ntg, 8u), dim3(256), 0, sq, (const DhTgt *)Rn.D.tg, s.ntg, A.nb_idx,
-                               (const float *)c->d_cor, p, Rn.D.tmat);
+                               (const float *)c->d_cor, p, cb.tmat);
             FW_HIP(c, hipGetLastError());
         }
         Rn.P = dh_make_params(c, s.ntg, Rn.y.spec_depth, Rn.y.spec0_depth);
@@ -3912,18 +3917,12 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
         }
         int rc = DhRounds(Rn, E).run();
         const bool append = !rc && feed_forward && r + 1 < nrounds;
-        {
-            std::lock_guard<std::mutex> lk(dh_cnt_mu);
-            if (Rn.timed_n > 0) c->cnt.t_dev_subsets_s += Rn.timed_s * (double)Rn.launches_n / (double)Rn.timed_n;
-            c->cnt.subsets_launches += Rn.launches_n;
-            // the four kernels of every round of the segment kernel, as in fwi_devhiton_run, and what this round of targets launched
-            // besides: the round-begin kernel, the local matrices and the append where they run
-            c->cnt.kernel_launches += 4 * Rn.launches_n + 1 + (Rn.D.tmat ? 1 : 0) + (append ? 1 : 0);
-        }
+        // besides the kernels of every round of the segment kernel, what this round of targets launches: the round-begin kernel, the
+        // local matrices and the append where they run
+        dh_count_run(Rn, 1 + (cb.tmat ? 1 : 0) + (append ? 1 : 0));
         if (rc) return rc;
-        if (append) {  // interleaved.jl:136-140, kept where a later round reads it
-            hipLaunchKernelGGL(dh_wl_append_kernel, dim3((unsigned)((s.ntg + 3) / 4)), dim3(256), 0, sq, (const DhTgt *)Rn.D.tg, s.ntg,
-                               (const int32_t *)A.pc_key, (const int32_t *)D.round_of, r, D.wl, c->d_nb_off, D.wl_cnt);
+        if (append) {
+            dh_sched_append(c, sq, D.S, Rn.D.tg, s.ntg, r);
             FW_HIP(c, hipGetLastError());
         }
         return FW_OK;
@@ -3950,33 +3949,12 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     }
     if (bar.rc) return bar.rc;
     const double th2 = fwi_now_s();
-    // ---- results: packed on the device, one small download (every chain has retired its last batch: the device is idle) ----
-    hipLaunchKernelGGL(dh_sched_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)D.tg, nt, (const int32_t *)A.pc_key,
-                       (const double *)A.pc_stat, (const double *)A.pc_p, D.ot, D.ou, D.os, D.op, D.tot, (double *)(D.tot + 5));
-    FW_HIP(c, hipGetLastError());
+    // ---- results (every chain has retired its last batch: the device is idle) ----
+    if (int rc = dh_sched_pack(c, st, D.S, nt)) return rc;
     unsigned long long htot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    FW_HIP(c, hipMemcpyAsync(htot, D.tot, 64, hipMemcpyDeviceToHost, st));
-    FW_HIP(c, hipStreamSynchronize(st));
-    if (htot[4]) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %llu targets did not finish", htot[4]);
-    const size_t nres = (size_t)htot[0], at0 = all.size();
-    if (nres > nnz) return fw_fail(c, FW_ERR_DEVICE, "device schedule: %zu result entries for %zu level-0 entries", nres, nnz);
-    all.resize(at0 + nres);
-    if (nres) {  // (pageable destinations: staged copies that may block in the call -- 0.9 ms for cfg3's 3.6 MB, as in fwi_devhiton_mi_schedule)
-        FW_HIP(c, hipMemcpyAsync(all.t.data() + at0, D.ot, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all.u.data() + at0, D.ou, 4 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all.s.data() + at0, D.os, 8 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipMemcpyAsync(all.p.data() + at0, D.op, 8 * nres, hipMemcpyDeviceToHost, st));
-        FW_HIP(c, hipStreamSynchronize(st));
-    }
-    c->cnt.cond_tests_ref += (int64_t)htot[1];
-    c->cnt.subsets_calls += (int64_t)htot[2];
-    c->cnt.cond_tests_evaluated += (int64_t)htot[3];
-    {
-        double alg;
-        memcpy(&alg, &htot[5], sizeof(double));
-        c->cnt.alg_bytes_subsets += alg;
-    }
-    c->cnt.kernel_launches += 2;  // dh_fz_init_kernel, dh_sched_pack_kernel
+    if (int rc = dh_sched_totals(c, st, D.S, htot)) return rc;
+    if (int rc = dh_sched_finish(c, st, D.S, htot, nnz, all)) return rc;
+    c->cnt.kernel_launches += 2;  // dh_sched_init_kernel, dh_sched_pack_kernel
     if (trace_host) {
         fprintf(stderr, "[fw] fz device schedule: %d targets in %d rounds on %d chains, set-up %.2f ms, rounds %.2f ms, results %.2f ms; rounds start at", nt,
                 nrounds, K, 1e3 * (th1 - th0), 1e3 * (th2 - th1), 1e3 * (fwi_now_s() - th2));

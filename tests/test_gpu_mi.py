@@ -385,6 +385,34 @@ def test_whole_schedule_on_the_device_equals_the_per_round_loop_and_oracle(ctx, 
         assert int(np.isnan(exp["pc_weight"]).sum()) > 0
 
 
+def test_whole_schedule_on_the_device_leaves_nothing_behind_for_the_next_call(ctx, monkeypatch):
+    """Two runs of the device schedule (fwi_devhiton_mi_schedule) on one engine, feed-forward rounds of 100 targets: the second network
+    equals the first to the byte.  The schedule's arena is the engine's and is not cleared between calls: whitelist counts, target
+    records, queue records or packed results left over from the first call would show here (tests/test_gpu_fz_sched.py: _run does
+    the same for the Fisher-z schedule, with which this one shares its set-up).  That the schedule is what ran is read off the
+    launch counts: one persistent launch per round, and 2 * rounds + 1 kernels (the launches, the appends between them, init and pack)
+    -- against a third run in ONE round (3 kernels), everything else an lgl call launches being the same in both."""
+    kind, data, n, p = ctx["kind"], ctx["data"], ctx["n"], ctx["p"]
+    monkeypatch.setenv("FW_DEV_MIN_TARGETS", "64")
+    eng = fw.Engine(kind, n, p, max_k=3)
+    eng.set_data(data)
+    first = eng.lgl(feed_forward=True, round_size=100, edge_dict=False)
+    eng.reset_counters()
+    second = eng.lgl(feed_forward=True, round_size=100, edge_dict=False)
+    c100 = eng.counters()
+    eng.reset_counters()
+    eng.lgl(feed_forward=True, round_size=p, edge_dict=False)
+    c1 = eng.counters()
+    eng.close()
+    assert len(first["pc_idx"]) > 0
+    for key in ("pc_off", "pc_idx", "pc_weight", "pc_pval"):
+        assert first[key].tobytes() == second[key].tobytes(), key
+    nrounds = -(-p // 100)
+    print("rounds", nrounds, "subsets_launches", c100["subsets_launches"], c1["subsets_launches"], "kernel_launches", c100["kernel_launches"], c1["kernel_launches"])
+    assert nrounds > 1 and c100["subsets_launches"] == nrounds and c1["subsets_launches"] == 1
+    assert c100["kernel_launches"] - c1["kernel_launches"] == (2 * nrounds + 1) - 3
+
+
 @pytest.mark.parametrize("seq,win0,cmin", [(1, 2, 1), (2, 8, 2), (4, 64, 8)])
 def test_persistent_kernel_boards_equal_oracle(ctx, seq, win0, cmin, monkeypatch):
     """dh_mi_target_kernel with the board machinery forced on for nearly every job (the owner runs `seq` tests alone, then
