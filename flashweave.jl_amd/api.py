@@ -71,7 +71,8 @@ def _sparse_refusals(who, test_name, normalize, prec, device_normalize, meta_dat
         raise ValueError("%s: sparse data with prec=64 is not supported: the Float64 path takes a dense matrix" % who)
     if meta_data is not None:
         raise ValueError("%s: sparse data with meta_data is not supported: append the prepared meta columns to "
-                         "`data` yourself (preprocess.normalize_with_meta)" % who)
+                         "`data` yourself (preprocess.normalize_with_meta), or pass the meta columns inside `data` and mark them "
+                         "with meta_mask" % who)
     if test_name == "fz" and not normalize:
         raise ValueError("%s: sparse data with sensitive=True, heterogeneous=False, normalize=False is not supported: "
                          "the plain fz test needs the dense matrix, pass one" % who)
@@ -90,13 +91,71 @@ def _shape(t):
     return tuple(t[3]) if isinstance(t, CSC) else tuple(t.shape)
 
 
-def _extra_tables(who, data, extra_data, test_name, normalize):
+def _meta_mask_vector(who, meta_mask, meta_data, data):
+    """learn_network's / normalize_data's meta_mask against the table (an array or a sparse table) -> a bool vector, or None when no
+    column is marked (an all-False mask is no mask)."""
+    if meta_mask is None:
+        return None
+    if meta_data is not None:
+        raise ValueError("%s: meta_mask together with meta_data is not supported: meta variables come inside `data` under a "
+                         "meta_mask or as a table of their own, not both" % who)
+    if len(_shape(data)) != 2:
+        raise ValueError("%s: meta_mask needs a samples x variables matrix, got %d dimensions" % (who, len(_shape(data))))
+    m, cols = np.asarray(meta_mask), _shape(data)[1]
+    if m.ndim != 1 or m.size != cols:
+        raise ValueError("%s: meta_mask has %s for the %d columns of data: one entry per column, the meta columns included"
+                         % (who, "%d entries" % m.size if m.ndim == 1 else "%d dimensions" % m.ndim, cols))
+    if m.dtype.kind not in "biuf" or not np.all((m == 0) | (m == 1)):
+        raise ValueError("%s: meta_mask must hold booleans (or 0 / 1), True marking a meta variable" % who)
+    m = m.astype(bool)
+    if m.all():
+        raise ValueError("%s: meta_mask marks every column: no OTU column is left to normalise" % who)
+    return m if m.any() else None
+
+
+def _finite_meta(who, values):
+    if values.dtype.kind not in "biuf":
+        raise ValueError("%s: the columns meta_mask marks must be numbers (got %s); string factors go through meta_data" % (who, values.dtype))
+    if values.dtype.kind == "f" and not np.all(np.isfinite(values)):
+        raise ValueError("%s: a column meta_mask marks holds a non-finite value (NaN or Inf)" % who)
+
+
+def _csc_arrays(data):
+    """A sparse table as it comes -> (colptr, rowval, nzval, (n, p)) without the count check (values, duplicates and order as stored)."""
+    if isinstance(data, (CSC, tuple)):
+        return data[0], data[1], data[2], tuple(int(v) for v in data[3])
+    import scipy.sparse as sp
+    m = sp.csc_matrix(data)
+    return m.indptr, m.indices, m.data, tuple(int(v) for v in m.shape)
+
+
+def _split_meta(who, data, mask, header, test_name):
+    """The table of a normalising run under its meta_mask -> (OTU block, its header, meta block, its header), before anything is checked
+    as a count: the unmarked columns are the count table (a sparse one canonical, _canonical_csc), the marked ones a dense Float64
+    samples x meta-variables matrix (a continuous covariate is not a count).  A sparse table is split on its CSC arrays, O(nnz); only
+    the few meta columns are densified."""
+    otu_header, meta_header = [h for h, m in zip(header, mask) if not m], [h for h, m in zip(header, mask) if m]
+    if not (is_sparse(data) or isinstance(data, CSC)):
+        meta = data[:, mask]
+        _finite_meta(who, meta)
+        return data[:, ~mask], otu_header, meta.astype(np.float64), meta_header
+    colptr, rowval, nzval, (n, p) = _csc_arrays(data)
+    q = int(mask.sum())
+    otu = _canonical_csc(who, pre._csc_take_cols(colptr, rowval, nzval, np.nonzero(~mask)[0]) + ((n, p - q),), test_name, True)
+    meta = as_csc(pre._csc_take_cols(colptr, rowval, nzval, np.nonzero(mask)[0]) + ((n, q),), np.float64)
+    _finite_meta(who, meta.nzval)
+    return otu, otu_header, pre._csc_to_dense(meta.colptr, meta.rowval, meta.nzval, n), meta_header
+
+
+def _extra_tables(who, data, extra_data, test_name, normalize, n_named=None):
     """Checks learn_network's / normalize_data's extra_data against the main table (an array or what as_csc returned) before anything
     reaches a device -> [(table, header)] in the caller's order, sparse tables canonical.  A missing header is numbered on from the
-    main table's columns, as the reference does (learning.jl:506-520)."""
+    main table's columns (n_named when the meta columns have been split off `data` already), as the reference does
+    (learning.jl:506-520)."""
     if extra_data is None:
         return []
-    sparse, (n, n_named) = isinstance(data, CSC), _shape(data)
+    sparse, (n, cols) = isinstance(data, CSC), _shape(data)
+    n_named = cols if n_named is None else n_named
     if not isinstance(extra_data, (list, tuple)):
         raise ValueError("%s: extra_data must be a list of (table, header) pairs, got %s" % (who, type(extra_data).__name__))
     out = []
@@ -155,7 +214,7 @@ def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, ma
 
 
 def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
-                   device_normalize=True, device=0):
+                   device_normalize=True, device=0, meta_mask=None):
     """normalize_data (preprocessing.jl:660-701), both forms: what learn_network(normalize=True) does to its tables, as a function of
     its own.  data: samples x OTUs counts (array or scipy.sparse); extra_data: a list of (table, header) pairs, count tables of further
     sequencing experiments on the same samples.  Every table is normalised on its own for `test_name` ("fz" clr_adapt, "fz_nz" clr_nz,
@@ -163,6 +222,9 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
     columns laid out as [last extra, ..., first extra, data (+ meta columns)] (preprocess.combine_data).  All tables take one
     front-end: the device one (integral counts, prec == 32, device_normalize) or, if any table is not integral, the host one.  Sparse
     tables need the device front-end and are refused with what learn_network refuses them with; sparse and dense do not mix.
+    meta_mask: one boolean (or 0 / 1) per column of `data`, True marking a meta variable that sits inside the table, dense or sparse
+    (see learn_network): the unmarked columns are normalised as the count table, the marked ones prepared like a numeric meta_data
+    and appended last; `header` names all columns.
     -> dict(data, header, meta_mask, row_mask): row_mask over the input samples, data a scipy.sparse.csc_matrix for sparse tables
     (dense for "fz")."""
     who = "normalize_data"
@@ -170,23 +232,30 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
         raise ValueError("%s: unsupported test_name %r" % (who, test_name))
     if prec not in (32, 64):
         raise ValueError("%s: prec=%r is not supported (32 or 64)" % (who, prec))
-    if is_sparse(data) or isinstance(data, CSC):
+    sparse = is_sparse(data) or isinstance(data, CSC)
+    data = data if sparse else np.asarray(data)
+    mask = _meta_mask_vector(who, meta_mask, meta_data, data)
+    if sparse:
         _sparse_refusals(who, test_name, True, prec, device_normalize, meta_data)
-        data = _canonical_csc(who, data, test_name, True)
-    else:
-        data = np.asarray(data)
-    extra = _extra_tables(who, data, extra_data, test_name, True)
+    if mask is None:
+        data = _canonical_csc(who, data, test_name, True) if sparse else data
+        extra = _extra_tables(who, data, extra_data, test_name, True)
+    cols = _shape(data)[1]
     if header is None:
-        header = ["X%d" % (i + 1) for i in range(_shape(data)[1])]
-    elif len(header) != _shape(data)[1]:
-        raise ValueError("%s: a header of %d names for %d columns" % (who, len(header), _shape(data)[1]))
+        header = ["X%d" % (i + 1) for i in range(cols)]
+    elif len(header) != cols:
+        raise ValueError("%s: a header of %d names for %d columns" % (who, len(header), cols))
+    if mask is not None:  # the meta columns leave the table before anything is checked as a count and return prepared, at its end
+        data, header, meta_data, meta_header = _split_meta(who, data, mask, list(header), test_name)
+        make_onehot = False  # (numbers: nothing to encode)
+        extra = _extra_tables(who, data, extra_data, test_name, True, n_named=cols)
     return _normalize_tables(data, list(header), extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device)[0]
 
 
 def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
                   meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
-                  no_red_tests=True, track_rejections=False, csc_resident=False, extra_data=None, transposed=False, **unsupported):
+                  no_red_tests=True, track_rejections=False, csc_resident=False, extra_data=None, transposed=False, meta_mask=None, **unsupported):
     """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False); a numpy array or a scipy.sparse
     matrix.  A sparse table stays sparse end to end (what the reference does with make_sparse, learning.jl:470): normalize=True runs
     the device CSC front-end (integer counts only) and the sparse upload, normalize=False uploads the matrix as it is (Int32 levels
@@ -232,6 +301,21 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     front-end (if any table is not integral, all take the host one).  A table with another number of rows, a header of another length,
     a sparse / dense mix and an entry that is no pair raise ValueError naming extra_data before any device call.
     counters["n_tables"] and parameters["extra_data"] record the count; t_normalize_s covers all tables.
+    meta_mask (learning.jl:468,502-504, preprocessing.jl:425-446,527-558): meta variables inside `data` -- one boolean (or 0 / 1) per
+    column, True marking a meta variable, anywhere in the table; `header`, when given, names all columns.  This is the form a sparse
+    table carries its meta variables in, and the form a prepared matrix carries its mask in.  normalize=True: the unmarked columns
+    are the count table, normalised exactly as without a mask (one front-end per run, chosen by the OTU block alone); the marked
+    columns get what a numeric meta_data gets (they follow the row mask, continuous ones are discretised into 2 bins for mi / mi_nz,
+    columns holding a zero are shifted by +1 for fz_nz, zero-variance ones are dropped) and come LAST: [kept OTU columns, kept meta
+    columns], variable_ids and meta_variable_mask to match.  A sparse table is split on its CSC arrays before the count check (a
+    continuous covariate is no count), the few meta columns alone are densified on the host, and the result stays CSC (Int32 levels,
+    a zero level absent; Float32 for fz_nz); csc_resident=True works on it as on any sparse table.  normalize=False: the matrix is
+    taken as it is, dense or sparse, columns neither reordered nor filtered, and the mask goes into meta_variable_mask.  With
+    extra_data the mask belongs to the main table.  The marked columns are numbers, so make_onehot has nothing to encode: string
+    factors keep going through meta_data (dense tables only).  meta_mask with meta_data, with the path form (files bring
+    meta_data_path), of another length than the table has columns, with entries other than booleans or 0 / 1, marking every column,
+    or marking a column with a non-finite value raises ValueError naming meta_mask before any device call; an all-False mask is no
+    mask.  parameters["meta_mask"] records the number of marked columns.
     Path form (learning.jl:354-401): data may be a path (str / os.PathLike) or a list of paths, read with io.load_data (.tsv, .csv,
     BIOM 1.0 JSON; anything else raises what load_data raises): the first is the main table, the others become extra_data under their
     file headers; meta_data_path (second positional argument, as in the reference) is the main table's meta data file;
@@ -254,6 +338,9 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
             raise TypeError("learn_network: meta_data_path must be a path, got %s (options are keywords)" % type(meta_data_path).__name__)
         if header is not None or meta_data is not None or meta_header is not None:
             raise ValueError("learn_network: header, meta_data and meta_header come from the files in the path form")
+        if meta_mask is not None:
+            raise ValueError("learn_network: meta_mask goes with an array or a sparse matrix; in the path form the meta variables come "
+                             "from meta_data_path")
         data, header, meta_data, meta_header, from_files = _load_paths(paths, meta_data_path, transposed)
         extra_data = from_files + list(extra_data or []) if (from_files or extra_data is not None) else None
     test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
@@ -281,22 +368,37 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
                       "running with recursive_pcor=False (conditional tests from the data)", stacklevel=2)
         recursive_pcor = False
     sparse = is_sparse(data)
+    data = data if sparse else np.asarray(data)
+    mask = _meta_mask_vector("learn_network", meta_mask, meta_data, data)
     if sparse:
         # a sparse table stays sparse from here to the device (fw_normalize_counts_csc, fw_set_data_csc_*); what would need the dense
         # matrix is refused by name before any device call -- densifying silently would defeat the point
         _sparse_refusals("learn_network", test_name, normalize, prec, device_normalize, meta_data)
-        data = _canonical_csc("learn_network", data, test_name, normalize)
+    n_marked = 0 if mask is None else int(mask.sum())
+    if mask is not None and header is not None and len(header) != _shape(data)[1]:
+        raise ValueError("learn_network: a header of %d names for %d columns: with a meta_mask the header names all columns of data, "
+                         "the meta ones included" % (len(header), _shape(data)[1]))
+    if mask is None or not normalize:
+        data = _canonical_csc("learn_network", data, test_name, normalize) if sparse else data
+        if mask is not None:  # the prepared matrix is taken as it is; its marked columns are only looked at
+            _finite_meta("learn_network", pre._csc_take_cols(*data[:3], np.nonzero(mask)[0])[2] if sparse else data[:, mask])
+        extra = _extra_tables("learn_network", data, extra_data, test_name, normalize)  # (refused by name before any device call)
+        if header is None:
+            header = ["X%d" % (i + 1) for i in range(_shape(data)[1])]
     else:
-        data = np.asarray(data)
-    extra = _extra_tables("learn_network", data, extra_data, test_name, normalize)  # (refused by name before any device call)
-    if header is None:
-        header = ["X%d" % (i + 1) for i in range(_shape(data)[1])]
-    meta_mask = None
+        # normalize=True: the meta columns leave the table before anything is checked as a count -- a continuous covariate is no
+        # count -- and come back prepared, at its end (preprocessing.jl:425-446,527-558); from here on they are a numeric meta_data
+        cols = _shape(data)[1]
+        data, header, meta_data, meta_header = _split_meta("learn_network", data, mask, list(header) if header is not None else
+                                                           ["X%d" % (i + 1) for i in range(cols)], test_name)
+        make_onehot = False  # (numbers: nothing to encode)
+        extra = _extra_tables("learn_network", data, extra_data, test_name, normalize, n_named=cols)
+    meta_mask = None if mask is None else [bool(v) for v in mask]  # (normalize=False keeps it; normalize=True returns its own)
     if meta_data is not None and not normalize:
         # the reference appends the meta columns as they are and keeps their mask (learning.jl:500-520); here an already
         # normalised matrix must already hold them -- silently dropping the argument would lose the mask
         raise ValueError("learn_network: meta_data with normalize=False is not supported: append the prepared meta columns to "
-                         "`data` yourself (preprocess.normalize_with_meta) or pass normalize=True")
+                         "`data` yourself (preprocess.normalize_with_meta) and mark them with meta_mask, or pass normalize=True")
     t_norm0 = time.perf_counter()
     on_device = False
     if normalize:
@@ -306,8 +408,9 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     elif extra:
         # already normalised tables are only laid side by side (learning.jl:537-541): no filter, no alignment, extra tables first
         everyone = np.ones(_shape(data)[0], dtype=bool)
-        mat, header, _, _ = pre.combine_data([t for t, _ in extra] + [data], [h for _, h in extra] + [header],
-                                             [None] * (len(extra) + 1), [everyone] * (len(extra) + 1))
+        mat, header, combined_mask, _ = pre.combine_data([t for t, _ in extra] + [data], [h for _, h in extra] + [header],
+                                                         [None] * len(extra) + [mask], [everyone] * (len(extra) + 1))
+        meta_mask = None if mask is None else [bool(v) for v in combined_mask]
     elif sparse:
         mat = tuple(data[:3])  # the prepared matrix as it is: Int32 CSC for mi / mi_nz, Float32 CSC for fz_nz
     else:
@@ -339,7 +442,7 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,
                                     recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
                                     no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections), prec=eng_prec,
-                                    csc_resident=csc_resident, extra_data=len(extra),
+                                    csc_resident=csc_resident, extra_data=len(extra), meta_mask=n_marked,
                                     schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
                                               else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
                                               else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),

@@ -119,17 +119,12 @@ def discretize(x, n_bins):
     return np.floor(r / step)
 
 
-def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_header=None, make_onehot=True, normalizer=None):
-    """preprocess_data with a meta_mask (preprocessing.jl:412-563): OTU columns are normalised as in normalize(); meta
-    variables are one-hot encoded, follow the row filters, are discretised into 2 bins for the discrete tests when they look
-    continuous, are shifted by +1 for "fz_nz" if they hold zeros (zeros mean "absent" there), lose zero-variance columns
-    and are appended.  -> dict(data, header, meta_mask, row_mask)"""
-    if make_onehot:
-        md, mh = onehot(meta, meta_header)
-    else:
-        md, mh = np.asarray(meta, dtype=np.float64), list(meta_header or [""] * np.asarray(meta).shape[1])
-    # normalizer: the OTU part on the device (engine.normalize_counts); the handful of meta columns stay here
-    data, row_mask, col_mask = normalizer(counts, test_name) if normalizer is not None else normalize(counts, test_name, prec=prec)
+def prepare_meta_block(md, mh, test_name, row_mask):
+    """What preprocess_data does to the meta block (preprocessing.jl:527-558), for both ways the block arrives (a meta_data table,
+    or the columns a meta_mask marks in `data`): md, a samples x meta-variables Float64 matrix, follows the row mask of the OTU
+    normalisation; columns that look continuous are discretised into 2 bins for the discrete tests; columns holding a zero are shifted
+    by +1 for "fz_nz" (zeros mean "absent" there); zero-variance columns are dropped.  The caller's matrix is left alone.
+    -> (Float64 matrix, names)"""
     md = md[row_mask]
     if test_name in ("mi", "mi_nz"):
         for j in range(md.shape[1]):
@@ -140,12 +135,32 @@ def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_head
             if (md[:, j] == 0).any():
                 md[:, j] += 1
     keep = np.var(md, axis=0) > 0.0
-    md, mh = md[:, keep], [h for h, k in zip(mh, keep) if k]
-    out = np.concatenate([data, md.astype(data.dtype)], axis=1)
+    return md[:, keep], [h for h, k in zip(mh, keep) if k]
+
+
+def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_header=None, make_onehot=True, normalizer=None):
+    """preprocess_data with a meta_mask (preprocessing.jl:412-563): OTU columns are normalised as in normalize(); meta
+    variables are one-hot encoded, follow the row filters, are discretised into 2 bins for the discrete tests when they look
+    continuous, are shifted by +1 for "fz_nz" if they hold zeros (zeros mean "absent" there), lose zero-variance columns
+    and are appended.  A normalizer that hands back a CSC table (the device front-end on a sparse count table) gets the meta block
+    appended in CSC form as well: Int32 levels / Float32 values, a zero is an absent entry, the OTU part's stored zeros stay stored.
+    -> dict(data, header, meta_mask, row_mask)"""
+    if make_onehot:
+        md, mh = onehot(meta, meta_header)
+    else:
+        md, mh = np.asarray(meta, dtype=np.float64), list(meta_header or [""] * np.asarray(meta).shape[1])
+    # normalizer: the OTU part on the device (engine.normalize_counts); the handful of meta columns stay here
+    data, row_mask, col_mask = normalizer(counts, test_name) if normalizer is not None else normalize(counts, test_name, prec=prec)
+    md, mh = prepare_meta_block(md, mh, test_name, row_mask)
+    if _is_csc(data):
+        *otu, rows = _csc_parts(data)
+        out = _csc_hstack([tuple(otu), _csc_from_dense(md.astype(otu[2].dtype))], int(row_mask.sum()) if rows is None else rows)
+    else:
+        out = np.concatenate([data, md.astype(data.dtype)], axis=1)
     hdr = None
     if header is not None:
         hdr = [h for h, k in zip(header, col_mask) if k] + mh
-    return dict(data=out, header=hdr, meta_header=mh, meta_mask=np.r_[np.zeros(data.shape[1], bool), np.ones(md.shape[1], bool)],
+    return dict(data=out, header=hdr, meta_header=mh, meta_mask=np.r_[np.zeros(out.shape[1] - md.shape[1], bool), np.ones(md.shape[1], bool)],
                 row_mask=row_mask)
 
 
@@ -208,6 +223,48 @@ def _csc_take_rows(colptr, rowval, nzval, keep):
     return upto[colptr], newrow[rowval[sel]], nzval[sel]
 
 
+def _csc_take_cols(colptr, rowval, nzval, cols):
+    """Columns `cols` (ascending indices) of a CSC triple, in that order; O(nnz), the entries of a column stay as they are stored
+    (order, duplicates, stored zeros).  How a meta_mask splits a sparse table into its OTU block and its meta block."""
+    colptr, rowval, nzval = np.asarray(colptr, dtype=np.int64), np.asarray(rowval), np.asarray(nzval)
+    cols = np.asarray(cols, dtype=np.int64)
+    lens = colptr[cols + 1] - colptr[cols]
+    upto = np.concatenate(([0], np.cumsum(lens, dtype=np.int64)))
+    src = np.repeat(colptr[cols] - upto[:-1], lens) + np.arange(upto[-1], dtype=np.int64)  # position k of the output reads src[k]
+    return upto, rowval[src], nzval[src]
+
+
+def _csc_to_dense(colptr, rowval, nzval, n):
+    """A canonical CSC triple (no duplicates) as an n x q Float64 matrix, by a scatter of its own: for the few meta columns only (the
+    reference's discretize_meta! densifies them, too) -- a table's OTU block never comes here."""
+    q = len(colptr) - 1
+    out = np.zeros((n, q), dtype=np.float64)
+    out[np.asarray(rowval, dtype=np.int64), np.repeat(np.arange(q), np.diff(colptr))] = nzval
+    return out
+
+
+def _csc_from_dense(block):
+    """A dense n x q block -> CSC triple of the block's dtype; a zero is an absent entry, rows ascending within a column."""
+    cols, rows = np.nonzero(block.T)
+    colptr = np.concatenate(([0], np.cumsum(np.bincount(cols, minlength=block.shape[1]), dtype=np.int64)))
+    return colptr, rows, block[rows, cols]
+
+
+def _csc_hstack(parts, n):
+    """CSC triples over the same n rows, side by side -> scipy.sparse.csc_matrix assembled field by field (the constructor would
+    re-check and could drop the stored 0.0f of clr_nz)."""
+    import scipy.sparse as sp
+    parts = [(np.asarray(c, dtype=np.int64), r, v) for c, r, v in parts]
+    nnz = [int(c[-1]) for c, _, _ in parts]
+    offs = np.concatenate(([0], np.cumsum(nnz)))
+    colptr = np.concatenate([parts[0][0][:1]] + [c[1:] + o for (c, _, _), o in zip(parts, offs)])
+    nzval = np.concatenate([v for _, _, v in parts])
+    idx = np.int32 if max(n, len(colptr), int(offs[-1])) < 2**31 else np.int64  # (one index type, as scipy keeps it)
+    out = sp.csc_matrix((n, len(colptr) - 1), dtype=nzval.dtype)
+    out.indptr, out.indices, out.data = colptr.astype(idx), np.concatenate([r for _, r, _ in parts]).astype(idx), nzval
+    return out
+
+
 def combine_data(tables, headers, meta_masks, row_masks):
     """combine_data (preprocessing.jl:596-635): column-wise union of several normalised tables of the same n samples.
     tables[-1] is the main table (meta columns appended already), tables[:-1] the extra ones in the caller's order; row_masks[i] is
@@ -255,12 +312,4 @@ def combine_data(tables, headers, meta_masks, row_masks):
     meta_mask = np.concatenate(meta_mask)
     if not sparse[0]:
         return np.concatenate(parts, axis=1), header, meta_mask, common
-    import scipy.sparse as sp
-    n, nnz = int(common.sum()), [int(c[-1]) for c, _, _ in parts]
-    offs = np.concatenate(([0], np.cumsum(nnz)))
-    colptr = np.concatenate([parts[0][0][:1]] + [c[1:] + o for (c, _, _), o in zip(parts, offs)])
-    nzval = np.concatenate([v for _, _, v in parts])
-    idx = np.int32 if max(n, len(colptr), int(offs[-1])) < 2**31 else np.int64  # (one index type, as scipy keeps it)
-    out = sp.csc_matrix((n, len(colptr) - 1), dtype=nzval.dtype)
-    out.indptr, out.indices, out.data = colptr.astype(idx), np.concatenate([r for _, r, _ in parts]).astype(idx), nzval
-    return out, header, meta_mask, common
+    return _csc_hstack(parts, int(common.sum())), header, meta_mask, common

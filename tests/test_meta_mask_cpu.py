@@ -1,0 +1,356 @@
+"""learn_network(meta_mask=...) / normalize_data(meta_mask=...), the parts that need no device: the mask form against the meta_data
+form it must equal (preprocess.normalize_with_meta on the OTU block and the meta block), the sparse split with the device front-end
+replaced by a host stand-in, every refusal (all raised before any device call), normalize=False, extra_data and the .gml round trip.
+All comparisons are exact: both sides run the same front-end on the same bytes.  The table is tests/meta_mask_table.py."""
+import inspect
+import os
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import flashweave_jl_amd as fw
+from flashweave_jl_amd import io as fio
+from flashweave_jl_amd import preprocess as pre
+from flashweave_jl_amd.engine import CSC
+from tests.meta_mask_table import META_NAMES, edge_kinds, oracle_network, table
+from tests.util import GOLDEN
+
+KINDS = ["fz", "fz_nz", "mi", "mi_nz"]
+
+
+def _scatter(colptr, rowval, nzval, shape):
+    """a CSC triple as a dense matrix, without scipy's toarray (test_the_split_never_densifies_the_table patches that to raise)"""
+    out = np.zeros(shape, dtype=np.asarray(nzval).dtype)
+    out[np.asarray(rowval), np.repeat(np.arange(shape[1]), np.diff(colptr))] = nzval
+    return out
+
+
+def _host_stand_in(counts, test_name, device=0):
+    """engine.normalize_counts on the host: preprocess.normalize + the CSC conversion of the device front-end -- an entry per present
+    count, so the clr_nz value 0.0f of a sample's only OTU is a STORED zero.  Sparse tables only (what the tests below hand it)."""
+    assert isinstance(counts, CSC) and counts.nzval.dtype == np.int32, "the OTU block must arrive as canonical Int32 counts"
+    dense = _scatter(*counts)
+    data, row_mask, col_mask = pre.normalize(dense, test_name)
+    if test_name == "fz":
+        return data, row_mask, col_mask
+    data = data.astype(np.float32 if test_name == "fz_nz" else np.int32)
+    present = dense[row_mask][:, col_mask] != 0 if test_name == "fz_nz" else data != 0
+    cols, rows = np.nonzero(present.T)
+    out = sp.csc_matrix(data.shape, dtype=data.dtype)
+    out.indptr = np.concatenate(([0], np.cumsum(np.bincount(cols, minlength=data.shape[1])))).astype(np.int32)
+    out.indices, out.data = rows.astype(np.int32), data[rows, cols]
+    return out, row_mask, col_mask
+
+
+def _no_device(monkeypatch):
+    def no_device(*a, **k):
+        raise AssertionError("a device call was made before the refusal")
+    monkeypatch.setattr(fw.api, "Engine", no_device)
+    monkeypatch.setattr(fw.api, "normalize_counts", no_device)
+
+
+class _FakeEngine:
+    """records what learn_network hands the engine; returns the edges the test planted"""
+    seen, edges = [], {}
+
+    def __init__(self, test_name, n, p, **kw):
+        self.L, self.shape, self.data = object(), (n, p), None
+        _FakeEngine.seen.append(self)
+
+    def set_data(self, data, csc_resident=False):
+        self.data = data
+
+    def compute_cor(self):
+        pass
+
+    def lgl(self, **kw):
+        return dict(edges=dict(_FakeEngine.edges), rejections={})
+
+    def counters(self):
+        return {}
+
+    def close(self):
+        pass
+
+
+@pytest.fixture
+def fake_engine(monkeypatch):
+    _FakeEngine.seen, _FakeEngine.edges = [], {}
+    monkeypatch.setattr(fw.api, "Engine", _FakeEngine)
+    return _FakeEngine
+
+
+def test_the_keyword_exists():
+    """On the parent commit meta_mask falls into **unsupported and raises TypeError: the test that fails without the feature."""
+    for f in (fw.learn_network, fw.normalize_data):
+        assert inspect.signature(f).parameters["meta_mask"].default is None
+    full, mask, header, _, _ = table()
+    try:
+        fw.learn_network(full, meta_mask=mask, device_normalize=False)
+    except TypeError as e:  # the parent: "unsupported options ['meta_mask']"
+        pytest.fail("learn_network does not take meta_mask: %s" % e)
+    except fw.FlashWeaveError:
+        pass  # no device here: the table was split, normalised and put together, and the engine said what is missing
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_table_makes_the_gpu_tests_mean_something(kind):
+    """The condition on the inputs: the oracle's network of the matrix the existing meta_data path normalises holds an edge with a meta
+    endpoint and an edge between OTUs, in every mode at max_k = 2; and the table is what the tests say it is."""
+    full, mask, header, counts, meta = table()
+    assert full.shape == (200, 52) and np.nonzero(mask)[0].tolist() == [3, 17, 30, 51] and [header[j] for j in (3, 17, 30, 51)] == META_NAMES
+    assert 0.30 < (counts == 0).mean() < 0.37 and (counts[0] != 0).sum() == 1 and (counts.sum(axis=1) > 0).all()
+    assert set(np.unique(meta[:, 0])) == {0.0, 1.0} and np.any(meta[:, 1] != np.floor(meta[:, 1]))
+    assert set(np.unique(meta[:, 2])) == {0.0, 1.0, 2.0, 3.0} and np.ptp(meta[:, 3]) == 0
+    r = pre.normalize_with_meta(counts, kind, meta)
+    with_meta, between_otus = edge_kinds(oracle_network(kind, r["data"]), r["meta_mask"])
+    print(kind, "edges with a meta endpoint", with_meta, "between OTUs", between_otus)
+    assert with_meta >= 1 and between_otus >= 1
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_dense_mask_form_is_the_meta_data_form(kind):
+    full, mask, header, counts, meta = table()
+    got = fw.normalize_data(full, test_name=kind, header=header, meta_mask=mask, device_normalize=False)
+    exp = pre.normalize_with_meta(counts, kind, meta, header=[h for h, m in zip(header, mask) if not m], meta_header=META_NAMES)
+    assert got["data"].dtype == exp["data"].dtype and got["data"].shape == exp["data"].shape
+    assert got["data"].tobytes() == exp["data"].tobytes()
+    assert got["header"] == exp["header"] and got["header"][-3:] == META_NAMES[:3]  # the constant column is gone, the meta columns last
+    assert np.array_equal(got["meta_mask"], exp["meta_mask"]) and got["meta_mask"].sum() == 3 and got["meta_mask"][-3:].all()
+    assert np.array_equal(got["row_mask"], exp["row_mask"])
+    # 0 / 1 and a list are masks too; without a header the columns are numbered over the whole table
+    again = fw.normalize_data(full, test_name=kind, meta_mask=[int(m) for m in mask], device_normalize=False)
+    assert again["data"].tobytes() == exp["data"].tobytes() and again["header"][-3:] == ["X4", "X18", "X31"] and again["header"][3] == "X5"
+    # an all-False mask is no mask
+    none = fw.normalize_data(counts, test_name=kind, meta_mask=np.zeros(counts.shape[1], bool), device_normalize=False)
+    plain = fw.normalize_data(counts, test_name=kind, device_normalize=False)
+    assert none["data"].tobytes() == plain["data"].tobytes() and none["header"] == plain["header"] and not none["meta_mask"].any()
+
+
+def _parent_normalize_with_meta(counts, test_name, meta, meta_header):
+    """the meta-block step as normalize_with_meta had it inline before prepare_meta_block was factored out"""
+    md, mh = pre.onehot(meta, meta_header)
+    data, row_mask, col_mask = pre.normalize(counts, test_name)
+    md = md[row_mask]
+    if test_name in ("mi", "mi_nz"):
+        for j in range(md.shape[1]):
+            if pre.is_continuous_vec(md[:, j]):
+                md[:, j] = pre.discretize(md[:, j], 2)
+    if test_name == "fz_nz":
+        for j in range(md.shape[1]):
+            if (md[:, j] == 0).any():
+                md[:, j] += 1
+    keep = np.var(md, axis=0) > 0.0
+    md, mh = md[:, keep], [h for h, k in zip(mh, keep) if k]
+    return np.concatenate([data, md.astype(data.dtype)], axis=1), mh, row_mask
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_normalize_with_meta_on_the_fixtures_is_unchanged(kind):
+    rows = [ln.rstrip("\n").split("\t") for ln in open(os.path.join(GOLDEN, "HMP_SRA_gut_tiny.tsv"))]
+    header, counts = rows[0], np.array(rows[1:], dtype=np.float64)
+    mrows = [ln.rstrip("\n").split("\t") for ln in open(os.path.join(GOLDEN, "HMP_SRA_gut_tiny_meta_oneHotTest.tsv"))]
+    mheader, meta = mrows[0], np.empty((len(mrows) - 1, len(mrows[0])), dtype=object)
+    for i, r in enumerate(mrows[1:]):
+        for j, v in enumerate(r):
+            try:
+                meta[i, j] = float(v)
+            except ValueError:
+                meta[i, j] = v
+    eheader = open(os.path.join(GOLDEN, "meta_tiny_oneHotTest.tsv")).readline().rstrip("\n").split("\t")
+    got = pre.normalize_with_meta(counts, kind, meta, header=header, meta_header=mheader)
+    exp_data, exp_mh, exp_rows = _parent_normalize_with_meta(counts, kind, meta, mheader)
+    assert got["data"].dtype == exp_data.dtype and got["data"].tobytes() == exp_data.tobytes()
+    assert got["meta_header"] == exp_mh == eheader and np.array_equal(got["row_mask"], exp_rows)
+    assert got["meta_mask"].tolist() == [False] * (exp_data.shape[1] - len(exp_mh)) + [True] * len(exp_mh)
+    assert got["header"][-len(exp_mh):] == exp_mh and len(got["header"]) == exp_data.shape[1]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("form", ["csc", "csr", "coo"])
+def test_sparse_mask_form_equals_the_dense_one(kind, form, monkeypatch):
+    monkeypatch.setattr(fw.api, "normalize_counts", _host_stand_in)
+    full, mask, header, counts, meta = table()
+    dense = fw.normalize_data(full, test_name=kind, header=header, meta_mask=mask, device_normalize=False)
+    # the table holds the non-integral covariate: only a split BEFORE the count check lets it through
+    got = fw.normalize_data(getattr(sp, form + "_matrix")(full), test_name=kind, header=header, meta_mask=mask)
+    assert got["header"] == dense["header"] and np.array_equal(got["meta_mask"], dense["meta_mask"])
+    assert np.array_equal(got["row_mask"], dense["row_mask"])
+    if kind == "fz":
+        assert isinstance(got["data"], np.ndarray) and got["data"].tobytes() == dense["data"].tobytes()
+        return
+    m = got["data"]
+    assert sp.issparse(m) and m.format == "csc" and m.dtype == (np.float32 if kind == "fz_nz" else np.int32)
+    assert m.indptr.dtype == m.indices.dtype and m.has_sorted_indices
+    assert m.toarray().tobytes() == np.ascontiguousarray(dense["data"].astype(m.dtype)).tobytes()
+    if kind == "fz_nz":
+        # the sample with one OTU: clr_nz gives log(x / x) = 0.0f, a present count -- stored, in the OTU part, after the append
+        col = got["header"].index("otu5")
+        run = slice(m.indptr[col], m.indptr[col + 1])
+        at = np.nonzero(m.indices[run] == 0)[0]
+        assert at.size == 1 and m.data[run][at[0]] == 0.0 and m.indptr[1] - m.indptr[0] < 200  # (stored, and not because all cells are)
+        # the shifted meta columns hold no zero: every sample is stored; hab 0 / 1 became 1 / 2
+        hab = got["header"].index("hab")
+        assert m.indptr[hab + 1] - m.indptr[hab] == 200 and set(np.unique(m.data[m.indptr[hab]:m.indptr[hab + 1]])) == {1.0, 2.0}
+    else:
+        assert np.all(m.data != 0)  # a zero level is an absent entry, in the OTU part and in the meta part
+
+
+@pytest.mark.parametrize("kind", ["fz_nz", "mi_nz"])
+def test_the_split_never_densifies_the_table(kind, monkeypatch):
+    """scipy's toarray / todense raise for the whole run.  The q meta columns are densified by a scatter of the library's own
+    (preprocess._csc_to_dense), so the patch is not lifted for them either; the stand-in front-end scatters as well."""
+    monkeypatch.setattr(fw.api, "normalize_counts", _host_stand_in)
+    full, mask, header, _, _ = table()
+    exp = fw.normalize_data(sp.csc_matrix(full), test_name=kind, header=header, meta_mask=mask)
+
+    def boom(self, *a, **k):
+        raise AssertionError("the sparse table was densified")
+    for name in ("csc_matrix", "csr_matrix", "coo_matrix", "csc_array", "csr_array", "coo_array"):
+        for method in ("toarray", "todense"):
+            monkeypatch.setattr(getattr(sp, name), method, boom)
+    with pytest.raises(AssertionError, match="densified"):
+        sp.csc_matrix(full).toarray()
+    got = fw.normalize_data(sp.csr_matrix(full), test_name=kind, header=header, meta_mask=mask)
+    for field in ("indptr", "indices", "data"):
+        assert getattr(got["data"], field).tobytes() == getattr(exp["data"], field).tobytes()
+    assert got["header"] == exp["header"] and got["data"].shape == exp["data"].shape
+
+
+def test_csc_column_split_is_a_gather():
+    full, mask, _, counts, meta = table()
+    m = sp.csc_matrix(full)
+    for cols in (np.nonzero(mask)[0], np.nonzero(~mask)[0], np.array([], dtype=np.int64)):
+        colptr, rowval, nzval = pre._csc_take_cols(m.indptr, m.indices, m.data, cols)
+        assert colptr.dtype == np.int64 and colptr[0] == 0 and colptr[-1] == rowval.size == nzval.size
+        assert np.array_equal(_scatter(colptr, rowval, nzval, (200, len(cols))), full[:, cols])
+    # stored zeros and the order inside a column stay as they are
+    colptr, rowval, nzval = pre._csc_take_cols([0, 2, 3, 5], [4, 1, 0, 2, 3], [0.0, 7.0, 1.0, 2.0, 0.0], [0, 2])
+    assert colptr.tolist() == [0, 2, 4] and rowval.tolist() == [4, 1, 2, 3] and nzval.tolist() == [0.0, 7.0, 2.0, 0.0]
+
+
+def _bad_value(full, mask, value):
+    bad = np.array(full)
+    bad[5, 17] = value
+    return dict(data=bad, meta_mask=mask)
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("case, words", [
+    (lambda f, m: dict(data=f, meta_mask=m, meta_data=np.ones((200, 1))), "meta_data"),
+    (lambda f, m: dict(data=f, meta_mask=m[:-1]), "51 entries"),
+    (lambda f, m: dict(data=f, meta_mask=np.stack([m, m])), "dimensions"),
+    (lambda f, m: dict(data=f, meta_mask=np.where(m, 2, 0)), "booleans"),
+    (lambda f, m: dict(data=f, meta_mask=np.where(m, 0.5, 0.0)), "booleans"),
+    (lambda f, m: dict(data=f, meta_mask=["yes" if v else "no" for v in m]), "booleans"),
+    (lambda f, m: dict(data=f, meta_mask=np.ones(52, bool)), "every column"),
+    (lambda f, m: _bad_value(f, m, np.nan), "non-finite"),
+    (lambda f, m: _bad_value(f, m, np.inf), "non-finite"),
+])
+def test_refusals_name_meta_mask_before_any_device_call(case, words, normalize, sparse, monkeypatch):
+    _no_device(monkeypatch)
+    full, mask, _, _, _ = table()
+    kw = case(full, mask)
+    data = kw.pop("data")  # (normalize=False: the table stands for prepared clr_nz values; only the non-finite case looks at them)
+    data = sp.csc_matrix(data) if sparse else data
+    calls = [lambda: fw.learn_network(data, normalize=normalize, sensitive=True, heterogeneous=True, **kw)]
+    if normalize:
+        calls.append(lambda: fw.normalize_data(data, test_name="fz_nz", **kw))
+    for call in calls:
+        with pytest.raises(ValueError) as ei:
+            call()
+        assert "meta_mask" in str(ei.value) and words in str(ei.value), str(ei.value)
+
+
+def test_path_form_and_the_older_refusals(tmp_path, monkeypatch):
+    _no_device(monkeypatch)
+    full, mask, header, counts, meta = table()
+    path = str(tmp_path / "table.tsv")
+    fio.write_table(path, full, header)
+    with pytest.raises(ValueError, match="meta_mask.*meta_data_path"):
+        fw.learn_network(path, meta_mask=mask)
+    with pytest.raises(ValueError, match="meta_mask.*meta_data_path"):
+        fw.learn_network([path, path], meta_mask=mask)
+    # a header that does not name the meta columns as well
+    with pytest.raises(ValueError, match="meta_mask"):
+        fw.learn_network(full, meta_mask=mask, header=header[:48])
+    # what was refused before stays refused, in the words it had: sparse + meta_data, meta_data + normalize=False
+    with pytest.raises(ValueError, match="learn_network: sparse data with meta_data is not supported"):
+        fw.learn_network(sp.csc_matrix(counts), meta_data=meta)
+    with pytest.raises(ValueError, match="normalize_data: sparse data with meta_data is not supported"):
+        fw.normalize_data(sp.csc_matrix(counts), test_name="mi", meta_data=meta)
+    with pytest.raises(ValueError, match="learn_network: meta_data with normalize=False is not supported"):
+        fw.learn_network(counts.astype(np.float32), normalize=False, meta_data=meta)
+    with pytest.raises(ValueError, match="transposed"):
+        fw.learn_network(full, meta_mask=mask, transposed=True)
+    # a sparse table still has to hold counts where the mask does not say otherwise
+    wrong = np.zeros(52, bool)
+    wrong[[3, 30, 51]] = True  # the covariate is left among the OTU columns
+    with pytest.raises(ValueError, match="integer counts"):
+        fw.learn_network(sp.csc_matrix(full), meta_mask=wrong, sensitive=False)
+    with pytest.raises(TypeError, match="meta_masks"):
+        fw.learn_network(full, meta_masks=mask)
+
+
+@pytest.mark.parametrize("sparse", [False, True])
+@pytest.mark.parametrize("kind", ["fz_nz", "mi_nz"])
+def test_prepared_matrix_keeps_its_mask_and_its_columns(kind, sparse, fake_engine):
+    full, mask, header, _, _ = table()
+    prepared = (np.clip(full, 0, 2).astype(np.int32) if kind == "mi_nz" else full.astype(np.float32))  # stands for a prepared matrix
+    given = sp.csc_matrix(prepared) if sparse else prepared
+    fake_engine.edges = {(3, 5): 1.0, (0, 1): 0.5}
+    net = fw.learn_network(given, normalize=False, meta_mask=mask, header=header, sensitive=kind == "fz_nz", heterogeneous=True, max_k=2)
+    assert net["meta_variable_mask"] == mask.tolist() and net["variable_ids"] == header
+    assert net["parameters"]["meta_mask"] == 4 and net["counters"]["normalized_on_device"] is False
+    eng, = fake_engine.seen
+    assert eng.shape == (200, 52)
+    if sparse:
+        ref = sp.csc_matrix(prepared)
+        assert len(eng.data) == 3 and all(np.array_equal(a, b) for a, b in zip(eng.data, (ref.indptr, ref.indices, ref.data)))
+    else:
+        assert eng.data is prepared  # the caller's matrix, untouched
+    # no mask: nothing is marked, and the parameter says 0
+    plain = fw.learn_network(given, normalize=False, sensitive=kind == "fz_nz", heterogeneous=True, max_k=2)
+    assert not any(plain["meta_variable_mask"]) and plain["parameters"]["meta_mask"] == 0
+
+
+def test_extra_data_the_mask_belongs_to_the_main_table(fake_engine):
+    full, mask, header, counts, meta = table()
+    rng = np.random.default_rng(7)
+    e1, e2 = rng.poisson(5.0, (200, 6)), rng.poisson(5.0, (200, 4))
+    extra = [(e1, ["a%d" % j for j in range(6)]), (e2, None)]
+    nd = fw.normalize_data(full, extra, test_name="mi_nz", header=header, meta_mask=mask, device_normalize=False)
+    main = pre.normalize_with_meta(counts, "mi_nz", meta, header=[h for h, m in zip(header, mask) if not m], meta_header=META_NAMES)
+    k1, k2 = pre.normalize(e1, "mi_nz")[2], pre.normalize(e2, "mi_nz")[2]
+    # [last extra, first extra, the main table's OTU columns, its meta columns]; a missing header is numbered on from ALL 52 columns
+    assert nd["header"] == ["X%d" % (53 + j) for j in np.nonzero(k2)[0]] + ["a%d" % j for j in np.nonzero(k1)[0]] + main["header"]
+    assert nd["header"][-3:] == META_NAMES[:3]
+    assert nd["meta_mask"].tolist() == [False] * (len(nd["header"]) - 3) + [True] * 3
+    assert np.array_equal(nd["data"][:, -main["data"].shape[1]:], main["data"])
+    # normalize=False: tables side by side, the mask where the main table has it
+    prepared = np.clip(full, 0, 2).astype(np.int32)
+    net = fw.learn_network(prepared, normalize=False, meta_mask=mask, header=header, sensitive=False, heterogeneous=True, max_k=2,
+                           extra_data=[(np.minimum(e1, 2), extra[0][1]), (np.minimum(e2, 2), None)])
+    assert net["variable_ids"] == ["X%d" % (53 + j) for j in range(4)] + extra[0][1] + header
+    assert net["meta_variable_mask"] == [False] * 10 + mask.tolist() and net["parameters"]["meta_mask"] == 4
+    eng, = fake_engine.seen
+    assert eng.shape == (200, 62) and np.array_equal(eng.data[:, 10:], prepared)
+
+
+def test_gml_marks_the_meta_variables(tmp_path, fake_engine, monkeypatch):
+    monkeypatch.setattr(fw.api, "normalize_counts", lambda c, t, device=0: pre.normalize(c, t))  # (the device front-end, on the host)
+    full, mask, header, _, _ = table()
+    last = 50  # after normalisation: 48 OTUs, then hab, cov, cat = 48, 49, 50
+    fake_engine.edges = {(0, 48): 2.5, (11, 49): -1.25, (2, 3): 0.75, (49, last): 1.0}
+    net = fw.learn_network(full, meta_mask=mask, header=header, sensitive=False, heterogeneous=True, max_k=2)
+    assert net["variable_ids"][-3:] == META_NAMES[:3] and net["meta_variable_mask"] == [False] * 48 + [True] * 3
+    assert net["parameters"]["meta_mask"] == 4 and net["counters"]["normalized_on_device"] is True
+    path = str(tmp_path / "net.gml")
+    net.save(path)
+    edges, ids, marked = fio.read_gml(path)
+    assert ids == net["variable_ids"] and marked == net["meta_variable_mask"]
+    assert [i for i, m in zip(ids, marked) if m] == META_NAMES[:3]
+    assert edges == net["edges"]
+    assert open(path).read().count("mv 1") == 3
