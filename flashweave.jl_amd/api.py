@@ -213,6 +213,62 @@ def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, ma
     return dict(data=mat, header=hdr, meta_mask=meta_mask, row_mask=row_mask), on_device
 
 
+def _digest_update(h, obj):
+    """One argument of learn_network into the hash of the distributed input check: arrays by shape, dtype and bytes, a sparse table by
+    its three CSC arrays, containers element by element, anything else by its repr."""
+    if is_sparse(obj) or isinstance(obj, CSC):
+        colptr, rowval, nzval, shape = _csc_arrays(obj)
+        h.update(("csc%r" % (shape,)).encode())
+        for a in (colptr, rowval, nzval):
+            _digest_update(h, np.asarray(a))
+    elif isinstance(obj, np.ndarray):
+        h.update(("nd%r%s" % (obj.shape, obj.dtype.str)).encode())
+        h.update(repr(obj.tolist()).encode() if obj.dtype.kind == "O" else np.ascontiguousarray(obj).tobytes())
+    elif isinstance(obj, (list, tuple)):
+        h.update(("seq%d" % len(obj)).encode())
+        for v in obj:
+            _digest_update(h, v)
+    elif hasattr(obj, "__array__") and not isinstance(obj, (str, bytes)):
+        _digest_update(h, np.asarray(obj))
+    else:
+        h.update(("%s:%r" % (type(obj).__name__, obj)).encode())
+
+
+def _distributed_world():
+    """learn_network(distributed=True): the default torch.distributed group must be up -> (torch.distributed, rank, world size)."""
+    try:
+        import torch.distributed as dist
+        up = dist.is_available() and dist.is_initialized()
+    except ImportError:
+        dist, up = None, False
+    if not up:
+        raise ValueError("learn_network: distributed=True needs an initialised torch.distributed default group: start the ranks with "
+                         "torchrun (or call torch.distributed.init_process_group on every rank) before learn_network; ranks are not "
+                         "spawned here")
+    return dist, dist.get_rank(), dist.get_world_size()
+
+
+def _distributed_input_check(dist, rank, world, device, tables, keywords):
+    """First step of a distributed learn_network: every rank hashes the arguments that decide the result and the ranks compare.
+    Ranks that disagree on the data would disagree on level 0 and wait for each other in a later collective."""
+    import hashlib
+    import torch
+    h = hashlib.sha256()
+    _digest_update(h, tables)
+    _digest_update(h, sorted(keywords.items()))
+    on_gpu = dist.get_backend() == "nccl"  # (a CPU backend compares on the host: no device call before the refusals)
+    mine = torch.frombuffer(bytearray(h.digest()), dtype=torch.uint8)
+    mine = mine.to(torch.device("cuda", device)) if on_gpu else mine
+    everyone = torch.empty(world * mine.numel(), dtype=torch.uint8, device=mine.device)
+    dist.all_gather_into_tensor(everyone, mine)
+    everyone = everyone.cpu().view(world, -1)
+    differ = [r for r in range(world) if not bool((everyone[r] == everyone[0]).all())]
+    if differ:
+        raise ValueError("learn_network: distributed=True: the ranks were not called with the same arguments -- the digest of the table "
+                         "(shape, dtype, bytes) and the mode keywords on rank(s) %s differs from rank 0's (this is rank %d of %d); "
+                         "every rank must pass the same data and options, only `device` may differ" % (differ, rank, world))
+
+
 def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
                    device_normalize=True, device=0, meta_mask=None):
     """normalize_data (preprocessing.jl:660-701), both forms: what learn_network(normalize=True) does to its tables, as a function of
@@ -255,7 +311,8 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
 def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
                   meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
-                  no_red_tests=True, track_rejections=False, csc_resident=False, extra_data=None, transposed=False, meta_mask=None, **unsupported):
+                  no_red_tests=True, track_rejections=False, csc_resident=False, extra_data=None, transposed=False, meta_mask=None, distributed=False,
+                  **unsupported):
     """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False); a numpy array or a scipy.sparse
     matrix.  A sparse table stays sparse end to end (what the reference does with make_sparse, learning.jl:470): normalize=True runs
     the device CSC front-end (integer counts only) and the sparse upload, normalize=False uploads the matrix as it is (Int32 levels
@@ -316,6 +373,23 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     meta_data_path), of another length than the table has columns, with entries other than booleans or 0 / 1, marking every column,
     or marking a column with a non-finite value raises ValueError naming meta_mask before any device call; an all-False mask is no
     mask.  parameters["meta_mask"] records the number of marked columns.
+    distributed (default False): True runs the call SPMD over the ranks of an already initialised torch.distributed default group
+    (the reference's workers, learning.jl:130-199, as one process per GPU): every rank calls learn_network with the same arguments, each
+    with its own `device`, and every rank gets the same FWResult.  Results do not depend on the number of ranks.  First the ranks
+    compare a digest of the table (shape, dtype, bytes; a sparse table's three CSC arrays) and of the mode keywords: a mismatch
+    raises ValueError naming distributed on every rank instead of a deadlock later.  Then every rank normalises for itself (the
+    front-ends are deterministic: all four modes, sparse tables, extra_data, meta_mask, the path form and csc_resident stay available),
+    level 0 of the discrete kinds screens this rank's share of the pair tiles (the Fisher-z kinds stay replicated, as does the Pearson
+    matrix), the targets of every feed-forward round are dealt to the ranks, the round's neighbour sets are exchanged in device
+    memory (dist.make_dev_exchange) and, with track_rejections, the rejection log is gathered the same way
+    (Engine.gather_rejections), so that result["rejections"] is the whole log everywhere.  Ranks are not spawned here:
+        torchrun --nproc-per-node 8 run.py          # run.py:
+        torch.distributed.init_process_group("nccl")
+        net = learn_network(counts, distributed=True, device=int(os.environ["LOCAL_RANK"]))
+    Without an initialised group: ValueError naming distributed, before any device call; a world of one rank takes the ordinary path.
+    prec=64 with the plain fz test is refused (ValueError naming prec=64 and distributed): the Float64 mode has no sharded entry points.
+    parameters["distributed"] records the world size (0 when off), counters["world_size"] and counters["rank"] the rank's place; the
+    other counters are the rank's own.
     Path form (learning.jl:354-401): data may be a path (str / os.PathLike) or a list of paths, read with io.load_data (.tsv, .csv,
     BIOM 1.0 JSON; anything else raises what load_data raises): the first is the main table, the others become extra_data under their
     file headers; meta_data_path (second positional argument, as in the reference) is the main table's meta data file;
@@ -345,6 +419,18 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
         extra_data = from_files + list(extra_data or []) if (from_files or extra_data is not None) else None
     test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
     eng_prec = 64 if (prec == 64 and test_name == "fz") else 32  # the element type of the device pipeline
+    dist, rank, world = _distributed_world() if distributed else (None, 0, 0)
+    sharded = world > 1  # (a world of one rank takes the ordinary path)
+    if sharded:
+        if eng_prec == 64:
+            raise ValueError("learn_network: prec=64 with distributed=True is not supported for the plain fz test: the Float64 mode has no "
+                             "sharded entry points (DESIGN.md section 7); run it on one rank or pass prec=32")
+        _distributed_input_check(dist, rank, world, device, [data if (is_sparse(data) or isinstance(data, CSC)) else np.asarray(data), meta_data, meta_header, header, meta_mask, extra_data],
+                                 dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=feed_forward,
+                                      normalize=normalize, hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec,
+                                      round_size=round_size, make_onehot=make_onehot, recursive_pcor=recursive_pcor, dense_cor=dense_cor,
+                                      device_normalize=device_normalize, fast_elim=fast_elim, no_red_tests=no_red_tests,
+                                      track_rejections=track_rejections, csc_resident=csc_resident))
     csc_resident = bool(csc_resident)
     if csc_resident:  # what the CSC-resident layout does not serve is refused by name, never densified
         if test_name != "fz_nz":
@@ -425,10 +511,29 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
         # (what the device front-end returned is canonical already: its triple goes up as it is, stored 0.0f of clr_nz included)
         eng.set_data((mat.indptr, mat.indices, mat.data) if is_sparse(mat) else mat, csc_resident=csc_resident)
         if test_name == "fz" and dense_cor:
-            eng.compute_cor()
-        net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests,
-                      track_rejections=track_rejections)
+            eng.compute_cor()  # (replicated in a distributed run: row-block sharding stays an Engine-level tool, dist.sharded_cor)
+        gathered = None
+        if sharded:
+            import torch
+            from .dist import make_dev_exchange
+            from .engine import rejections_dict
+            xchg = make_dev_exchange(dist, torch.device("cuda", device))
+            if test_name in ("mi", "mi_nz"):
+                eng.level0_dev(rank, world, xchg)  # this rank's share of the pair tiles
+            else:
+                eng.level0()  # the Fisher-z kinds stay replicated (include/flashweave_amd.h)
+            net = eng.lgl(feed_forward=feed_forward, round_size=round_size, rank=rank, world_size=world, dev_exchange=xchg,
+                          fast_elim=fast_elim, no_red_tests=no_red_tests, track_rejections=track_rejections)
+            if track_rejections:  # every rank holds its own targets' records: all of them everywhere
+                gathered = eng.gather_rejections(xchg)
+                net["rejections"] = rejections_dict(eng.rejection_records())
+        else:
+            net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests,
+                          track_rejections=track_rejections)
         counters = eng.counters()
+        counters["world_size"], counters["rank"] = max(world, 1), rank
+        for k in ("packed_host", "packed_dev", "received"):  # the log gather of a distributed run (None: there was none)
+            counters["rejections_" + k] = None if gathered is None else gathered[k]
         counters["data_resident_bytes"] = eng.data_resident_bytes() if (test_name == "fz_nz" and hasattr(eng.L, "fw_data_resident_bytes")) else None
     finally:
         eng.close()
@@ -442,7 +547,7 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
                                     feed_forward=feed_forward, test_name=test_name, round_size=round_size,
                                     recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
                                     no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections), prec=eng_prec,
-                                    csc_resident=csc_resident, extra_data=len(extra), meta_mask=n_marked,
+                                    csc_resident=csc_resident, extra_data=len(extra), meta_mask=n_marked, distributed=world,
                                     schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
                                               else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
                                               else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),

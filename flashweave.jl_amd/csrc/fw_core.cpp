@@ -174,6 +174,7 @@ int fw_ctx_destroy(fw_ctx *c)
     free_dev(c->d_arena);
     free_dev(c->d_bh);
     free_dev(c->d_rej);
+    free_dev(c->d_rej_x);
     free_dev(c->d_l0m_i);
     free_dev(c->d_l0m_d);
     for (FwDevBuf &b : c->d_mig_tab) free_dev(b);

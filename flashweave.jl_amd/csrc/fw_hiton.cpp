@@ -129,7 +129,11 @@ struct RejGuard {
 int rej_begin(fw_ctx *c, size_t *rej_n)
 {
     c->rej.clear();
+    c->rej_slot.clear();
+    c->rej_host.clear();
+    c->rej_gathered = false;
     *rej_n = c->track_rej != 0 && c->P.max_k > 0 ? (size_t)c->nb_off[c->P.p] : 0;
+    c->rej_n_last = *rej_n;
     if (!*rej_n) return FW_OK;
     fw_rejection none;
     memset(&none, 0xff, sizeof(none));  // n_zs = -1: no record
@@ -160,22 +164,37 @@ void rej_store(fw_ctx *c, const FwLevel0 &l0, const Target &t, int32_t cand, con
     r.pval = o.pval;
 }
 
-// device records win their slot (a target ran on one path only: at most one of the two copies is filled)
-int rej_finish(fw_ctx *c, size_t rej_n)
+// The slot -> list pass.  Device records win their slot (a target ran on one path only: at most one of the two copies is filled);
+// host_slots may be null (fw_rejections_allgather_*: every record is in device memory by then).  Beside every entry the context keeps
+// its slot and which side wrote it: what fw_rejections_allgather_* needs of the job pool's slots once they are gone.
+int rej_compact(fw_ctx *c, size_t rej_n, const fw_rejection *host_slots)
 {
+    c->rej.clear();
+    c->rej_slot.clear();
+    c->rej_host.clear();
     if (rej_n) {
         std::vector<fw_rejection> dev(rej_n);
         FW_HIP(c, hipMemcpy(dev.data(), c->d_rej.ptr, sizeof(fw_rejection) * rej_n, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < rej_n; ++i) {
-            fw_rejection r = dev[i].n_zs >= 0 ? dev[i] : c->rej_slots[i];
+            const bool from_host = dev[i].n_zs < 0;
+            if (from_host && !host_slots) continue;
+            fw_rejection r = from_host ? host_slots[i] : dev[i];
             if (r.n_zs < 0) continue;
             double total = 0.0;  // tests.jl:313,327-332: every subset of sizes max_k .. 1, not capped by max_tests (integer binomials)
             for (int s = c->P.max_k; s >= 1; --s) total += (double)fw_binom_any(r.n_acc, s);
             r.frac = r.num_tests > 0 && total > 0.0 ? (double)r.num_tests / total : 0.0;
             for (int q = r.n_zs; q < FW_MAX_K; ++q) r.zs[q] = 0;
             c->rej.push_back(r);
+            c->rej_slot.push_back((int64_t)i);
+            c->rej_host.push_back(from_host ? 1 : 0);
         }
     }
+    return FW_OK;
+}
+
+int rej_finish(fw_ctx *c, size_t rej_n)
+{
+    if (int rc = rej_compact(c, rej_n, c->rej_slots.data())) return rc;
     if (c->track_rej != 0) c->have_rej = true;
     return FW_OK;
 }
@@ -719,6 +738,7 @@ struct ElimGuard {  // the device rounds read the mode from the context (fw_devh
 }  // namespace
 
 int fwi_chain_count(const fw_ctx *c, size_t n_targets) { return chain_count(c, n_targets); }
+int fwi_rej_compact(fw_ctx *c, size_t rej_n, const fw_rejection *host_slots) { return rej_compact(c, rej_n, host_slots); }
 void fwi_deal_chains(size_t n, int K, std::vector<int> &chain_of, std::vector<size_t> &chain_idx) { deal_chains(n, K, chain_of, chain_idx); }
 
 void fwi_host_workers_free(fw_ctx *c)
@@ -749,6 +769,8 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
     c->elim_mode = opt.elim_mode;
     RejGuard rej_guard{c};
     if (int rc = rej_begin(c, &L.rej_n)) return rc;
+    c->rej_rank = opt.rank;
+    c->rej_world = opt.world_size;
     L.t0 = fwi_now_s();
     L.order = fw_target_order(level0_view(c));
     L.nt = opt.max_targets > 0 && opt.max_targets < c->P.p ? opt.max_targets : c->P.p;

@@ -207,6 +207,15 @@ struct fw_ctx {
     std::vector<fw_rejection> rej, rej_slots;
     FwDevBuf d_rej;
     fw_rejection *d_rej_run = nullptr;  // non-null while a tracked fw_learn_network runs (read by fw_devhiton.hip)
+    // fw_rejections_allgather_* (fw_xchg.hip): what the last fw_learn_network left for it.  The device slots stay as the run wrote
+    // them; of the host job pool's slots only the filled ones are kept, as (slot, which side wrote it) beside every entry of rej.
+    size_t rej_n_last = 0;            // slots of the last run (0: it logged nothing)
+    int rej_rank = 0, rej_world = 1;  // its fw_learn_opts.rank / world_size
+    bool rej_gathered = false;        // rej already holds every rank's entries
+    std::vector<int64_t> rej_slot;    // per entry of rej: its slot
+    std::vector<uint8_t> rej_host;    // per entry of rej: 1 = written by the host job pool (not in d_rej yet)
+    FwDevBuf d_rej_x;                 // counters + staging of the host-written records on their way into d_rej
+    int64_t rej_packed_host = 0, rej_packed_dev = 0, rej_received = 0;  // last gather: records packed by origin, records of other ranks placed
 
     fw_counters cnt{};
 
@@ -355,6 +364,10 @@ int fwi_pool_round(fw_ctx *ctx, FwPool &pool, std::vector<FwPoolJob> &finished);
 int fwi_bh_csr_device(fw_ctx *ctx, const FwL0Dev &in, int64_t m_reliable);
 // device-resident all-gather of the ranks' significant level-0 pairs (fw_xchg.hip)
 int fwi_l0_exchange_dev(fw_ctx *c, const fw_dev_exchange *x, int world, const FwL0Dev &local, int64_t m_local, FwL0Dev *merged, int64_t *m_sum);
+// all-gather of the ranks' rejection logs through a fw_dev_exchange (fw_xchg.hip); `who` names the entry point in messages
+int fwi_rej_allgather(fw_ctx *c, const fw_dev_exchange *x, const char *who);
+// fw_hiton.cpp: slot array in device memory (+ host_slots, may be null: the job pool's) -> ctx->rej, ascending (target, candidate)
+int fwi_rej_compact(fw_ctx *c, size_t rej_n, const fw_rejection *host_slots);
 int fwi_selftest_div(fw_ctx *ctx, unsigned long long cases, unsigned long long seed, unsigned long long *mismatches);  // fw_fz.hip
 void fwi_comm_free(fw_ctx *ctx);  // fw_rccl.cpp
 int fwi_nb_host_ensure(fw_ctx *ctx);  // download partners / statistics / adjusted p if only the device holds them

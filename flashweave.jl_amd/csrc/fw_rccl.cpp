@@ -287,6 +287,19 @@ int fw_learn_network_comm(fw_ctx *c, const fw_learn_opts *opts_in, int64_t *n_ed
     return fw_learn_network_dev(c, &opt, &x, n_edges_out);
 }
 
+// the rejection log of every rank's targets on every rank (fw_xchg.hip): header + payload all-gather, as fw_learn_network_comm's rounds
+int fw_rejections_allgather_comm(fw_ctx *c)
+{
+    if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
+    if (!c->comm) return fw_fail(c, FW_ERR_ARG, "fw_rejections_allgather_comm: no communicator (fw_comm_init)");
+    if (c->have_rej && !c->rej_gathered && (c->rej_rank != c->comm->rank || c->rej_world != c->comm->world))
+        return fw_fail(c, FW_ERR_STATE, "fw_rejections_allgather_comm: the tracked run was rank %d of %d, the communicator is rank %d of %d", c->rej_rank, c->rej_world,
+                       c->comm->rank, c->comm->world);
+    CommX X{c, 0.0};
+    fw_dev_exchange x{&X, comm_prepare, comm_exchange};
+    return fwi_rej_allgather(c, &x, "fw_rejections_allgather_comm");
+}
+
 // FW_FZ row-block sharding (fw_use_cor_buffer / fw_compute_cor_mat_rows): the in-place all-gather of the row blocks
 int fw_cor_mat_allgather_comm(fw_ctx *c, int64_t rows_per_rank)
 {

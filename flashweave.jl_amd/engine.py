@@ -171,6 +171,10 @@ def load_library():
         L.fw_level0_comm.argtypes = [vp, vp]
         L.fw_cor_mat_allgather_comm.argtypes = [vp, C.c_int64]
         L.fw_learn_network_comm.argtypes = [vp, vp, vp]
+    if hasattr(L, "fw_rejections_allgather_dev"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        L.fw_rejections_allgather_dev.argtypes = [vp, C.POINTER(_DevExchange)]
+        L.fw_rejections_allgather_comm.argtypes = [vp]
+        L.fw_rejections_allgather_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(L, "fw_selftest"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
         L.fw_selftest.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     L.fw_effective_n_obs_min.restype = C.c_int64
@@ -607,6 +611,28 @@ class Engine:
         rec = np.zeros(max(n.value, 1), REJECTION_DTYPE)
         self._ck(self.L.fw_rejections_get(self.h, _ptr(rec)))
         return rec[:n.value]
+
+    def gather_rejections(self, dev_exchange):
+        """fw_rejections_allgather_dev: COLLECTIVE -- every rank of a target-sharded run calls it once after a tracked lgl; afterwards
+        rejection_records() is the log of all targets on every rank, the bytes of a one-rank log.  dev_exchange: the (prepare, exchange)
+        pair lgl took (dist.make_dev_exchange).  A second call is a no-op.  -> dict(packed_host, packed_dev, received): records this
+        rank sent that the host job pool / the device paths had written, and records of other ranks placed here."""
+        self._need("fw_rejections_allgather_dev", "gather_rejections()")
+        x = _DevExchange(None, PREPARE_FN(dev_exchange[0]), EXCHANGE_FN(dev_exchange[1]))
+        self._xdev_rej = x
+        self._ck(self.L.fw_rejections_allgather_dev(self.h, C.byref(x)))
+        return self._gather_stats()
+
+    def gather_rejections_comm(self):
+        """fw_rejections_allgather_comm: gather_rejections on the library's own communicator (comm_init), after a tracked lgl_comm."""
+        self._need("fw_rejections_allgather_comm", "gather_rejections_comm()")
+        self._ck(self.L.fw_rejections_allgather_comm(self.h))
+        return self._gather_stats()
+
+    def _gather_stats(self):
+        a, b, c_ = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.fw_rejections_allgather_stats(self.h, C.byref(a), C.byref(b), C.byref(c_)))
+        return dict(packed_host=a.value, packed_dev=b.value, received=c_.value)
 
     def _network(self, n_edges, edge_dict, track_rejections=False):
         ne = C.c_int64(n_edges)

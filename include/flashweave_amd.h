@@ -359,12 +359,27 @@ typedef struct fw_rejection {
 } fw_rejection;
 /* on = 1: the following fw_learn_network* calls keep the log (default 0; a switch of the context like fw_set_row_views, so that
  * fw_learn_opts keeps its layout).  The log is a diagnostic mode: the network is the same bytes either way.  In a target-sharded run
- * every rank holds the entries of its own targets; gathering them across ranks is left to the caller. */
+ * every rank holds the entries of its own targets until fw_rejections_allgather_dev / _comm (below) gives every rank all of them. */
 int fw_set_track_rejections(fw_ctx *ctx, int32_t on);
 /* entries of the last fw_learn_network* (0 if it ran with tracking off); FW_ERR_STATE before the first tracked run */
 int fw_rejections_count(const fw_ctx *ctx, int64_t *n);
 /* out[0 .. n): ascending (target, candidate) */
 int fw_rejections_get(const fw_ctx *ctx, fw_rejection *out);
+/* Target-sharded runs: the whole log on every rank, as the reference's master collects every worker's rej_dict (src/learning.jl:196-199).
+ * COLLECTIVE: every rank of the run calls it once, after a tracked fw_learn_network_dev / _comm (or fw_learn_network with
+ * world_size > 1); a rank with nothing logged (max_k = 0, no record of its own) takes part with 0 records.  Afterwards
+ * fw_rejections_count / fw_rejections_get return the entries of ALL targets on every rank -- ascending (target, candidate), frac filled:
+ * the bytes of a one-rank log wherever the run's tests are.  The payload stays in device memory: the filled slots are packed into the
+ * exchange's send buffer as 96-byte records (the 88 bytes + the slot index), gathered, and scattered into this rank's slots by
+ * csrc/fw_xchg.hip.  A second call is a no-op (FW_OK, no collective); without the call nothing changes: every rank keeps the entries of
+ * its own targets.  FW_ERR_STATE before the first tracked run (and when fw_level0 ran again since it); FW_ERR_ARG for a NULL exchange
+ * and for _comm without a communicator (fw_comm_init); FW_ERR_DEVICE, with a message, when two ranks deliver a record for one slot --
+ * targets are dealt to one rank each, no winner is picked. */
+int fw_rejections_allgather_dev(fw_ctx *ctx, const fw_dev_exchange *exchange);
+int fw_rejections_allgather_comm(fw_ctx *ctx); /* the same on the library's own communicator (fw_comm_init) */
+/* the last gather of this context: records this rank packed that the host job pool / the device paths had written, and records of
+ * other ranks placed here; FW_ERR_STATE when the log is not a gathered one */
+int fw_rejections_allgather_stats(const fw_ctx *ctx, int64_t *packed_host, int64_t *packed_dev, int64_t *received);
 
 /* ---- normalisation front-end on the device -------------------------------------- */
 
