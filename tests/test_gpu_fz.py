@@ -4,6 +4,11 @@ Tolerances (stated per the north star):
   * Pearson matrix (fp32 MFMA accumulation vs Float64 accumulation rounded to Float32): |diff| <= 5e-6.
   * partial correlations / edge weights, given the SAME Float32 matrix: bit-exact (only + - * / sqrt rint).
   * p-values: relative 1e-12 (device log/erfc vs libm).
+
+NOT covered here: the Float32 screen of the size-3 fast loop.  The test_subsets cases below use accepted lists of 9-30 variables in batches of
+a few dozen jobs: the host cuts such launches into segments of 256 ranks, so a lane holds ONE test (R = 1) and the screen has no earlier bound
+to compare with (lists under 13 variables do not even give a chunk inside the size-3 enumeration: the general form).  The screen needs runs of
+R >= 2 ranks per lane, i.e. launches of more than 786 432 ranks, or |accepted| >= 48 in one segment: tests/test_gpu_fz_screen.py.
 """
 import numpy as np
 import pytest
