@@ -2,12 +2,15 @@
 composition of the normalisation front-end, the device engine and the host driver.  Keyword names and defaults
 follow the reference; unsupported options raise instead of being silently ignored."""
 import os
+import time
+import warnings
+from collections import namedtuple
 
 import numpy as np
 
 from . import io as fio
 from . import preprocess as pre
-from .engine import CSC, Engine, as_csc, is_sparse, normalize_counts
+from .engine import CSC, Engine, as_csc, is_sparse, normalize_counts, rejections_dict
 
 
 class FWResult(dict):
@@ -47,19 +50,52 @@ def _integral(a):
                 a.max() < 2**31 and a.min() >= 0)
 
 _TEST_NAMES = ("fz", "fz_nz", "mi", "mi_nz")
+# learn_network's keywords by where they go.  All of them -- the caller's values, before anything is resolved -- go into the digest
+# of a distributed run; parameters= reports _REPORTED, the Engine takes _ENGINE_KEYS and lgl _LGL_KEYS, each with the resolved values
+# (test_name, round_size, recursive_pcor, dense_cor, csc_resident, prec = the engine's element type) laid over the caller's.
+_REPORTED = ("sensitive", "heterogeneous", "max_k", "alpha", "feed_forward", "test_name", "round_size", "recursive_pcor", "dense_cor",
+             "fast_elim", "no_red_tests", "track_rejections", "prec", "csc_resident")
+_ENGINE_KEYS = ("max_k", "alpha", "hps", "n_obs_min", "max_tests", "FDR", "device", "recursive_pcor", "dense_cor", "prec")
+_LGL_KEYS = ("feed_forward", "round_size", "fast_elim", "no_red_tests", "track_rejections")
 
 
 def _is_path(x):
     return isinstance(x, (str, os.PathLike))
 
 
-def _load_paths(paths, meta_data_path, transposed):
-    """learn_network(data_path | all_data_paths, meta_data_path) (learning.jl:354-401): the first path is the main table, the others
-    become extra_data with their file headers; only the main table has meta data.  io.load_data decides what is readable."""
+def _any_sparse(x):
+    """A sparse table in any of its forms: a scipy.sparse matrix / array, or the canonical triple as_csc returned."""
+    return is_sparse(x) or isinstance(x, CSC)
+
+
+def _default_header(cols, start=0):
+    """X(start + 1) .. X(start + cols): the names of columns that came without any, numbered on from `start` columns before them."""
+    return ["X%d" % (start + j + 1) for j in range(cols)]
+
+
+def _path_form(data, meta_data_path, transposed, header, meta_data, meta_header, meta_mask, extra_data):
+    """learn_network(data_path | all_data_paths, meta_data_path) (learning.jl:354-401) -> (data, header, meta_data, meta_header,
+    extra_data) as arrays: the first path is the main table, the others become extra_data with their file headers, ahead of the
+    caller's; only the main table has meta data.  io.load_data decides what is readable.  Arrays pass through as they are."""
+    paths = [data] if _is_path(data) else list(data) if (isinstance(data, (list, tuple)) and len(data) and all(_is_path(q) for q in data)) else None
+    if paths is None:
+        if meta_data_path is not None:
+            raise ValueError("learn_network: meta_data_path goes with a data path (learn_network(data_path, meta_data_path)); with an "
+                             "array pass meta_data")
+        if transposed:
+            raise ValueError("learn_network: transposed=True is served for the path form; pass the transposed array")
+        return data, header, meta_data, meta_header, extra_data
+    if not (meta_data_path is None or _is_path(meta_data_path)):
+        raise TypeError("learn_network: meta_data_path must be a path, got %s (options are keywords)" % type(meta_data_path).__name__)
+    if header is not None or meta_data is not None or meta_header is not None:
+        raise ValueError("learn_network: header, meta_data and meta_header come from the files in the path form")
+    if meta_mask is not None:
+        raise ValueError("learn_network: meta_mask goes with an array or a sparse matrix; in the path form the meta variables come "
+                         "from meta_data_path")
     meta_path = None if meta_data_path is None else os.fspath(meta_data_path)
     data, header, meta_data, meta_header = fio.load_data(os.fspath(paths[0]), meta_path, transposed=transposed)
-    extra = [fio.load_data(os.fspath(q), None, transposed=transposed)[:2] for q in paths[1:]]
-    return data, header, meta_data, meta_header, extra
+    from_files = [fio.load_data(os.fspath(q), None, transposed=transposed)[:2] for q in paths[1:]]
+    return data, header, meta_data, meta_header, (from_files + list(extra_data or []) if (from_files or extra_data is not None) else None)
 
 
 def _sparse_refusals(who, test_name, normalize, prec, device_normalize, meta_data):
@@ -135,7 +171,7 @@ def _split_meta(who, data, mask, header, test_name):
     samples x meta-variables matrix (a continuous covariate is not a count).  A sparse table is split on its CSC arrays, O(nnz); only
     the few meta columns are densified."""
     otu_header, meta_header = [h for h, m in zip(header, mask) if not m], [h for h, m in zip(header, mask) if m]
-    if not (is_sparse(data) or isinstance(data, CSC)):
+    if not _any_sparse(data):
         meta = data[:, mask]
         _finite_meta(who, meta)
         return data[:, ~mask], otu_header, meta.astype(np.float64), meta_header
@@ -163,14 +199,14 @@ def _extra_tables(who, data, extra_data, test_name, normalize, n_named=None):
         if not (isinstance(entry, (list, tuple)) and len(entry) == 2):
             raise ValueError("%s: extra_data[%d] is not a (table, header) pair" % (who, i))
         tab, hdr = entry
-        if not (is_sparse(tab) or isinstance(tab, CSC)):
+        if not _any_sparse(tab):
             tab = np.asarray(tab)
             if tab.ndim != 2 or tab.dtype.kind not in "biuf":
                 raise ValueError("%s: extra_data[%d] is not a (table, header) pair: the table must be a samples x OTUs matrix of "
                                  "numbers" % (who, i))
         if hdr is not None and (isinstance(hdr, (str, bytes)) or not hasattr(hdr, "__len__")):
             raise ValueError("%s: extra_data[%d] is not a (table, header) pair: the header must be a list of names or None" % (who, i))
-        if (is_sparse(tab) or isinstance(tab, CSC)) != sparse:
+        if _any_sparse(tab) != sparse:
             raise ValueError("%s: extra_data[%d] is %s while data is %s: a mix of sparse and dense tables is not supported, pass all "
                              "of them in one form" % (who, i, "dense" if sparse else "sparse", "sparse" if sparse else "dense"))
         rows, cols = _shape(tab)
@@ -178,7 +214,7 @@ def _extra_tables(who, data, extra_data, test_name, normalize, n_named=None):
             raise ValueError("%s: extra_data[%d] has %d rows, data has %d: every table holds the same samples in the same order"
                              % (who, i, rows, n))
         if hdr is None:
-            hdr = ["X%d" % (n_named + j + 1) for j in range(cols)]
+            hdr = _default_header(cols, n_named)
             n_named += cols
         elif len(hdr) != cols:
             raise ValueError("%s: extra_data[%d] has a header of %d names for %d columns" % (who, i, len(hdr), cols))
@@ -192,31 +228,29 @@ def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, ma
     filters), then preprocess.combine_data.  -> (dict(data, header, meta_mask, row_mask), on_device)"""
     on_device = bool(device_normalize and prec == 32 and all(isinstance(t, CSC) or _integral(t) for t in [data] + [t for t, _ in extra]))
     dev_norm = (lambda c, t: normalize_counts(c, t, device=device)) if on_device else None
+
+    def one(tab, hdr):  # a count table on its own -> (matrix, the kept columns' names, row mask)
+        mat, row_mask, col_mask = dev_norm(tab, test_name) if on_device else pre.normalize(tab, test_name, prec=prec)
+        return mat, [h for h, k in zip(hdr, col_mask) if k], row_mask
     if meta_data is not None:
         r = pre.normalize_with_meta(data, test_name, meta_data, prec=prec, header=header, meta_header=meta_header,
                                     make_onehot=make_onehot, normalizer=dev_norm)
         main = dict(data=r["data"], header=r["header"], meta_mask=np.asarray(r["meta_mask"], dtype=bool), row_mask=r["row_mask"])
     else:
-        mat, row_mask, col_mask = dev_norm(data, test_name) if on_device else pre.normalize(data, test_name, prec=prec)
-        hdr = [h for h, k in zip(header, col_mask) if k]
+        mat, hdr, row_mask = one(data, header)
         main = dict(data=mat, header=hdr, meta_mask=np.zeros(len(hdr), dtype=bool), row_mask=row_mask)
     if not extra:
         return main, on_device
-    tabs, hdrs, masks = [], [], []
-    for tab, hdr in extra:
-        mat, row_mask, col_mask = dev_norm(tab, test_name) if on_device else pre.normalize(tab, test_name, prec=prec)
-        tabs.append(mat)
-        hdrs.append([h for h, k in zip(hdr, col_mask) if k])
-        masks.append(row_mask)
-    mat, hdr, meta_mask, row_mask = pre.combine_data(tabs + [main["data"]], hdrs + [main["header"]],
-                                                     [None] * len(extra) + [main["meta_mask"]], masks + [main["row_mask"]])
+    tabs, hdrs, masks = zip(*[one(tab, hdr) for tab, hdr in extra])
+    mat, hdr, meta_mask, row_mask = pre.combine_data(list(tabs) + [main["data"]], list(hdrs) + [main["header"]],
+                                                     [None] * len(extra) + [main["meta_mask"]], list(masks) + [main["row_mask"]])
     return dict(data=mat, header=hdr, meta_mask=meta_mask, row_mask=row_mask), on_device
 
 
 def _digest_update(h, obj):
     """One argument of learn_network into the hash of the distributed input check: arrays by shape, dtype and bytes, a sparse table by
     its three CSC arrays, containers element by element, anything else by its repr."""
-    if is_sparse(obj) or isinstance(obj, CSC):
+    if _any_sparse(obj):
         colptr, rowval, nzval, shape = _csc_arrays(obj)
         h.update(("csc%r" % (shape,)).encode())
         for a in (colptr, rowval, nzval):
@@ -248,13 +282,18 @@ def _distributed_world():
     return dist, dist.get_rank(), dist.get_world_size()
 
 
-def _distributed_input_check(dist, rank, world, device, tables, keywords):
-    """First step of a distributed learn_network: every rank hashes the arguments that decide the result and the ranks compare.
-    Ranks that disagree on the data would disagree on level 0 and wait for each other in a later collective."""
+def _distributed_input_check(dist, rank, world, eng_prec, device, tables, keywords):
+    """First step of a sharded learn_network (world > 1), ahead of every other refusal: the one mode without sharded entry points is
+    refused, then every rank hashes the arguments that decide the result -- `tables`, the main table first, and the mode `keywords` as
+    the caller passed them -- and the ranks compare.  Ranks that disagree on the data would disagree on level 0 and wait for each other
+    in a later collective."""
+    if eng_prec == 64:
+        raise ValueError("learn_network: prec=64 with distributed=True is not supported for the plain fz test: the Float64 mode has no "
+                         "sharded entry points (DESIGN.md section 7); run it on one rank or pass prec=32")
     import hashlib
     import torch
     h = hashlib.sha256()
-    _digest_update(h, tables)
+    _digest_update(h, [tables[0] if _any_sparse(tables[0]) else np.asarray(tables[0])] + list(tables[1:]))
     _digest_update(h, sorted(keywords.items()))
     on_gpu = dist.get_backend() == "nccl"  # (a CPU backend compares on the host: no device call before the refusals)
     mine = torch.frombuffer(bytearray(h.digest()), dtype=torch.uint8)
@@ -267,6 +306,145 @@ def _distributed_input_check(dist, rank, world, device, tables, keywords):
         raise ValueError("learn_network: distributed=True: the ranks were not called with the same arguments -- the digest of the table "
                          "(shape, dtype, bytes) and the mode keywords on rank(s) %s differs from rank 0's (this is rank %d of %d); "
                          "every rank must pass the same data and options, only `device` may differ" % (differ, rank, world))
+
+
+_Tables = namedtuple("_Tables", "data header meta_data meta_header make_onehot extra mask sparse n_marked")
+
+
+def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec, device_normalize,
+                    normalize, csc_tuple_is_sparse, strict_header):
+    """The table stage of both entry points, everything before a front-end or a device sees a table: sparse or dense, the mask vector,
+    the sparse refusals, the canonical CSC form, the header, the meta columns split off (normalize=True) or only looked at (a prepared
+    matrix keeps them and its mask), the extra tables.  The entry points differ in two rules, which they pass: csc_tuple_is_sparse
+    (is an engine.CSC tuple a sparse table?) and strict_header (is a header of another length than the table refused without a mask
+    as well?).  -> _Tables; header is the caller's object when one was given and nothing was split off."""
+    sparse = _any_sparse(data) if csc_tuple_is_sparse else is_sparse(data)
+    data = data if sparse else np.asarray(data)
+    mask = _meta_mask_vector(who, meta_mask, meta_data, data)
+    if sparse:
+        # a sparse table stays sparse from here to the device (fw_normalize_counts_csc, fw_set_data_csc_*); what would need the dense
+        # matrix is refused by name before any device call -- densifying silently would defeat the point
+        _sparse_refusals(who, test_name, normalize, prec, device_normalize, meta_data)
+    if mask is not None and header is not None and len(header) != _shape(data)[1]:
+        raise ValueError("%s: a header of %d names for %d columns%s" % (who, len(header), _shape(data)[1], "" if strict_header else
+                         ": with a meta_mask the header names all columns of data, the meta ones included"))
+    if mask is None or not normalize:
+        data = _canonical_csc(who, data, test_name, normalize) if sparse else data
+        if mask is not None:  # the prepared matrix is taken as it is; its marked columns are only looked at
+            _finite_meta(who, pre._csc_take_cols(*data[:3], np.nonzero(mask)[0])[2] if sparse else data[:, mask])
+        extra = _extra_tables(who, data, extra_data, test_name, normalize)  # (refused by name before any device call)
+        if header is None:  # after the extra tables: a call with a bad header AND a bad extra table is told about the table
+            header = _default_header(_shape(data)[1])
+        elif strict_header and len(header) != _shape(data)[1]:
+            raise ValueError("%s: a header of %d names for %d columns" % (who, len(header), _shape(data)[1]))
+    else:
+        # normalize=True: the meta columns leave the table before anything is checked as a count -- a continuous covariate is no
+        # count -- and come back prepared, at its end (preprocessing.jl:425-446,527-558); from here on they are a numeric meta_data
+        cols = _shape(data)[1]
+        data, header, meta_data, meta_header = _split_meta(who, data, mask, _default_header(cols) if header is None else list(header), test_name)
+        make_onehot = False  # (numbers: nothing to encode)
+        extra = _extra_tables(who, data, extra_data, test_name, normalize, n_named=cols)
+    return _Tables(data, header, meta_data, meta_header, make_onehot, extra, mask, sparse, 0 if mask is None else int(mask.sum()))
+
+
+def _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense_cor):
+    """The engine options of learn_network against the test kind and the table as the caller gave it: what the CSC-resident layout
+    and the Float64 path do not serve is refused, and dense_cor / recursive_pcor become what will run (with the warning, attributed
+    to learn_network's caller).  -> (csc_resident, recursive_pcor, dense_cor)"""
+    csc_resident = bool(csc_resident)
+    if csc_resident:  # what the CSC-resident layout does not serve is refused by name, never densified
+        if test_name != "fz_nz":
+            raise ValueError("learn_network: csc_resident=True is served for sensitive=True, heterogeneous=True (fz_nz) only; the discrete "
+                             "kinds are bit-packed already and the plain fz test needs the dense matrix")
+        if not is_sparse(data):
+            raise ValueError("learn_network: csc_resident=True needs sparse data (a scipy.sparse matrix); a dense table is not "
+                             "converted silently")
+        if not recursive_pcor:
+            raise ValueError("learn_network: csc_resident=True with recursive_pcor=False is not supported: those conditional tests "
+                             "stream whole dense columns")
+    if eng_prec == 64 and not (recursive_pcor and dense_cor):
+        raise ValueError("learn_network: prec=64 with %s is not supported: the Float64 path conditions on the resident Float64 "
+                         "Pearson matrix (recursive_pcor=True, dense_cor=True)"
+                         % ("recursive_pcor=False" if not recursive_pcor else "dense_cor=False"))
+    if test_name != "fz":
+        dense_cor = True  # (learning.jl:42: only the plain fz test ever builds a matrix; the engine takes the flag for fz alone)
+    elif not dense_cor and recursive_pcor:
+        warnings.warn("learn_network: dense_cor=False leaves no correlation matrix for recursive partial correlations; "
+                      "running with recursive_pcor=False (conditional tests from the data)", stacklevel=3)
+        recursive_pcor = False
+    return csc_resident, recursive_pcor, dense_cor
+
+
+def _matrix(t, test_name, normalize, prec, device_normalize, device):
+    """The prepared tables (_Tables) -> (matrix for the engine, header, meta mask as a list or None, normalised on the device?,
+    seconds): normalised and combined (normalize=True), prepared tables laid side by side, or the prepared matrix as it is.  The
+    seconds are counters["t_normalize_s"]: this step alone."""
+    meta_mask = None if t.mask is None else [bool(v) for v in t.mask]  # (normalize=False keeps it; normalize=True returns its own)
+    header, on_device, t0 = t.header, False, time.perf_counter()
+    if normalize:
+        r, on_device = _normalize_tables(t.data, t.header, t.extra, test_name, t.meta_data, t.meta_header, t.make_onehot, prec,
+                                         device_normalize, device)
+        mat, header, meta_mask = r["data"], r["header"], [bool(v) for v in r["meta_mask"]]
+    elif t.extra:
+        # already normalised tables are only laid side by side (learning.jl:537-541): no filter, no alignment, extra tables first
+        everyone = np.ones(_shape(t.data)[0], dtype=bool)
+        mat, header, combined_mask, _ = pre.combine_data([x for x, _ in t.extra] + [t.data], [h for _, h in t.extra] + [t.header],
+                                                         [None] * len(t.extra) + [t.mask], [everyone] * (len(t.extra) + 1))
+        meta_mask = None if t.mask is None else [bool(v) for v in combined_mask]
+    else:  # the prepared matrix as it is: dense, or Int32 CSC for mi / mi_nz, Float32 CSC for fz_nz
+        mat = tuple(t.data[:3]) if t.sparse else t.data
+    return mat, header, meta_mask, on_device, time.perf_counter() - t0
+
+
+def _sharded_lgl(eng, test_name, lgl, dist, rank, world, device):
+    """level 0 and lgl of a distributed run on an engine that holds its data: this rank's share, the rounds' neighbour sets exchanged
+    in device memory and, with track_rejections, the whole log gathered.  -> (net, what gather_rejections returned or None)"""
+    import torch
+    from .dist import make_dev_exchange
+    xchg = make_dev_exchange(dist, torch.device("cuda", device))
+    if test_name in ("mi", "mi_nz"):
+        eng.level0_dev(rank, world, xchg)  # this rank's share of the pair tiles
+    else:
+        eng.level0()  # the Fisher-z kinds stay replicated (include/flashweave_amd.h)
+    net = eng.lgl(rank=rank, world_size=world, dev_exchange=xchg, **lgl)
+    if not lgl["track_rejections"]:
+        return net, None
+    gathered = eng.gather_rejections(xchg)  # every rank holds its own targets' records: all of them everywhere
+    net["rejections"] = rejections_dict(eng.rejection_records())
+    return net, gathered
+
+
+def _run_engine(mat, n, p, run, dist, rank, world):
+    """One engine for one run: the matrix goes up, the Pearson matrix is computed where the mode has one, lgl runs single or
+    sharded (world > 1), the counters are read; the engine is closed whatever happens.  run: learn_network's keywords with the
+    resolved values.  -> (net, counters)"""
+    test_name = run["test_name"]
+    eng = Engine(test_name, n, p, **{k: run[k] for k in _ENGINE_KEYS})
+    try:
+        # (what the device front-end returned is canonical already: its triple goes up as it is, stored 0.0f of clr_nz included)
+        eng.set_data((mat.indptr, mat.indices, mat.data) if is_sparse(mat) else mat, csc_resident=run["csc_resident"])
+        if test_name == "fz" and run["dense_cor"]:
+            eng.compute_cor()  # (replicated in a distributed run: row-block sharding stays an Engine-level tool, dist.sharded_cor)
+        lgl, gathered = {k: run[k] for k in _LGL_KEYS}, None
+        if world > 1:
+            net, gathered = _sharded_lgl(eng, test_name, lgl, dist, rank, world, run["device"])
+        else:
+            net = eng.lgl(**lgl)
+        counters = eng.counters()
+        counters["world_size"], counters["rank"] = max(world, 1), rank
+        for k in ("packed_host", "packed_dev", "received"):  # the log gather of a distributed run (None: there was none)
+            counters["rejections_" + k] = None if gathered is None else gathered[k]
+        counters["data_resident_bytes"] = eng.data_resident_bytes() if (test_name == "fz_nz" and hasattr(eng.L, "fw_data_resident_bytes")) else None
+    finally:
+        eng.close()
+    return net, counters
+
+
+def _schedule(round_size, feed_forward, p):
+    """parameters["schedule"]: the sentence that says which feed-forward schedule ran."""
+    return ("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
+            else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
+            else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)
 
 
 def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
@@ -288,24 +466,11 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
         raise ValueError("%s: unsupported test_name %r" % (who, test_name))
     if prec not in (32, 64):
         raise ValueError("%s: prec=%r is not supported (32 or 64)" % (who, prec))
-    sparse = is_sparse(data) or isinstance(data, CSC)
-    data = data if sparse else np.asarray(data)
-    mask = _meta_mask_vector(who, meta_mask, meta_data, data)
-    if sparse:
-        _sparse_refusals(who, test_name, True, prec, device_normalize, meta_data)
-    if mask is None:
-        data = _canonical_csc(who, data, test_name, True) if sparse else data
-        extra = _extra_tables(who, data, extra_data, test_name, True)
-    cols = _shape(data)[1]
-    if header is None:
-        header = ["X%d" % (i + 1) for i in range(cols)]
-    elif len(header) != cols:
-        raise ValueError("%s: a header of %d names for %d columns" % (who, len(header), cols))
-    if mask is not None:  # the meta columns leave the table before anything is checked as a count and return prepared, at its end
-        data, header, meta_data, meta_header = _split_meta(who, data, mask, list(header), test_name)
-        make_onehot = False  # (numbers: nothing to encode)
-        extra = _extra_tables(who, data, extra_data, test_name, True, n_named=cols)
-    return _normalize_tables(data, list(header), extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device)[0]
+    # this entry point's rules of the table stage: an engine.CSC tuple is a sparse table, and a header always has the table's length
+    t = _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec, device_normalize,
+                        normalize=True, csc_tuple_is_sparse=True, strict_header=True)
+    return _normalize_tables(t.data, list(t.header), t.extra, test_name, t.meta_data, t.meta_header, t.make_onehot, prec, device_normalize,
+                             device)[0]
 
 
 def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
@@ -399,156 +564,36 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
     if prec not in (32, 64):
         raise ValueError("learn_network: prec=%r is not supported (32 or 64; the reference's 16 and 128 are not served)" % (prec,))
-    import time
-    paths = [data] if _is_path(data) else list(data) if (isinstance(data, (list, tuple)) and len(data) and all(_is_path(q) for q in data)) else None
-    if paths is None:
-        if meta_data_path is not None:
-            raise ValueError("learn_network: meta_data_path goes with a data path (learn_network(data_path, meta_data_path)); with an "
-                             "array pass meta_data")
-        if transposed:
-            raise ValueError("learn_network: transposed=True is served for the path form; pass the transposed array")
-    else:
-        if not (meta_data_path is None or _is_path(meta_data_path)):
-            raise TypeError("learn_network: meta_data_path must be a path, got %s (options are keywords)" % type(meta_data_path).__name__)
-        if header is not None or meta_data is not None or meta_header is not None:
-            raise ValueError("learn_network: header, meta_data and meta_header come from the files in the path form")
-        if meta_mask is not None:
-            raise ValueError("learn_network: meta_mask goes with an array or a sparse matrix; in the path form the meta variables come "
-                             "from meta_data_path")
-        data, header, meta_data, meta_header, from_files = _load_paths(paths, meta_data_path, transposed)
-        extra_data = from_files + list(extra_data or []) if (from_files or extra_data is not None) else None
+    # the mode keywords as the caller passed them, before any is resolved: what the ranks of a distributed run compare
+    caller = dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=feed_forward, normalize=normalize,
+                  hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec, round_size=round_size, make_onehot=make_onehot,
+                  recursive_pcor=recursive_pcor, dense_cor=dense_cor, device_normalize=device_normalize, fast_elim=fast_elim,
+                  no_red_tests=no_red_tests, track_rejections=track_rejections, csc_resident=csc_resident)
+    data, header, meta_data, meta_header, extra_data = _path_form(data, meta_data_path, transposed, header, meta_data, meta_header, meta_mask,
+                                                                  extra_data)
     test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
     eng_prec = 64 if (prec == 64 and test_name == "fz") else 32  # the element type of the device pipeline
     dist, rank, world = _distributed_world() if distributed else (None, 0, 0)
-    sharded = world > 1  # (a world of one rank takes the ordinary path)
-    if sharded:
-        if eng_prec == 64:
-            raise ValueError("learn_network: prec=64 with distributed=True is not supported for the plain fz test: the Float64 mode has no "
-                             "sharded entry points (DESIGN.md section 7); run it on one rank or pass prec=32")
-        _distributed_input_check(dist, rank, world, device, [data if (is_sparse(data) or isinstance(data, CSC)) else np.asarray(data), meta_data, meta_header, header, meta_mask, extra_data],
-                                 dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=feed_forward,
-                                      normalize=normalize, hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec,
-                                      round_size=round_size, make_onehot=make_onehot, recursive_pcor=recursive_pcor, dense_cor=dense_cor,
-                                      device_normalize=device_normalize, fast_elim=fast_elim, no_red_tests=no_red_tests,
-                                      track_rejections=track_rejections, csc_resident=csc_resident))
-    csc_resident = bool(csc_resident)
-    if csc_resident:  # what the CSC-resident layout does not serve is refused by name, never densified
-        if test_name != "fz_nz":
-            raise ValueError("learn_network: csc_resident=True is served for sensitive=True, heterogeneous=True (fz_nz) only; the discrete "
-                             "kinds are bit-packed already and the plain fz test needs the dense matrix")
-        if not is_sparse(data):
-            raise ValueError("learn_network: csc_resident=True needs sparse data (a scipy.sparse matrix); a dense table is not "
-                             "converted silently")
-        if not recursive_pcor:
-            raise ValueError("learn_network: csc_resident=True with recursive_pcor=False is not supported: those conditional tests "
-                             "stream whole dense columns")
-    if eng_prec == 64 and not (recursive_pcor and dense_cor):
-        raise ValueError("learn_network: prec=64 with %s is not supported: the Float64 path conditions on the resident Float64 "
-                         "Pearson matrix (recursive_pcor=True, dense_cor=True)"
-                         % ("recursive_pcor=False" if not recursive_pcor else "dense_cor=False"))
-    if test_name != "fz":
-        dense_cor = True  # (learning.jl:42: only the plain fz test ever builds a matrix; the engine takes the flag for fz alone)
-    elif not dense_cor and recursive_pcor:
-        import warnings
-        warnings.warn("learn_network: dense_cor=False leaves no correlation matrix for recursive partial correlations; "
-                      "running with recursive_pcor=False (conditional tests from the data)", stacklevel=2)
-        recursive_pcor = False
-    sparse = is_sparse(data)
-    data = data if sparse else np.asarray(data)
-    mask = _meta_mask_vector("learn_network", meta_mask, meta_data, data)
-    if sparse:
-        # a sparse table stays sparse from here to the device (fw_normalize_counts_csc, fw_set_data_csc_*); what would need the dense
-        # matrix is refused by name before any device call -- densifying silently would defeat the point
-        _sparse_refusals("learn_network", test_name, normalize, prec, device_normalize, meta_data)
-    n_marked = 0 if mask is None else int(mask.sum())
-    if mask is not None and header is not None and len(header) != _shape(data)[1]:
-        raise ValueError("learn_network: a header of %d names for %d columns: with a meta_mask the header names all columns of data, "
-                         "the meta ones included" % (len(header), _shape(data)[1]))
-    if mask is None or not normalize:
-        data = _canonical_csc("learn_network", data, test_name, normalize) if sparse else data
-        if mask is not None:  # the prepared matrix is taken as it is; its marked columns are only looked at
-            _finite_meta("learn_network", pre._csc_take_cols(*data[:3], np.nonzero(mask)[0])[2] if sparse else data[:, mask])
-        extra = _extra_tables("learn_network", data, extra_data, test_name, normalize)  # (refused by name before any device call)
-        if header is None:
-            header = ["X%d" % (i + 1) for i in range(_shape(data)[1])]
-    else:
-        # normalize=True: the meta columns leave the table before anything is checked as a count -- a continuous covariate is no
-        # count -- and come back prepared, at its end (preprocessing.jl:425-446,527-558); from here on they are a numeric meta_data
-        cols = _shape(data)[1]
-        data, header, meta_data, meta_header = _split_meta("learn_network", data, mask, list(header) if header is not None else
-                                                           ["X%d" % (i + 1) for i in range(cols)], test_name)
-        make_onehot = False  # (numbers: nothing to encode)
-        extra = _extra_tables("learn_network", data, extra_data, test_name, normalize, n_named=cols)
-    meta_mask = None if mask is None else [bool(v) for v in mask]  # (normalize=False keeps it; normalize=True returns its own)
+    if world > 1:  # a sharded run (a world of one rank takes the ordinary path): its refusals first, the same on every rank
+        _distributed_input_check(dist, rank, world, eng_prec, device, (data, meta_data, meta_header, header, meta_mask, extra_data), caller)
+    csc_resident, recursive_pcor, dense_cor = _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense_cor)
+    # this entry point's rules of the table stage: an engine.CSC tuple is no sparse table here, and without a mask a header of
+    # another length than the table passes (zip truncates)
+    t = _prepare_tables("learn_network", data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec,
+                        device_normalize, normalize=normalize, csc_tuple_is_sparse=False, strict_header=False)
     if meta_data is not None and not normalize:
         # the reference appends the meta columns as they are and keeps their mask (learning.jl:500-520); here an already
         # normalised matrix must already hold them -- silently dropping the argument would lose the mask
         raise ValueError("learn_network: meta_data with normalize=False is not supported: append the prepared meta columns to "
                          "`data` yourself (preprocess.normalize_with_meta) and mark them with meta_mask, or pass normalize=True")
-    t_norm0 = time.perf_counter()
-    on_device = False
-    if normalize:
-        r, on_device = _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device)
-        mat, header = r["data"], r["header"]
-        meta_mask = [bool(v) for v in r["meta_mask"]]
-    elif extra:
-        # already normalised tables are only laid side by side (learning.jl:537-541): no filter, no alignment, extra tables first
-        everyone = np.ones(_shape(data)[0], dtype=bool)
-        mat, header, combined_mask, _ = pre.combine_data([t for t, _ in extra] + [data], [h for _, h in extra] + [header],
-                                                         [None] * len(extra) + [mask], [everyone] * (len(extra) + 1))
-        meta_mask = None if mask is None else [bool(v) for v in combined_mask]
-    elif sparse:
-        mat = tuple(data[:3])  # the prepared matrix as it is: Int32 CSC for mi / mi_nz, Float32 CSC for fz_nz
-    else:
-        mat = data
-    t_norm = time.perf_counter() - t_norm0
-    n, p = data[3] if isinstance(mat, tuple) else mat.shape
-    if round_size is None:
-        round_size = default_round_size(p)
-    eng = Engine(test_name, n, p, max_k=max_k, alpha=alpha, hps=hps, n_obs_min=n_obs_min, max_tests=max_tests, FDR=FDR,
-                 device=device, recursive_pcor=recursive_pcor, dense_cor=dense_cor, prec=eng_prec)
-    try:
-        # (what the device front-end returned is canonical already: its triple goes up as it is, stored 0.0f of clr_nz included)
-        eng.set_data((mat.indptr, mat.indices, mat.data) if is_sparse(mat) else mat, csc_resident=csc_resident)
-        if test_name == "fz" and dense_cor:
-            eng.compute_cor()  # (replicated in a distributed run: row-block sharding stays an Engine-level tool, dist.sharded_cor)
-        gathered = None
-        if sharded:
-            import torch
-            from .dist import make_dev_exchange
-            from .engine import rejections_dict
-            xchg = make_dev_exchange(dist, torch.device("cuda", device))
-            if test_name in ("mi", "mi_nz"):
-                eng.level0_dev(rank, world, xchg)  # this rank's share of the pair tiles
-            else:
-                eng.level0()  # the Fisher-z kinds stay replicated (include/flashweave_amd.h)
-            net = eng.lgl(feed_forward=feed_forward, round_size=round_size, rank=rank, world_size=world, dev_exchange=xchg,
-                          fast_elim=fast_elim, no_red_tests=no_red_tests, track_rejections=track_rejections)
-            if track_rejections:  # every rank holds its own targets' records: all of them everywhere
-                gathered = eng.gather_rejections(xchg)
-                net["rejections"] = rejections_dict(eng.rejection_records())
-        else:
-            net = eng.lgl(feed_forward=feed_forward, round_size=round_size, fast_elim=fast_elim, no_red_tests=no_red_tests,
-                          track_rejections=track_rejections)
-        counters = eng.counters()
-        counters["world_size"], counters["rank"] = max(world, 1), rank
-        for k in ("packed_host", "packed_dev", "received"):  # the log gather of a distributed run (None: there was none)
-            counters["rejections_" + k] = None if gathered is None else gathered[k]
-        counters["data_resident_bytes"] = eng.data_resident_bytes() if (test_name == "fz_nz" and hasattr(eng.L, "fw_data_resident_bytes")) else None
-    finally:
-        eng.close()
-    counters["t_normalize_s"] = t_norm
-    counters["normalized_on_device"] = on_device
-    counters["sparse_input"] = sparse
-    counters["n_tables"] = 1 + len(extra)
-    counters["csc_resident"] = csc_resident
-    return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header),
-                    parameters=dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha,
-                                    feed_forward=feed_forward, test_name=test_name, round_size=round_size,
-                                    recursive_pcor=recursive_pcor, dense_cor=dense_cor, fast_elim=bool(fast_elim),
-                                    no_red_tests=bool(no_red_tests), track_rejections=bool(track_rejections), prec=eng_prec,
-                                    csc_resident=csc_resident, extra_data=len(extra), meta_mask=n_marked, distributed=world,
-                                    schedule=("single_il (one target per round: the reference's deterministic schedule)" if round_size == 1
-                                              else "one round (parallel=\"single\": no whitelists)" if (round_size == 0 or not feed_forward or round_size >= p)
-                                              else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)),
+    mat, header, meta_mask, on_device, t_norm = _matrix(t, test_name, normalize, prec, device_normalize, device)
+    n, p = t.data[3] if isinstance(mat, tuple) else mat.shape
+    run = dict(caller, device=device, test_name=test_name, prec=eng_prec, csc_resident=csc_resident, recursive_pcor=recursive_pcor,
+               dense_cor=dense_cor, round_size=default_round_size(p) if round_size is None else round_size)
+    net, counters = _run_engine(mat, n, p, run, dist, rank, world)
+    counters.update(t_normalize_s=t_norm, normalized_on_device=on_device, sparse_input=t.sparse, n_tables=1 + len(t.extra),
+                    csc_resident=csc_resident)
+    parameters = {k: bool(run[k]) if k in ("fast_elim", "no_red_tests", "track_rejections") else run[k] for k in _REPORTED}
+    parameters.update(extra_data=len(t.extra), meta_mask=t.n_marked, distributed=world, schedule=_schedule(run["round_size"], feed_forward, p))
+    return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header), parameters=parameters,
                     counters=counters, rejections=net["rejections"])

@@ -13,34 +13,11 @@ import flashweave_jl_amd as fw
 from flashweave_jl_amd import io as fio
 from flashweave_jl_amd import preprocess as pre
 from flashweave_jl_amd.engine import CSC
+from tests.api_trace import _host_stand_in, _scatter  # (the host stand-in for the device front-end, shared with the call traces)
 from tests.meta_mask_table import META_NAMES, edge_kinds, oracle_network, table
 from tests.util import GOLDEN
 
 KINDS = ["fz", "fz_nz", "mi", "mi_nz"]
-
-
-def _scatter(colptr, rowval, nzval, shape):
-    """a CSC triple as a dense matrix, without scipy's toarray (test_the_split_never_densifies_the_table patches that to raise)"""
-    out = np.zeros(shape, dtype=np.asarray(nzval).dtype)
-    out[np.asarray(rowval), np.repeat(np.arange(shape[1]), np.diff(colptr))] = nzval
-    return out
-
-
-def _host_stand_in(counts, test_name, device=0):
-    """engine.normalize_counts on the host: preprocess.normalize + the CSC conversion of the device front-end -- an entry per present
-    count, so the clr_nz value 0.0f of a sample's only OTU is a STORED zero.  Sparse tables only (what the tests below hand it)."""
-    assert isinstance(counts, CSC) and counts.nzval.dtype == np.int32, "the OTU block must arrive as canonical Int32 counts"
-    dense = _scatter(*counts)
-    data, row_mask, col_mask = pre.normalize(dense, test_name)
-    if test_name == "fz":
-        return data, row_mask, col_mask
-    data = data.astype(np.float32 if test_name == "fz_nz" else np.int32)
-    present = dense[row_mask][:, col_mask] != 0 if test_name == "fz_nz" else data != 0
-    cols, rows = np.nonzero(present.T)
-    out = sp.csc_matrix(data.shape, dtype=data.dtype)
-    out.indptr = np.concatenate(([0], np.cumsum(np.bincount(cols, minlength=data.shape[1])))).astype(np.int32)
-    out.indices, out.data = rows.astype(np.int32), data[rows, cols]
-    return out, row_mask, col_mask
 
 
 def _no_device(monkeypatch):
