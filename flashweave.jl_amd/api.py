@@ -10,7 +10,7 @@ import numpy as np
 
 from . import io as fio
 from . import preprocess as pre
-from .engine import CSC, Engine, as_csc, is_sparse, normalize_counts, rejections_dict
+from .engine import CSC, Engine, abundance_defect, as_csc, is_sparse, normalize_abundances, normalize_counts, rejections_dict
 
 
 class FWResult(dict):
@@ -114,7 +114,12 @@ def _sparse_refusals(who, test_name, normalize, prec, device_normalize, meta_dat
                          "the plain fz test needs the dense matrix, pass one" % who)
 
 
-def _canonical_csc(who, data, test_name, normalize):
+def _canonical_csc(who, data, test_name, normalize, abundances=False):
+    if abundances and normalize:  # real values: nothing is checked as a count (the values themselves: _abundance_refusals)
+        try:
+            return as_csc(data, np.float64)
+        except ValueError as e:
+            raise ValueError("%s: abundances=True: sparse data needs real values (%s)" % (who, e)) from None
     try:
         return as_csc(data, np.int32 if (normalize or test_name in ("mi", "mi_nz")) else np.float32)
     except ValueError as e:
@@ -165,7 +170,7 @@ def _csc_arrays(data):
     return m.indptr, m.indices, m.data, tuple(int(v) for v in m.shape)
 
 
-def _split_meta(who, data, mask, header, test_name):
+def _split_meta(who, data, mask, header, test_name, abundances=False):
     """The table of a normalising run under its meta_mask -> (OTU block, its header, meta block, its header), before anything is checked
     as a count: the unmarked columns are the count table (a sparse one canonical, _canonical_csc), the marked ones a dense Float64
     samples x meta-variables matrix (a continuous covariate is not a count).  A sparse table is split on its CSC arrays, O(nnz); only
@@ -177,13 +182,13 @@ def _split_meta(who, data, mask, header, test_name):
         return data[:, ~mask], otu_header, meta.astype(np.float64), meta_header
     colptr, rowval, nzval, (n, p) = _csc_arrays(data)
     q = int(mask.sum())
-    otu = _canonical_csc(who, pre._csc_take_cols(colptr, rowval, nzval, np.nonzero(~mask)[0]) + ((n, p - q),), test_name, True)
+    otu = _canonical_csc(who, pre._csc_take_cols(colptr, rowval, nzval, np.nonzero(~mask)[0]) + ((n, p - q),), test_name, True, abundances)
     meta = as_csc(pre._csc_take_cols(colptr, rowval, nzval, np.nonzero(mask)[0]) + ((n, q),), np.float64)
     _finite_meta(who, meta.nzval)
     return otu, otu_header, pre._csc_to_dense(meta.colptr, meta.rowval, meta.nzval, n), meta_header
 
 
-def _extra_tables(who, data, extra_data, test_name, normalize, n_named=None):
+def _extra_tables(who, data, extra_data, test_name, normalize, n_named=None, abundances=False):
     """Checks learn_network's / normalize_data's extra_data against the main table (an array or what as_csc returned) before anything
     reaches a device -> [(table, header)] in the caller's order, sparse tables canonical.  A missing header is numbered on from the
     main table's columns (n_named when the meta columns have been split off `data` already), as the reference does
@@ -219,22 +224,38 @@ def _extra_tables(who, data, extra_data, test_name, normalize, n_named=None):
         elif len(hdr) != cols:
             raise ValueError("%s: extra_data[%d] has a header of %d names for %d columns" % (who, i, len(hdr), cols))
         out.append((tab, [str(h) for h in hdr]))
-    return [(_canonical_csc(who, t, test_name, normalize), h) for t, h in out] if sparse else out
+    return [(_canonical_csc(who, t, test_name, normalize, abundances), h) for t, h in out] if sparse else out
 
 
-def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device):
+def _abundance_refusals(who, data, extra):
+    """abundances=True: every table of real values (the OTU block where a meta_mask split the table) holds finite values >= 0."""
+    for name, tab in [("data", data)] + [("extra_data[%d]" % i, t) for i, (t, _) in enumerate(extra)]:
+        defect = abundance_defect(tab.nzval if isinstance(tab, CSC) else tab)
+        if defect:
+            raise ValueError("%s: abundances=True: %s holds %s; abundances are finite and >= 0" % (who, name, defect))
+
+
+def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device, abundances=False):
     """Every table through ONE front-end -- the device one when all of them are count tables it takes (sparse, or _integral) and
     prec == 32 and device_normalize, else the host one -- each on its own (its own row sums, geometric means, pseudo-counts and
-    filters), then preprocess.combine_data.  -> (dict(data, header, meta_mask, row_mask), on_device)"""
-    on_device = bool(device_normalize and prec == 32 and all(isinstance(t, CSC) or _integral(t) for t in [data] + [t for t, _ in extra]))
-    dev_norm = (lambda c, t: normalize_counts(c, t, device=device)) if on_device else None
+    filters), then preprocess.combine_data.  abundances: the tables are declared real-valued, _integral is not asked and the device
+    front-end is the Float64 one (engine.normalize_abundances).  -> (dict(data, header, meta_mask, row_mask), on_device)"""
+    on_device = bool(device_normalize and prec == 32 and
+                     (abundances or all(isinstance(t, CSC) or _integral(t) for t in [data] + [t for t, _ in extra])))
+    norm = None  # (None: the host front-end as it is)
+    if on_device and abundances:  # (a dense table is handed over as the Float64 values the front-end reads; Float32 widens exactly)
+        norm = lambda c, t: normalize_abundances(c if isinstance(c, CSC) else np.asarray(c, dtype=np.float64), t, device=device)
+    elif on_device:
+        norm = lambda c, t: normalize_counts(c, t, device=device)
+    elif abundances:  # the host front-end with the anchor rule of the Float64 device front-end (preprocess.adaptive_clr)
+        norm = lambda c, t: pre.normalize(c, t, prec=prec, tie_anchor=True)
 
     def one(tab, hdr):  # a count table on its own -> (matrix, the kept columns' names, row mask)
-        mat, row_mask, col_mask = dev_norm(tab, test_name) if on_device else pre.normalize(tab, test_name, prec=prec)
+        mat, row_mask, col_mask = norm(tab, test_name) if norm else pre.normalize(tab, test_name, prec=prec)
         return mat, [h for h, k in zip(hdr, col_mask) if k], row_mask
     if meta_data is not None:
         r = pre.normalize_with_meta(data, test_name, meta_data, prec=prec, header=header, meta_header=meta_header,
-                                    make_onehot=make_onehot, normalizer=dev_norm)
+                                    make_onehot=make_onehot, normalizer=norm)
         main = dict(data=r["data"], header=r["header"], meta_mask=np.asarray(r["meta_mask"], dtype=bool), row_mask=r["row_mask"])
     else:
         mat, hdr, row_mask = one(data, header)
@@ -312,12 +333,13 @@ _Tables = namedtuple("_Tables", "data header meta_data meta_header make_onehot e
 
 
 def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec, device_normalize,
-                    normalize, csc_tuple_is_sparse, strict_header):
+                    normalize, csc_tuple_is_sparse, strict_header, abundances=False):
     """The table stage of both entry points, everything before a front-end or a device sees a table: sparse or dense, the mask vector,
     the sparse refusals, the canonical CSC form, the header, the meta columns split off (normalize=True) or only looked at (a prepared
     matrix keeps them and its mask), the extra tables.  The entry points differ in two rules, which they pass: csc_tuple_is_sparse
     (is an engine.CSC tuple a sparse table?) and strict_header (is a header of another length than the table refused without a mask
-    as well?).  -> _Tables; header is the caller's object when one was given and nothing was split off."""
+    as well?).  abundances (with normalize): a sparse block is made canonical as Float64 instead of as counts, and the value refusals
+    come last.  -> _Tables; header is the caller's object when one was given and nothing was split off."""
     sparse = _any_sparse(data) if csc_tuple_is_sparse else is_sparse(data)
     data = data if sparse else np.asarray(data)
     mask = _meta_mask_vector(who, meta_mask, meta_data, data)
@@ -329,10 +351,10 @@ def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extr
         raise ValueError("%s: a header of %d names for %d columns%s" % (who, len(header), _shape(data)[1], "" if strict_header else
                          ": with a meta_mask the header names all columns of data, the meta ones included"))
     if mask is None or not normalize:
-        data = _canonical_csc(who, data, test_name, normalize) if sparse else data
+        data = _canonical_csc(who, data, test_name, normalize, abundances) if sparse else data
         if mask is not None:  # the prepared matrix is taken as it is; its marked columns are only looked at
             _finite_meta(who, pre._csc_take_cols(*data[:3], np.nonzero(mask)[0])[2] if sparse else data[:, mask])
-        extra = _extra_tables(who, data, extra_data, test_name, normalize)  # (refused by name before any device call)
+        extra = _extra_tables(who, data, extra_data, test_name, normalize, abundances=abundances)  # (refused by name before any device call)
         if header is None:  # after the extra tables: a call with a bad header AND a bad extra table is told about the table
             header = _default_header(_shape(data)[1])
         elif strict_header and len(header) != _shape(data)[1]:
@@ -341,9 +363,12 @@ def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extr
         # normalize=True: the meta columns leave the table before anything is checked as a count -- a continuous covariate is no
         # count -- and come back prepared, at its end (preprocessing.jl:425-446,527-558); from here on they are a numeric meta_data
         cols = _shape(data)[1]
-        data, header, meta_data, meta_header = _split_meta(who, data, mask, _default_header(cols) if header is None else list(header), test_name)
+        data, header, meta_data, meta_header = _split_meta(who, data, mask, _default_header(cols) if header is None else list(header), test_name,
+                                                              abundances)
         make_onehot = False  # (numbers: nothing to encode)
-        extra = _extra_tables(who, data, extra_data, test_name, normalize, n_named=cols)
+        extra = _extra_tables(who, data, extra_data, test_name, normalize, n_named=cols, abundances=abundances)
+    if abundances and normalize:
+        _abundance_refusals(who, data, extra)
     return _Tables(data, header, meta_data, meta_header, make_onehot, extra, mask, sparse, 0 if mask is None else int(mask.sum()))
 
 
@@ -375,7 +400,7 @@ def _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense
     return csc_resident, recursive_pcor, dense_cor
 
 
-def _matrix(t, test_name, normalize, prec, device_normalize, device):
+def _matrix(t, test_name, normalize, prec, device_normalize, device, abundances=False):
     """The prepared tables (_Tables) -> (matrix for the engine, header, meta mask as a list or None, normalised on the device?,
     seconds): normalised and combined (normalize=True), prepared tables laid side by side, or the prepared matrix as it is.  The
     seconds are counters["t_normalize_s"]: this step alone."""
@@ -383,7 +408,7 @@ def _matrix(t, test_name, normalize, prec, device_normalize, device):
     header, on_device, t0 = t.header, False, time.perf_counter()
     if normalize:
         r, on_device = _normalize_tables(t.data, t.header, t.extra, test_name, t.meta_data, t.meta_header, t.make_onehot, prec,
-                                         device_normalize, device)
+                                         device_normalize, device, abundances)
         mat, header, meta_mask = r["data"], r["header"], [bool(v) for v in r["meta_mask"]]
     elif t.extra:
         # already normalised tables are only laid side by side (learning.jl:537-541): no filter, no alignment, extra tables first
@@ -448,7 +473,7 @@ def _schedule(round_size, feed_forward, p):
 
 
 def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
-                   device_normalize=True, device=0, meta_mask=None):
+                   device_normalize=True, device=0, meta_mask=None, abundances=False):
     """normalize_data (preprocessing.jl:660-701), both forms: what learn_network(normalize=True) does to its tables, as a function of
     its own.  data: samples x OTUs counts (array or scipy.sparse); extra_data: a list of (table, header) pairs, count tables of further
     sequencing experiments on the same samples.  Every table is normalised on its own for `test_name` ("fz" clr_adapt, "fz_nz" clr_nz,
@@ -459,6 +484,9 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
     meta_mask: one boolean (or 0 / 1) per column of `data`, True marking a meta variable that sits inside the table, dense or sparse
     (see learn_network): the unmarked columns are normalised as the count table, the marked ones prepared like a numeric meta_data
     and appended last; `header` names all columns.
+    abundances=True declares the tables real-valued (see learn_network): every table, dense or sparse, takes the Float64 device
+    front-end when device_normalize and prec == 32; a NaN, an infinite or a negative value raises ValueError naming abundances and the
+    table.
     -> dict(data, header, meta_mask, row_mask): row_mask over the input samples, data a scipy.sparse.csc_matrix for sparse tables
     (dense for "fz")."""
     who = "normalize_data"
@@ -468,16 +496,16 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
         raise ValueError("%s: prec=%r is not supported (32 or 64)" % (who, prec))
     # this entry point's rules of the table stage: an engine.CSC tuple is a sparse table, and a header always has the table's length
     t = _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec, device_normalize,
-                        normalize=True, csc_tuple_is_sparse=True, strict_header=True)
+                        normalize=True, csc_tuple_is_sparse=True, strict_header=True, abundances=bool(abundances))
     return _normalize_tables(t.data, list(t.header), t.extra, test_name, t.meta_data, t.meta_header, t.make_onehot, prec, device_normalize,
-                             device)[0]
+                             device, bool(abundances))[0]
 
 
 def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
                   header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, round_size=None, device=0,
                   meta_data=None, meta_header=None, make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True,
                   no_red_tests=True, track_rejections=False, csc_resident=False, extra_data=None, transposed=False, meta_mask=None, distributed=False,
-                  **unsupported):
+                  abundances=False, **unsupported):
     """data: samples x OTUs count matrix (or an already normalised matrix with normalize=False); a numpy array or a scipy.sparse
     matrix.  A sparse table stays sparse end to end (what the reference does with make_sparse, learning.jl:470): normalize=True runs
     the device CSC front-end (integer counts only) and the sparse upload, normalize=False uploads the matrix as it is (Int32 levels
@@ -555,6 +583,15 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     prec=64 with the plain fz test is refused (ValueError naming prec=64 and distributed): the Float64 mode has no sharded entry points.
     parameters["distributed"] records the world size (0 when off), counters["world_size"] and counters["rank"] the rank's place; the
     other counters are the rank's own.
+    abundances (default False): True declares the tables real-valued -- relative abundances, percentages, coverage-normalised counts,
+    counts beyond 2^31 - 1 -- as the reference normalises any Real matrix (adaptive_pseudocount!: a smallest abundance below 1 sets the
+    floor at a tenth of it).  Every table -- the main one, each of extra_data, the OTU block under a meta_mask -- then takes the Float64
+    device front-end (engine.normalize_abundances) when device_normalize and prec == 32, dense or sparse; whether a table is integral
+    is not asked, and a sparse block is made canonical as Float64.  A dense table with device_normalize=False or prec=64 goes to the
+    host front-end, a sparse one keeps its refusals.  abundances=True with normalize=False (nothing to normalise) and a NaN, an
+    infinite or a negative value in a table (named: data or extra_data[i]) raise ValueError naming abundances before any device call.
+    Without the option a real-valued dense table goes to the host front-end and a sparse one is refused, as before.
+    parameters["abundances"] is there (True) only when the option is on.
     Path form (learning.jl:354-401): data may be a path (str / os.PathLike) or a list of paths, read with io.load_data (.tsv, .csv,
     BIOM 1.0 JSON; anything else raises what load_data raises): the first is the main table, the others become extra_data under their
     file headers; meta_data_path (second positional argument, as in the reference) is the main table's meta data file;
@@ -564,11 +601,12 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
     if prec not in (32, 64):
         raise ValueError("learn_network: prec=%r is not supported (32 or 64; the reference's 16 and 128 are not served)" % (prec,))
+    abundances = bool(abundances)  # (before the digest: ranks passing 1 and True make the same run)
     # the mode keywords as the caller passed them, before any is resolved: what the ranks of a distributed run compare
     caller = dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=feed_forward, normalize=normalize,
                   hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec, round_size=round_size, make_onehot=make_onehot,
                   recursive_pcor=recursive_pcor, dense_cor=dense_cor, device_normalize=device_normalize, fast_elim=fast_elim,
-                  no_red_tests=no_red_tests, track_rejections=track_rejections, csc_resident=csc_resident)
+                  no_red_tests=no_red_tests, track_rejections=track_rejections, csc_resident=csc_resident, abundances=abundances)
     data, header, meta_data, meta_header, extra_data = _path_form(data, meta_data_path, transposed, header, meta_data, meta_header, meta_mask,
                                                                   extra_data)
     test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
@@ -579,14 +617,17 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     csc_resident, recursive_pcor, dense_cor = _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense_cor)
     # this entry point's rules of the table stage: an engine.CSC tuple is no sparse table here, and without a mask a header of
     # another length than the table passes (zip truncates)
+    if abundances and not normalize:
+        raise ValueError("learn_network: abundances=True with normalize=False is not supported: the option chooses the front-end of a "
+                         "table that is normalised here, and a prepared matrix has nothing left to normalise")
     t = _prepare_tables("learn_network", data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec,
-                        device_normalize, normalize=normalize, csc_tuple_is_sparse=False, strict_header=False)
+                        device_normalize, normalize=normalize, csc_tuple_is_sparse=False, strict_header=False, abundances=abundances)
     if meta_data is not None and not normalize:
         # the reference appends the meta columns as they are and keeps their mask (learning.jl:500-520); here an already
         # normalised matrix must already hold them -- silently dropping the argument would lose the mask
         raise ValueError("learn_network: meta_data with normalize=False is not supported: append the prepared meta columns to "
                          "`data` yourself (preprocess.normalize_with_meta) and mark them with meta_mask, or pass normalize=True")
-    mat, header, meta_mask, on_device, t_norm = _matrix(t, test_name, normalize, prec, device_normalize, device)
+    mat, header, meta_mask, on_device, t_norm = _matrix(t, test_name, normalize, prec, device_normalize, device, abundances)
     n, p = t.data[3] if isinstance(mat, tuple) else mat.shape
     run = dict(caller, device=device, test_name=test_name, prec=eng_prec, csc_resident=csc_resident, recursive_pcor=recursive_pcor,
                dense_cor=dense_cor, round_size=default_round_size(p) if round_size is None else round_size)
@@ -595,5 +636,7 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
                     csc_resident=csc_resident)
     parameters = {k: bool(run[k]) if k in ("fast_elim", "no_red_tests", "track_rejections") else run[k] for k in _REPORTED}
     parameters.update(extra_data=len(t.extra), meta_mask=t.n_marked, distributed=world, schedule=_schedule(run["round_size"], feed_forward, p))
+    if abundances:
+        parameters["abundances"] = True
     return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header), parameters=parameters,
                     counters=counters, rejections=net["rejections"])

@@ -13,7 +13,8 @@ enum {
     FW_CSC_BAD_ROW = 2,     // row < 0 or row >= n
     FW_CSC_UNSORTED = 4,    // row <= its predecessor in the column (unsorted or duplicate)
     FW_CSC_ZERO = 8,        // stored zero where counts are expected
-    FW_CSC_NEGATIVE = 16    // negative count
+    FW_CSC_NEGATIVE = 16,   // negative count
+    FW_CSC_NONFINITE = 32   // NaN or +-Inf where real values are expected
 };
 
 __device__ inline int fw_wave_or(int v)
@@ -48,6 +49,7 @@ inline const char *fw_csc_reason(int flags)
     if (flags & FW_CSC_BAD_COLPTR) return "colptr is not monotone within 0 .. nnz";
     if (flags & FW_CSC_BAD_ROW) return "a row index lies outside 0 .. n-1";
     if (flags & FW_CSC_UNSORTED) return "rows are not strictly ascending (unsorted or duplicate)";
+    if (flags & FW_CSC_NONFINITE) return "non-finite value (NaN or Inf)";
     if (flags & FW_CSC_NEGATIVE) return "negative count";
     if (flags & FW_CSC_ZERO) return "stored zero";
     return "invalid";

@@ -11,6 +11,10 @@
 // (convert_to_target_prec with prec = 32).  Layout: n samples x p variables, column-major, as Julia holds it; one thread
 // per sample row and column chunk (adjacent lanes = adjacent samples: coalesced), chunk partials reduced in a fixed order.
 // HBM-bound elementwise work: 4 B read per count and pass (3 passes) + 4 B written.
+// Value type: every kernel that reads the table is a template over V = int32_t (counts: fw_normalize_counts*, the instantiation
+// that runs for them as before) or double (real-valued tables: fw_normalize_abund*, 8 B read per cell and pass).  Both
+// instantiations take the same expressions in the same order -- (double)v is the identity for V = double -- so a table of
+// integers gives the same bits through either.
 #include <cmath>
 #include <vector>
 
@@ -23,15 +27,34 @@ namespace {
 
 #define NORM_CHUNKS 64
 
+// What the value type is more than a type name for: the identities of min / max, the value check (a count is good when it is
+// >= 0; a real value when it is >= 0 and finite -- anything else reads as -1, so that the one "smallest value < 0" test of the
+// host refuses both; -0.0 is >= 0 and == 0: a zero), the words of the refusal, and which row sums count as equal (norm_row_params).
+template <typename V> struct NormVal;
+template <> struct NormVal<int32_t> {
+    __host__ __device__ static int32_t vmax() { return 0x7fffffff; }
+    __host__ __device__ static int32_t vmin() { return (int32_t)0x80000000; }
+    __device__ static int32_t checked(int32_t v) { return v; }
+    static const char *bad() { return "negative count"; }
+    static double tie_rel(int) { return 0.0; }
+};
+template <> struct NormVal<double> {
+    __host__ __device__ static double vmax() { return INFINITY; }
+    __host__ __device__ static double vmin() { return -INFINITY; }
+    __device__ static double checked(double v) { return (v >= 0.0 && v <= 1.7976931348623157e308) ? v : -1.0; }
+    static const char *bad() { return "negative or non-finite (NaN, Inf) value"; }
+    static double tie_rel(int pk) { return (double)pk * 0x1p-52; }
+};
+
 // per column: min and max over the samples (variance > 0 <=> min != max)
-__global__ __launch_bounds__(256) void norm_col_minmax_kernel(const int32_t *__restrict__ x, int n, int p, int32_t *__restrict__ cmin,
-                                                              int32_t *__restrict__ cmax)
+template <typename V>
+__global__ __launch_bounds__(256) void norm_col_minmax_kernel(const V *__restrict__ x, int n, int p, V *__restrict__ cmin, V *__restrict__ cmax)
 {
-    __shared__ int32_t s_lo[256], s_hi[256];
+    __shared__ V s_lo[256], s_hi[256];
     const int j = blockIdx.x;
-    int32_t lo = 0x7fffffff, hi = (int32_t)0x80000000;
+    V lo = NormVal<V>::vmax(), hi = NormVal<V>::vmin();
     for (int i = threadIdx.x; i < n; i += 256) {
-        const int32_t v = x[(size_t)j * n + i];
+        const V v = NormVal<V>::checked(x[(size_t)j * n + i]);
         lo = v < lo ? v : lo;
         hi = v > hi ? v : hi;
     }
@@ -52,9 +75,10 @@ __global__ __launch_bounds__(256) void norm_col_minmax_kernel(const int32_t *__r
 }
 
 // per (row, column chunk) over the kept columns: read sum, number of zeros, sum of log over the non-zeros, smallest non-zero
-__global__ __launch_bounds__(256) void norm_row_stats_kernel(const int32_t *__restrict__ x, int n, const int32_t *__restrict__ cols, int pk,
+template <typename V>
+__global__ __launch_bounds__(256) void norm_row_stats_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ cols, int pk,
                                                              double *__restrict__ rsum, int32_t *__restrict__ rzero,
-                                                             double *__restrict__ rlog, int32_t *__restrict__ rmin)
+                                                             double *__restrict__ rlog, V *__restrict__ rmin)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -62,9 +86,10 @@ __global__ __launch_bounds__(256) void norm_row_stats_kernel(const int32_t *__re
     const int per = (pk + NORM_CHUNKS - 1) / NORM_CHUNKS;
     const int j0 = c * per, j1 = (j0 + per) < pk ? (j0 + per) : pk;
     double s = 0.0, sl = 0.0;
-    int nz = 0, mn = 0x7fffffff;
+    int nz = 0;
+    V mn = NormVal<V>::vmax();
     for (int q = j0; q < j1; ++q) {
-        const int32_t v = x[(size_t)cols[q] * n + i];
+        const V v = x[(size_t)cols[q] * n + i];
         s += (double)v;
         if (v == 0) {
             ++nz;
@@ -82,14 +107,15 @@ __global__ __launch_bounds__(256) void norm_row_stats_kernel(const int32_t *__re
 // out[r][q] for kept rows r and kept columns q (column-major n_out x p_out)
 //   mode 0 (clr_adapt): log(x' / g_r), x' = x or the row's pseudo-count, g_r = exp(mean log x')
 //   mode 1 (clr_nz):    x == 0 ? 0 : log(x / g_r), g_r = exp(mean log of the non-zeros)
-__global__ __launch_bounds__(256) void norm_clr_out_kernel(const int32_t *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
+template <typename V>
+__global__ __launch_bounds__(256) void norm_clr_out_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
                                                            const int32_t *__restrict__ cols, int pk, const double *__restrict__ pseudo,
                                                            const double *__restrict__ gmean, int mode, float *__restrict__ out)
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= nk) return;
     for (int q = blockIdx.y; q < pk; q += gridDim.y) {  // (grid.y is capped at NORM_GRID_Y: tables with more kept columns loop)
-        const int32_t v = x[(size_t)cols[q] * n + rows[r]];
+        const V v = x[(size_t)cols[q] * n + rows[r]];
         double o;
         if (mode == 0)
             o = log((v == 0 ? pseudo[r] : (double)v) / gmean[r]);
@@ -99,7 +125,8 @@ __global__ __launch_bounds__(256) void norm_clr_out_kernel(const int32_t *__rest
     }
 }
 
-__global__ __launch_bounds__(256) void norm_binary_out_kernel(const int32_t *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
+template <typename V>
+__global__ __launch_bounds__(256) void norm_binary_out_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
                                                               const int32_t *__restrict__ cols, int pk, int32_t *__restrict__ out)
 {
     const int r = blockIdx.x * 256 + threadIdx.x;
@@ -108,7 +135,8 @@ __global__ __launch_bounds__(256) void norm_binary_out_kernel(const int32_t *__r
 }
 
 // per kept column over the kept rows: does it hold both a zero and a non-zero?
-__global__ __launch_bounds__(256) void norm_col_levels_kernel(const int32_t *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
+template <typename V>
+__global__ __launch_bounds__(256) void norm_col_levels_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
                                                               const int32_t *__restrict__ cols, int pk, int32_t *__restrict__ two)
 {
     __shared__ int s_z, s_nz;
@@ -117,7 +145,7 @@ __global__ __launch_bounds__(256) void norm_col_levels_kernel(const int32_t *__r
     __syncthreads();
     int z = 0, nzz = 0;
     for (int r = threadIdx.x; r < nk; r += 256) {
-        const int32_t v = x[(size_t)cols[q] * n + rows[r]];
+        const V v = x[(size_t)cols[q] * n + rows[r]];
         z |= v == 0;
         nzz |= v != 0;
     }
@@ -223,7 +251,8 @@ __device__ inline int nb_bin(const NbKeys &K, int m, double rmax, double c)
     return (int)floor((rank / rmax) / step) + 1;
 }
 
-__global__ __launch_bounds__(1024) void norm_binned_kernel(const int32_t *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
+template <typename V>
+__global__ __launch_bounds__(1024) void norm_binned_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
                                                            const int32_t *__restrict__ cols, int pk, const double *__restrict__ gmean,
                                                            int32_t *__restrict__ out, int32_t *__restrict__ two, int M, double *gkeys)
 {
@@ -232,12 +261,12 @@ __global__ __launch_bounds__(1024) void norm_binned_kernel(const int32_t *__rest
     const int tid = threadIdx.x;
     const NbKeys K{gkeys ? gkeys + (size_t)blockIdx.x * (size_t)M : s_key_lds, gkeys != nullptr};
   for (int q = blockIdx.x; q < pk; q += gridDim.x) {
-    const int32_t *col = x + (size_t)cols[q] * n;
+    const V *col = x + (size_t)cols[q] * n;
     __syncthreads();  // (the previous column's last readers of the keys / s_b1 / s_b2)
     if (tid == 0) s_cnt = s_b1 = s_b2 = 0;
     __syncthreads();
     for (int r = tid; r < nk; r += 1024) {
-        const int32_t v = col[rows[r]];
+        const V v = col[rows[r]];
         if (v != 0) K.st(atomicAdd(&s_cnt, 1), log((double)v / gmean[r]));  // order does not matter: sorted below
     }
     K.sync();
@@ -246,7 +275,7 @@ __global__ __launch_bounds__(1024) void norm_binned_kernel(const int32_t *__rest
     const double rmax = nb_rank_max(K, m);
     int b1 = 0, b2 = 0;
     for (int r = tid; r < nk; r += 1024) {
-        const int32_t v = col[rows[r]];
+        const V v = col[rows[r]];
         int bin = 0;
         if (v != 0) {
             bin = nb_bin(K, m, rmax, log((double)v / gmean[r]));  // the same operations as above: the same bits
@@ -284,15 +313,23 @@ __global__ __launch_bounds__(256) void norm_gather_cols_kernel(const int32_t *__
 
 // Per-row totals over the kept columns -> kept samples and their parameters, on the host (n values each; shared by the dense
 // and the CSC front-end, so that both take the same libm calls on the same bits).  S read sum, SL sum of log over the non-zeros,
-// NZ number of zeros, RMIN smallest non-zero.  rows = samples with reads; FW_FZ: adaptive pseudo-counts (a sample whose
+// NZ number of zeros, RMIN smallest non-zero (as Float64, exact for either value type).  rows = samples with reads; FW_FZ: adaptive pseudo-counts (a sample whose
 // pseudo-count underflows to 0 is dropped) and the geometric mean of the filled row; FW_FZ_NZ / FW_MI_NZ: geometric mean of the
 // non-zeros.
-int norm_row_params(const char *fn, int kind, int n, int pk, const std::vector<double> &S, const std::vector<double> &SL,
-                    const std::vector<int64_t> &NZ, const std::vector<int32_t> &RMIN, uint8_t *row_mask, std::vector<int32_t> &rows,
+// tie_rel: the anchor of the pseudo-counts is the sample of maximal depth, and in a table of relative abundances every sample has
+// the depth 1 up to the rounding of its sum, so the largest Float64 sum would be picked by the order of the additions (the dense
+// and the CSC kernel, numpy and the reference each have their own).  Samples whose sums lie within tie_rel of the largest take part
+// and the first of them is the anchor.  Real values: pk * 2^-52, the bound |fl(sum) - sum| <= (pk - 1) 2^-53 sum of any order of
+// additions, on either side.  Not order-proof at the window's edge: the largest sum carries the rounding of this order too, so a
+// sample whose true depth lies about one bound below the maximum can fall inside under one order and outside under another;
+// samples of equal true depth (the relative-abundance case) are always inside.  Counts: 0 -- their sums are exact -- which is the
+// rule "first sample of maximal sum" as before.  The host front-end has the rule as preprocess.adaptive_clr(tie_anchor=True).
+int norm_row_params(const char *fn, int kind, int n, int pk, double tie_rel, const std::vector<double> &S, const std::vector<double> &SL,
+                    const std::vector<int64_t> &NZ, const std::vector<double> &RMIN, uint8_t *row_mask, std::vector<int32_t> &rows,
                     std::vector<double> &pseudo, std::vector<double> &g)
 {
     rows.clear();
-    int32_t min_abund = 0x7fffffff;
+    double min_abund = INFINITY;
     for (int i = 0; i < n; ++i) {
         row_mask[i] = S[i] > 0.0;  // sum(data, dims=2) .> 0
         if (row_mask[i]) {
@@ -305,10 +342,15 @@ int norm_row_params(const char *fn, int kind, int n, int pk, const std::vector<d
     pseudo.assign((size_t)nk, 0.0);
     g.assign((size_t)nk, 1.0);
     if (kind == FW_FZ) {  // adaptive_pseudocount! (:157-190): row of maximal depth as the anchor
+        double smax = 0.0;
+        for (int i : rows) smax = std::max(smax, S[i]);
         int md = rows[0];
         for (int i : rows)
-            if (S[i] > S[md]) md = i;
-        const double base = min_abund >= 1 ? 1.0 : (double)min_abund / 10.0;
+            if (S[i] >= smax * (1.0 - tie_rel)) {
+                md = i;
+                break;
+            }
+        const double base = min_abund >= 1.0 ? 1.0 : min_abund / 10.0;  // (counts: always 1; abundances below 1: a tenth of the smallest)
         const double k = (double)NZ[md], P = (double)pk, Nprod1 = SL[md];
         std::vector<int32_t> rows2;
         std::vector<double> ps2;
@@ -343,36 +385,41 @@ int norm_row_params(const char *fn, int kind, int n, int pk, const std::vector<d
 
 }  // namespace
 
-extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *counts, float *out_f32,
-                                   int32_t *out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
+namespace {
+
+// The dense front-end for either value type (fn: the entry point's name, for the messages).
+template <typename V>
+int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const V *counts, float *out_f32, int32_t *out_i32,
+               uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
 {
     if (!counts || !row_mask || !col_mask || !n_out || !p_out || n <= 0 || p <= 0)
-        return fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: invalid argument");
+        return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
     if (kind != FW_FZ && kind != FW_FZ_NZ && kind != FW_MI && kind != FW_MI_NZ)
-        return fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: unknown kind %d", kind);
+        return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
     const bool discrete = kind == FW_MI || kind == FW_MI_NZ;
-    if (discrete ? !out_i32 : !out_f32) return fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: missing output buffer");
+    if (discrete ? !out_i32 : !out_f32) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
     int rc = FW_OK;
-    int32_t *d_x = nullptr, *d_cmin = nullptr, *d_cmax = nullptr, *d_cols = nullptr, *d_rows = nullptr, *d_rzero = nullptr, *d_rmin = nullptr,
-            *d_two = nullptr, *d_oi = nullptr, *d_tmp = nullptr, *d_sel = nullptr;
+    V *d_x = nullptr, *d_cmin = nullptr, *d_cmax = nullptr, *d_rmin = nullptr;
+    int32_t *d_cols = nullptr, *d_rows = nullptr, *d_rzero = nullptr, *d_two = nullptr, *d_oi = nullptr, *d_tmp = nullptr, *d_sel = nullptr;
     double *d_rsum = nullptr, *d_rlog = nullptr, *d_pseudo = nullptr, *d_g = nullptr, *d_keys = nullptr;
     float *d_of = nullptr;
-    std::vector<int32_t> cmin((size_t)p), cmax((size_t)p), cols, rows, rzero, rmin;
+    std::vector<V> cmin((size_t)p), cmax((size_t)p), rmin;
+    std::vector<int32_t> cols, rows, rzero;
     std::vector<double> rsum, rlog;
     int pk = 0, nk = 0;
     {
         NHIP(hipSetDevice(device));
-        NHIP(hipMalloc((void **)&d_x, sizeof(int32_t) * (size_t)n * p));
-        NHIP(hipMemcpy(d_x, counts, sizeof(int32_t) * (size_t)n * p, hipMemcpyHostToDevice));
-        NHIP(hipMalloc((void **)&d_cmin, sizeof(int32_t) * p));
-        NHIP(hipMalloc((void **)&d_cmax, sizeof(int32_t) * p));
-        hipLaunchKernelGGL(norm_col_minmax_kernel, dim3(p), dim3(256), 0, 0, d_x, n, p, d_cmin, d_cmax);
+        NHIP(hipMalloc((void **)&d_x, sizeof(V) * (size_t)n * p));
+        NHIP(hipMemcpy(d_x, counts, sizeof(V) * (size_t)n * p, hipMemcpyHostToDevice));
+        NHIP(hipMalloc((void **)&d_cmin, sizeof(V) * p));
+        NHIP(hipMalloc((void **)&d_cmax, sizeof(V) * p));
+        hipLaunchKernelGGL(norm_col_minmax_kernel<V>, dim3(p), dim3(256), 0, 0, d_x, n, p, d_cmin, d_cmax);
         NHIP(hipGetLastError());
-        NHIP(hipMemcpy(cmin.data(), d_cmin, sizeof(int32_t) * p, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(cmax.data(), d_cmax, sizeof(int32_t) * p, hipMemcpyDeviceToHost));
+        NHIP(hipMemcpy(cmin.data(), d_cmin, sizeof(V) * p, hipMemcpyDeviceToHost));
+        NHIP(hipMemcpy(cmax.data(), d_cmax, sizeof(V) * p, hipMemcpyDeviceToHost));
         for (int j = 0; j < p; ++j) {
             if (cmin[j] < 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: negative count in column %d", j);
+                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: %s in column %d", fn, NormVal<V>::bad(), j);
                 goto done;
             }
             col_mask[j] = cmin[j] != cmax[j];  // var(data, dims=1) .> 0
@@ -380,7 +427,7 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
         }
         pk = (int)cols.size();
         if (pk == 0) {
-            rc = fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: every column is constant");
+            rc = fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
             goto done;
         }
         NHIP(hipMalloc((void **)&d_cols, sizeof(int32_t) * pk));
@@ -389,8 +436,8 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
         NHIP(hipMalloc((void **)&d_rsum, sizeof(double) * cn));
         NHIP(hipMalloc((void **)&d_rlog, sizeof(double) * cn));
         NHIP(hipMalloc((void **)&d_rzero, sizeof(int32_t) * cn));
-        NHIP(hipMalloc((void **)&d_rmin, sizeof(int32_t) * cn));
-        hipLaunchKernelGGL(norm_row_stats_kernel, dim3((n + 255) / 256, NORM_CHUNKS), dim3(256), 0, 0, d_x, n, d_cols, pk, d_rsum, d_rzero,
+        NHIP(hipMalloc((void **)&d_rmin, sizeof(V) * cn));
+        hipLaunchKernelGGL(norm_row_stats_kernel<V>, dim3((n + 255) / 256, NORM_CHUNKS), dim3(256), 0, 0, d_x, n, d_cols, pk, d_rsum, d_rzero,
                            d_rlog, d_rmin);
         NHIP(hipGetLastError());
         rsum.resize(cn);
@@ -400,7 +447,7 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
         NHIP(hipMemcpy(rsum.data(), d_rsum, sizeof(double) * cn, hipMemcpyDeviceToHost));
         NHIP(hipMemcpy(rlog.data(), d_rlog, sizeof(double) * cn, hipMemcpyDeviceToHost));
         NHIP(hipMemcpy(rzero.data(), d_rzero, sizeof(int32_t) * cn, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(rmin.data(), d_rmin, sizeof(int32_t) * cn, hipMemcpyDeviceToHost));
+        NHIP(hipMemcpy(rmin.data(), d_rmin, sizeof(V) * cn, hipMemcpyDeviceToHost));
         // chunk partials -> per-row totals, in chunk order (deterministic)
         std::vector<double> S((size_t)n, 0.0), SL((size_t)n, 0.0);
         std::vector<int64_t> NZ((size_t)n, 0);
@@ -410,18 +457,18 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
                 SL[i] += rlog[(size_t)c * n + i];
                 NZ[i] += rzero[(size_t)c * n + i];
             }
-        std::vector<int32_t> RMIN((size_t)n, 0x7fffffff);
+        std::vector<double> RMIN((size_t)n, INFINITY);
         for (int c = 0; c < NORM_CHUNKS; ++c)
-            for (int i = 0; i < n; ++i) RMIN[i] = std::min(RMIN[i], rmin[(size_t)c * n + i]);
+            for (int i = 0; i < n; ++i) RMIN[i] = std::min(RMIN[i], (double)rmin[(size_t)c * n + i]);
         std::vector<double> pseudo, g;
-        if ((rc = norm_row_params("fw_normalize_counts", kind, n, pk, S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
+        if ((rc = norm_row_params(fn, kind, n, pk, NormVal<V>::tie_rel(pk), S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
         nk = (int)rows.size();
         NHIP(hipMalloc((void **)&d_rows, sizeof(int32_t) * nk));
         NHIP(hipMemcpy(d_rows, rows.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice));
         if (kind == FW_MI) {
             // presabs_norm! + columns with exactly two levels among the kept samples
             NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * pk));
-            hipLaunchKernelGGL(norm_col_levels_kernel, dim3(pk), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_two);
+            hipLaunchKernelGGL(norm_col_levels_kernel<V>, dim3(pk), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_two);
             NHIP(hipGetLastError());
             std::vector<int32_t> two((size_t)pk);
             NHIP(hipMemcpy(two.data(), d_two, sizeof(int32_t) * pk, hipMemcpyDeviceToHost));
@@ -435,12 +482,12 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
             cols.swap(cols2);
             pk = (int)cols.size();
             if (pk == 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: no column with two levels");
+                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column with two levels", fn);
                 goto done;
             }
             NHIP(hipMemcpy(d_cols, cols.data(), sizeof(int32_t) * pk, hipMemcpyHostToDevice));
             NHIP(hipMalloc((void **)&d_oi, sizeof(int32_t) * (size_t)nk * pk));
-            hipLaunchKernelGGL(norm_binary_out_kernel, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_oi);
+            hipLaunchKernelGGL(norm_binary_out_kernel<V>, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_oi);
             NHIP(hipGetLastError());
             NHIP(hipMemcpy(out_i32, d_oi, sizeof(int32_t) * (size_t)nk * pk, hipMemcpyDeviceToHost));
         } else if (kind == FW_MI_NZ) {
@@ -453,8 +500,8 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
             NHIP(hipMemcpy(d_g, g.data(), sizeof(double) * nk, hipMemcpyHostToDevice));
             NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * pk));
             NHIP(hipMalloc((void **)&d_tmp, sizeof(int32_t) * (size_t)nk * pk));
-            NHIP(hipFuncSetAttribute((const void *)norm_binned_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
-            hipLaunchKernelGGL(norm_binned_kernel, dim3(bgrid), dim3(1024), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_x, n, d_rows, nk, d_cols, pk,
+            NHIP(hipFuncSetAttribute((const void *)norm_binned_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
+            hipLaunchKernelGGL(norm_binned_kernel<V>, dim3(bgrid), dim3(1024), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_x, n, d_rows, nk, d_cols, pk,
                                d_g, d_tmp, d_two, M, d_keys);
             NHIP(hipGetLastError());
             std::vector<int32_t> two((size_t)pk), sel;
@@ -467,7 +514,7 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
             }
             pk = (int)sel.size();
             if (pk == 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "fw_normalize_counts: no column whose non-zero abundances fall into two bins");
+                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column whose non-zero abundances fall into two bins", fn);
                 goto done;
             }
             NHIP(hipMalloc((void **)&d_sel, sizeof(int32_t) * pk));
@@ -482,7 +529,7 @@ extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int3
             NHIP(hipMemcpy(d_pseudo, pseudo.data(), sizeof(double) * nk, hipMemcpyHostToDevice));
             NHIP(hipMemcpy(d_g, g.data(), sizeof(double) * nk, hipMemcpyHostToDevice));
             NHIP(hipMalloc((void **)&d_of, sizeof(float) * (size_t)nk * pk));
-            hipLaunchKernelGGL(norm_clr_out_kernel, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_pseudo, d_g,
+            hipLaunchKernelGGL(norm_clr_out_kernel<V>, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_pseudo, d_g,
                                kind == FW_FZ ? 0 : 1, d_of);
             NHIP(hipGetLastError());
             NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * (size_t)nk * pk, hipMemcpyDeviceToHost));
@@ -497,15 +544,35 @@ done:
     return rc;
 }
 
+}  // namespace
+
+extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *counts, float *out_f32,
+                                   int32_t *out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
+{
+    return norm_dense<int32_t>("fw_normalize_counts", device, kind, n, p, counts, out_f32, out_i32, row_mask, col_mask, n_out, p_out);
+}
+
+extern "C" int fw_normalize_abund(int32_t device, int32_t kind, int32_t n, int32_t p, const double *values, float *out_f32,
+                                  int32_t *out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
+{
+    return norm_dense<double>("fw_normalize_abund", device, kind, n, p, values, out_f32, out_i32, row_mask, col_mask, n_out, p_out);
+}
+
 // ---- the same front-end on a CSC count table (fw_normalize_counts_csc) ---------------------------------------------------------
 // The table stays sparse from the caller's triple to the output triple: the work is O(nnz) (FW_FZ: plus its dense output).
+// Bytes per entry: Int32 counts | Float64 values (fw_normalize_abund_csc).
 //   csc_col_scan_kernel    one wavefront per column: structure and value check, min / max with the implicit zeros counted (the
-//                          variance filter), and the (column, count) payload of every entry for the sort            12 B / entry
-//   rocprim radix sort     stable, by row: the CSR view; inside a row the entries keep their ascending column order  ~24 B / entry and pass
-//   csc_row_stats_kernel   one thread per row over its CSR run: the sums of norm_row_stats_kernel in its order       12 B / entry
-//   csc_binned_kernel      one workgroup per kept column: norm_binned_kernel on the column's stored run              16 B / entry
-//   csc_emit_kernel        one wavefront per output column: renumbered rows + values                                 16 B / entry
+//                          variance filter), and the payload of every entry for the sort                             12 | 20 B / entry
+//   rocprim radix sort     stable, by row: the CSR view; inside a row the entries keep their ascending column order  ~24 | ~16 B / entry and pass
+//   csc_row_stats_kernel   one thread per row over its CSR run: the sums of norm_row_stats_kernel in its order       12 | 20 B / entry
+//   csc_binned_kernel      one workgroup per kept column: norm_binned_kernel on the column's stored run              16 | 24 B / entry
+//   csc_emit_kernel        one wavefront per output column: renumbered rows + values                                 16 | 20 B / entry
 //   csc_adapt_*_kernel     FW_FZ: the dense clr_adapt matrix, pseudo-count cells first, stored entries over them
+// The payload of the sort (CscPay): a count travels beside its column in one 64-bit word, column << 32 | count.  A Float64 value
+// does not fit beside its column, so for V = double the payload is the entry's index (32 bits: nnz < 2^31), the scan writes the
+// entry's column into a uint32 of its own (ecol), and the row pass gathers value and column through the sorted index: 8 B / entry
+// (index + ecol) where the packed word takes 8, and a sort that moves 8 B per entry and pass instead of 12; the row pass pays with
+// two gathers (12 B / entry, uncoalesced).  Searching colptr for the column instead would save ecol's 4 B and cost log2(p) loads.
 // Bit-identity with the dense form: norm_row_stats_kernel adds a row's terms chunk by chunk of the kept-column index and the host adds
 // the 64 chunk partials in chunk order, each from 0.0.  An absent entry adds +0.0 to the read sum and nothing to the log sum, and
 // a chunk without entries contributes a partial of +0.0: neither changes a bit, so adding the stored terms in column order with a
@@ -513,40 +580,67 @@ done:
 // (norm_row_params), the values from the same device expressions.
 namespace {
 
-// colstat[j]: 1 kept, 0 constant (dropped), < 0: -(FW_CSC_* flags).  pay[e] = column << 32 | count.
+template <typename V> struct CscPay;
+template <> struct CscPay<int32_t> {
+    typedef unsigned long long T;
+    __device__ static T make(int j, long long, int32_t v, uint32_t *) { return ((unsigned long long)(uint32_t)j << 32) | (uint32_t)v; }
+    __device__ static int col(T w, const uint32_t *) { return (int)(w >> 32); }
+    __device__ static int32_t val(T w, const int32_t *) { return (int32_t)(uint32_t)w; }
+    __device__ static int bad(int32_t v) { return v > 0 ? 0 : v == 0 ? FW_CSC_ZERO : FW_CSC_NEGATIVE; }
+};
+template <> struct CscPay<double> {
+    typedef uint32_t T;
+    __device__ static T make(int j, long long e, double, uint32_t *ecol)
+    {
+        ecol[e] = (uint32_t)j;
+        return (uint32_t)e;
+    }
+    __device__ static int col(T w, const uint32_t *ecol) { return (int)ecol[w]; }
+    __device__ static double val(T w, const double *nzval) { return nzval[w]; }
+    __device__ static int bad(double v)  // (-0.0 == 0: a stored zero; NaN fails every comparison)
+    {
+        return (v > 0.0 && v <= 1.7976931348623157e308) ? 0 : v == 0.0 ? FW_CSC_ZERO : v < 0.0 && v >= -1.7976931348623157e308 ? FW_CSC_NEGATIVE : FW_CSC_NONFINITE;
+    }
+};
+
+// colstat[j]: 1 kept, 0 constant (dropped), < 0: -(FW_CSC_* flags).  pay[e] = the entry's payload for the sort by row (CscPay).
+template <typename V>
 __global__ __launch_bounds__(256) void csc_col_scan_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
-                                                           const int32_t *__restrict__ nzval, int n, int p, long long nnz,
-                                                           int32_t *__restrict__ colstat, unsigned long long *__restrict__ pay)
+                                                           const V *__restrict__ nzval, int n, int p, long long nnz,
+                                                           int32_t *__restrict__ colstat, typename CscPay<V>::T *__restrict__ pay,
+                                                           uint32_t *__restrict__ ecol)
 {
     const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (j >= p) return;
     long long a, b;
     int bad = fw_csc_check_column(colptr, rowval, j, n, nnz, lane, &a, &b);
-    int32_t lo = 0x7fffffff, hi = (int32_t)0x80000000;
+    V lo = NormVal<V>::vmax(), hi = NormVal<V>::vmin();
     for (long long e = a + lane; e < b; e += 64) {
-        const int32_t v = nzval[e];
-        if (v <= 0) bad |= v == 0 ? FW_CSC_ZERO : FW_CSC_NEGATIVE;
+        const V v = nzval[e];
+        bad |= CscPay<V>::bad(v);
         lo = v < lo ? v : lo;
         hi = v > hi ? v : hi;
-        pay[e] = ((unsigned long long)(uint32_t)j << 32) | (uint32_t)v;
+        pay[e] = CscPay<V>::make(j, e, v, ecol);
     }
     bad = fw_wave_or(bad);
     for (int o = 32; o > 0; o >>= 1) {
-        const int32_t l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+        const V l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
         lo = l2 < lo ? l2 : lo;
         hi = h2 > hi ? h2 : hi;
     }
     if (lane == 0) {
-        const long long cnt = b - a;  // (cnt < n: the implicit zeros differ from the stored counts >= 1)
+        const long long cnt = b - a;  // (cnt < n: the implicit zeros differ from the stored values > 0)
         colstat[j] = bad ? -bad : (cnt == 0 || (cnt == (long long)n && lo == hi)) ? 0 : 1;
     }
 }
 
 // one thread per row over its run of the row-sorted entries: the totals of norm_row_stats_kernel + the host's chunk reduction
-__global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__restrict__ krow, const unsigned long long *__restrict__ pay,
+template <typename V>
+__global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__restrict__ krow, const typename CscPay<V>::T *__restrict__ pay,
+                                                            const V *__restrict__ nzval, const uint32_t *__restrict__ ecol,
                                                             long long nnz, int n, const int32_t *__restrict__ colq, int pk,
                                                             double *__restrict__ S, double *__restrict__ SL, int32_t *__restrict__ CNT,
-                                                            int32_t *__restrict__ MN)
+                                                            V *__restrict__ MN)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -560,12 +654,13 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
     }
     const int per = (pk + NORM_CHUNKS - 1) / NORM_CHUNKS;
     double s = 0.0, sl = 0.0, cs = 0.0, csl = 0.0;
-    int cc = 0, cnt = 0, mn = 0x7fffffff;
+    int cc = 0, cnt = 0;
+    V mn = NormVal<V>::vmax();
     for (long long e = lo; e < nnz && krow[e] == (uint32_t)i; ++e) {
-        const unsigned long long w = pay[e];
-        const int q = colq[(int)(w >> 32)];
+        const typename CscPay<V>::T w = pay[e];
+        const int q = colq[CscPay<V>::col(w, ecol)];
         if (q < 0) continue;
-        const int32_t v = (int32_t)(uint32_t)w;
+        const V v = CscPay<V>::val(w, nzval);
         const int c = q / per;
         if (c != cc) {  // chunk boundary of the dense kernel: its partial joins the total, the next starts from 0.0
             s += cs;
@@ -589,8 +684,9 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
 // length of the longest kept column (sizes the key storage), each column sorts its own power of two.  One kernel for both
 // launch shapes (256 threads while M <= 2 048, the HE case; 1 024 beyond): the bound of 1 024 caps it at 128 VGPRs, it uses 66, so
 // the short form loses no occupancy to the cap.
+template <typename V>
 __global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
-                                                          const int32_t *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
+                                                          const V *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
                                                           const int32_t *__restrict__ rownew, const double *__restrict__ gmean,
                                                           int32_t *__restrict__ bins, int32_t *__restrict__ two, int M, double *gkeys)
 {
@@ -625,8 +721,9 @@ __global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restr
 
 // one wavefront per output column f = input column fcols[f]: rows renumbered, values by mode
 //   0 FW_MI: 1    1 FW_MI_NZ: bins[e]    2 FW_FZ_NZ: (float)log(x / g_row), as norm_clr_out_kernel's mode 1
+template <typename V>
 __global__ __launch_bounds__(256) void csc_emit_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
-                                                       const int32_t *__restrict__ nzval, const int32_t *__restrict__ fcols, int pf,
+                                                       const V *__restrict__ nzval, const int32_t *__restrict__ fcols, int pf,
                                                        const int64_t *__restrict__ ocolptr, const int32_t *__restrict__ rownew,
                                                        const double *__restrict__ gmean, const int32_t *__restrict__ bins, int mode,
                                                        int32_t *__restrict__ orow, int32_t *__restrict__ oi, float *__restrict__ of)
@@ -658,8 +755,9 @@ __global__ __launch_bounds__(256) void csc_adapt_fill_kernel(int nk, int pk, con
 }
 
 // ... then the stored entries of the kept columns over them, one wavefront per kept column (entries of dropped rows are skipped)
+template <typename V>
 __global__ __launch_bounds__(256) void csc_adapt_scatter_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
-                                                                const int32_t *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
+                                                                const V *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
                                                                 const int32_t *__restrict__ rownew, int nk, const double *__restrict__ gmean,
                                                                 float *__restrict__ out)
 {
@@ -674,11 +772,16 @@ __global__ __launch_bounds__(256) void csc_adapt_scatter_kernel(const int64_t *_
 
 }  // namespace
 
-extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
-                                       const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
-                                       uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
+namespace {
+
+// The CSC front-end for either value type (fn: the entry point's name, for the messages).
+template <typename V>
+int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval, const V *nzval,
+             int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out,
+             int32_t *p_out, int64_t *nnz_out)
 {
-    const char *fn = "fw_normalize_counts_csc";
+    typedef typename CscPay<V>::T Pay;
+    const bool indexed = sizeof(Pay) == sizeof(uint32_t);  // (Float64: the payload is the entry's index, the column sits in d_ecol)
     if (!colptr || !row_mask || !col_mask || !n_out || !p_out || !nnz_out || n <= 0 || p <= 0)
         return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
     if (kind != FW_FZ && kind != FW_FZ_NZ && kind != FW_MI && kind != FW_MI_NZ) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
@@ -692,10 +795,10 @@ extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, 
     if (nnz == 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
     int rc = FW_OK;
     int64_t *d_colptr = nullptr, *d_ocolptr = nullptr;
-    int32_t *d_rowval = nullptr, *d_nzval = nullptr, *d_colstat = nullptr, *d_colq = nullptr, *d_cols = nullptr, *d_cnt = nullptr, *d_mn = nullptr,
-            *d_rownew = nullptr, *d_bins = nullptr, *d_two = nullptr, *d_orow = nullptr, *d_oi = nullptr;
-    uint32_t *d_krow = nullptr;
-    unsigned long long *d_pay = nullptr, *d_pay2 = nullptr;
+    V *d_nzval = nullptr, *d_mn = nullptr;
+    int32_t *d_rowval = nullptr, *d_colstat = nullptr, *d_colq = nullptr, *d_cols = nullptr, *d_cnt = nullptr, *d_rownew = nullptr, *d_bins = nullptr, *d_two = nullptr, *d_orow = nullptr, *d_oi = nullptr;
+    uint32_t *d_krow = nullptr, *d_ecol = nullptr;
+    Pay *d_pay = nullptr, *d_pay2 = nullptr;
     double *d_S = nullptr, *d_SL = nullptr, *d_pseudo = nullptr, *d_g = nullptr, *d_keys = nullptr;
     float *d_of = nullptr;
     void *d_tmp = nullptr;
@@ -704,13 +807,14 @@ extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, 
         NHIP(hipSetDevice(device));
         NHIP(hipMalloc((void **)&d_colptr, sizeof(int64_t) * ((size_t)p + 1)));
         NHIP(hipMalloc((void **)&d_rowval, sizeof(int32_t) * (size_t)nnz));
-        NHIP(hipMalloc((void **)&d_nzval, sizeof(int32_t) * (size_t)nnz));
+        NHIP(hipMalloc((void **)&d_nzval, sizeof(V) * (size_t)nnz));
         NHIP(hipMalloc((void **)&d_colstat, sizeof(int32_t) * (size_t)p));
-        NHIP(hipMalloc((void **)&d_pay, sizeof(unsigned long long) * (size_t)nnz));
+        NHIP(hipMalloc((void **)&d_pay, sizeof(Pay) * (size_t)nnz));
+        if (indexed) NHIP(hipMalloc((void **)&d_ecol, sizeof(uint32_t) * (size_t)nnz));
         NHIP(hipMemcpy(d_colptr, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice));
         NHIP(hipMemcpy(d_rowval, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-        NHIP(hipMemcpy(d_nzval, nzval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(csc_col_scan_kernel, dim3(wgrid_p), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, n, p, nnz, d_colstat, d_pay);
+        NHIP(hipMemcpy(d_nzval, nzval, sizeof(V) * (size_t)nnz, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(csc_col_scan_kernel<V>, dim3(wgrid_p), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, n, p, nnz, d_colstat, d_pay, d_ecol);
         NHIP(hipGetLastError());
         std::vector<int32_t> colstat((size_t)p), cols, colq((size_t)p, -1);
         NHIP(hipMemcpy(colstat.data(), d_colstat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost));
@@ -730,34 +834,39 @@ extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, 
             rc = fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
             goto done;
         }
-        // CSR view: stable sort of the entries by row (the payload carries column and count)
+        // CSR view: stable sort of the entries by row (the payload carries column and count, or the entry's index: CscPay)
         int bits = 1;
         while ((1ll << bits) < (long long)n) ++bits;
         size_t tb = 0;
         NHIP(hipMalloc((void **)&d_krow, sizeof(uint32_t) * (size_t)nnz));
-        NHIP(hipMalloc((void **)&d_pay2, sizeof(unsigned long long) * (size_t)nnz));
-        NHIP((rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)d_rowval, d_krow, (const unsigned long long *)d_pay, d_pay2, (size_t)nnz, 0u,
+        NHIP(hipMalloc((void **)&d_pay2, sizeof(Pay) * (size_t)nnz));
+        NHIP((rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)d_rowval, d_krow, (const Pay *)d_pay, d_pay2, (size_t)nnz, 0u,
                                         (unsigned int)bits, (hipStream_t)0)));
         NHIP(hipMalloc(&d_tmp, tb ? tb : 1));
-        NHIP((rocprim::radix_sort_pairs(d_tmp, tb, (const uint32_t *)d_rowval, d_krow, (const unsigned long long *)d_pay, d_pay2, (size_t)nnz, 0u,
+        NHIP((rocprim::radix_sort_pairs(d_tmp, tb, (const uint32_t *)d_rowval, d_krow, (const Pay *)d_pay, d_pay2, (size_t)nnz, 0u,
                                         (unsigned int)bits, (hipStream_t)0)));
         NHIP(hipMalloc((void **)&d_colq, sizeof(int32_t) * (size_t)p));
         NHIP(hipMemcpy(d_colq, colq.data(), sizeof(int32_t) * (size_t)p, hipMemcpyHostToDevice));
         NHIP(hipMalloc((void **)&d_S, sizeof(double) * (size_t)n));
         NHIP(hipMalloc((void **)&d_SL, sizeof(double) * (size_t)n));
         NHIP(hipMalloc((void **)&d_cnt, sizeof(int32_t) * (size_t)n));
-        NHIP(hipMalloc((void **)&d_mn, sizeof(int32_t) * (size_t)n));
-        hipLaunchKernelGGL(csc_row_stats_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow, d_pay2, nnz, n, d_colq, pk, d_S, d_SL, d_cnt, d_mn);
+        NHIP(hipMalloc((void **)&d_mn, sizeof(V) * (size_t)n));
+        hipLaunchKernelGGL(csc_row_stats_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow, d_pay2, d_nzval, d_ecol, nnz, n, d_colq, pk, d_S, d_SL, d_cnt, d_mn);
         NHIP(hipGetLastError());
         std::vector<double> S((size_t)n), SL((size_t)n), pseudo, g;
-        std::vector<int32_t> CNT((size_t)n), RMIN((size_t)n), rows;
+        std::vector<int32_t> CNT((size_t)n), rows;
+        std::vector<V> MN((size_t)n);
         NHIP(hipMemcpy(S.data(), d_S, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
         NHIP(hipMemcpy(SL.data(), d_SL, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
         NHIP(hipMemcpy(CNT.data(), d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(RMIN.data(), d_mn, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        NHIP(hipMemcpy(MN.data(), d_mn, sizeof(V) * (size_t)n, hipMemcpyDeviceToHost));
         std::vector<int64_t> NZ((size_t)n);
-        for (int i = 0; i < n; ++i) NZ[i] = (int64_t)pk - CNT[i];
-        if ((rc = norm_row_params(fn, kind, n, pk, S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
+        std::vector<double> RMIN((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            NZ[i] = (int64_t)pk - CNT[i];
+            RMIN[i] = (double)MN[i];
+        }
+        if ((rc = norm_row_params(fn, kind, n, pk, NormVal<V>::tie_rel(pk), S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
         const int nk = (int)rows.size();
         std::vector<int32_t> rownew((size_t)n, -1);  // row renumbering: the prefix sum over the row mask, on the host (n entries, uploaded)
         for (int r = 0; r < nk; ++r) rownew[rows[r]] = r;
@@ -776,7 +885,7 @@ extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, 
             NHIP(hipMemcpy(d_pseudo, pseudo.data(), sizeof(double) * (size_t)nk, hipMemcpyHostToDevice));
             NHIP(hipMalloc((void **)&d_of, sizeof(float) * (size_t)nk * pk));
             hipLaunchKernelGGL(csc_adapt_fill_kernel, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, nk, pk, d_pseudo, d_g, d_of);
-            hipLaunchKernelGGL(csc_adapt_scatter_kernel, dim3((unsigned)((pk + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pk, d_rownew,
+            hipLaunchKernelGGL(csc_adapt_scatter_kernel<V>, dim3((unsigned)((pk + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pk, d_rownew,
                                nk, d_g, d_of);
             NHIP(hipGetLastError());
             NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * (size_t)nk * pk, hipMemcpyDeviceToHost));
@@ -811,8 +920,8 @@ extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, 
             if (!keys_in_lds) NHIP(hipMalloc((void **)&d_keys, sizeof(double) * (size_t)M * (size_t)bgrid));
             NHIP(hipMalloc((void **)&d_bins, sizeof(int32_t) * (size_t)nnz));
             NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * (size_t)pk));
-            NHIP(hipFuncSetAttribute((const void *)csc_binned_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
-            hipLaunchKernelGGL(csc_binned_kernel, dim3(bgrid), dim3(bthreads), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_colptr, d_rowval, d_nzval,
+            NHIP(hipFuncSetAttribute((const void *)csc_binned_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
+            hipLaunchKernelGGL(csc_binned_kernel<V>, dim3(bgrid), dim3(bthreads), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_colptr, d_rowval, d_nzval,
                                d_cols, pk, d_rownew, d_g, d_bins, d_two, M, d_keys);
             NHIP(hipGetLastError());
             std::vector<int32_t> two((size_t)pk);
@@ -840,7 +949,7 @@ extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, 
             NHIP(hipMalloc((void **)&d_oi, sizeof(int32_t) * onnz));
         else
             NHIP(hipMalloc((void **)&d_of, sizeof(float) * onnz));
-        hipLaunchKernelGGL(csc_emit_kernel, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pf, d_ocolptr, d_rownew, d_g,
+        hipLaunchKernelGGL(csc_emit_kernel<V>, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pf, d_ocolptr, d_rownew, d_g,
                            d_bins, kind == FW_MI ? 0 : kind == FW_MI_NZ ? 1 : 2, d_orow, d_oi, d_of);
         NHIP(hipGetLastError());
         NHIP(hipMemcpy(out_rowval, d_orow, sizeof(int32_t) * onnz, hipMemcpyDeviceToHost));
@@ -855,8 +964,26 @@ extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, 
     }
 done:
     void *ptrs[] = {d_colptr, d_ocolptr, d_rowval, d_nzval, d_colstat, d_colq, d_cols, d_cnt, d_mn, d_rownew, d_bins, d_two, d_orow, d_oi,
-                    d_krow, d_pay, d_pay2, d_S, d_SL, d_pseudo, d_g, d_keys, d_of, d_tmp};
+                    d_krow, d_ecol, d_pay, d_pay2, d_S, d_SL, d_pseudo, d_g, d_keys, d_of, d_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     return rc;
+}
+
+}  // namespace
+
+extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                                       const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                                       uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
+{
+    return norm_csc<int32_t>("fw_normalize_counts_csc", device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32, out_f32, row_mask,
+                             col_mask, n_out, p_out, nnz_out);
+}
+
+extern "C" int fw_normalize_abund_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                                      const double *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                                      uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
+{
+    return norm_csc<double>("fw_normalize_abund_csc", device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32, out_f32, row_mask,
+                            col_mask, n_out, p_out, nnz_out);
 }

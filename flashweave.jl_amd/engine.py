@@ -147,6 +147,9 @@ def load_library():
         L.fw_normalize_counts_csc.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.fw_set_data_csc_f32.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "fw_normalize_abund"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        L.fw_normalize_abund.argtypes = L.fw_normalize_counts.argtypes
+        L.fw_normalize_abund_csc.argtypes = L.fw_normalize_counts_csc.argtypes
     if hasattr(L, "fw_set_data_csc_f32_resident"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
         L.fw_set_data_csc_f32_resident.argtypes = [vp, vp, vp, vp]
         L.fw_data_resident_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -239,11 +242,13 @@ def as_csc(data, dtype):
                np.ascontiguousarray(v, dtype=dtype), (int(n), int(p)))
 
 
-def _normalize_counts_csc(L, counts, test_name, device):
+def _normalize_csc(front_end, who, triple, test_name, device):
+    """fw_normalize_counts_csc / fw_normalize_abund_csc (front_end) on the canonical triple -> (data, row_mask, col_mask)"""
     import scipy.sparse as sp
-    colptr, rowval, nzval, (n, p) = as_csc(counts, np.int32)
+    L = load_library()
+    colptr, rowval, nzval, (n, p) = triple
     if n <= 0 or p <= 0:
-        raise ValueError("normalize_counts: counts must be a samples x OTUs matrix")
+        raise ValueError("%s: counts must be a samples x OTUs matrix" % who)
     kind = _KINDS[test_name]
     nnz = int(colptr[-1])
     rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
@@ -251,8 +256,8 @@ def _normalize_counts_csc(L, counts, test_name, device):
     ocp, orow = np.zeros(p + 1, np.int64), np.zeros(max(nnz, 1), np.int32)
     of = np.zeros(n * p if kind == FW_FZ else max(nnz, 1), np.float32) if kind in (FW_FZ, FW_FZ_NZ) else None
     oi = np.zeros(max(nnz, 1), np.int32) if kind in (FW_MI, FW_MI_NZ) else None
-    rc = L.fw_normalize_counts_csc(device, kind, n, p, _ptr(colptr), _ptr(rowval), _ptr(nzval), _ptr(ocp), _ptr(orow), _ptr(oi), _ptr(of),
-                                   _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), C.byref(nz))
+    rc = front_end(device, kind, n, p, _ptr(colptr), _ptr(rowval), _ptr(nzval), _ptr(ocp), _ptr(orow), _ptr(oi), _ptr(of),
+                   _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), C.byref(nz))
     if rc != 0:
         raise FlashWeaveError(rc, L.fw_last_error(None).decode())
     if kind == FW_FZ:
@@ -272,7 +277,7 @@ def normalize_counts(counts, test_name, device=0):
     is 0) and a dense array for "fz"; the values are the bits the dense table gives."""
     L = load_library()
     if is_sparse(counts) or isinstance(counts, CSC):  # (any other tuple is a dense table, as before)
-        return _normalize_counts_csc(L, counts, test_name, device)
+        return _normalize_csc(L.fw_normalize_counts_csc, "normalize_counts", as_csc(counts, np.int32), test_name, device)
     raw = np.asarray(counts)
     if raw.ndim != 2:
         raise ValueError("normalize_counts: counts must be a samples x OTUs matrix")
@@ -281,18 +286,60 @@ def normalize_counts(counts, test_name, device=0):
             raise TypeError("normalize_counts: the device front-end takes integer counts (got non-integral %s values)" % raw.dtype)
     if raw.size and (raw.min() < 0 or raw.max() > np.iinfo(np.int32).max):
         raise ValueError("normalize_counts: counts must lie in [0, 2^31 - 1]")
-    x = np.asfortranarray(raw.astype(np.int32))
+    return _normalize_dense(L.fw_normalize_counts, np.asfortranarray(raw.astype(np.int32)), test_name, device)
+
+
+def _normalize_dense(front_end, x, test_name, device):
+    """fw_normalize_counts / fw_normalize_abund (front_end) on the column-major table -> (data, row_mask, col_mask)"""
+    L = load_library()
     n, p = x.shape
     rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
     no, po = C.c_int32(0), C.c_int32(0)
     kind = _KINDS[test_name]
     of = np.zeros(n * p, np.float32) if kind in (FW_FZ, FW_FZ_NZ) else None
     oi = np.zeros(n * p, np.int32) if kind in (FW_MI, FW_MI_NZ) else None
-    rc = L.fw_normalize_counts(device, kind, n, p, _ptr(x), _ptr(of), _ptr(oi), _ptr(rm), _ptr(cm), C.byref(no), C.byref(po))
+    rc = front_end(device, kind, n, p, _ptr(x), _ptr(of), _ptr(oi), _ptr(rm), _ptr(cm), C.byref(no), C.byref(po))
     if rc != 0:
         raise FlashWeaveError(rc, L.fw_last_error(None).decode())
     out = (of if of is not None else oi)[:no.value * po.value].reshape((no.value, po.value), order="F")
     return out, rm.astype(bool), cm.astype(bool)
+
+
+def abundance_defect(values):
+    """What keeps real values from being abundances, as words for a refusal, or None: a NaN, an infinite or a negative value."""
+    v = np.asarray(values)
+    if v.size and v.dtype.kind == "f" and not np.all(np.isfinite(v)):
+        return "a NaN or an infinite value"
+    if v.size and v.dtype.kind in "if" and v.min() < 0:
+        return "a negative value"
+    return None
+
+
+def normalize_abundances(table, test_name, device=0):
+    """normalize_counts for a real-valued table -- relative abundances, percentages, coverage-normalised counts, counts beyond
+    2^31 - 1 -- on the device (fw_normalize_abund, fw_normalize_abund_csc): -> (data, row_mask, col_mask) in the forms normalize_counts
+    returns.  The values are taken as Float64 (a dense array of booleans, integers or floats is widened, Float32 exactly; a sparse
+    table goes through as_csc(table, np.float64)); a table of integers gives the bits normalize_counts gives.  A NaN, an infinite or a
+    negative value and a table that is not two-dimensional raise ValueError before any device call."""
+    who = "normalize_abundances"
+    sparse = is_sparse(table) or isinstance(table, CSC)
+    if sparse:
+        triple = as_csc(table, np.float64)
+        values = triple.nzval
+    else:
+        raw = np.asarray(table)
+        if raw.ndim != 2 or raw.dtype.kind not in "biuf":
+            raise ValueError("%s: the table must be a samples x OTUs matrix of real numbers" % who)
+        values = np.asfortranarray(raw, dtype=np.float64)
+    defect = abundance_defect(values)
+    if defect:
+        raise ValueError("%s: the table holds %s: abundances are finite and >= 0" % (who, defect))
+    L = load_library()
+    if not hasattr(L, "fw_normalize_abund"):
+        raise FlashWeaveError(-2, "%s: the loaded library has no fw_normalize_abund (an older build)" % who)
+    if sparse:
+        return _normalize_csc(L.fw_normalize_abund_csc, who, triple, test_name, device)
+    return _normalize_dense(L.fw_normalize_abund, values, test_name, device)
 
 
 class Engine:

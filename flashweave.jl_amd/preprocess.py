@@ -19,11 +19,17 @@ def filter_by_variance(data):
     return data[row_mask, :], row_mask, col_mask
 
 
-def adaptive_clr(counts):
+def adaptive_clr(counts, tie_anchor=False):
     """clr_adapt for a dense count matrix (what preprocessing.jl:157-214 computes): every sample's zeros are replaced by ONE fill value
     chosen so that the filled sample is as far from its own geometric mean as the deepest sample is when ITS zeros hold the floor
     value -- in logs,  fill_i = exp( [ (z* - w) log(floor) + L* - L_i ] / (z_i - w) )  with z = zeros of the sample, L = sum of the logs
     of its non-zero counts, w = the table's width, * = the sample with the largest total -- followed by the centred log-ratio.
+    The sample with the largest total is the first of maximal Float64 sum, as in the reference (findmax, preprocessing.jl:158).
+    tie_anchor=True (what abundances=True asks for, and what the device front-end does for real values): sums within width * 2^-52 of
+    the largest take part as well, and the first of those samples is the anchor.  In a table of relative abundances every sample
+    sums to 1 up to rounding and the plain rule is decided by the order of the additions; the window is the rounding bound
+    (width - 1) * 2^-53 of a sum of `width` non-negative terms in any order, taken on either side.  It makes the choice independent of
+    the order unless a sample's true depth lies about one bound below the maximum, where it can still go either way.
     Returns (matrix, kept-samples mask); a sample whose fill value underflows to zero is dropped."""
     M = np.array(counts, dtype=np.float64)
     n_samples, width = M.shape
@@ -32,7 +38,8 @@ def adaptive_clr(counts):
     if (zeros >= width).any():
         raise ValueError("samples with all zero abundances are not allowed")
     log_mass = np.array([np.log(M[i, present[i]]).sum() for i in range(n_samples)])
-    deepest = int(np.argmax(M.sum(axis=1)))
+    depth = M.sum(axis=1)
+    deepest = int(np.argmax(depth >= depth.max() * (1.0 - width * 2.0 ** -52))) if tie_anchor else int(np.argmax(depth))
     smallest = M[present].min()
     floor = 1.0 if smallest >= 1 else smallest / 10
     anchor = (zeros[deepest] - width) * np.log(floor) + log_mass[deepest]
@@ -164,13 +171,13 @@ def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_head
                 row_mask=row_mask)
 
 
-def normalize(counts, test_name, prec=32):
-    """-> (data, row_mask, col_mask).  row/col masks refer to the input matrix."""
+def normalize(counts, test_name, prec=32, tie_anchor=False):
+    """-> (data, row_mask, col_mask).  row/col masks refer to the input matrix.  tie_anchor: see adaptive_clr ("fz" only)."""
     counts = np.asarray(counts)
     data, row_mask, col_mask = filter_by_variance(counts.astype(np.float64))
     cols = np.nonzero(col_mask)[0]
     if test_name == "fz":
-        out, keep = adaptive_clr(data)
+        out, keep = adaptive_clr(data, tie_anchor=tie_anchor)
         rows = np.nonzero(row_mask)[0]
         row_mask = np.zeros_like(row_mask)
         row_mask[rows[keep]] = True

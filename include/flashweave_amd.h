@@ -407,6 +407,22 @@ int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, int32_t p, 
                             const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
                             uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out);
 
+/* The same two front-ends on a real-valued table (relative abundances, percentages, coverage-normalised counts, counts beyond
+ * 2^31-1): the reference normalises any Real matrix, and adaptive_pseudocount! (:157-190) takes a tenth of the smallest abundance
+ * as its floor when that lies below 1.  The same kernels instantiated for Float64 values (csrc/fw_norm.hip): contracts, outputs
+ * and limits are those of the _counts siblings, and a table of integers gives the bits its Int32 form gives.  values / nzval:
+ * Float64, each >= 0 and finite (-0.0 is a zero); a negative value, a NaN or an Inf gives FW_ERR_ARG naming the first offending
+ * column (dense) or the column (CSC), as does a stored zero in the CSC form.  Integers beyond 2^53 are no longer exact.  The
+ * variance filter stays min != max (a CSC column's implicit zeros counted): exact, where a floating-point variance of a constant
+ * column can be a rounding residue.  Device memory: 8 bytes per dense cell (the count form takes 4); the CSC form holds 8 B per
+ * stored value and sorts a 32-bit entry index with a 32-bit column per entry beside it, where the count form sorts one packed
+ * 64-bit (column, count) word. */
+int fw_normalize_abund(int32_t device, int32_t kind, int32_t n, int32_t p, const double *values, float *out_f32, int32_t *out_i32,
+                       uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out);
+int fw_normalize_abund_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                           const double *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                           uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out);
+
 /* Device self-test of hand-written arithmetic sequences that replace a compiler-generated IEEE sequence and must return the
  * same bits.  which = FW_SELFTEST_DIV: the unscaled Float64 division of the NaN-free partial-correlation path (statfuns.jl:44-62
  * `/`) against the compiler's division on `cases` hashed operand pairs of that path's ranges; *mismatches = pairs that differ. */
