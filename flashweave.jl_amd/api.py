@@ -10,7 +10,8 @@ import numpy as np
 
 from . import io as fio
 from . import preprocess as pre
-from .engine import CSC, Engine, abundance_defect, as_csc, is_sparse, normalize_abundances, normalize_counts, rejections_dict
+from .engine import (CSC, Engine, abundance_defect, as_csc, is_sparse, normalize_abundances, normalize_counts, rejections_dict,
+                     tss_range_defect)
 
 
 class FWResult(dict):
@@ -50,6 +51,9 @@ def _integral(a):
                 a.max() < 2**31 and a.min() >= 0)
 
 _TEST_NAMES = ("fz", "fz_nz", "mi", "mi_nz")
+# normalize_data's norm_mode (preprocessing.jl:660-684) -> the test_name it stands for (four aliases) or goes with (the two TSS modes,
+# preprocess.TSS_NORMS: no test_name selects them)
+_NORM_MODES = {"clr-adapt": "fz", "clr-nonzero": "fz_nz", "clr-nonzero-binned": "mi_nz", "pres-abs": "mi", **pre.TSS_NORMS}
 # learn_network's keywords by where they go.  All of them -- the caller's values, before anything is resolved -- go into the digest
 # of a distributed run; parameters= reports _REPORTED, the Engine takes _ENGINE_KEYS and lgl _LGL_KEYS, each with the resolved values
 # (test_name, round_size, recursive_pcor, dense_cor, csc_resident, prec = the engine's element type) laid over the caller's.
@@ -235,20 +239,26 @@ def _abundance_refusals(who, data, extra):
             raise ValueError("%s: abundances=True: %s holds %s; abundances are finite and >= 0" % (who, name, defect))
 
 
-def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device, abundances=False):
+def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device, abundances=False,
+                      tss=None):
     """Every table through ONE front-end -- the device one when all of them are count tables it takes (sparse, or _integral) and
     prec == 32 and device_normalize, else the host one -- each on its own (its own row sums, geometric means, pseudo-counts and
     filters), then preprocess.combine_data.  abundances: the tables are declared real-valued, _integral is not asked and the device
-    front-end is the Float64 one (engine.normalize_abundances).  -> (dict(data, header, meta_mask, row_mask), on_device)"""
+    front-end is the Float64 one (engine.normalize_abundances).  tss: one of preprocess.TSS_NORMS, handed to whichever front-end runs
+    as norm= (test_name is then the one the norm goes with); None hands every front-end what it was always handed.
+    -> (dict(data, header, meta_mask, row_mask), on_device)"""
     on_device = bool(device_normalize and prec == 32 and
                      (abundances or all(isinstance(t, CSC) or _integral(t) for t in [data] + [t for t, _ in extra])))
+    kw = {} if tss is None else {"norm": tss}
     norm = None  # (None: the host front-end as it is)
     if on_device and abundances:  # (a dense table is handed over as the Float64 values the front-end reads; Float32 widens exactly)
-        norm = lambda c, t: normalize_abundances(c if isinstance(c, CSC) else np.asarray(c, dtype=np.float64), t, device=device)
+        norm = lambda c, t: normalize_abundances(c if isinstance(c, CSC) else np.asarray(c, dtype=np.float64), t, device=device, **kw)
     elif on_device:
-        norm = lambda c, t: normalize_counts(c, t, device=device)
+        norm = lambda c, t: normalize_counts(c, t, device=device, **kw)
     elif abundances:  # the host front-end with the anchor rule of the Float64 device front-end (preprocess.adaptive_clr)
-        norm = lambda c, t: pre.normalize(c, t, prec=prec, tie_anchor=True)
+        norm = lambda c, t: pre.normalize(c, t, prec=prec, tie_anchor=True, **kw)
+    elif tss is not None:
+        norm = lambda c, t: pre.normalize(c, t, prec=prec, **kw)
 
     def one(tab, hdr):  # a count table on its own -> (matrix, the kept columns' names, row mask)
         mat, row_mask, col_mask = norm(tab, test_name) if norm else pre.normalize(tab, test_name, prec=prec)
@@ -472,8 +482,17 @@ def _schedule(round_size, feed_forward, p):
             else "rounds of %d targets (whitelists refresh once per round; deviates from single_il)" % round_size)
 
 
-def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
-                   device_normalize=True, device=0, meta_mask=None, abundances=False):
+def _tss_range_refusals(who, norm_mode, data, extra):
+    """A TSS norm_mode on tables of real values: every positive value lies in [2^-126, 2^96], so that it does not vanish as a Float32
+    and the Float32 sum of a sample (fewer than 2^31 terms) stays finite."""
+    for name, tab in [("data", data)] + [("extra_data[%d]" % i, t) for i, (t, _) in enumerate(extra)]:
+        defect = tss_range_defect(tab.nzval if isinstance(tab, CSC) else tab)
+        if defect:
+            raise ValueError("%s: norm_mode=%r with abundances=True: %s holds %s" % (who, norm_mode, name, defect))
+
+
+def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
+                   device_normalize=True, device=0, meta_mask=None, abundances=False, norm_mode=None):
     """normalize_data (preprocessing.jl:660-701), both forms: what learn_network(normalize=True) does to its tables, as a function of
     its own.  data: samples x OTUs counts (array or scipy.sparse); extra_data: a list of (table, header) pairs, count tables of further
     sequencing experiments on the same samples.  Every table is normalised on its own for `test_name` ("fz" clr_adapt, "fz_nz" clr_nz,
@@ -487,9 +506,29 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
     abundances=True declares the tables real-valued (see learn_network): every table, dense or sparse, takes the Float64 device
     front-end when device_normalize and prec == 32; a NaN, an infinite or a negative value raises ValueError naming abundances and the
     table.
+    norm_mode: the reference's other way to choose the transform, by its own names, instead of test_name (giving both raises
+    ValueError; giving neither means test_name "fz"): "clr-adapt" = "fz", "clr-nonzero" = "fz_nz", "clr-nonzero-binned" = "mi_nz",
+    "pres-abs" = "mi" -- aliases, the same calls and results -- and the two total-sum-scaling modes no test_name selects: "tss"
+    (x / the sample's sum over the kept columns, computed in Float{prec} like the reference: Float32 sums in ascending column order;
+    dense Float32 or CSC Float32 out, meta variables as for "fz") and "tss-nonzero-binned" (the non-zero TSS values of a column ranked
+    into two bins, zeros stay 0: Int32 levels, dense or CSC; meta variables as for "mi_nz").  They take the same front-end choice, host
+    and device giving the same bits; with abundances=True a positive value outside [2^-126, 2^96] raises ValueError.  learn_network
+    takes such a table with normalize=False.
     -> dict(data, header, meta_mask, row_mask): row_mask over the input samples, data a scipy.sparse.csc_matrix for sparse tables
     (dense for "fz")."""
     who = "normalize_data"
+    tss = None
+    if norm_mode is not None:
+        if test_name is not None:
+            raise ValueError("%s: test_name=%r and norm_mode=%r are two ways to choose one transform: give one of them"
+                             % (who, test_name, norm_mode))
+        if norm_mode not in _NORM_MODES:
+            raise ValueError("%s: unsupported norm_mode %r; the modes are %s" % (who, norm_mode, ", ".join(map(repr, _NORM_MODES))))
+        test_name = _NORM_MODES[norm_mode]
+        if norm_mode in pre.TSS_NORMS:
+            tss = norm_mode
+    elif test_name is None:
+        test_name = "fz"
     if test_name not in _TEST_NAMES:
         raise ValueError("%s: unsupported test_name %r" % (who, test_name))
     if prec not in (32, 64):
@@ -497,8 +536,10 @@ def normalize_data(data, extra_data=None, test_name="fz", header=None, meta_data
     # this entry point's rules of the table stage: an engine.CSC tuple is a sparse table, and a header always has the table's length
     t = _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec, device_normalize,
                         normalize=True, csc_tuple_is_sparse=True, strict_header=True, abundances=bool(abundances))
+    if tss is not None and abundances:
+        _tss_range_refusals(who, norm_mode, t.data, t.extra)
     return _normalize_tables(t.data, list(t.header), t.extra, test_name, t.meta_data, t.meta_header, t.make_onehot, prec, device_normalize,
-                             device, bool(abundances))[0]
+                             device, bool(abundances), tss=tss)[0]
 
 
 def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,

@@ -15,6 +15,17 @@
 // that runs for them as before) or double (real-valued tables: fw_normalize_abund*, 8 B read per cell and pass).  Both
 // instantiations take the same expressions in the same order -- (double)v is the identity for V = double -- so a table of
 // integers gives the same bits through either.
+// Two further transforms, not test kinds (norm_mode of normalize_data, preprocessing.jl:660-684), under the same filters:
+//   FW_NORM_TSS         rows            :348-361   x / (sum of the row over the kept columns)                 -> Float32
+//   FW_NORM_TSS_BINNED  binned_nz_rows  :492-521   the ranks / bins of "mi_nz" with the TSS value as the key   -> Int32 {0, 1, 2}
+// These stay in Float32 like the reference (check_convert_sparse converts the table to Float{prec} first, rownorm! divides by
+// sum(X, dims=2)): x32 = (float)x; s_i = the Float32 sum of row i over the kept columns in ascending column order from +0.0f
+// (a zero cell adds +0.0f, no bit changes: the CSC form adds the stored terms alone, in that order); out = x32 / s_i, one correctly
+// rounded IEEE division (the Makefile passes no fast-math and no flush-to-zero flag).  Only + and / and no libm call: host,
+// dense and CSC form agree to the bit, and so do the ties among the quotients, which decide the tied ranks.  The Float64 chunk
+// partials of norm_row_stats_kernel are NOT s_i -- Float32 addition does not reassociate -- they only give the row filter.
+// One more pass over the kept cells for s_i (4 | 8 B read per cell, 4 B written per row), then 4 | 8 B read + 4 B written per cell.
+#include <cfloat>
 #include <cmath>
 #include <vector>
 
@@ -102,6 +113,32 @@ __global__ __launch_bounds__(256) void norm_row_stats_kernel(const V *__restrict
     rzero[(size_t)c * n + i] = nz;
     rlog[(size_t)c * n + i] = sl;
     rmin[(size_t)c * n + i] = mn;
+}
+
+// TSS: per sample the Float32 sum over the kept columns, left to right from +0.0f (one thread per sample, adjacent lanes on
+// adjacent samples: coalesced; the order IS the result, so no chunks).  rsum32[i] for every input row i.
+template <typename V>
+__global__ __launch_bounds__(256) void norm_row_tss_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ cols, int pk,
+                                                           float *__restrict__ rsum32)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.0f;
+    for (int q = 0; q < pk; ++q) s += (float)x[(size_t)cols[q] * n + i];
+    rsum32[i] = s;
+}
+
+// TSS: out[r][q] = (float)x / rsum32[row] for kept rows r and kept columns q (column-major n_out x p_out)
+template <typename V>
+__global__ __launch_bounds__(256) void norm_tss_out_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
+                                                           const int32_t *__restrict__ cols, int pk, const float *__restrict__ rsum32,
+                                                           float *__restrict__ out)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nk) return;
+    const int i = rows[r];
+    const float s = rsum32[i];
+    for (int q = blockIdx.y; q < pk; q += gridDim.y) out[(size_t)q * nk + r] = (float)x[(size_t)cols[q] * n + i] / s;
 }
 
 // out[r][q] for kept rows r and kept columns q (column-major n_out x p_out)
@@ -251,10 +288,20 @@ __device__ inline int nb_bin(const NbKeys &K, int m, double rmax, double c)
     return (int)floor((rank / rmax) / step) + 1;
 }
 
-template <typename V>
+// The sort key of a non-zero entry v in kept row r = input row i.  binned_nz_clr: its clr_nz value.  TSS (binned_nz_rows): its
+// Float32 quotient, widened -- which keeps order and ties.
+template <bool TSS, typename V>
+__device__ inline double nb_key(V v, const double *__restrict__ gmean, int r, const float *__restrict__ rsum32, int i)
+{
+    if (TSS) return (double)((float)v / rsum32[i]);
+    return log((double)v / gmean[r]);
+}
+
+template <typename V, bool TSS>
 __global__ __launch_bounds__(1024) void norm_binned_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
                                                            const int32_t *__restrict__ cols, int pk, const double *__restrict__ gmean,
-                                                           int32_t *__restrict__ out, int32_t *__restrict__ two, int M, double *gkeys)
+                                                           const float *__restrict__ rsum32, int32_t *__restrict__ out,
+                                                           int32_t *__restrict__ two, int M, double *gkeys)
 {
     extern __shared__ double s_key_lds[];
     __shared__ int s_cnt, s_b1, s_b2;
@@ -267,7 +314,7 @@ __global__ __launch_bounds__(1024) void norm_binned_kernel(const V *__restrict__
     __syncthreads();
     for (int r = tid; r < nk; r += 1024) {
         const V v = col[rows[r]];
-        if (v != 0) K.st(atomicAdd(&s_cnt, 1), log((double)v / gmean[r]));  // order does not matter: sorted below
+        if (v != 0) K.st(atomicAdd(&s_cnt, 1), nb_key<TSS>(v, gmean, r, rsum32, rows[r]));  // order does not matter: sorted below
     }
     K.sync();
     const int m = s_cnt;
@@ -278,7 +325,7 @@ __global__ __launch_bounds__(1024) void norm_binned_kernel(const V *__restrict__
         const V v = col[rows[r]];
         int bin = 0;
         if (v != 0) {
-            bin = nb_bin(K, m, rmax, log((double)v / gmean[r]));  // the same operations as above: the same bits
+            bin = nb_bin(K, m, rmax, nb_key<TSS>(v, gmean, r, rsum32, rows[r]));  // the same operations as above: the same bits
             b1 |= bin == 1;
             b2 |= bin == 2;
         }
@@ -383,6 +430,23 @@ int norm_row_params(const char *fn, int kind, int n, int pk, double tie_rel, con
     return FW_OK;
 }
 
+bool norm_kind_known(int kind)
+{
+    return kind == FW_FZ || kind == FW_FZ_NZ || kind == FW_MI || kind == FW_MI_NZ || kind == FW_NORM_TSS || kind == FW_NORM_TSS_BINNED;
+}
+
+// TSS: the Float32 row sums of the kept samples must be divisors -- positive and finite.  A kept sample has a Float64 sum > 0; its
+// Float32 sum is 0 only when every value vanishes as a Float32 (< 2^-150), and infinite only beyond the Float32 range: real-valued
+// tables alone, and the Python front-ends refuse such values by name before any device call.
+int norm_tss_sums_ok(const char *fn, const std::vector<int32_t> &rows, const std::vector<float> &s32)
+{
+    for (int i : rows)
+        if (!(s32[i] > 0.0f && s32[i] <= FLT_MAX))
+            return fw_fail(nullptr, FW_ERR_ARG, "%s: the Float32 sum of sample %d is %s: total-sum scaling needs values within the Float32 range",
+                           fn, i, s32[i] > 0.0f ? "infinite" : "zero");
+    return FW_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -394,15 +458,15 @@ int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t 
 {
     if (!counts || !row_mask || !col_mask || !n_out || !p_out || n <= 0 || p <= 0)
         return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
-    if (kind != FW_FZ && kind != FW_FZ_NZ && kind != FW_MI && kind != FW_MI_NZ)
-        return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
-    const bool discrete = kind == FW_MI || kind == FW_MI_NZ;
+    if (!norm_kind_known(kind)) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
+    const bool discrete = kind == FW_MI || kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED;
+    const bool tss = kind == FW_NORM_TSS || kind == FW_NORM_TSS_BINNED;
     if (discrete ? !out_i32 : !out_f32) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
     int rc = FW_OK;
     V *d_x = nullptr, *d_cmin = nullptr, *d_cmax = nullptr, *d_rmin = nullptr;
     int32_t *d_cols = nullptr, *d_rows = nullptr, *d_rzero = nullptr, *d_two = nullptr, *d_oi = nullptr, *d_tmp = nullptr, *d_sel = nullptr;
     double *d_rsum = nullptr, *d_rlog = nullptr, *d_pseudo = nullptr, *d_g = nullptr, *d_keys = nullptr;
-    float *d_of = nullptr;
+    float *d_of = nullptr, *d_s32 = nullptr;
     std::vector<V> cmin((size_t)p), cmax((size_t)p), rmin;
     std::vector<int32_t> cols, rows, rzero;
     std::vector<double> rsum, rlog;
@@ -465,6 +529,14 @@ int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t 
         nk = (int)rows.size();
         NHIP(hipMalloc((void **)&d_rows, sizeof(int32_t) * nk));
         NHIP(hipMemcpy(d_rows, rows.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice));
+        if (tss) {  // the Float32 row sums, in their own order (the Float64 chunk partials above gave the row filter only)
+            std::vector<float> s32((size_t)n);
+            NHIP(hipMalloc((void **)&d_s32, sizeof(float) * (size_t)n));
+            hipLaunchKernelGGL(norm_row_tss_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_x, n, d_cols, pk, d_s32);
+            NHIP(hipGetLastError());
+            NHIP(hipMemcpy(s32.data(), d_s32, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+            if ((rc = norm_tss_sums_ok(fn, rows, s32))) goto done;
+        }
         if (kind == FW_MI) {
             // presabs_norm! + columns with exactly two levels among the kept samples
             NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * pk));
@@ -490,7 +562,8 @@ int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t 
             hipLaunchKernelGGL(norm_binary_out_kernel<V>, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_oi);
             NHIP(hipGetLastError());
             NHIP(hipMemcpy(out_i32, d_oi, sizeof(int32_t) * (size_t)nk * pk, hipMemcpyDeviceToHost));
-        } else if (kind == FW_MI_NZ) {
+        } else if (kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED) {
+            const auto binned = kind == FW_MI_NZ ? norm_binned_kernel<V, false> : norm_binned_kernel<V, true>;  // (the key: nb_key)
             int M = 2;
             while (M < nk) M <<= 1;
             const bool keys_in_lds = M <= NORM_BIN_MAX;  // beyond: one slice of device memory per workgroup
@@ -500,9 +573,9 @@ int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t 
             NHIP(hipMemcpy(d_g, g.data(), sizeof(double) * nk, hipMemcpyHostToDevice));
             NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * pk));
             NHIP(hipMalloc((void **)&d_tmp, sizeof(int32_t) * (size_t)nk * pk));
-            NHIP(hipFuncSetAttribute((const void *)norm_binned_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
-            hipLaunchKernelGGL(norm_binned_kernel<V>, dim3(bgrid), dim3(1024), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_x, n, d_rows, nk, d_cols, pk,
-                               d_g, d_tmp, d_two, M, d_keys);
+            NHIP(hipFuncSetAttribute((const void *)binned, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
+            hipLaunchKernelGGL(binned, dim3(bgrid), dim3(1024), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_x, n, d_rows, nk, d_cols, pk,
+                               d_g, d_s32, d_tmp, d_two, M, d_keys);
             NHIP(hipGetLastError());
             std::vector<int32_t> two((size_t)pk), sel;
             NHIP(hipMemcpy(two.data(), d_two, sizeof(int32_t) * pk, hipMemcpyDeviceToHost));
@@ -523,6 +596,12 @@ int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t 
             hipLaunchKernelGGL(norm_gather_cols_kernel, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_tmp, d_sel, nk, pk, d_oi);
             NHIP(hipGetLastError());
             NHIP(hipMemcpy(out_i32, d_oi, sizeof(int32_t) * (size_t)nk * pk, hipMemcpyDeviceToHost));
+        } else if (kind == FW_NORM_TSS) {
+            NHIP(hipMalloc((void **)&d_of, sizeof(float) * (size_t)nk * pk));
+            hipLaunchKernelGGL(norm_tss_out_kernel<V>, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_s32,
+                               d_of);
+            NHIP(hipGetLastError());
+            NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * (size_t)nk * pk, hipMemcpyDeviceToHost));
         } else {
             NHIP(hipMalloc((void **)&d_pseudo, sizeof(double) * nk));
             NHIP(hipMalloc((void **)&d_g, sizeof(double) * nk));
@@ -538,7 +617,7 @@ int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t 
         *p_out = pk;
     }
 done:
-    void *ptrs[] = {d_x, d_cmin, d_cmax, d_cols, d_rows, d_rzero, d_rmin, d_two, d_oi, d_tmp, d_sel, d_rsum, d_rlog, d_pseudo, d_g, d_of, d_keys};
+    void *ptrs[] = {d_x, d_cmin, d_cmax, d_cols, d_rows, d_rzero, d_rmin, d_two, d_oi, d_tmp, d_sel, d_rsum, d_rlog, d_pseudo, d_g, d_of, d_keys, d_s32};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     return rc;
@@ -578,6 +657,9 @@ extern "C" int fw_normalize_abund(int32_t device, int32_t kind, int32_t n, int32
 // a chunk without entries contributes a partial of +0.0: neither changes a bit, so adding the stored terms in column order with a
 // fresh partial at every chunk boundary gives the same Float64 totals.  The per-row parameters come from the same host code
 // (norm_row_params), the values from the same device expressions.
+// The TSS kinds: csc_row_stats_kernel also adds the run's values as Float32, in the run's order -- the stable sort keeps a row's
+// entries in ascending column order, so this is norm_row_tss_kernel's sum without its +0.0f terms (4 B written per row);
+// csc_binned_kernel takes the Float32 quotient as its key, csc_emit_kernel writes it (sparse Float32 output, like FW_FZ_NZ).
 namespace {
 
 template <typename V> struct CscPay;
@@ -640,7 +722,7 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
                                                             const V *__restrict__ nzval, const uint32_t *__restrict__ ecol,
                                                             long long nnz, int n, const int32_t *__restrict__ colq, int pk,
                                                             double *__restrict__ S, double *__restrict__ SL, int32_t *__restrict__ CNT,
-                                                            V *__restrict__ MN)
+                                                            V *__restrict__ MN, float *__restrict__ S32)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -654,6 +736,7 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
     }
     const int per = (pk + NORM_CHUNKS - 1) / NORM_CHUNKS;
     double s = 0.0, sl = 0.0, cs = 0.0, csl = 0.0;
+    float s32 = 0.0f;  // TSS: norm_row_tss_kernel's sum -- the run holds the row's stored terms in ascending column order
     int cc = 0, cnt = 0;
     V mn = NormVal<V>::vmax();
     for (long long e = lo; e < nnz && krow[e] == (uint32_t)i; ++e) {
@@ -670,6 +753,7 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
         }
         cs += (double)v;
         csl += log((double)v);
+        s32 += (float)v;
         ++cnt;
         mn = v < mn ? v : mn;
     }
@@ -677,6 +761,7 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
     SL[i] = sl + csl;
     CNT[i] = cnt;
     MN[i] = mn;
+    if (S32) S32[i] = s32;
 }
 
 // binned_nz_clr, one workgroup per kept column: norm_binned_kernel with the keys read from the column's stored run (every entry
@@ -684,11 +769,12 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
 // length of the longest kept column (sizes the key storage), each column sorts its own power of two.  One kernel for both
 // launch shapes (256 threads while M <= 2 048, the HE case; 1 024 beyond): the bound of 1 024 caps it at 128 VGPRs, it uses 66, so
 // the short form loses no occupancy to the cap.
-template <typename V>
+template <typename V, bool TSS>
 __global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
                                                           const V *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
                                                           const int32_t *__restrict__ rownew, const double *__restrict__ gmean,
-                                                          int32_t *__restrict__ bins, int32_t *__restrict__ two, int M, double *gkeys)
+                                                          const float *__restrict__ rsum32, int32_t *__restrict__ bins,
+                                                          int32_t *__restrict__ two, int M, double *gkeys)
 {
     extern __shared__ double s_key_lds[];
     __shared__ int s_b1, s_b2;
@@ -701,13 +787,13 @@ __global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restr
         while (Mq < m) Mq <<= 1;
         __syncthreads();  // (the previous column's last readers of the keys / s_b1 / s_b2)
         if (tid == 0) s_b1 = s_b2 = 0;
-        for (int k = tid; k < m; k += nt) K.st(k, log((double)nzval[a + k] / gmean[rownew[rowval[a + k]]]));
+        for (int k = tid; k < m; k += nt) K.st(k, nb_key<TSS>(nzval[a + k], gmean, rownew[rowval[a + k]], rsum32, rowval[a + k]));
         K.sync();
         nb_pad_sort(K, m, Mq, tid, nt);
         const double rmax = nb_rank_max(K, m);
         int b1 = 0, b2 = 0;
         for (int k = tid; k < m; k += nt) {
-            const int bin = nb_bin(K, m, rmax, log((double)nzval[a + k] / gmean[rownew[rowval[a + k]]]));
+            const int bin = nb_bin(K, m, rmax, nb_key<TSS>(nzval[a + k], gmean, rownew[rowval[a + k]], rsum32, rowval[a + k]));
             b1 |= bin == 1;
             b2 |= bin == 2;
             bins[a + k] = bin;
@@ -720,12 +806,14 @@ __global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restr
 }
 
 // one wavefront per output column f = input column fcols[f]: rows renumbered, values by mode
-//   0 FW_MI: 1    1 FW_MI_NZ: bins[e]    2 FW_FZ_NZ: (float)log(x / g_row), as norm_clr_out_kernel's mode 1
+//   0 FW_MI: 1    1 FW_MI_NZ / FW_NORM_TSS_BINNED: bins[e]    2 FW_FZ_NZ: (float)log(x / g_row), as norm_clr_out_kernel's mode 1
+//   3 FW_NORM_TSS: (float)x / rsum32[input row], as norm_tss_out_kernel; a quotient that underflows to 0.0f stays a stored entry
 template <typename V>
 __global__ __launch_bounds__(256) void csc_emit_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
                                                        const V *__restrict__ nzval, const int32_t *__restrict__ fcols, int pf,
                                                        const int64_t *__restrict__ ocolptr, const int32_t *__restrict__ rownew,
-                                                       const double *__restrict__ gmean, const int32_t *__restrict__ bins, int mode,
+                                                       const double *__restrict__ gmean, const float *__restrict__ rsum32,
+                                                       const int32_t *__restrict__ bins, int mode,
                                                        int32_t *__restrict__ orow, int32_t *__restrict__ oi, float *__restrict__ of)
 {
     const int lane = threadIdx.x & 63, f = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -739,8 +827,10 @@ __global__ __launch_bounds__(256) void csc_emit_kernel(const int64_t *__restrict
             oi[dst + k] = 1;
         else if (mode == 1)
             oi[dst + k] = bins[a + k];
-        else
+        else if (mode == 2)
             of[dst + k] = (float)log((double)nzval[a + k] / gmean[r]);
+        else
+            of[dst + k] = (float)nzval[a + k] / rsum32[rowval[a + k]];
     }
 }
 
@@ -784,8 +874,9 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
     const bool indexed = sizeof(Pay) == sizeof(uint32_t);  // (Float64: the payload is the entry's index, the column sits in d_ecol)
     if (!colptr || !row_mask || !col_mask || !n_out || !p_out || !nnz_out || n <= 0 || p <= 0)
         return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
-    if (kind != FW_FZ && kind != FW_FZ_NZ && kind != FW_MI && kind != FW_MI_NZ) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
-    const bool discrete = kind == FW_MI || kind == FW_MI_NZ;
+    if (!norm_kind_known(kind)) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
+    const bool discrete = kind == FW_MI || kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED;
+    const bool tss = kind == FW_NORM_TSS || kind == FW_NORM_TSS_BINNED;
     if ((discrete ? !out_i32 : !out_f32) || (kind != FW_FZ && (!out_colptr || !out_rowval)))
         return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
     const long long nnz = colptr[p];
@@ -800,7 +891,7 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
     uint32_t *d_krow = nullptr, *d_ecol = nullptr;
     Pay *d_pay = nullptr, *d_pay2 = nullptr;
     double *d_S = nullptr, *d_SL = nullptr, *d_pseudo = nullptr, *d_g = nullptr, *d_keys = nullptr;
-    float *d_of = nullptr;
+    float *d_of = nullptr, *d_s32 = nullptr;
     void *d_tmp = nullptr;
     const unsigned wgrid_p = (unsigned)((p + 3) / 4);
     {
@@ -851,7 +942,9 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
         NHIP(hipMalloc((void **)&d_SL, sizeof(double) * (size_t)n));
         NHIP(hipMalloc((void **)&d_cnt, sizeof(int32_t) * (size_t)n));
         NHIP(hipMalloc((void **)&d_mn, sizeof(V) * (size_t)n));
-        hipLaunchKernelGGL(csc_row_stats_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow, d_pay2, d_nzval, d_ecol, nnz, n, d_colq, pk, d_S, d_SL, d_cnt, d_mn);
+        if (tss) NHIP(hipMalloc((void **)&d_s32, sizeof(float) * (size_t)n));
+        hipLaunchKernelGGL(csc_row_stats_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow, d_pay2, d_nzval, d_ecol, nnz, n, d_colq, pk, d_S, d_SL, d_cnt, d_mn,
+                           d_s32);
         NHIP(hipGetLastError());
         std::vector<double> S((size_t)n), SL((size_t)n), pseudo, g;
         std::vector<int32_t> CNT((size_t)n), rows;
@@ -868,6 +961,11 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
         }
         if ((rc = norm_row_params(fn, kind, n, pk, NormVal<V>::tie_rel(pk), S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
         const int nk = (int)rows.size();
+        if (tss) {
+            std::vector<float> s32((size_t)n);
+            NHIP(hipMemcpy(s32.data(), d_s32, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+            if ((rc = norm_tss_sums_ok(fn, rows, s32))) goto done;
+        }
         std::vector<int32_t> rownew((size_t)n, -1);  // row renumbering: the prefix sum over the row mask, on the host (n entries, uploaded)
         for (int r = 0; r < nk; ++r) rownew[rows[r]] = r;
         NHIP(hipMalloc((void **)&d_rownew, sizeof(int32_t) * (size_t)n));
@@ -896,7 +994,7 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
         }
         // the sparse kinds: every entry of a kept column lies in a kept row, so a column keeps its stored length
         std::vector<int32_t> fcols;  // output columns, as input column ids
-        if (kind == FW_FZ_NZ) {
+        if (kind == FW_FZ_NZ || kind == FW_NORM_TSS) {
             fcols = cols;
         } else if (kind == FW_MI) {  // presabs_norm!: two levels among the kept samples <=> an absence among them
             for (int j : cols) {
@@ -910,6 +1008,7 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
                 goto done;
             }
         } else {
+            const auto binned = kind == FW_MI_NZ ? csc_binned_kernel<V, false> : csc_binned_kernel<V, true>;  // (the key: nb_key)
             int64_t mmax = 0;
             for (int j : cols) mmax = std::max(mmax, colptr[j + 1] - colptr[j]);
             int M = 2;
@@ -920,9 +1019,9 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
             if (!keys_in_lds) NHIP(hipMalloc((void **)&d_keys, sizeof(double) * (size_t)M * (size_t)bgrid));
             NHIP(hipMalloc((void **)&d_bins, sizeof(int32_t) * (size_t)nnz));
             NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * (size_t)pk));
-            NHIP(hipFuncSetAttribute((const void *)csc_binned_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
-            hipLaunchKernelGGL(csc_binned_kernel<V>, dim3(bgrid), dim3(bthreads), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_colptr, d_rowval, d_nzval,
-                               d_cols, pk, d_rownew, d_g, d_bins, d_two, M, d_keys);
+            NHIP(hipFuncSetAttribute((const void *)binned, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
+            hipLaunchKernelGGL(binned, dim3(bgrid), dim3(bthreads), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_colptr, d_rowval, d_nzval,
+                               d_cols, pk, d_rownew, d_g, d_s32, d_bins, d_two, M, d_keys);
             NHIP(hipGetLastError());
             std::vector<int32_t> two((size_t)pk);
             NHIP(hipMemcpy(two.data(), d_two, sizeof(int32_t) * (size_t)pk, hipMemcpyDeviceToHost));
@@ -950,7 +1049,7 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
         else
             NHIP(hipMalloc((void **)&d_of, sizeof(float) * onnz));
         hipLaunchKernelGGL(csc_emit_kernel<V>, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pf, d_ocolptr, d_rownew, d_g,
-                           d_bins, kind == FW_MI ? 0 : kind == FW_MI_NZ ? 1 : 2, d_orow, d_oi, d_of);
+                           d_s32, d_bins, kind == FW_MI ? 0 : (kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED) ? 1 : kind == FW_FZ_NZ ? 2 : 3, d_orow, d_oi, d_of);
         NHIP(hipGetLastError());
         NHIP(hipMemcpy(out_rowval, d_orow, sizeof(int32_t) * onnz, hipMemcpyDeviceToHost));
         if (discrete)
@@ -964,7 +1063,7 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
     }
 done:
     void *ptrs[] = {d_colptr, d_ocolptr, d_rowval, d_nzval, d_colstat, d_colq, d_cols, d_cnt, d_mn, d_rownew, d_bins, d_two, d_orow, d_oi,
-                    d_krow, d_ecol, d_pay, d_pay2, d_S, d_SL, d_pseudo, d_g, d_keys, d_of, d_tmp};
+                    d_krow, d_ecol, d_pay, d_pay2, d_S, d_SL, d_pseudo, d_g, d_keys, d_of, d_s32, d_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     return rc;

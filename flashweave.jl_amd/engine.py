@@ -5,10 +5,17 @@ from collections import namedtuple
 
 import numpy as np
 
+from .preprocess import norm_check
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 FW_MI, FW_MI_NZ, FW_FZ, FW_FZ_NZ = 0, 1, 2, 3
 FW_MAX_K = 7
 _KINDS = {"mi": FW_MI, "mi_nz": FW_MI_NZ, "fz": FW_FZ, "fz_nz": FW_FZ_NZ}
+# The two transforms of the normalisation front-end that are no test kinds (normalize_data's norm_mode; preprocess.TSS_NORMS):
+# the constants the fw_normalize_* entry points take as `kind`.
+FW_NORM_TSS, FW_NORM_TSS_BINNED = 4, 5
+_NORMS = {"tss": FW_NORM_TSS, "tss-nonzero-binned": FW_NORM_TSS_BINNED}
+TSS_MIN, TSS_MAX = 2.0 ** -126, 2.0 ** 96  # positive real values a TSS norm takes: (float)x > 0, and fewer than 2^31 of them sum finitely
 
 TestResult = namedtuple("TestResult", "stat pval df suff_power")  # src/types.jl:140-145
 
@@ -242,20 +249,40 @@ def as_csc(data, dtype):
                np.ascontiguousarray(v, dtype=dtype), (int(n), int(p)))
 
 
-def _normalize_csc(front_end, who, triple, test_name, device):
+def _front_end_kind(who, test_name, norm):
+    """The `kind` a fw_normalize_* entry point is called with: the test kind, or the constant of a TSS norm (preprocess.norm_check
+    says which test_name such a norm goes with)."""
+    if norm is None:
+        return _KINDS[test_name]
+    norm_check(who, test_name, norm)
+    return _NORMS[norm]
+
+
+def tss_range_defect(values):
+    """What keeps real values out of a TSS norm, as words for a refusal, or None: a positive value outside [2^-126, 2^96] (as a
+    Float32 it could vanish, or the Float32 sum of a sample could overflow)."""
+    v = np.asarray(values)
+    if v.size and v.dtype.kind == "f":
+        pos = v[v > 0]
+        if pos.size and (pos.min() < TSS_MIN or pos.max() > TSS_MAX):
+            return "a positive value outside [2^-126, 2^96] (%r)" % float(pos.min() if pos.min() < TSS_MIN else pos.max())
+    return None
+
+
+def _normalize_csc(front_end, who, triple, test_name, device, norm=None):
     """fw_normalize_counts_csc / fw_normalize_abund_csc (front_end) on the canonical triple -> (data, row_mask, col_mask)"""
     import scipy.sparse as sp
     L = load_library()
     colptr, rowval, nzval, (n, p) = triple
     if n <= 0 or p <= 0:
         raise ValueError("%s: counts must be a samples x OTUs matrix" % who)
-    kind = _KINDS[test_name]
+    kind = _front_end_kind(who, test_name, norm)
     nnz = int(colptr[-1])
     rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
     no, po, nz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     ocp, orow = np.zeros(p + 1, np.int64), np.zeros(max(nnz, 1), np.int32)
-    of = np.zeros(n * p if kind == FW_FZ else max(nnz, 1), np.float32) if kind in (FW_FZ, FW_FZ_NZ) else None
-    oi = np.zeros(max(nnz, 1), np.int32) if kind in (FW_MI, FW_MI_NZ) else None
+    of = np.zeros(n * p if kind == FW_FZ else max(nnz, 1), np.float32) if kind in (FW_FZ, FW_FZ_NZ, FW_NORM_TSS) else None
+    oi = np.zeros(max(nnz, 1), np.int32) if kind in (FW_MI, FW_MI_NZ, FW_NORM_TSS_BINNED) else None
     rc = front_end(device, kind, n, p, _ptr(colptr), _ptr(rowval), _ptr(nzval), _ptr(ocp), _ptr(orow), _ptr(oi), _ptr(of),
                    _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), C.byref(nz))
     if rc != 0:
@@ -269,15 +296,25 @@ def _normalize_csc(front_end, who, triple, test_name, device):
     return out, rm.astype(bool), cm.astype(bool)
 
 
-def normalize_counts(counts, test_name, device=0):
+def _norm_kw(norm):
+    """norm as a keyword for the next layer, only when one is given: a call without it is handed on as it always was."""
+    return {} if norm is None else {"norm": norm}
+
+
+def normalize_counts(counts, test_name, device=0, norm=None):
     """Normalisation front-end on the device (fw_normalize_counts): -> (data, row_mask, col_mask) like preprocess.normalize,
     for every test_name ("fz": clr_adapt, "fz_nz": clr_nz, "mi": binary, "mi_nz": binned_nz_clr).
     A scipy.sparse count table (or what as_csc returned) takes fw_normalize_counts_csc and stays sparse: data is then a
     scipy.sparse.csc_matrix (Int32 for "mi" / "mi_nz", Float32 for "fz_nz", where a stored 0.0 is a present count whose clr_nz value
-    is 0) and a dense array for "fz"; the values are the bits the dense table gives."""
+    is 0) and a dense array for "fz"; the values are the bits the dense table gives.
+    norm: "tss" (with test_name "fz") or "tss-nonzero-binned" (with "mi_nz") replaces the test's transform by total-sum scaling in
+    Float32 / by the binned ranks of its non-zero values, as preprocess.normalize(norm=...) computes them, bit for bit; a sparse table
+    comes back sparse for both (Float32 / Int32)."""
+    if norm is not None:
+        _front_end_kind("normalize_counts", test_name, norm)  # (an unknown or misplaced norm is refused before anything is loaded)
     L = load_library()
     if is_sparse(counts) or isinstance(counts, CSC):  # (any other tuple is a dense table, as before)
-        return _normalize_csc(L.fw_normalize_counts_csc, "normalize_counts", as_csc(counts, np.int32), test_name, device)
+        return _normalize_csc(L.fw_normalize_counts_csc, "normalize_counts", as_csc(counts, np.int32), test_name, device, **_norm_kw(norm))
     raw = np.asarray(counts)
     if raw.ndim != 2:
         raise ValueError("normalize_counts: counts must be a samples x OTUs matrix")
@@ -286,18 +323,18 @@ def normalize_counts(counts, test_name, device=0):
             raise TypeError("normalize_counts: the device front-end takes integer counts (got non-integral %s values)" % raw.dtype)
     if raw.size and (raw.min() < 0 or raw.max() > np.iinfo(np.int32).max):
         raise ValueError("normalize_counts: counts must lie in [0, 2^31 - 1]")
-    return _normalize_dense(L.fw_normalize_counts, np.asfortranarray(raw.astype(np.int32)), test_name, device)
+    return _normalize_dense(L.fw_normalize_counts, np.asfortranarray(raw.astype(np.int32)), test_name, device, **_norm_kw(norm))
 
 
-def _normalize_dense(front_end, x, test_name, device):
+def _normalize_dense(front_end, x, test_name, device, norm=None):
     """fw_normalize_counts / fw_normalize_abund (front_end) on the column-major table -> (data, row_mask, col_mask)"""
     L = load_library()
     n, p = x.shape
     rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
     no, po = C.c_int32(0), C.c_int32(0)
-    kind = _KINDS[test_name]
-    of = np.zeros(n * p, np.float32) if kind in (FW_FZ, FW_FZ_NZ) else None
-    oi = np.zeros(n * p, np.int32) if kind in (FW_MI, FW_MI_NZ) else None
+    kind = _front_end_kind("normalize", test_name, norm)
+    of = np.zeros(n * p, np.float32) if kind in (FW_FZ, FW_FZ_NZ, FW_NORM_TSS) else None
+    oi = np.zeros(n * p, np.int32) if kind in (FW_MI, FW_MI_NZ, FW_NORM_TSS_BINNED) else None
     rc = front_end(device, kind, n, p, _ptr(x), _ptr(of), _ptr(oi), _ptr(rm), _ptr(cm), C.byref(no), C.byref(po))
     if rc != 0:
         raise FlashWeaveError(rc, L.fw_last_error(None).decode())
@@ -315,13 +352,17 @@ def abundance_defect(values):
     return None
 
 
-def normalize_abundances(table, test_name, device=0):
+def normalize_abundances(table, test_name, device=0, norm=None):
     """normalize_counts for a real-valued table -- relative abundances, percentages, coverage-normalised counts, counts beyond
     2^31 - 1 -- on the device (fw_normalize_abund, fw_normalize_abund_csc): -> (data, row_mask, col_mask) in the forms normalize_counts
     returns.  The values are taken as Float64 (a dense array of booleans, integers or floats is widened, Float32 exactly; a sparse
     table goes through as_csc(table, np.float64)); a table of integers gives the bits normalize_counts gives.  A NaN, an infinite or a
-    negative value and a table that is not two-dimensional raise ValueError before any device call."""
+    negative value and a table that is not two-dimensional raise ValueError before any device call.
+    norm: as for normalize_counts; every value is rounded to Float32 first, and a positive value outside [2^-126, 2^96] raises
+    ValueError before any device call."""
     who = "normalize_abundances"
+    if norm is not None:
+        _front_end_kind(who, test_name, norm)
     sparse = is_sparse(table) or isinstance(table, CSC)
     if sparse:
         triple = as_csc(table, np.float64)
@@ -334,12 +375,15 @@ def normalize_abundances(table, test_name, device=0):
     defect = abundance_defect(values)
     if defect:
         raise ValueError("%s: the table holds %s: abundances are finite and >= 0" % (who, defect))
+    defect = tss_range_defect(values) if norm is not None else None
+    if defect:
+        raise ValueError("%s: norm=%r: the table holds %s" % (who, norm, defect))
     L = load_library()
     if not hasattr(L, "fw_normalize_abund"):
         raise FlashWeaveError(-2, "%s: the loaded library has no fw_normalize_abund (an older build)" % who)
     if sparse:
-        return _normalize_csc(L.fw_normalize_abund_csc, who, triple, test_name, device)
-    return _normalize_dense(L.fw_normalize_abund, values, test_name, device)
+        return _normalize_csc(L.fw_normalize_abund_csc, who, triple, test_name, device, **_norm_kw(norm))
+    return _normalize_dense(L.fw_normalize_abund, values, test_name, device, **_norm_kw(norm))
 
 
 class Engine:

@@ -7,6 +7,8 @@ variables: variance / zero-read filters (:367-409), then
   "mi_nz" -> binned_nz_clr  non-zero CLR, 2-bin median discretisation of the non-zeros (:492-521) -> int {0,1,2}
 Computation is in Float64 like the reference (clrnorm converts to Matrix{Float64}, :330-341); `prec` only
 selects the output type of the continuous mode (convert_to_target_prec, misc.jl:54-62).
+The two total-sum-scaling modes (normalize(norm=...), TSS_NORMS) are the exception: like the reference they compute in
+Float{prec} (tss()).
 """
 import numpy as np
 
@@ -131,6 +133,8 @@ def prepare_meta_block(md, mh, test_name, row_mask):
     or the columns a meta_mask marks in `data`): md, a samples x meta-variables Float64 matrix, follows the row mask of the OTU
     normalisation; columns that look continuous are discretised into 2 bins for the discrete tests; columns holding a zero are shifted
     by +1 for "fz_nz" (zeros mean "absent" there); zero-variance columns are dropped.  The caller's matrix is left alone.
+    A TSS norm comes with the test_name it goes with (TSS_NORMS): "tss" with "fz" -- a continuous norm, nothing is discretised or
+    shifted -- and "tss-nonzero-binned" with "mi_nz" -- discretised, not shifted.
     -> (Float64 matrix, names)"""
     md = md[row_mask]
     if test_name in ("mi", "mi_nz"):
@@ -145,19 +149,25 @@ def prepare_meta_block(md, mh, test_name, row_mask):
     return md[:, keep], [h for h, k in zip(mh, keep) if k]
 
 
-def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_header=None, make_onehot=True, normalizer=None):
+def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_header=None, make_onehot=True, normalizer=None, norm=None):
     """preprocess_data with a meta_mask (preprocessing.jl:412-563): OTU columns are normalised as in normalize(); meta
     variables are one-hot encoded, follow the row filters, are discretised into 2 bins for the discrete tests when they look
     continuous, are shifted by +1 for "fz_nz" if they hold zeros (zeros mean "absent" there), lose zero-variance columns
     and are appended.  A normalizer that hands back a CSC table (the device front-end on a sparse count table) gets the meta block
     appended in CSC form as well: Int32 levels / Float32 values, a zero is an absent entry, the OTU part's stored zeros stay stored.
+    norm (TSS_NORMS): the OTU columns take normalize(norm=...) -- a normalizer is expected to do the same -- and the meta variables
+    the rules of the test_name the norm goes with: never shifted, discretised under "tss-nonzero-binned" only.
     -> dict(data, header, meta_mask, row_mask)"""
+    norm_check("normalize_with_meta", test_name, norm)
     if make_onehot:
         md, mh = onehot(meta, meta_header)
     else:
         md, mh = np.asarray(meta, dtype=np.float64), list(meta_header or [""] * np.asarray(meta).shape[1])
     # normalizer: the OTU part on the device (engine.normalize_counts); the handful of meta columns stay here
-    data, row_mask, col_mask = normalizer(counts, test_name) if normalizer is not None else normalize(counts, test_name, prec=prec)
+    if normalizer is not None:
+        data, row_mask, col_mask = normalizer(counts, test_name)
+    else:
+        data, row_mask, col_mask = normalize(counts, test_name, prec=prec, **({} if norm is None else {"norm": norm}))
     md, mh = prepare_meta_block(md, mh, test_name, row_mask)
     if _is_csc(data):
         *otu, rows = _csc_parts(data)
@@ -171,11 +181,56 @@ def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_head
                 row_mask=row_mask)
 
 
-def normalize(counts, test_name, prec=32, tie_anchor=False):
-    """-> (data, row_mask, col_mask).  row/col masks refer to the input matrix.  tie_anchor: see adaptive_clr ("fz" only)."""
+# The two norm modes of normalize_data that no test_name selects (preprocessing.jl:660-684), and the test_name a table so normalised
+# is for: "tss" ("rows") is a continuous norm like clr_adapt, "tss-nonzero-binned" ("binned_nz_rows") a discrete one whose zeros are
+# absences like binned_nz_clr.  The test_name is what the meta variables follow (prepare_meta_block): under "tss" they are neither
+# discretised nor shifted, under "tss-nonzero-binned" continuous-looking ones go into 2 bins and none is shifted (:527-558).
+TSS_NORMS = {"tss": "fz", "tss-nonzero-binned": "mi_nz"}
+
+
+def norm_check(who, test_name, norm):
+    """norm: None, or one of TSS_NORMS together with the test_name it goes with; anything else raises ValueError."""
+    if norm is None:
+        return
+    if norm not in TSS_NORMS:
+        raise ValueError("%s: unsupported norm %r (%s)" % (who, norm, ", ".join(map(repr, TSS_NORMS))))
+    if test_name != TSS_NORMS[norm]:
+        raise ValueError("%s: norm=%r goes with test_name=%r, got %r" % (who, norm, TSS_NORMS[norm], test_name))
+
+
+def tss(data, prec=32):
+    """rownorm! on a table converted to Float{prec} (preprocessing.jl:348-361 after check_convert_sparse): every value as a
+    Float{prec}; s_i = the sum of sample i in that type, the columns added one after the other in ascending order from +0 (what
+    Base's sum(X, dims=2) does; numpy's sum(axis=1) is pairwise and gives other bits); x / s_i, one IEEE division.  Only + and /:
+    the device front-end returns the same bits."""
+    X = np.asarray(data).astype(np.float32 if prec == 32 else np.float64)
+    s = np.zeros(X.shape[0], dtype=X.dtype)
+    for j in range(X.shape[1]):
+        s = s + X[:, j]
+    with np.errstate(under="ignore"):  # (a quotient below the smallest normal number is a subnormal, as on the device)
+        return X / s[:, None]
+
+
+def normalize(counts, test_name, prec=32, tie_anchor=False, norm=None):
+    """-> (data, row_mask, col_mask).  row/col masks refer to the input matrix.  tie_anchor: see adaptive_clr ("fz" only).
+    norm (TSS_NORMS, with the test_name it goes with) replaces the test's transform, under the same filters:
+      "tss"                 tss() of the filtered table                                               -> Float{prec} dense
+      "tss-nonzero-binned"  the ranks, bins and column rule of "mi_nz" with the tss() value as the key; the non-zero mask is taken
+                            before the division (a quotient may underflow to 0)                      -> Int32 {0,1,2}"""
     counts = np.asarray(counts)
+    norm_check("normalize", test_name, norm)
     data, row_mask, col_mask = filter_by_variance(counts.astype(np.float64))
     cols = np.nonzero(col_mask)[0]
+    if norm == "tss":
+        return tss(data, prec), row_mask, col_mask
+    if norm == "tss-nonzero-binned":
+        nzm = data != 0
+        c = tss(data, prec).astype(np.float64)  # (widening keeps order and ties)
+        d = np.stack([discretize_nz(c[:, j], nzm[:, j]) for j in range(c.shape[1])], axis=1)
+        km = np.array([len(np.unique(d[d[:, j] != 0, j])) == 2 for j in range(d.shape[1])])
+        cm = np.zeros_like(col_mask)
+        cm[cols[km]] = True
+        return d[:, km].astype(np.int32), row_mask, cm
     if test_name == "fz":
         out, keep = adaptive_clr(data, tie_anchor=tie_anchor)
         rows = np.nonzero(row_mask)[0]

@@ -33,6 +33,10 @@ extern "C" {
 #define FW_MI_NZ 1
 #define FW_FZ 2
 #define FW_FZ_NZ 3 /* "fz_nz": FlashWeaveHE-S, zero-ignoring Fisher-z tests */
+/* Not test kinds: two further transforms of the normalisation front-end, taken as `kind` by the four fw_normalize_* entry points
+ * only (fw_params.kind refuses them).  Additive: the ABI version stays. */
+#define FW_NORM_TSS 4        /* norm_mode "tss": total-sum scaling in Float32 */
+#define FW_NORM_TSS_BINNED 5 /* norm_mode "tss-nonzero-binned": the tied ranks of the non-zero TSS values in two bins */
 
 #define FW_OK 0
 #define FW_ERR_ARG (-1)     /* invalid argument */
@@ -389,7 +393,13 @@ int fw_rejections_allgather_stats(const fw_ctx *ctx, int64_t *packed_host, int64
  * column sort runs in LDS up to 16 384 samples and through device memory beyond).  counts: n x p column-major Int32.  Outputs (host buffers sized for n x p): out_f32 (FW_FZ / FW_FZ_NZ) or
  * out_i32 (FW_MI / FW_MI_NZ), column-major *n_out x *p_out; row_mask[n] / col_mask[p] = kept samples / variables.  No context
  * needed: create one with the resulting shape afterwards.  Meta variables (a handful of columns) are prepared by the caller
- * (one-hot, discretisation: preprocess.py) and appended. */
+ * (one-hot, discretisation: preprocess.py) and appended.
+ * kind may also be one of the two total-sum-scaling transforms (norm_mode of normalize_data, :660-684), under the same filters:
+ * FW_NORM_TSS ("rows", :348-361): out_f32 = (float)x / s_i, s_i the Float32 sum of sample i over the kept columns, added in ascending
+ * column order from +0.0f, one IEEE Float32 division per cell -- the arithmetic stays in Float32 as the reference's does.
+ * FW_NORM_TSS_BINNED ("binned_nz_rows", :492-521): out_i32 = FW_MI_NZ's ranks, bins and column rule with that quotient as the key.
+ * The CSC siblings return both sparse (FW_NORM_TSS: Float32 values, a quotient that underflows to 0 is a stored 0.0f).  A kept
+ * sample whose Float32 sum is 0 or infinite (real values outside the Float32 range) gives FW_ERR_ARG. */
 int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *counts, float *out_f32, int32_t *out_i32,
                         uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out);
 
