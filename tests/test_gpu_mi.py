@@ -1,7 +1,8 @@
 """GPU parity tests of the discrete (FlashWeave-F "mi" / FlashWeaveHE-F "mi_nz") HIP path against the CPU oracle,
 through the C ABI.  Integer outputs (df, suff_power, test counts, edge sets, conditioning sets) are compared
 bit-exact; MI statistics within 1e-12 relative (fp64 summation order / device log), p-values within 1e-10
-relative (device lgamma / exp in the incomplete gamma function)."""
+relative (device lgamma / exp in the incomplete gamma function).
+Sample counts on and next to the switches between kernel forms live in tests/test_gpu_mi_edges.py."""
 import numpy as np
 import pytest
 
