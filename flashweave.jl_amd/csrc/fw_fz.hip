@@ -1665,69 +1665,50 @@ int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32
     FW_HIP(ctx, (rocprim::exclusive_scan(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, cells, rocprim::plus<uint32_t>(), ctx->stream)));
     if ((rc = fw_dev_reserve(ctx, ctx->d_tmp2, std::max<size_t>(scan_bytes, 1)))) return rc;
     // the new layout is built beside whatever the context holds and takes its place only when the triple is good
-    unsigned long long *plane = nullptr;
-    uint32_t *base = nullptr;
-    float *vals = nullptr;
-    auto drop = [&]() {
-        if (plane) (void)hipFree(plane);
-        if (base) (void)hipFree(base);
-        if (vals) (void)hipFree(vals);
-    };
-#define FZNZ_RES_HIP(call)                                                                                                         \
-    do {                                                                                                                           \
-        hipError_t e__ = (call);                                                                                                   \
-        if (e__ != hipSuccess) {                                                                                                   \
-            drop();                                                                                                                \
-            return fw_fail(ctx, e__ == hipErrorOutOfMemory ? FW_ERR_NOMEM : FW_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), \
-                           __FILE__, __LINE__);                                                                                    \
-        }                                                                                                                          \
-    } while (0)
-    FZNZ_RES_HIP(hipMalloc((void **)&plane, sizeof(unsigned long long) * cells));
-    FZNZ_RES_HIP(hipMalloc((void **)&base, sizeof(uint32_t) * cells));
+    // (owned here until the install step, so a refused triple leaves the context as it was; out of memory is FW_ERR_NOMEM: FW_HIP_MEM)
+    FwDevArray<unsigned long long> plane;
+    FwDevArray<uint32_t> base;
+    FwDevArray<float> vals;
+    FW_HIP_MEM(ctx, plane.alloc(cells));
+    FW_HIP_MEM(ctx, base.alloc(cells));
     char *B = (char *)ctx->d_tmp1.ptr;
-    FZNZ_RES_HIP(hipMemcpyAsync(B, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice, ctx->stream));
+    FW_HIP_MEM(ctx, hipMemcpyAsync(B, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice, ctx->stream));
     if (nnz > 0) {
-        FZNZ_RES_HIP(hipMemcpyAsync(B + o_row, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-        FZNZ_RES_HIP(hipMemcpyAsync(B + o_val, nzval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        FW_HIP_MEM(ctx, hipMemcpyAsync(B + o_row, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        FW_HIP_MEM(ctx, hipMemcpyAsync(B + o_val, nzval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
     }
-    FZNZ_RES_HIP(hipMemsetAsync(B + o_tot, 0, sizeof(unsigned long long), ctx->stream));
+    FW_HIP_MEM(ctx, hipMemsetAsync(B + o_tot, 0, sizeof(unsigned long long), ctx->stream));
     const dim3 grid((unsigned)((p + 3) / 4));
     hipLaunchKernelGGL(fznz_cscres_plane_kernel, grid, dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val),
-                       n, p, W, nnz, plane, base, (int32_t *)(B + o_stat), (unsigned long long *)(B + o_tot));
-    FZNZ_RES_HIP(hipGetLastError());
+                       n, p, W, nnz, plane.get(), base.get(), (int32_t *)(B + o_stat), (unsigned long long *)(B + o_tot));
+    FW_HIP_MEM(ctx, hipGetLastError());
     std::vector<int32_t> colstat((size_t)p);
     unsigned long long nvals = 0;
-    FZNZ_RES_HIP(hipMemcpyAsync(colstat.data(), B + o_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
-    FZNZ_RES_HIP(hipMemcpyAsync(&nvals, B + o_tot, sizeof(nvals), hipMemcpyDeviceToHost, ctx->stream));
-    FZNZ_RES_HIP(hipStreamSynchronize(ctx->stream));
+    FW_HIP_MEM(ctx, hipMemcpyAsync(colstat.data(), B + o_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP_MEM(ctx, hipMemcpyAsync(&nvals, B + o_tot, sizeof(nvals), hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP_MEM(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cnt.kernel_launches += 1;
     for (int j = 0; j < p; ++j)
-        if (colstat[j]) {
-            drop();
-            return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32_resident: column %d: %s", j, fw_csc_reason(colstat[j]));
-        }
-    if (nvals >= (1ull << 32)) {
-        drop();
+        if (colstat[j]) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32_resident: column %d: %s", j, fw_csc_reason(colstat[j]));
+    if (nvals >= (1ull << 32))
         return fw_fail(ctx, FW_ERR_LIMIT, "fw_set_data_csc_f32_resident: %llu values != 0 exceed the 32-bit positions of the CSC-resident layout", nvals);
-    }
     // (vals holds at least one float: position 0 stands in for an absent entry in fw_cscres_word_value)
-    FZNZ_RES_HIP(hipMalloc((void **)&vals, sizeof(float) * (size_t)std::max<unsigned long long>(nvals, 1)));
-    if (nvals == 0) FZNZ_RES_HIP(hipMemsetAsync(vals, 0, sizeof(float), ctx->stream));
-    FZNZ_RES_HIP((rocprim::exclusive_scan(ctx->d_tmp2.ptr, scan_bytes, (const uint32_t *)base, base, 0u, cells, rocprim::plus<uint32_t>(), ctx->stream)));
+    FW_HIP_MEM(ctx, vals.alloc((size_t)std::max<unsigned long long>(nvals, 1)));
+    if (nvals == 0) FW_HIP_MEM(ctx, hipMemsetAsync(vals.get(), 0, sizeof(float), ctx->stream));
+    FW_HIP_MEM(ctx, (rocprim::exclusive_scan(ctx->d_tmp2.ptr, scan_bytes, (const uint32_t *)base.get(), base.get(), 0u, cells, rocprim::plus<uint32_t>(), ctx->stream)));
     hipLaunchKernelGGL(fznz_cscres_compact_kernel, grid, dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val), p,
-                       W, (const unsigned long long *)plane, (const uint32_t *)base, vals, nvals);
-    FZNZ_RES_HIP(hipGetLastError());
-    FZNZ_RES_HIP(hipStreamSynchronize(ctx->stream));
-#undef FZNZ_RES_HIP
+                       W, (const unsigned long long *)plane.get(), (const uint32_t *)base.get(), vals.get(), nvals);
+    FW_HIP_MEM(ctx, hipGetLastError());
+    FW_HIP_MEM(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cnt.kernel_launches += 2;
     // install: whatever either layout held before goes
     fznz_drop_cscres(ctx);
     if (ctx->d_data) (void)hipFree(ctx->d_data);
     ctx->d_data = nullptr;
     if (ctx->d_nzbits) (void)hipFree(ctx->d_nzbits);
-    ctx->d_nzbits = (uint64_t *)plane;
-    ctx->d_cbase = base;
-    ctx->d_cvals = vals;
+    ctx->d_nzbits = (uint64_t *)plane.release();
+    ctx->d_cbase = base.release();
+    ctx->d_cvals = vals.release();
     ctx->cvals_n = (int64_t)nvals;
     ctx->csc_resident = true;
     ctx->W = W;
@@ -2025,13 +2006,12 @@ __global__ void fz_selftest_div_kernel(unsigned long long cases, unsigned long l
 
 int fwi_selftest_div(fw_ctx *ctx, unsigned long long cases, unsigned long long seed, unsigned long long *mismatches)
 {
-    unsigned long long *d = nullptr;
-    FW_HIP(ctx, hipMalloc((void **)&d, 8));
-    FW_HIP(ctx, hipMemsetAsync(d, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(fz_selftest_div_kernel, dim3(4096), dim3(256), 0, ctx->stream, cases, seed, d);
+    FwDevArray<unsigned long long> d;
+    FW_HIP(ctx, d.alloc(1));
+    FW_HIP(ctx, hipMemsetAsync(d.get(), 0, 8, ctx->stream));
+    hipLaunchKernelGGL(fz_selftest_div_kernel, dim3(4096), dim3(256), 0, ctx->stream, cases, seed, d.get());
     FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipMemcpyAsync(mismatches, d, 8, hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP(ctx, hipMemcpyAsync(mismatches, d.get(), 8, hipMemcpyDeviceToHost, ctx->stream));
     FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d);
     return FW_OK;
 }

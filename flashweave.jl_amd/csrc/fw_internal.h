@@ -28,6 +28,51 @@ struct FwPinned {
     size_t cap = 0;
 };
 
+// A device array that owns its memory (move-only, hipFree in the destructor): the scratch of a host driver that returns on error.
+// The copies are the synchronous hipMemcpy on the null stream; the caller maps the hipError_t to its code (FW_HIP, FW_HIP_MEM).
+// release() hands the pointer on, e.g. into the context.
+template <typename T> class FwDevArray {
+    T *p_ = nullptr;
+
+public:
+    FwDevArray() = default;
+    FwDevArray(FwDevArray &&o) noexcept : p_(o.release()) {}
+    FwDevArray &operator=(FwDevArray &&o) noexcept
+    {
+        if (this != &o) {
+            if (p_) (void)hipFree(p_);
+            p_ = o.release();
+        }
+        return *this;
+    }
+    FwDevArray(const FwDevArray &) = delete;
+    FwDevArray &operator=(const FwDevArray &) = delete;
+    ~FwDevArray()
+    {
+        if (p_) (void)hipFree(p_);
+    }
+    hipError_t alloc(size_t count)
+    {
+        *this = FwDevArray();
+        return hipMalloc((void **)&p_, sizeof(T) * count);
+    }
+    hipError_t upload(const T *src, size_t count)
+    {
+        const hipError_t e = alloc(count);
+        return e != hipSuccess ? e : hipMemcpy(p_, src, sizeof(T) * count, hipMemcpyHostToDevice);
+    }
+    hipError_t upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
+    hipError_t download(T *dst, size_t count) const { return hipMemcpy(dst, p_, sizeof(T) * count, hipMemcpyDeviceToHost); }
+    hipError_t download(std::vector<T> &v) const { return download(v.data(), v.size()); }  // (v.size() elements)
+    T *get() const { return p_; }
+    T *release()
+    {
+        T *p = p_;
+        p_ = nullptr;
+        return p;
+    }
+};
+
 // Job descriptor for the test_subsets kernels (device layout)
 struct FwJob {
     int32_t X;        // T
@@ -257,6 +302,15 @@ int fw_pin_reserve(fw_ctx *ctx, FwPinned &b, size_t bytes);
         if (e__ != hipSuccess)                                                                   \
             return fw_fail(ctx, FW_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), \
                            __FILE__, __LINE__);                                                  \
+    } while (0)
+
+// FW_HIP where running out of device memory is a capacity answer (FW_ERR_NOMEM), not a device error
+#define FW_HIP_MEM(ctx, call)                                                                    \
+    do {                                                                                         \
+        hipError_t e__ = (call);                                                                 \
+        if (e__ != hipSuccess)                                                                   \
+            return fw_fail(ctx, e__ == hipErrorOutOfMemory ? FW_ERR_NOMEM : FW_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, \
+                           hipGetErrorString(e__), __FILE__, __LINE__);                          \
     } while (0)
 
 // ---- fz (fw_fz.hip) ----

@@ -25,18 +25,13 @@
 // dense and CSC form agree to the bit, and so do the ties among the quotients, which decide the tied ranks.  The Float64 chunk
 // partials of norm_row_stats_kernel are NOT s_i -- Float32 addition does not reassociate -- they only give the row filter.
 // One more pass over the kept cells for s_i (4 | 8 B read per cell, 4 B written per row), then 4 | 8 B read + 4 B written per cell.
-#include <cfloat>
-#include <cmath>
-#include <vector>
-
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "fw_csc.h"
 #include "fw_internal.h"
+#include "fw_norm_host.h"
 
 namespace {
-
-#define NORM_CHUNKS 64
 
 // What the value type is more than a type name for: the identities of min / max, the value check (a count is good when it is
 // >= 0; a real value when it is >= 0 and finite -- anything else reads as -1, so that the one "smallest value < 0" test of the
@@ -348,279 +343,165 @@ __global__ __launch_bounds__(256) void norm_gather_cols_kernel(const int32_t *__
 }
 
 #define NORM_GRID_Y 65535  // HIP's limit on grid.y: the per-column output kernels loop beyond it
+// ---- the host half: a driver is a sequence of stages (the filters: kept columns, then row totals -> kept samples; the output), each a
+// function that returns on error; device scratch lives in FwDevArray, the rules without device code in fw_norm_host.h.  NormCall: what the
+// stages share (fn: the entry point's name, for the messages) and leave for the next: kept columns (input ids), kept samples, TSS row sums.
+struct NormCall {
+    const char *fn;
+    int kind;
+    NormKind K;
+    int n;
+    uint8_t *row_mask, *col_mask;
+    std::vector<int32_t> cols;
+    NormRows R;
+    FwDevArray<int32_t> d_cols;
+    FwDevArray<float> d_s32;
+};
 
-#define NHIP(call)                                                                                           \
-    do {                                                                                                     \
-        hipError_t e__ = (call);                                                                             \
-        if (e__ != hipSuccess) {                                                                             \
-            rc = fw_fail(nullptr, FW_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
-            goto done;                                                                                       \
-        }                                                                                                    \
-    } while (0)
+dim3 norm_out_grid(int nk, int pk) { return dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)); }
+int norm_all_constant(const char *fn) { return fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn); }
+// the kind's own filter (norm_keep_columns) left nothing, or -- FW_FZ -- the pseudo-counts did
+int norm_none_left(const NormCall &c) { return fw_fail(nullptr, FW_ERR_ARG, "%s: %s", c.fn, c.K.none_left); }
 
-// Per-row totals over the kept columns -> kept samples and their parameters, on the host (n values each; shared by the dense
-// and the CSC front-end, so that both take the same libm calls on the same bits).  S read sum, SL sum of log over the non-zeros,
-// NZ number of zeros, RMIN smallest non-zero (as Float64, exact for either value type).  rows = samples with reads; FW_FZ: adaptive pseudo-counts (a sample whose
-// pseudo-count underflows to 0 is dropped) and the geometric mean of the filled row; FW_FZ_NZ / FW_MI_NZ: geometric mean of the
-// non-zeros.
-// tie_rel: the anchor of the pseudo-counts is the sample of maximal depth, and in a table of relative abundances every sample has
-// the depth 1 up to the rounding of its sum, so the largest Float64 sum would be picked by the order of the additions (the dense
-// and the CSC kernel, numpy and the reference each have their own).  Samples whose sums lie within tie_rel of the largest take part
-// and the first of them is the anchor.  Real values: pk * 2^-52, the bound |fl(sum) - sum| <= (pk - 1) 2^-53 sum of any order of
-// additions, on either side.  Not order-proof at the window's edge: the largest sum carries the rounding of this order too, so a
-// sample whose true depth lies about one bound below the maximum can fall inside under one order and outside under another;
-// samples of equal true depth (the relative-abundance case) are always inside.  Counts: 0 -- their sums are exact -- which is the
-// rule "first sample of maximal sum" as before.  The host front-end has the rule as preprocess.adaptive_clr(tie_anchor=True).
-int norm_row_params(const char *fn, int kind, int n, int pk, double tie_rel, const std::vector<double> &S, const std::vector<double> &SL,
-                    const std::vector<int64_t> &NZ, const std::vector<double> &RMIN, uint8_t *row_mask, std::vector<int32_t> &rows,
-                    std::vector<double> &pseudo, std::vector<double> &g)
+// row totals -> kept samples, pseudo-counts, geometric means and the TSS divisors (norm_row_params), a refusal in words
+int norm_rows(NormCall &c, double tie_rel, const NormTotals &T, const std::vector<float> &s32)
 {
-    rows.clear();
-    double min_abund = INFINITY;
-    for (int i = 0; i < n; ++i) {
-        row_mask[i] = S[i] > 0.0;  // sum(data, dims=2) .> 0
-        if (row_mask[i]) {
-            rows.push_back(i);
-            min_abund = std::min(min_abund, RMIN[i]);
-        }
-    }
-    int nk = (int)rows.size();
-    if (nk == 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: no sample has reads", fn);
-    pseudo.assign((size_t)nk, 0.0);
-    g.assign((size_t)nk, 1.0);
-    if (kind == FW_FZ) {  // adaptive_pseudocount! (:157-190): row of maximal depth as the anchor
-        double smax = 0.0;
-        for (int i : rows) smax = std::max(smax, S[i]);
-        int md = rows[0];
-        for (int i : rows)
-            if (S[i] >= smax * (1.0 - tie_rel)) {
-                md = i;
-                break;
-            }
-        const double base = min_abund >= 1.0 ? 1.0 : min_abund / 10.0;  // (counts: always 1; abundances below 1: a tenth of the smallest)
-        const double k = (double)NZ[md], P = (double)pk, Nprod1 = SL[md];
-        std::vector<int32_t> rows2;
-        std::vector<double> ps2;
-        for (int i : rows) {
-            const double nz = (double)NZ[i];
-            if (!(nz < P && k < P)) return fw_fail(nullptr, FW_ERR_ARG, "%s: samples with all zero abundances are not allowed", fn);
-            const double ps = std::exp((1.0 / (nz - P)) * ((k - P) * std::log(base) + Nprod1 - SL[i]));
-            if (ps != 0.0) {
-                rows2.push_back(i);
-                ps2.push_back(ps);
-            } else {
-                row_mask[i] = 0;
-            }
-        }
-        rows.swap(rows2);
-        nk = (int)rows.size();
-        pseudo.assign(ps2.begin(), ps2.end());
-        g.resize((size_t)nk);
-        for (int r = 0; r < nk; ++r) {  // clr!(pseudo_count = 0): geometric mean of the filled row
-            const int i = rows[r];
-            g[r] = std::exp((SL[i] + (double)NZ[i] * std::log(pseudo[r])) / P);
-        }
-    } else if (kind == FW_FZ_NZ || kind == FW_MI_NZ) {  // geometric mean of the non-zeros
-        for (int r = 0; r < nk; ++r) {
-            const int i = rows[r];
-            const double cnt = (double)pk - (double)NZ[i];
-            g[r] = cnt > 0 ? std::exp(SL[i] / cnt) : 1.0;
-        }
-    }
+    const NormRefusal no = norm_row_params(c.kind, c.n, (int)c.cols.size(), tie_rel, T, c.K.tss ? &s32 : nullptr, c.row_mask, c.R);
+    if (!no.reason) return FW_OK;
+    if (no.sample < 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: %s", c.fn, no.reason);
+    return fw_fail(nullptr, FW_ERR_ARG, "%s: the Float32 sum of sample %d is %s: total-sum scaling needs values within the Float32 range", c.fn, no.sample, no.reason);
+}
+
+// The launch shape of the binned kernels.  M = the padded length of the longest run of keys: dense the kept samples, on 1 024 threads;
+// CSC the longest kept column, on 256 | 1 024 threads (csc_binned_kernel).  The keys in LDS up to NORM_BIN_MAX, beyond in device memory.
+struct NormBinShape {
+    int M = 2, grid = 0, threads = 0;
+    FwDevArray<double> keys;  // (nullptr: the keys live in LDS, M doubles)
+    size_t lds() const { return keys.get() ? 0 : sizeof(double) * (size_t)M; }
+};
+int norm_bin_shape(const void *kernel, long long longest, int pk, bool dense, NormBinShape &B)
+{
+    while (B.M < longest) B.M <<= 1;
+    const bool keys_in_lds = B.M <= NORM_BIN_MAX;  // beyond: one slice of device memory per workgroup
+    B.grid = keys_in_lds ? pk : std::min(pk, 1024);
+    B.threads = dense || B.M > 2048 ? 1024 : 256;  // short columns (the HE case): more workgroups per CU instead of idle lanes
+    if (!keys_in_lds) FW_HIP(nullptr, B.keys.alloc((size_t)B.M * (size_t)B.grid));
+    FW_HIP(nullptr, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
     return FW_OK;
 }
 
-bool norm_kind_known(int kind)
+// The dense filters.  Columns: the value check and var(data, dims=1) .> 0.  Row totals over the kept columns: the chunk partials, reduced
+// on the host; TSS: the Float32 row sums in their own order (the Float64 partials give the row filter only).
+template <typename V> int dense_filters(NormCall &c, const V *d_x, int p)
 {
-    return kind == FW_FZ || kind == FW_FZ_NZ || kind == FW_MI || kind == FW_MI_NZ || kind == FW_NORM_TSS || kind == FW_NORM_TSS_BINNED;
+    const int n = c.n;
+    const size_t cn = (size_t)NORM_CHUNKS * n;
+    FwDevArray<V> d_cmin, d_cmax, d_rmin;
+    FwDevArray<double> d_rsum, d_rlog;
+    FwDevArray<int32_t> d_rzero;
+    std::vector<V> cmin((size_t)p), cmax((size_t)p), rmin(cn);
+    std::vector<double> rsum(cn), rlog(cn);
+    std::vector<int32_t> rzero(cn);
+    std::vector<float> s32(c.K.tss ? (size_t)n : 0);
+    FW_HIP(nullptr, d_cmin.alloc((size_t)p));
+    FW_HIP(nullptr, d_cmax.alloc((size_t)p));
+    hipLaunchKernelGGL(norm_col_minmax_kernel<V>, dim3(p), dim3(256), 0, 0, d_x, n, p, d_cmin.get(), d_cmax.get());
+    FW_HIP(nullptr, hipGetLastError());
+    FW_HIP(nullptr, d_cmin.download(cmin));
+    FW_HIP(nullptr, d_cmax.download(cmax));
+    for (int j = 0; j < p; ++j) {
+        if (cmin[j] < 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: %s in column %d", c.fn, NormVal<V>::bad(), j);
+        c.col_mask[j] = cmin[j] != cmax[j];  // var(data, dims=1) .> 0
+        if (c.col_mask[j]) c.cols.push_back(j);
+    }
+    const int pk = (int)c.cols.size();
+    if (pk == 0) return norm_all_constant(c.fn);
+    FW_HIP(nullptr, c.d_cols.upload(c.cols));
+    FW_HIP(nullptr, d_rsum.alloc(cn));
+    FW_HIP(nullptr, d_rlog.alloc(cn));
+    FW_HIP(nullptr, d_rzero.alloc(cn));
+    FW_HIP(nullptr, d_rmin.alloc(cn));
+    hipLaunchKernelGGL(norm_row_stats_kernel<V>, dim3((n + 255) / 256, NORM_CHUNKS), dim3(256), 0, 0, d_x, n, c.d_cols.get(), pk, d_rsum.get(), d_rzero.get(), d_rlog.get(), d_rmin.get());
+    FW_HIP(nullptr, hipGetLastError());
+    FW_HIP(nullptr, d_rsum.download(rsum));
+    FW_HIP(nullptr, d_rlog.download(rlog));
+    FW_HIP(nullptr, d_rzero.download(rzero));
+    FW_HIP(nullptr, d_rmin.download(rmin));
+    if (c.K.tss) {
+        FW_HIP(nullptr, c.d_s32.alloc((size_t)n));
+        hipLaunchKernelGGL(norm_row_tss_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_x, n, c.d_cols.get(), pk, c.d_s32.get());
+        FW_HIP(nullptr, hipGetLastError());
+        FW_HIP(nullptr, c.d_s32.download(s32));
+    }
+    return norm_rows(c, NormVal<V>::tie_rel(pk), norm_reduce_chunks(n, rsum, rlog, rzero, rmin), s32);
 }
 
-// TSS: the Float32 row sums of the kept samples must be divisors -- positive and finite.  A kept sample has a Float64 sum > 0; its
-// Float32 sum is 0 only when every value vanishes as a Float32 (< 2^-150), and infinite only beyond the Float32 range: real-valued
-// tables alone, and the Python front-ends refuse such values by name before any device call.
-int norm_tss_sums_ok(const char *fn, const std::vector<int32_t> &rows, const std::vector<float> &s32)
+// dense output: the kind's transform over the kept cells -> out_i32 | out_f32 (column-major, kept samples x the columns left in cols)
+template <typename V> int dense_output(NormCall &c, const V *d_x, float *out_f32, int32_t *out_i32)
 {
-    for (int i : rows)
-        if (!(s32[i] > 0.0f && s32[i] <= FLT_MAX))
-            return fw_fail(nullptr, FW_ERR_ARG, "%s: the Float32 sum of sample %d is %s: total-sum scaling needs values within the Float32 range",
-                           fn, i, s32[i] > 0.0f ? "infinite" : "zero");
+    const int n = c.n, nk = (int)c.R.rows.size(), pk = (int)c.cols.size();
+    FwDevArray<int32_t> d_rows, d_two, d_oi, d_tmp, d_sel;
+    FwDevArray<double> d_pseudo, d_g;
+    FwDevArray<float> d_of;
+    std::vector<int32_t> two((size_t)pk);
+    FW_HIP(nullptr, d_rows.upload(c.R.rows));
+    if (!c.K.i32) FW_HIP(nullptr, d_of.alloc((size_t)nk * pk));
+    if (c.K.i32 && !c.K.binned) {  // FW_MI: presabs_norm! + columns with exactly two levels among the kept samples
+        FW_HIP(nullptr, d_two.alloc((size_t)pk));
+        hipLaunchKernelGGL(norm_col_levels_kernel<V>, dim3(pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_two.get());
+        FW_HIP(nullptr, hipGetLastError());
+        FW_HIP(nullptr, d_two.download(two));
+        if (norm_keep_columns(two, c.cols, c.col_mask).empty()) return norm_none_left(c);
+        const int pf = (int)c.cols.size();
+        FW_HIP(nullptr, hipMemcpy(c.d_cols.get(), c.cols.data(), sizeof(int32_t) * pf, hipMemcpyHostToDevice));
+        FW_HIP(nullptr, d_oi.alloc((size_t)nk * pf));
+        hipLaunchKernelGGL(norm_binary_out_kernel<V>, norm_out_grid(nk, pf), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pf, d_oi.get());
+    } else if (c.K.binned) {  // every kept column is binned, then the columns that show both bins are gathered
+        const auto binned = !c.K.tss ? norm_binned_kernel<V, false> : norm_binned_kernel<V, true>;  // (the key: nb_key)
+        NormBinShape B;
+        if (int rc = norm_bin_shape((const void *)binned, nk, pk, true, B)) return rc;
+        FW_HIP(nullptr, d_g.upload(c.R.g));
+        FW_HIP(nullptr, d_two.alloc((size_t)pk));
+        FW_HIP(nullptr, d_tmp.alloc((size_t)nk * pk));
+        hipLaunchKernelGGL(binned, dim3(B.grid), dim3(B.threads), B.lds(), 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_g.get(), c.d_s32.get(), d_tmp.get(), d_two.get(), B.M, B.keys.get());
+        FW_HIP(nullptr, hipGetLastError());
+        FW_HIP(nullptr, d_two.download(two));
+        const std::vector<int32_t> sel = norm_keep_columns(two, c.cols, c.col_mask);
+        const int pf = (int)sel.size();
+        if (pf == 0) return norm_none_left(c);
+        FW_HIP(nullptr, d_sel.upload(sel));
+        FW_HIP(nullptr, d_oi.alloc((size_t)nk * pf));
+        hipLaunchKernelGGL(norm_gather_cols_kernel, norm_out_grid(nk, pf), dim3(256), 0, 0, d_tmp.get(), d_sel.get(), nk, pf, d_oi.get());
+    } else if (c.K.tss) {
+        hipLaunchKernelGGL(norm_tss_out_kernel<V>, norm_out_grid(nk, pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, c.d_s32.get(), d_of.get());
+    } else {
+        FW_HIP(nullptr, d_pseudo.upload(c.R.pseudo));
+        FW_HIP(nullptr, d_g.upload(c.R.g));
+        hipLaunchKernelGGL(norm_clr_out_kernel<V>, norm_out_grid(nk, pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_pseudo.get(), d_g.get(), c.K.clr_mode, d_of.get());
+    }
+    FW_HIP(nullptr, hipGetLastError());
+    if (c.K.i32) FW_HIP(nullptr, d_oi.download(out_i32, (size_t)nk * c.cols.size()));
+    if (!c.K.i32) FW_HIP(nullptr, d_of.download(out_f32, (size_t)nk * c.cols.size()));
     return FW_OK;
 }
-
-}  // namespace
-
-namespace {
 
 // The dense front-end for either value type (fn: the entry point's name, for the messages).
 template <typename V>
 int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const V *counts, float *out_f32, int32_t *out_i32,
                uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
 {
-    if (!counts || !row_mask || !col_mask || !n_out || !p_out || n <= 0 || p <= 0)
-        return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
-    if (!norm_kind_known(kind)) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
-    const bool discrete = kind == FW_MI || kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED;
-    const bool tss = kind == FW_NORM_TSS || kind == FW_NORM_TSS_BINNED;
-    if (discrete ? !out_i32 : !out_f32) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
-    int rc = FW_OK;
-    V *d_x = nullptr, *d_cmin = nullptr, *d_cmax = nullptr, *d_rmin = nullptr;
-    int32_t *d_cols = nullptr, *d_rows = nullptr, *d_rzero = nullptr, *d_two = nullptr, *d_oi = nullptr, *d_tmp = nullptr, *d_sel = nullptr;
-    double *d_rsum = nullptr, *d_rlog = nullptr, *d_pseudo = nullptr, *d_g = nullptr, *d_keys = nullptr;
-    float *d_of = nullptr, *d_s32 = nullptr;
-    std::vector<V> cmin((size_t)p), cmax((size_t)p), rmin;
-    std::vector<int32_t> cols, rows, rzero;
-    std::vector<double> rsum, rlog;
-    int pk = 0, nk = 0;
-    {
-        NHIP(hipSetDevice(device));
-        NHIP(hipMalloc((void **)&d_x, sizeof(V) * (size_t)n * p));
-        NHIP(hipMemcpy(d_x, counts, sizeof(V) * (size_t)n * p, hipMemcpyHostToDevice));
-        NHIP(hipMalloc((void **)&d_cmin, sizeof(V) * p));
-        NHIP(hipMalloc((void **)&d_cmax, sizeof(V) * p));
-        hipLaunchKernelGGL(norm_col_minmax_kernel<V>, dim3(p), dim3(256), 0, 0, d_x, n, p, d_cmin, d_cmax);
-        NHIP(hipGetLastError());
-        NHIP(hipMemcpy(cmin.data(), d_cmin, sizeof(V) * p, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(cmax.data(), d_cmax, sizeof(V) * p, hipMemcpyDeviceToHost));
-        for (int j = 0; j < p; ++j) {
-            if (cmin[j] < 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: %s in column %d", fn, NormVal<V>::bad(), j);
-                goto done;
-            }
-            col_mask[j] = cmin[j] != cmax[j];  // var(data, dims=1) .> 0
-            if (col_mask[j]) cols.push_back(j);
-        }
-        pk = (int)cols.size();
-        if (pk == 0) {
-            rc = fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
-            goto done;
-        }
-        NHIP(hipMalloc((void **)&d_cols, sizeof(int32_t) * pk));
-        NHIP(hipMemcpy(d_cols, cols.data(), sizeof(int32_t) * pk, hipMemcpyHostToDevice));
-        const size_t cn = (size_t)NORM_CHUNKS * n;
-        NHIP(hipMalloc((void **)&d_rsum, sizeof(double) * cn));
-        NHIP(hipMalloc((void **)&d_rlog, sizeof(double) * cn));
-        NHIP(hipMalloc((void **)&d_rzero, sizeof(int32_t) * cn));
-        NHIP(hipMalloc((void **)&d_rmin, sizeof(V) * cn));
-        hipLaunchKernelGGL(norm_row_stats_kernel<V>, dim3((n + 255) / 256, NORM_CHUNKS), dim3(256), 0, 0, d_x, n, d_cols, pk, d_rsum, d_rzero,
-                           d_rlog, d_rmin);
-        NHIP(hipGetLastError());
-        rsum.resize(cn);
-        rlog.resize(cn);
-        rzero.resize(cn);
-        rmin.resize(cn);
-        NHIP(hipMemcpy(rsum.data(), d_rsum, sizeof(double) * cn, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(rlog.data(), d_rlog, sizeof(double) * cn, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(rzero.data(), d_rzero, sizeof(int32_t) * cn, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(rmin.data(), d_rmin, sizeof(V) * cn, hipMemcpyDeviceToHost));
-        // chunk partials -> per-row totals, in chunk order (deterministic)
-        std::vector<double> S((size_t)n, 0.0), SL((size_t)n, 0.0);
-        std::vector<int64_t> NZ((size_t)n, 0);
-        for (int c = 0; c < NORM_CHUNKS; ++c)
-            for (int i = 0; i < n; ++i) {
-                S[i] += rsum[(size_t)c * n + i];
-                SL[i] += rlog[(size_t)c * n + i];
-                NZ[i] += rzero[(size_t)c * n + i];
-            }
-        std::vector<double> RMIN((size_t)n, INFINITY);
-        for (int c = 0; c < NORM_CHUNKS; ++c)
-            for (int i = 0; i < n; ++i) RMIN[i] = std::min(RMIN[i], (double)rmin[(size_t)c * n + i]);
-        std::vector<double> pseudo, g;
-        if ((rc = norm_row_params(fn, kind, n, pk, NormVal<V>::tie_rel(pk), S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
-        nk = (int)rows.size();
-        NHIP(hipMalloc((void **)&d_rows, sizeof(int32_t) * nk));
-        NHIP(hipMemcpy(d_rows, rows.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice));
-        if (tss) {  // the Float32 row sums, in their own order (the Float64 chunk partials above gave the row filter only)
-            std::vector<float> s32((size_t)n);
-            NHIP(hipMalloc((void **)&d_s32, sizeof(float) * (size_t)n));
-            hipLaunchKernelGGL(norm_row_tss_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_x, n, d_cols, pk, d_s32);
-            NHIP(hipGetLastError());
-            NHIP(hipMemcpy(s32.data(), d_s32, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-            if ((rc = norm_tss_sums_ok(fn, rows, s32))) goto done;
-        }
-        if (kind == FW_MI) {
-            // presabs_norm! + columns with exactly two levels among the kept samples
-            NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * pk));
-            hipLaunchKernelGGL(norm_col_levels_kernel<V>, dim3(pk), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_two);
-            NHIP(hipGetLastError());
-            std::vector<int32_t> two((size_t)pk);
-            NHIP(hipMemcpy(two.data(), d_two, sizeof(int32_t) * pk, hipMemcpyDeviceToHost));
-            std::vector<int32_t> cols2;
-            for (int q = 0; q < pk; ++q) {
-                if (two[q])
-                    cols2.push_back(cols[q]);
-                else
-                    col_mask[cols[q]] = 0;
-            }
-            cols.swap(cols2);
-            pk = (int)cols.size();
-            if (pk == 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column with two levels", fn);
-                goto done;
-            }
-            NHIP(hipMemcpy(d_cols, cols.data(), sizeof(int32_t) * pk, hipMemcpyHostToDevice));
-            NHIP(hipMalloc((void **)&d_oi, sizeof(int32_t) * (size_t)nk * pk));
-            hipLaunchKernelGGL(norm_binary_out_kernel<V>, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_oi);
-            NHIP(hipGetLastError());
-            NHIP(hipMemcpy(out_i32, d_oi, sizeof(int32_t) * (size_t)nk * pk, hipMemcpyDeviceToHost));
-        } else if (kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED) {
-            const auto binned = kind == FW_MI_NZ ? norm_binned_kernel<V, false> : norm_binned_kernel<V, true>;  // (the key: nb_key)
-            int M = 2;
-            while (M < nk) M <<= 1;
-            const bool keys_in_lds = M <= NORM_BIN_MAX;  // beyond: one slice of device memory per workgroup
-            const int bgrid = keys_in_lds ? pk : std::min(pk, 1024);
-            if (!keys_in_lds) NHIP(hipMalloc((void **)&d_keys, sizeof(double) * (size_t)M * (size_t)bgrid));
-            NHIP(hipMalloc((void **)&d_g, sizeof(double) * nk));
-            NHIP(hipMemcpy(d_g, g.data(), sizeof(double) * nk, hipMemcpyHostToDevice));
-            NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * pk));
-            NHIP(hipMalloc((void **)&d_tmp, sizeof(int32_t) * (size_t)nk * pk));
-            NHIP(hipFuncSetAttribute((const void *)binned, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
-            hipLaunchKernelGGL(binned, dim3(bgrid), dim3(1024), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_x, n, d_rows, nk, d_cols, pk,
-                               d_g, d_s32, d_tmp, d_two, M, d_keys);
-            NHIP(hipGetLastError());
-            std::vector<int32_t> two((size_t)pk), sel;
-            NHIP(hipMemcpy(two.data(), d_two, sizeof(int32_t) * pk, hipMemcpyDeviceToHost));
-            for (int q = 0; q < pk; ++q) {
-                if (two[q])
-                    sel.push_back(q);
-                else
-                    col_mask[cols[q]] = 0;
-            }
-            pk = (int)sel.size();
-            if (pk == 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column whose non-zero abundances fall into two bins", fn);
-                goto done;
-            }
-            NHIP(hipMalloc((void **)&d_sel, sizeof(int32_t) * pk));
-            NHIP(hipMemcpy(d_sel, sel.data(), sizeof(int32_t) * pk, hipMemcpyHostToDevice));
-            NHIP(hipMalloc((void **)&d_oi, sizeof(int32_t) * (size_t)nk * pk));
-            hipLaunchKernelGGL(norm_gather_cols_kernel, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_tmp, d_sel, nk, pk, d_oi);
-            NHIP(hipGetLastError());
-            NHIP(hipMemcpy(out_i32, d_oi, sizeof(int32_t) * (size_t)nk * pk, hipMemcpyDeviceToHost));
-        } else if (kind == FW_NORM_TSS) {
-            NHIP(hipMalloc((void **)&d_of, sizeof(float) * (size_t)nk * pk));
-            hipLaunchKernelGGL(norm_tss_out_kernel<V>, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_s32,
-                               d_of);
-            NHIP(hipGetLastError());
-            NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * (size_t)nk * pk, hipMemcpyDeviceToHost));
-        } else {
-            NHIP(hipMalloc((void **)&d_pseudo, sizeof(double) * nk));
-            NHIP(hipMalloc((void **)&d_g, sizeof(double) * nk));
-            NHIP(hipMemcpy(d_pseudo, pseudo.data(), sizeof(double) * nk, hipMemcpyHostToDevice));
-            NHIP(hipMemcpy(d_g, g.data(), sizeof(double) * nk, hipMemcpyHostToDevice));
-            NHIP(hipMalloc((void **)&d_of, sizeof(float) * (size_t)nk * pk));
-            hipLaunchKernelGGL(norm_clr_out_kernel<V>, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, d_x, n, d_rows, nk, d_cols, pk, d_pseudo, d_g,
-                               kind == FW_FZ ? 0 : 1, d_of);
-            NHIP(hipGetLastError());
-            NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * (size_t)nk * pk, hipMemcpyDeviceToHost));
-        }
-        *n_out = nk;
-        *p_out = pk;
-    }
-done:
-    void *ptrs[] = {d_x, d_cmin, d_cmax, d_cols, d_rows, d_rzero, d_rmin, d_two, d_oi, d_tmp, d_sel, d_rsum, d_rlog, d_pseudo, d_g, d_of, d_keys, d_s32};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    return rc;
+    if (!counts || !row_mask || !col_mask || !n_out || !p_out || n <= 0 || p <= 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
+    NormCall c{fn, kind, norm_kind(kind), n, row_mask, col_mask};
+    if (!c.K.known) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
+    if (c.K.i32 ? !out_i32 : !out_f32) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
+    FwDevArray<V> d_x;
+    FW_HIP(nullptr, hipSetDevice(device));
+    FW_HIP(nullptr, d_x.upload(counts, (size_t)n * p));
+    if (int rc = dense_filters(c, d_x.get(), p)) return rc;
+    if (int rc = dense_output(c, d_x.get(), out_f32, out_i32)) return rc;
+    *n_out = (int32_t)c.R.rows.size();
+    *p_out = (int32_t)c.cols.size();
+    return FW_OK;
 }
 
 }  // namespace
@@ -860,213 +741,159 @@ __global__ __launch_bounds__(256) void csc_adapt_scatter_kernel(const int64_t *_
     }
 }
 
-}  // namespace
+// The input triple on the device and, per entry, its payload for the sort by row (Float64: the entry's index, its column in ecol).
+template <typename V> struct CscDev {
+    FwDevArray<int64_t> colptr;
+    FwDevArray<int32_t> rowval;
+    FwDevArray<V> nzval;
+    FwDevArray<typename CscPay<V>::T> pay;
+    FwDevArray<uint32_t> ecol;
+};
 
-namespace {
+// The CSC filters.  Columns: structure and value check, var(data, dims=1) .> 0 (colq: input column -> its place in cols, or -1).  Row
+// totals: the CSR view (a stable sort of the entries by row; the payload: CscPay), then one thread per row over its run.
+template <typename V> int csc_filters(NormCall &c, int p, long long nnz, const int64_t *colptr, const int32_t *rowval, const V *nzval, CscDev<V> &D)
+{
+    typedef typename CscPay<V>::T Pay;
+    const int n = c.n;
+    FwDevArray<int32_t> d_colstat, d_colq, d_cnt;
+    FwDevArray<uint32_t> d_krow;
+    FwDevArray<Pay> d_pay2;
+    FwDevArray<char> d_tmp;
+    FwDevArray<double> d_S, d_SL;
+    FwDevArray<V> d_mn;
+    std::vector<int32_t> colstat((size_t)p), colq((size_t)p, -1), CNT((size_t)n);
+    std::vector<V> MN((size_t)n);
+    std::vector<float> s32(c.K.tss ? (size_t)n : 0);
+    NormTotals T{std::vector<double>((size_t)n), std::vector<double>((size_t)n), std::vector<double>((size_t)n), std::vector<int64_t>((size_t)n)};
+    FW_HIP(nullptr, D.colptr.upload(colptr, (size_t)p + 1));
+    FW_HIP(nullptr, D.rowval.upload(rowval, (size_t)nnz));
+    FW_HIP(nullptr, D.nzval.upload(nzval, (size_t)nnz));
+    FW_HIP(nullptr, d_colstat.alloc((size_t)p));
+    FW_HIP(nullptr, D.pay.alloc((size_t)nnz));
+    if (sizeof(Pay) == sizeof(uint32_t)) FW_HIP(nullptr, D.ecol.alloc((size_t)nnz));  // (Float64: the payload is the entry's index)
+    hipLaunchKernelGGL(csc_col_scan_kernel<V>, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), n, p, nnz, d_colstat.get(), D.pay.get(), D.ecol.get());
+    FW_HIP(nullptr, hipGetLastError());
+    FW_HIP(nullptr, d_colstat.download(colstat));
+    for (int j = 0; j < p; ++j) {
+        if (colstat[j] < 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: column %d: %s", c.fn, j, fw_csc_reason(-colstat[j]));
+        c.col_mask[j] = colstat[j] != 0;  // var(data, dims=1) .> 0
+        if (c.col_mask[j]) {
+            colq[j] = (int32_t)c.cols.size();
+            c.cols.push_back(j);
+        }
+    }
+    const int pk = (int)c.cols.size();
+    if (pk == 0) return norm_all_constant(c.fn);
+    int bits = 1;
+    while ((1ll << bits) < (long long)n) ++bits;
+    size_t tb = 0;
+    FW_HIP(nullptr, d_krow.alloc((size_t)nnz));
+    FW_HIP(nullptr, d_pay2.alloc((size_t)nnz));
+    FW_HIP(nullptr, (rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)D.rowval.get(), d_krow.get(), (const Pay *)D.pay.get(), d_pay2.get(), (size_t)nnz, 0u, (unsigned int)bits, (hipStream_t)0)));
+    FW_HIP(nullptr, d_tmp.alloc(tb ? tb : 1));
+    FW_HIP(nullptr, (rocprim::radix_sort_pairs((void *)d_tmp.get(), tb, (const uint32_t *)D.rowval.get(), d_krow.get(), (const Pay *)D.pay.get(), d_pay2.get(), (size_t)nnz, 0u, (unsigned int)bits, (hipStream_t)0)));
+    FW_HIP(nullptr, d_colq.upload(colq));
+    FW_HIP(nullptr, d_S.alloc((size_t)n));
+    FW_HIP(nullptr, d_SL.alloc((size_t)n));
+    FW_HIP(nullptr, d_cnt.alloc((size_t)n));
+    FW_HIP(nullptr, d_mn.alloc((size_t)n));
+    if (c.K.tss) FW_HIP(nullptr, c.d_s32.alloc((size_t)n));
+    hipLaunchKernelGGL(csc_row_stats_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow.get(), d_pay2.get(), D.nzval.get(), D.ecol.get(), nnz, n, d_colq.get(),
+                       pk, d_S.get(), d_SL.get(), d_cnt.get(), d_mn.get(), c.d_s32.get());
+    FW_HIP(nullptr, hipGetLastError());
+    FW_HIP(nullptr, d_S.download(T.S));
+    FW_HIP(nullptr, d_SL.download(T.SL));
+    FW_HIP(nullptr, d_cnt.download(CNT));
+    FW_HIP(nullptr, d_mn.download(MN));
+    if (c.K.tss) FW_HIP(nullptr, c.d_s32.download(s32));
+    for (int i = 0; i < n; ++i) {
+        T.NZ[i] = (int64_t)pk - CNT[i];
+        T.RMIN[i] = (double)MN[i];
+    }
+    return norm_rows(c, NormVal<V>::tie_rel(pk), T, s32);
+}
+
+// CSC output.  FW_FZ (clr_adapt): the dense matrix, pseudo-count cells first, the stored entries over them.  The sparse kinds: the
+// kind's own column filter, then the output triple (every entry of a kept column lies in a kept row: a column keeps its length).
+template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *colptr, const CscDev<V> &D, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, int64_t *nnz_out)
+{
+    const int nk = (int)c.R.rows.size(), pk = (int)c.cols.size();
+    FwDevArray<int32_t> d_rownew, d_bins, d_two, d_orow, d_oi;
+    FwDevArray<int64_t> d_ocolptr;
+    FwDevArray<double> d_g, d_pseudo;
+    FwDevArray<float> d_of;
+    std::vector<int32_t> two(c.K.binned ? (size_t)pk : 0);
+    if (nk == 0) return norm_none_left(c);  // (FW_FZ alone drops samples with reads)
+    FW_HIP(nullptr, d_rownew.upload(norm_rownew(c.n, c.R.rows)));
+    FW_HIP(nullptr, c.d_cols.upload(c.cols));
+    FW_HIP(nullptr, d_g.upload(c.R.g));
+    if (c.kind == FW_FZ) {
+        FW_HIP(nullptr, d_pseudo.upload(c.R.pseudo));
+        FW_HIP(nullptr, d_of.alloc((size_t)nk * pk));
+        hipLaunchKernelGGL(csc_adapt_fill_kernel, norm_out_grid(nk, pk), dim3(256), 0, 0, nk, pk, d_pseudo.get(), d_g.get(), d_of.get());
+        hipLaunchKernelGGL(csc_adapt_scatter_kernel<V>, dim3((unsigned)((pk + 3) / 4)), dim3(256), 0, 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), c.d_cols.get(), pk, d_rownew.get(), nk, d_g.get(), d_of.get());
+        FW_HIP(nullptr, hipGetLastError());
+        FW_HIP(nullptr, d_of.download(out_f32, (size_t)nk * pk));
+        *nnz_out = (int64_t)nk * pk;
+        return FW_OK;
+    }
+    if (c.K.binned) {
+        const auto binned = !c.K.tss ? csc_binned_kernel<V, false> : csc_binned_kernel<V, true>;  // (the key: nb_key)
+        int64_t mmax = 0;
+        for (int j : c.cols) mmax = std::max(mmax, colptr[j + 1] - colptr[j]);
+        NormBinShape B;
+        if (int rc = norm_bin_shape((const void *)binned, mmax, pk, false, B)) return rc;
+        FW_HIP(nullptr, d_bins.alloc((size_t)nnz));
+        FW_HIP(nullptr, d_two.alloc((size_t)pk));
+        hipLaunchKernelGGL(binned, dim3(B.grid), dim3(B.threads), B.lds(), 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), c.d_cols.get(), pk, d_rownew.get(),
+                           d_g.get(), c.d_s32.get(), d_bins.get(), d_two.get(), B.M, B.keys.get());
+        FW_HIP(nullptr, hipGetLastError());
+        FW_HIP(nullptr, d_two.download(two));
+    } else if (c.K.none_left) {  // FW_MI, presabs_norm!: two levels among the kept samples <=> an absence among them
+        for (int j : c.cols) two.push_back(colptr[j + 1] - colptr[j] < (int64_t)nk);
+    }
+    if (!two.empty() && norm_keep_columns(two, c.cols, c.col_mask).empty()) return norm_none_left(c);
+    const int pf = (int)c.cols.size();
+    const std::vector<int64_t> ocolptr = norm_out_colptr(colptr, c.cols);
+    const size_t onnz = (size_t)ocolptr[pf];
+    FW_HIP(nullptr, hipMemcpy(c.d_cols.get(), c.cols.data(), sizeof(int32_t) * (size_t)pf, hipMemcpyHostToDevice));
+    FW_HIP(nullptr, d_ocolptr.upload(ocolptr));
+    FW_HIP(nullptr, d_orow.alloc(onnz));
+    if (c.K.i32) FW_HIP(nullptr, d_oi.alloc(onnz));
+    if (!c.K.i32) FW_HIP(nullptr, d_of.alloc(onnz));
+    hipLaunchKernelGGL(csc_emit_kernel<V>, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), c.d_cols.get(), pf,
+                       d_ocolptr.get(), d_rownew.get(), d_g.get(), c.d_s32.get(), d_bins.get(), c.K.emit_mode, d_orow.get(), d_oi.get(), d_of.get());
+    FW_HIP(nullptr, hipGetLastError());
+    FW_HIP(nullptr, d_orow.download(out_rowval, onnz));
+    if (c.K.i32) FW_HIP(nullptr, d_oi.download(out_i32, onnz));
+    if (!c.K.i32) FW_HIP(nullptr, d_of.download(out_f32, onnz));
+    std::copy(ocolptr.begin(), ocolptr.end(), out_colptr);
+    *nnz_out = (int64_t)onnz;
+    return FW_OK;
+}
 
 // The CSC front-end for either value type (fn: the entry point's name, for the messages).
 template <typename V>
 int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval, const V *nzval,
-             int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out,
-             int32_t *p_out, int64_t *nnz_out)
+             int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
 {
-    typedef typename CscPay<V>::T Pay;
-    const bool indexed = sizeof(Pay) == sizeof(uint32_t);  // (Float64: the payload is the entry's index, the column sits in d_ecol)
-    if (!colptr || !row_mask || !col_mask || !n_out || !p_out || !nnz_out || n <= 0 || p <= 0)
-        return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
-    if (!norm_kind_known(kind)) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
-    const bool discrete = kind == FW_MI || kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED;
-    const bool tss = kind == FW_NORM_TSS || kind == FW_NORM_TSS_BINNED;
-    if ((discrete ? !out_i32 : !out_f32) || (kind != FW_FZ && (!out_colptr || !out_rowval)))
-        return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
+    if (!colptr || !row_mask || !col_mask || !n_out || !p_out || !nnz_out || n <= 0 || p <= 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
+    NormCall c{fn, kind, norm_kind(kind), n, row_mask, col_mask};
+    if (!c.K.known) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
+    if ((c.K.i32 ? !out_i32 : !out_f32) || (kind != FW_FZ && (!out_colptr || !out_rowval))) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
     const long long nnz = colptr[p];
     if (colptr[0] != 0 || nnz < 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: colptr must run from 0 to nnz (column 0)", fn);
     if (nnz > 0x7fffffffll) return fw_fail(nullptr, FW_ERR_LIMIT, "%s: %lld stored entries exceed the 32-bit entry index", fn, nnz);
     if (nnz > 0 && (!rowval || !nzval)) return fw_fail(nullptr, FW_ERR_ARG, "%s: NULL array", fn);
-    if (nnz == 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
-    int rc = FW_OK;
-    int64_t *d_colptr = nullptr, *d_ocolptr = nullptr;
-    V *d_nzval = nullptr, *d_mn = nullptr;
-    int32_t *d_rowval = nullptr, *d_colstat = nullptr, *d_colq = nullptr, *d_cols = nullptr, *d_cnt = nullptr, *d_rownew = nullptr, *d_bins = nullptr, *d_two = nullptr, *d_orow = nullptr, *d_oi = nullptr;
-    uint32_t *d_krow = nullptr, *d_ecol = nullptr;
-    Pay *d_pay = nullptr, *d_pay2 = nullptr;
-    double *d_S = nullptr, *d_SL = nullptr, *d_pseudo = nullptr, *d_g = nullptr, *d_keys = nullptr;
-    float *d_of = nullptr, *d_s32 = nullptr;
-    void *d_tmp = nullptr;
-    const unsigned wgrid_p = (unsigned)((p + 3) / 4);
-    {
-        NHIP(hipSetDevice(device));
-        NHIP(hipMalloc((void **)&d_colptr, sizeof(int64_t) * ((size_t)p + 1)));
-        NHIP(hipMalloc((void **)&d_rowval, sizeof(int32_t) * (size_t)nnz));
-        NHIP(hipMalloc((void **)&d_nzval, sizeof(V) * (size_t)nnz));
-        NHIP(hipMalloc((void **)&d_colstat, sizeof(int32_t) * (size_t)p));
-        NHIP(hipMalloc((void **)&d_pay, sizeof(Pay) * (size_t)nnz));
-        if (indexed) NHIP(hipMalloc((void **)&d_ecol, sizeof(uint32_t) * (size_t)nnz));
-        NHIP(hipMemcpy(d_colptr, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice));
-        NHIP(hipMemcpy(d_rowval, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-        NHIP(hipMemcpy(d_nzval, nzval, sizeof(V) * (size_t)nnz, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(csc_col_scan_kernel<V>, dim3(wgrid_p), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, n, p, nnz, d_colstat, d_pay, d_ecol);
-        NHIP(hipGetLastError());
-        std::vector<int32_t> colstat((size_t)p), cols, colq((size_t)p, -1);
-        NHIP(hipMemcpy(colstat.data(), d_colstat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost));
-        for (int j = 0; j < p; ++j) {
-            if (colstat[j] < 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: column %d: %s", fn, j, fw_csc_reason(-colstat[j]));
-                goto done;
-            }
-            col_mask[j] = colstat[j] != 0;  // var(data, dims=1) .> 0
-            if (col_mask[j]) {
-                colq[j] = (int32_t)cols.size();
-                cols.push_back(j);
-            }
-        }
-        int pk = (int)cols.size();
-        if (pk == 0) {
-            rc = fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn);
-            goto done;
-        }
-        // CSR view: stable sort of the entries by row (the payload carries column and count, or the entry's index: CscPay)
-        int bits = 1;
-        while ((1ll << bits) < (long long)n) ++bits;
-        size_t tb = 0;
-        NHIP(hipMalloc((void **)&d_krow, sizeof(uint32_t) * (size_t)nnz));
-        NHIP(hipMalloc((void **)&d_pay2, sizeof(Pay) * (size_t)nnz));
-        NHIP((rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)d_rowval, d_krow, (const Pay *)d_pay, d_pay2, (size_t)nnz, 0u,
-                                        (unsigned int)bits, (hipStream_t)0)));
-        NHIP(hipMalloc(&d_tmp, tb ? tb : 1));
-        NHIP((rocprim::radix_sort_pairs(d_tmp, tb, (const uint32_t *)d_rowval, d_krow, (const Pay *)d_pay, d_pay2, (size_t)nnz, 0u,
-                                        (unsigned int)bits, (hipStream_t)0)));
-        NHIP(hipMalloc((void **)&d_colq, sizeof(int32_t) * (size_t)p));
-        NHIP(hipMemcpy(d_colq, colq.data(), sizeof(int32_t) * (size_t)p, hipMemcpyHostToDevice));
-        NHIP(hipMalloc((void **)&d_S, sizeof(double) * (size_t)n));
-        NHIP(hipMalloc((void **)&d_SL, sizeof(double) * (size_t)n));
-        NHIP(hipMalloc((void **)&d_cnt, sizeof(int32_t) * (size_t)n));
-        NHIP(hipMalloc((void **)&d_mn, sizeof(V) * (size_t)n));
-        if (tss) NHIP(hipMalloc((void **)&d_s32, sizeof(float) * (size_t)n));
-        hipLaunchKernelGGL(csc_row_stats_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow, d_pay2, d_nzval, d_ecol, nnz, n, d_colq, pk, d_S, d_SL, d_cnt, d_mn,
-                           d_s32);
-        NHIP(hipGetLastError());
-        std::vector<double> S((size_t)n), SL((size_t)n), pseudo, g;
-        std::vector<int32_t> CNT((size_t)n), rows;
-        std::vector<V> MN((size_t)n);
-        NHIP(hipMemcpy(S.data(), d_S, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(SL.data(), d_SL, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(CNT.data(), d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-        NHIP(hipMemcpy(MN.data(), d_mn, sizeof(V) * (size_t)n, hipMemcpyDeviceToHost));
-        std::vector<int64_t> NZ((size_t)n);
-        std::vector<double> RMIN((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            NZ[i] = (int64_t)pk - CNT[i];
-            RMIN[i] = (double)MN[i];
-        }
-        if ((rc = norm_row_params(fn, kind, n, pk, NormVal<V>::tie_rel(pk), S, SL, NZ, RMIN, row_mask, rows, pseudo, g))) goto done;
-        const int nk = (int)rows.size();
-        if (tss) {
-            std::vector<float> s32((size_t)n);
-            NHIP(hipMemcpy(s32.data(), d_s32, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-            if ((rc = norm_tss_sums_ok(fn, rows, s32))) goto done;
-        }
-        std::vector<int32_t> rownew((size_t)n, -1);  // row renumbering: the prefix sum over the row mask, on the host (n entries, uploaded)
-        for (int r = 0; r < nk; ++r) rownew[rows[r]] = r;
-        NHIP(hipMalloc((void **)&d_rownew, sizeof(int32_t) * (size_t)n));
-        NHIP(hipMemcpy(d_rownew, rownew.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-        NHIP(hipMalloc((void **)&d_cols, sizeof(int32_t) * (size_t)pk));
-        NHIP(hipMemcpy(d_cols, cols.data(), sizeof(int32_t) * (size_t)pk, hipMemcpyHostToDevice));
-        NHIP(hipMalloc((void **)&d_g, sizeof(double) * (size_t)std::max(nk, 1)));
-        NHIP(hipMemcpy(d_g, g.data(), sizeof(double) * (size_t)nk, hipMemcpyHostToDevice));
-        if (kind == FW_FZ) {
-            if ((long long)nk * pk == 0) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no sample is left after the pseudo-counts", fn);
-                goto done;
-            }
-            NHIP(hipMalloc((void **)&d_pseudo, sizeof(double) * (size_t)nk));
-            NHIP(hipMemcpy(d_pseudo, pseudo.data(), sizeof(double) * (size_t)nk, hipMemcpyHostToDevice));
-            NHIP(hipMalloc((void **)&d_of, sizeof(float) * (size_t)nk * pk));
-            hipLaunchKernelGGL(csc_adapt_fill_kernel, dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)), dim3(256), 0, 0, nk, pk, d_pseudo, d_g, d_of);
-            hipLaunchKernelGGL(csc_adapt_scatter_kernel<V>, dim3((unsigned)((pk + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pk, d_rownew,
-                               nk, d_g, d_of);
-            NHIP(hipGetLastError());
-            NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * (size_t)nk * pk, hipMemcpyDeviceToHost));
-            *n_out = nk;
-            *p_out = pk;
-            *nnz_out = (int64_t)nk * pk;
-            goto done;
-        }
-        // the sparse kinds: every entry of a kept column lies in a kept row, so a column keeps its stored length
-        std::vector<int32_t> fcols;  // output columns, as input column ids
-        if (kind == FW_FZ_NZ || kind == FW_NORM_TSS) {
-            fcols = cols;
-        } else if (kind == FW_MI) {  // presabs_norm!: two levels among the kept samples <=> an absence among them
-            for (int j : cols) {
-                if (colptr[j + 1] - colptr[j] < (int64_t)nk)
-                    fcols.push_back(j);
-                else
-                    col_mask[j] = 0;
-            }
-            if (fcols.empty()) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column with two levels", fn);
-                goto done;
-            }
-        } else {
-            const auto binned = kind == FW_MI_NZ ? csc_binned_kernel<V, false> : csc_binned_kernel<V, true>;  // (the key: nb_key)
-            int64_t mmax = 0;
-            for (int j : cols) mmax = std::max(mmax, colptr[j + 1] - colptr[j]);
-            int M = 2;
-            while (M < mmax) M <<= 1;
-            const bool keys_in_lds = M <= NORM_BIN_MAX;  // beyond: one slice of device memory per workgroup
-            const int bgrid = keys_in_lds ? pk : std::min(pk, 1024);
-            const int bthreads = M <= 2048 ? 256 : 1024;  // short columns (the HE case): more workgroups per CU instead of idle lanes
-            if (!keys_in_lds) NHIP(hipMalloc((void **)&d_keys, sizeof(double) * (size_t)M * (size_t)bgrid));
-            NHIP(hipMalloc((void **)&d_bins, sizeof(int32_t) * (size_t)nnz));
-            NHIP(hipMalloc((void **)&d_two, sizeof(int32_t) * (size_t)pk));
-            NHIP(hipFuncSetAttribute((const void *)binned, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * NORM_BIN_MAX)));
-            hipLaunchKernelGGL(binned, dim3(bgrid), dim3(bthreads), keys_in_lds ? sizeof(double) * (size_t)M : 0, 0, d_colptr, d_rowval, d_nzval,
-                               d_cols, pk, d_rownew, d_g, d_s32, d_bins, d_two, M, d_keys);
-            NHIP(hipGetLastError());
-            std::vector<int32_t> two((size_t)pk);
-            NHIP(hipMemcpy(two.data(), d_two, sizeof(int32_t) * (size_t)pk, hipMemcpyDeviceToHost));
-            for (int q = 0; q < pk; ++q) {
-                if (two[q])
-                    fcols.push_back(cols[q]);
-                else
-                    col_mask[cols[q]] = 0;
-            }
-            if (fcols.empty()) {
-                rc = fw_fail(nullptr, FW_ERR_ARG, "%s: no column whose non-zero abundances fall into two bins", fn);
-                goto done;
-            }
-        }
-        const int pf = (int)fcols.size();
-        std::vector<int64_t> ocolptr((size_t)pf + 1, 0);  // column compaction: the scan over the kept columns' lengths, on the host (p entries)
-        for (int f = 0; f < pf; ++f) ocolptr[f + 1] = ocolptr[f] + (colptr[fcols[f] + 1] - colptr[fcols[f]]);
-        const size_t onnz = (size_t)ocolptr[pf];
-        NHIP(hipMemcpy(d_cols, fcols.data(), sizeof(int32_t) * (size_t)pf, hipMemcpyHostToDevice));
-        NHIP(hipMalloc((void **)&d_ocolptr, sizeof(int64_t) * ((size_t)pf + 1)));
-        NHIP(hipMemcpy(d_ocolptr, ocolptr.data(), sizeof(int64_t) * ((size_t)pf + 1), hipMemcpyHostToDevice));
-        NHIP(hipMalloc((void **)&d_orow, sizeof(int32_t) * onnz));
-        if (discrete)
-            NHIP(hipMalloc((void **)&d_oi, sizeof(int32_t) * onnz));
-        else
-            NHIP(hipMalloc((void **)&d_of, sizeof(float) * onnz));
-        hipLaunchKernelGGL(csc_emit_kernel<V>, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, d_colptr, d_rowval, d_nzval, d_cols, pf, d_ocolptr, d_rownew, d_g,
-                           d_s32, d_bins, kind == FW_MI ? 0 : (kind == FW_MI_NZ || kind == FW_NORM_TSS_BINNED) ? 1 : kind == FW_FZ_NZ ? 2 : 3, d_orow, d_oi, d_of);
-        NHIP(hipGetLastError());
-        NHIP(hipMemcpy(out_rowval, d_orow, sizeof(int32_t) * onnz, hipMemcpyDeviceToHost));
-        if (discrete)
-            NHIP(hipMemcpy(out_i32, d_oi, sizeof(int32_t) * onnz, hipMemcpyDeviceToHost));
-        else
-            NHIP(hipMemcpy(out_f32, d_of, sizeof(float) * onnz, hipMemcpyDeviceToHost));
-        std::copy(ocolptr.begin(), ocolptr.end(), out_colptr);
-        *n_out = nk;
-        *p_out = pf;
-        *nnz_out = (int64_t)onnz;
-    }
-done:
-    void *ptrs[] = {d_colptr, d_ocolptr, d_rowval, d_nzval, d_colstat, d_colq, d_cols, d_cnt, d_mn, d_rownew, d_bins, d_two, d_orow, d_oi,
-                    d_krow, d_ecol, d_pay, d_pay2, d_S, d_SL, d_pseudo, d_g, d_keys, d_of, d_s32, d_tmp};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    return rc;
+    if (nnz == 0) return norm_all_constant(fn);
+    CscDev<V> D;
+    FW_HIP(nullptr, hipSetDevice(device));
+    if (int rc = csc_filters(c, p, nnz, colptr, rowval, nzval, D)) return rc;
+    if (int rc = csc_output(c, nnz, colptr, D, out_colptr, out_rowval, out_i32, out_f32, nnz_out)) return rc;
+    *n_out = (int32_t)c.R.rows.size();
+    *p_out = (int32_t)c.cols.size();
+    return FW_OK;
 }
 
 }  // namespace

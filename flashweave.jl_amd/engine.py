@@ -15,6 +15,9 @@ _KINDS = {"mi": FW_MI, "mi_nz": FW_MI_NZ, "fz": FW_FZ, "fz_nz": FW_FZ_NZ}
 # the constants the fw_normalize_* entry points take as `kind`.
 FW_NORM_TSS, FW_NORM_TSS_BINNED = 4, 5
 _NORMS = {"tss": FW_NORM_TSS, "tss-nonzero-binned": FW_NORM_TSS_BINNED}
+# The element type of what a fw_normalize_* entry point writes for a `kind` (out_f32 | out_i32; csrc/fw_norm_host.h: norm_kind).
+NORM_OUT_DTYPE = {FW_FZ: np.float32, FW_FZ_NZ: np.float32, FW_NORM_TSS: np.float32, FW_MI: np.int32, FW_MI_NZ: np.int32,
+                  FW_NORM_TSS_BINNED: np.int32}
 TSS_MIN, TSS_MAX = 2.0 ** -126, 2.0 ** 96  # positive real values a TSS norm takes: (float)x > 0, and fewer than 2^31 of them sum finitely
 
 TestResult = namedtuple("TestResult", "stat pval df suff_power")  # src/types.jl:140-145
@@ -281,8 +284,8 @@ def _normalize_csc(front_end, who, triple, test_name, device, norm=None):
     rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
     no, po, nz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     ocp, orow = np.zeros(p + 1, np.int64), np.zeros(max(nnz, 1), np.int32)
-    of = np.zeros(n * p if kind == FW_FZ else max(nnz, 1), np.float32) if kind in (FW_FZ, FW_FZ_NZ, FW_NORM_TSS) else None
-    oi = np.zeros(max(nnz, 1), np.int32) if kind in (FW_MI, FW_MI_NZ, FW_NORM_TSS_BINNED) else None
+    of = np.zeros(n * p if kind == FW_FZ else max(nnz, 1), np.float32) if NORM_OUT_DTYPE[kind] is np.float32 else None
+    oi = np.zeros(max(nnz, 1), np.int32) if NORM_OUT_DTYPE[kind] is np.int32 else None
     rc = front_end(device, kind, n, p, _ptr(colptr), _ptr(rowval), _ptr(nzval), _ptr(ocp), _ptr(orow), _ptr(oi), _ptr(of),
                    _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), C.byref(nz))
     if rc != 0:
@@ -333,8 +336,8 @@ def _normalize_dense(front_end, x, test_name, device, norm=None):
     rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
     no, po = C.c_int32(0), C.c_int32(0)
     kind = _front_end_kind("normalize", test_name, norm)
-    of = np.zeros(n * p, np.float32) if kind in (FW_FZ, FW_FZ_NZ, FW_NORM_TSS) else None
-    oi = np.zeros(n * p, np.int32) if kind in (FW_MI, FW_MI_NZ, FW_NORM_TSS_BINNED) else None
+    of = np.zeros(n * p, np.float32) if NORM_OUT_DTYPE[kind] is np.float32 else None
+    oi = np.zeros(n * p, np.int32) if NORM_OUT_DTYPE[kind] is np.int32 else None
     rc = front_end(device, kind, n, p, _ptr(x), _ptr(of), _ptr(oi), _ptr(rm), _ptr(cm), C.byref(no), C.byref(po))
     if rc != 0:
         raise FlashWeaveError(rc, L.fw_last_error(None).decode())
