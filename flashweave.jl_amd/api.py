@@ -240,16 +240,18 @@ def _abundance_refusals(who, data, extra):
 
 
 def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, make_onehot, prec, device_normalize, device, abundances=False,
-                      tss=None):
+                      tss=None, bins=None):
     """Every table through ONE front-end -- the device one when all of them are count tables it takes (sparse, or _integral) and
     prec == 32 and device_normalize, else the host one -- each on its own (its own row sums, geometric means, pseudo-counts and
     filters), then preprocess.combine_data.  abundances: the tables are declared real-valued, _integral is not asked and the device
     front-end is the Float64 one (engine.normalize_abundances).  tss: one of preprocess.TSS_NORMS, handed to whichever front-end runs
-    as norm= (test_name is then the one the norm goes with); None hands every front-end what it was always handed.
+    as norm= (test_name is then the one the norm goes with); None hands every front-end what it was always handed.  bins: those of
+    n_bins, rank_method and disc_method that are away from their defaults (preprocess.bins_kw), handed to whichever front-end runs as
+    keywords, for every table alike; None or {} adds no keyword.  The meta variables never take them (2 bins, preprocessing.jl:531-533).
     -> (dict(data, header, meta_mask, row_mask), on_device)"""
     on_device = bool(device_normalize and prec == 32 and
                      (abundances or all(isinstance(t, CSC) or _integral(t) for t in [data] + [t for t, _ in extra])))
-    kw = {} if tss is None else {"norm": tss}
+    kw = dict({} if tss is None else {"norm": tss}, **(bins or {}))
     norm = None  # (None: the host front-end as it is)
     if on_device and abundances:  # (a dense table is handed over as the Float64 values the front-end reads; Float32 widens exactly)
         norm = lambda c, t: normalize_abundances(c if isinstance(c, CSC) else np.asarray(c, dtype=np.float64), t, device=device, **kw)
@@ -257,7 +259,7 @@ def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, ma
         norm = lambda c, t: normalize_counts(c, t, device=device, **kw)
     elif abundances:  # the host front-end with the anchor rule of the Float64 device front-end (preprocess.adaptive_clr)
         norm = lambda c, t: pre.normalize(c, t, prec=prec, tie_anchor=True, **kw)
-    elif tss is not None:
+    elif kw:
         norm = lambda c, t: pre.normalize(c, t, prec=prec, **kw)
 
     def one(tab, hdr):  # a count table on its own -> (matrix, the kept columns' names, row mask)
@@ -492,7 +494,8 @@ def _tss_range_refusals(who, norm_mode, data, extra):
 
 
 def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data=None, meta_header=None, make_onehot=True, prec=32,
-                   device_normalize=True, device=0, meta_mask=None, abundances=False, norm_mode=None):
+                   device_normalize=True, device=0, meta_mask=None, abundances=False, norm_mode=None, n_bins=3, rank_method="tied",
+                   disc_method="median"):
     """normalize_data (preprocessing.jl:660-701), both forms: what learn_network(normalize=True) does to its tables, as a function of
     its own.  data: samples x OTUs counts (array or scipy.sparse); extra_data: a list of (table, header) pairs, count tables of further
     sequencing experiments on the same samples.  Every table is normalised on its own for `test_name` ("fz" clr_adapt, "fz_nz" clr_nz,
@@ -514,6 +517,18 @@ def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data
     into two bins, zeros stay 0: Int32 levels, dense or CSC; meta variables as for "mi_nz").  They take the same front-end choice, host
     and device giving the same bits; with abundances=True a positive value outside [2^-126, 2^96] raises ValueError.  learn_network
     takes such a table with normalize=False.
+    n_bins, rank_method, disc_method: the reference's preprocess_kwargs of the two binned modes, test_name "mi_nz" / norm_mode
+    "clr-nonzero-binned" and norm_mode "tss-nonzero-binned" (preprocessing.jl:217-291,412-416,492-521).  In every kept column the non-zero
+    entries are discretised into n_bins - 1 levels 1 .. n_bins - 1 by their keys (the clr_nz value / the TSS quotient), zeros stay 0:
+    disc_method "median" takes the rank r of a key -- rank_method "tied": the average rank, "dense": the distinct keys numbered in
+    ascending order -- and level = floor((r / max r) / (1 / (n_bins - 1) + 1e-5)) + 1; disc_method "mean" (n_bins=3 only) gives 1 to
+    the keys <= the column's mean and 2 to the others, the mean being preprocess.pairwise_mean of the keys, one number on the host and
+    on the device, within rounding of the reference's.  A column is kept iff its non-zero entries show exactly
+    n_bins - 1 distinct levels.  Every table of extra_data takes the same options; meta variables go into 2 bins whatever n_bins is.
+    Host and device front-end, dense and sparse, counts and abundances give the same levels; learn_network takes the table with
+    normalize=False (the discrete engine serves up to 62 levels).  ValueError naming the option, before any device call: n_bins no
+    integer in 3 .. 62, an unknown rank_method or disc_method, disc_method="mean" with n_bins > 3, and any of the three away from its
+    default with a mode that does not bin.
     -> dict(data, header, meta_mask, row_mask): row_mask over the input samples, data a scipy.sparse.csc_matrix for sparse tables
     (dense for "fz")."""
     who = "normalize_data"
@@ -533,13 +548,14 @@ def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data
         raise ValueError("%s: unsupported test_name %r" % (who, test_name))
     if prec not in (32, 64):
         raise ValueError("%s: prec=%r is not supported (32 or 64)" % (who, prec))
+    pre.bins_check(who, test_name, n_bins, rank_method, disc_method)
     # this entry point's rules of the table stage: an engine.CSC tuple is a sparse table, and a header always has the table's length
     t = _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec, device_normalize,
                         normalize=True, csc_tuple_is_sparse=True, strict_header=True, abundances=bool(abundances))
     if tss is not None and abundances:
         _tss_range_refusals(who, norm_mode, t.data, t.extra)
     return _normalize_tables(t.data, list(t.header), t.extra, test_name, t.meta_data, t.meta_header, t.make_onehot, prec, device_normalize,
-                             device, bool(abundances), tss=tss)[0]
+                             device, bool(abundances), tss=tss, bins=pre.bins_kw(n_bins, rank_method, disc_method))[0]
 
 
 def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,

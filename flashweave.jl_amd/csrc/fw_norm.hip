@@ -7,6 +7,12 @@
 //   "mi_nz"  binned_nz_clr              :217-291,492-521  clr_nz, then per column the tied (average) ranks of the non-zero entries,
 //                                       rank / max rank, bin = floor(. / (1/2 + 1e-5)) + 1 (two bins, disc_method "median"), zeros stay 0;
 //                                       columns whose non-zeros show exactly two bins
+//   The two binned kinds ("mi_nz" and FW_NORM_TSS_BINNED below) take the reference's options (fw_norm_opts; discretize, :217-291): n_bins
+//   (b = n_bins - 1 non-zero bins, 2 .. 61: step 1 / b + 1e-5, levels 1 .. b, a column is kept iff its non-zeros show exactly b levels,
+//   :511-515), rank_method ("dense": the distinct keys numbered 1 .. d -- the sorted keys are compacted in place, nb_compact) and
+//   disc_method ("mean", b = 2: key <= mean ? 1 : 2, the mean a pairwise sum over the sorted, zero-padded keys, nb_mean -- one number
+//   on the host, in the dense and in the CSC form).  The defaults run the kernels' instantiation without options (OPTS = false): the rule
+//   folded at compile time, the bits and the registers of the kernels before they took options.
 // Arithmetic is Float64 like the reference (clrnorm converts to Matrix{Float64}); the continuous modes return Float32
 // (convert_to_target_prec with prec = 32).  Layout: n samples x p variables, column-major, as Julia holds it; one thread
 // per sample row and column chunk (adjacent lanes = adjacent samples: coalesced), chunk partials reduced in a fixed order.
@@ -191,7 +197,11 @@ __global__ __launch_bounds__(256) void norm_col_levels_kernel(const V *__restric
 // to LDS and are sorted there (bitonic, +inf padding); an entry's tied rank is then (#smaller) + (#equal + 1) / 2 from two binary
 // searches, the largest rank m - (e_max - 1) / 2, and bin = floor((rank / max rank) / (1/2 + 1e-5)) + 1 exactly as discretize()
 // computes it in Float64 (preprocessing.jl:238-265 with n_bins - 1 = 2 for the non-zeros, :267-291).  two[q] = the non-zeros show
-// both bins.  The keys live in LDS, 8 bytes per padded entry, up to 16 384 kept rows; beyond (r04: preprocessing.jl:217-291 has no
+// both bins: every thread collects the levels it wrote as bits of a 64-bit mask, the masks are OR-ed over the workgroup (nb_all_levels)
+// and two[q] = (popcount == b).  With options (OPTS: b, rank_dense, disc_mean at run time) the step is 1 / b + 1e-5, the ranks are
+// searched among the distinct keys after nb_compact, or the level comes from nb_mean's threshold.  LDS: the keys (dynamic, up to
+// 128 KB) + 196 bytes of statics (s_cnt, the 16 wave totals of the compaction's scan, the 16 wave masks) of gfx950's 160 KB.
+// The keys live in LDS, 8 bytes per padded entry, up to 16 384 kept rows; beyond (r04: preprocessing.jl:217-291 has no
 // bound) in a slice of device memory per workgroup (gkeys, M doubles each: the same bitonic network, its passes through L2
 // instead of LDS -- the stores of a pass are visible to the workgroup's other wavefronts behind the barrier, one L1 per CU), the
 // workgroups striding over the columns so that the scratch stays at gridDim.x * M doubles.
@@ -259,11 +269,23 @@ __device__ inline double nb_rank_max(const NbKeys &K, int m)
     return (double)m - ((double)(m - lo) - 1.0) / 2.0;
 }
 
-// bin of the value c among the m sorted keys: tied rank (#smaller) + (#equal + 1) / 2, bin = floor((rank / max rank) / (1/2 + 1e-5)) + 1
-__device__ inline int nb_bin(const NbKeys &K, int m, double rmax, double c)
+// What the options of the binned kinds (NormOpts) come to for one column, the same in every thread of the workgroup: b non-zero bins;
+// m_eff = how many of the keys the ranks are searched in (tied: the m sorted keys; dense: the d distinct ones nb_compact left), rmax the
+// largest rank (dense: d); mean: the "mean" rule with its threshold instead of ranks.
+struct NbRule {
+    int b, m_eff;
+    bool dense, mean;
+    double rmax, thresh;
+};
+
+// level of the value c (one of the column's keys).  "median": rank / max rank, level = floor(. / (1 / b + 1e-5)) + 1, in 1 .. b -- the
+// tied rank (#smaller) + (#equal + 1) / 2 among the sorted keys, or the dense rank (#smaller distinct) + 1 among the distinct ones;
+// b = 2 gives the step 1/2 + 1e-5 to the bit.  "mean": c <= mean ? 1 : 2.
+__device__ inline int nb_bin(const NbKeys &K, const NbRule &R, double c)
 {
-    const double step = (1.0 / 2.0) + 1e-5;
-    int lo = 0, hi = m;
+    if (R.mean) return c <= R.thresh ? 1 : 2;
+    const double step = (1.0 / (double)R.b) + 1e-5;
+    int lo = 0, hi = R.m_eff;
     while (lo < hi) {  // #smaller
         const int mid = (lo + hi) >> 1;
         if (K.ld(mid) < c)
@@ -271,16 +293,122 @@ __device__ inline int nb_bin(const NbKeys &K, int m, double rmax, double c)
         else
             hi = mid;
     }
-    int lo2 = lo, hi2 = m;
-    while (lo2 < hi2) {  // first index with key > c
-        const int mid = (lo2 + hi2) >> 1;
-        if (K.ld(mid) <= c)
-            lo2 = mid + 1;
-        else
-            hi2 = mid;
+    double rank = (double)(lo + 1);
+    if (!R.dense) {
+        int lo2 = lo, hi2 = R.m_eff;
+        while (lo2 < hi2) {  // first index with key > c
+            const int mid = (lo2 + hi2) >> 1;
+            if (K.ld(mid) <= c)
+                lo2 = mid + 1;
+            else
+                hi2 = mid;
+        }
+        rank = (double)lo + ((double)(lo2 - lo) + 1.0) / 2.0;
     }
-    const double rank = (double)lo + ((double)(lo2 - lo) + 1.0) / 2.0;
-    return (int)floor((rank / rmax) / step) + 1;
+    return (int)floor((rank / R.rmax) / step) + 1;
+}
+
+// Dense ranks: the m sorted keys are compacted in place to the d distinct ones (-> d; what lies in [d, m) afterwards is stale and not
+// read again).  Tile by tile of nt * NB_RUN keys, in ascending order: every thread reads its contiguous run of NB_RUN keys (and the run's
+// predecessor) into registers and counts the keys that differ from their predecessor; wave scan (shuffles) + the wave totals through
+// s_part give every run its place among the distinct keys -- the barrier of that scan is also the one behind the tile's last read;
+// then each thread writes its distinct keys, and a second barrier (with the fence of the device-memory placement) closes the tile.
+// A destination never exceeds its source index (at most i distinct keys lie before key i), so a tile's writes stay below every key
+// that is still unread.  All nt threads call it (nt a multiple of 64, at most 1 024); s_part: 16 ints of LDS.
+#define NB_RUN 8
+__device__ inline int nb_compact(const NbKeys &K, int m, int tid, int nt, int *s_part)
+{
+    const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    int d = 0;
+    for (int base = 0; base < m; base += nt * NB_RUN) {
+        const int i0 = base + tid * NB_RUN;
+        double key[NB_RUN];
+        double prev = (i0 > 0 && i0 < m) ? K.ld(i0 - 1) : 0.0;
+        unsigned first = 0;  // bit u: key i0 + u is the first of its value
+        int cnt = 0;
+#pragma unroll
+        for (int u = 0; u < NB_RUN; ++u) {
+            key[u] = 0.0;
+            if (i0 + u < m) {
+                key[u] = K.ld(i0 + u);
+                if (i0 + u == 0 || key[u] != prev) {
+                    first |= 1u << u;
+                    ++cnt;
+                }
+                prev = key[u];
+            }
+        }
+        int incl = cnt;  // inclusive scan over the wavefront
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) s_part[wave] = incl;
+        __syncthreads();  // (every key of the tile has been read)
+        int dst = d + incl - cnt, total = 0;
+        for (int w = 0; w < nw; ++w) {
+            const int t = s_part[w];
+            if (w < wave) dst += t;
+            total += t;
+        }
+#pragma unroll
+        for (int u = 0; u < NB_RUN; ++u)
+            if (first & (1u << u)) K.st(dst++, key[u]);
+        d += total;
+        K.sync();  // (the writes are visible; s_part is free for the next tile)
+    }
+    return d;
+}
+
+// The "mean" rule's threshold: the m sorted keys, padded with +0.0 to P = the next power of two, added pairwise level by level
+// (a[2i] + a[2i+1]), divided by m.  In place over the keys, which the rule does not read again: level s leaves its sums at the multiples of 2s,
+// each written by the one thread that read it, its partner (+ s) written by nobody at that level; one barrier per level.
+__device__ inline double nb_mean(const NbKeys &K, int m, int tid, int nt)
+{
+    if (m <= 0) return 0.0;
+    int P = 1;
+    while (P < m) P <<= 1;
+    for (int i = m + tid; i < P; i += nt) K.st(i, 0.0);  // (+inf padding of the sort -> +0.0; P <= the padded length of the sort)
+    K.sync();
+    for (int s = 1; s < P; s <<= 1) {
+        for (int i = tid; i < P / (2 * s); i += nt) K.st(2 * s * i, K.ld(2 * s * i) + K.ld(2 * s * i + s));
+        K.sync();
+    }
+    return K.ld(0) / (double)m;
+}
+
+// The column's rule from its m sorted keys (all nt threads; the keys are synchronised on entry and on return).  OPTS = false is the
+// instantiation of the default options -- two bins, tied ranks, "median" -- with the rule folded at compile time: the code, and the
+// registers, the kernels had before they took options; dense and mean are not looked at (the host passes b = 2, which the column rule
+// counts the levels against).  The predecessor nb_compact reads across a tile's edge is still the original key: the tile before wrote
+// up to there only if all its keys were distinct, and then wrote each key onto itself.
+template <bool OPTS> __device__ inline NbRule nb_rule(const NbKeys &K, int m, int b, int dense, int mean, int tid, int nt, int *s_part)
+{
+    if (!OPTS) return NbRule{2, m, false, false, nb_rank_max(K, m), 0.0};
+    NbRule R{b, m, dense != 0, mean != 0, 1.0, 0.0};
+    if (R.mean) {
+        R.thresh = nb_mean(K, m, tid, nt);
+    } else if (R.dense) {
+        R.m_eff = nb_compact(K, m, tid, nt, s_part);
+        R.rmax = R.m_eff > 0 ? (double)R.m_eff : 1.0;
+    } else {
+        R.rmax = nb_rank_max(K, m);
+    }
+    return R;
+}
+
+// The levels the workgroup's threads saw (bit l: level l) -> true when they are exactly b: OR over the wavefront by shuffles, the wave
+// results through s_wmask (16 words of LDS), counted by every thread alike.  Ends behind a barrier; s_wmask is free after the next one.
+__device__ inline bool nb_all_levels(unsigned long long seen, int b, int tid, int nt, unsigned long long *s_wmask)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) seen |= __shfl_xor(seen, o, 64);
+    if ((tid & 63) == 0) s_wmask[tid >> 6] = seen;
+    __syncthreads();
+    unsigned long long all = 0;
+    for (int w = 0; w < (nt >> 6); ++w) all |= s_wmask[w];
+    return __popcll(all) == b;
 }
 
 // The sort key of a non-zero entry v in kept row r = input row i.  binned_nz_clr: its clr_nz value.  TSS (binned_nz_rows): its
@@ -292,20 +420,22 @@ __device__ inline double nb_key(V v, const double *__restrict__ gmean, int r, co
     return log((double)v / gmean[r]);
 }
 
-template <typename V, bool TSS>
+template <typename V, bool TSS, bool OPTS>
 __global__ __launch_bounds__(1024) void norm_binned_kernel(const V *__restrict__ x, int n, const int32_t *__restrict__ rows, int nk,
                                                            const int32_t *__restrict__ cols, int pk, const double *__restrict__ gmean,
                                                            const float *__restrict__ rsum32, int32_t *__restrict__ out,
-                                                           int32_t *__restrict__ two, int M, double *gkeys)
+                                                           int32_t *__restrict__ two, int M, double *gkeys, int nb, int rank_dense,
+                                                           int disc_mean)
 {
     extern __shared__ double s_key_lds[];
-    __shared__ int s_cnt, s_b1, s_b2;
+    __shared__ int s_cnt, s_part[16];
+    __shared__ unsigned long long s_wmask[16];
     const int tid = threadIdx.x;
     const NbKeys K{gkeys ? gkeys + (size_t)blockIdx.x * (size_t)M : s_key_lds, gkeys != nullptr};
   for (int q = blockIdx.x; q < pk; q += gridDim.x) {
     const V *col = x + (size_t)cols[q] * n;
-    __syncthreads();  // (the previous column's last readers of the keys / s_b1 / s_b2)
-    if (tid == 0) s_cnt = s_b1 = s_b2 = 0;
+    __syncthreads();  // (the previous column's last readers of the keys / s_cnt / s_wmask)
+    if (tid == 0) s_cnt = 0;
     __syncthreads();
     for (int r = tid; r < nk; r += 1024) {
         const V v = col[rows[r]];
@@ -314,22 +444,19 @@ __global__ __launch_bounds__(1024) void norm_binned_kernel(const V *__restrict__
     K.sync();
     const int m = s_cnt;
     nb_pad_sort(K, m, M, tid, 1024);
-    const double rmax = nb_rank_max(K, m);
-    int b1 = 0, b2 = 0;
+    const NbRule R = nb_rule<OPTS>(K, m, nb, rank_dense, disc_mean, tid, 1024, s_part);
+    unsigned long long seen = 0;
     for (int r = tid; r < nk; r += 1024) {
         const V v = col[rows[r]];
         int bin = 0;
         if (v != 0) {
-            bin = nb_bin(K, m, rmax, nb_key<TSS>(v, gmean, r, rsum32, rows[r]));  // the same operations as above: the same bits
-            b1 |= bin == 1;
-            b2 |= bin == 2;
+            bin = nb_bin(K, R, nb_key<TSS>(v, gmean, r, rsum32, rows[r]));  // the same operations as above: the same bits
+            seen |= 1ull << bin;
         }
         out[(size_t)q * nk + r] = bin;
     }
-    if (b1) s_b1 = 1;
-    if (b2) s_b2 = 1;
-    __syncthreads();
-    if (tid == 0) two[q] = s_b1 && s_b2;
+    const bool all = nb_all_levels(seen, nb, tid, 1024, s_wmask);
+    if (tid == 0) two[q] = all;
   }
 }
 
@@ -352,6 +479,7 @@ struct NormCall {
     NormKind K;
     int n;
     uint8_t *row_mask, *col_mask;
+    NormOpts O;  // the options of the binned kinds (fw_norm_opts, checked: norm_call_check)
     std::vector<int32_t> cols;
     NormRows R;
     FwDevArray<int32_t> d_cols;
@@ -360,8 +488,20 @@ struct NormCall {
 
 dim3 norm_out_grid(int nk, int pk) { return dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)); }
 int norm_all_constant(const char *fn) { return fw_fail(nullptr, FW_ERR_ARG, "%s: every column is constant", fn); }
-// the kind's own filter (norm_keep_columns) left nothing, or -- FW_FZ -- the pseudo-counts did
-int norm_none_left(const NormCall &c) { return fw_fail(nullptr, FW_ERR_ARG, "%s: %s", c.fn, c.K.none_left); }
+// the kind's own filter (norm_keep_columns) left nothing, or -- FW_FZ -- the pseudo-counts did; the binned kinds away from two non-zero
+// bins say how many levels were asked for
+int norm_none_left(const NormCall &c)
+{
+    if (c.K.binned && c.O.b != 2) return fw_fail(nullptr, FW_ERR_ARG, "%s: no column whose non-zero abundances show all %d non-zero levels (n_bins = %d)", c.fn, c.O.b, c.O.b + 1);
+    return fw_fail(nullptr, FW_ERR_ARG, "%s: %s", c.fn, c.K.none_left);
+}
+// kind and options of a call, before any device call: an unknown kind, or an option the kind does not take (norm_opts_check's words)
+int norm_call_check(NormCall &c, const fw_norm_opts *opts)
+{
+    if (!c.K.known) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", c.fn, c.kind);
+    if (const char *no = norm_opts_check(opts, c.K, c.O)) return fw_fail(nullptr, FW_ERR_ARG, "%s: fw_norm_opts: %s", c.fn, no);
+    return FW_OK;
+}
 
 // row totals -> kept samples, pseudo-counts, geometric means and the TSS divisors (norm_row_params), a refusal in words
 int norm_rows(NormCall &c, double tie_rel, const NormTotals &T, const std::vector<float> &s32)
@@ -457,13 +597,14 @@ template <typename V> int dense_output(NormCall &c, const V *d_x, float *out_f32
         FW_HIP(nullptr, d_oi.alloc((size_t)nk * pf));
         hipLaunchKernelGGL(norm_binary_out_kernel<V>, norm_out_grid(nk, pf), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pf, d_oi.get());
     } else if (c.K.binned) {  // every kept column is binned, then the columns that show both bins are gathered
-        const auto binned = !c.K.tss ? norm_binned_kernel<V, false> : norm_binned_kernel<V, true>;  // (the key: nb_key)
+        const auto binned = c.O.plain() ? (!c.K.tss ? norm_binned_kernel<V, false, false> : norm_binned_kernel<V, true, false>)  // (the key: nb_key)
+                                        : (!c.K.tss ? norm_binned_kernel<V, false, true> : norm_binned_kernel<V, true, true>);
         NormBinShape B;
         if (int rc = norm_bin_shape((const void *)binned, nk, pk, true, B)) return rc;
         FW_HIP(nullptr, d_g.upload(c.R.g));
         FW_HIP(nullptr, d_two.alloc((size_t)pk));
         FW_HIP(nullptr, d_tmp.alloc((size_t)nk * pk));
-        hipLaunchKernelGGL(binned, dim3(B.grid), dim3(B.threads), B.lds(), 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_g.get(), c.d_s32.get(), d_tmp.get(), d_two.get(), B.M, B.keys.get());
+        hipLaunchKernelGGL(binned, dim3(B.grid), dim3(B.threads), B.lds(), 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_g.get(), c.d_s32.get(), d_tmp.get(), d_two.get(), B.M, B.keys.get(), c.O.b, (int)c.O.dense, (int)c.O.mean);
         FW_HIP(nullptr, hipGetLastError());
         FW_HIP(nullptr, d_two.download(two));
         const std::vector<int32_t> sel = norm_keep_columns(two, c.cols, c.col_mask);
@@ -488,11 +629,11 @@ template <typename V> int dense_output(NormCall &c, const V *d_x, float *out_f32
 // The dense front-end for either value type (fn: the entry point's name, for the messages).
 template <typename V>
 int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const V *counts, float *out_f32, int32_t *out_i32,
-               uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
+               uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, const fw_norm_opts *opts)
 {
     if (!counts || !row_mask || !col_mask || !n_out || !p_out || n <= 0 || p <= 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
     NormCall c{fn, kind, norm_kind(kind), n, row_mask, col_mask};
-    if (!c.K.known) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
+    if (int rc = norm_call_check(c, opts)) return rc;
     if (c.K.i32 ? !out_i32 : !out_f32) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
     FwDevArray<V> d_x;
     FW_HIP(nullptr, hipSetDevice(device));
@@ -506,16 +647,31 @@ int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t 
 
 }  // namespace
 
+// The entry points without options forward to their _opts siblings with NULL (the defaults); a refusal names the sibling.
+extern "C" int fw_normalize_counts_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *counts, float *out_f32,
+                                        int32_t *out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out,
+                                        const fw_norm_opts *opts)
+{
+    return norm_dense<int32_t>(opts ? "fw_normalize_counts_opts" : "fw_normalize_counts", device, kind, n, p, counts, out_f32, out_i32, row_mask, col_mask, n_out, p_out, opts);
+}
+
 extern "C" int fw_normalize_counts(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *counts, float *out_f32,
                                    int32_t *out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
 {
-    return norm_dense<int32_t>("fw_normalize_counts", device, kind, n, p, counts, out_f32, out_i32, row_mask, col_mask, n_out, p_out);
+    return fw_normalize_counts_opts(device, kind, n, p, counts, out_f32, out_i32, row_mask, col_mask, n_out, p_out, nullptr);
+}
+
+extern "C" int fw_normalize_abund_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const double *values, float *out_f32,
+                                       int32_t *out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out,
+                                       const fw_norm_opts *opts)
+{
+    return norm_dense<double>(opts ? "fw_normalize_abund_opts" : "fw_normalize_abund", device, kind, n, p, values, out_f32, out_i32, row_mask, col_mask, n_out, p_out, opts);
 }
 
 extern "C" int fw_normalize_abund(int32_t device, int32_t kind, int32_t n, int32_t p, const double *values, float *out_f32,
                                   int32_t *out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out)
 {
-    return norm_dense<double>("fw_normalize_abund", device, kind, n, p, values, out_f32, out_i32, row_mask, col_mask, n_out, p_out);
+    return fw_normalize_abund_opts(device, kind, n, p, values, out_f32, out_i32, row_mask, col_mask, n_out, p_out, nullptr);
 }
 
 // ---- the same front-end on a CSC count table (fw_normalize_counts_csc) ---------------------------------------------------------
@@ -648,17 +804,19 @@ __global__ __launch_bounds__(256) void csc_row_stats_kernel(const uint32_t *__re
 // binned_nz_clr, one workgroup per kept column: norm_binned_kernel with the keys read from the column's stored run (every entry
 // of a kept column lies in a kept row: its count >= 1 gives the row reads).  bins[e] for the input entry e; M = the padded
 // length of the longest kept column (sizes the key storage), each column sorts its own power of two.  One kernel for both
-// launch shapes (256 threads while M <= 2 048, the HE case; 1 024 beyond): the bound of 1 024 caps it at 128 VGPRs, it uses 66, so
-// the short form loses no occupancy to the cap.
-template <typename V, bool TSS>
+// launch shapes (256 threads while M <= 2 048, the HE case; 1 024 beyond): the bound of 1 024 caps it at 128 VGPRs, it uses 74 at most (with
+// options 93: the registers of nb_compact's runs), so the short form loses no occupancy to the cap.
+template <typename V, bool TSS, bool OPTS>
 __global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
                                                           const V *__restrict__ nzval, const int32_t *__restrict__ cols, int pk,
                                                           const int32_t *__restrict__ rownew, const double *__restrict__ gmean,
                                                           const float *__restrict__ rsum32, int32_t *__restrict__ bins,
-                                                          int32_t *__restrict__ two, int M, double *gkeys)
+                                                          int32_t *__restrict__ two, int M, double *gkeys, int nb, int rank_dense,
+                                                          int disc_mean)
 {
     extern __shared__ double s_key_lds[];
-    __shared__ int s_b1, s_b2;
+    __shared__ int s_part[16];
+    __shared__ unsigned long long s_wmask[16];
     const int tid = threadIdx.x, nt = blockDim.x;
     const NbKeys K{gkeys ? gkeys + (size_t)blockIdx.x * (size_t)M : s_key_lds, gkeys != nullptr};
     for (int q = blockIdx.x; q < pk; q += gridDim.x) {
@@ -666,23 +824,19 @@ __global__ __launch_bounds__(1024) void csc_binned_kernel(const int64_t *__restr
         const int m = (int)(colptr[cols[q] + 1] - a);
         int Mq = 2;
         while (Mq < m) Mq <<= 1;
-        __syncthreads();  // (the previous column's last readers of the keys / s_b1 / s_b2)
-        if (tid == 0) s_b1 = s_b2 = 0;
+        __syncthreads();  // (the previous column's last readers of the keys / s_wmask)
         for (int k = tid; k < m; k += nt) K.st(k, nb_key<TSS>(nzval[a + k], gmean, rownew[rowval[a + k]], rsum32, rowval[a + k]));
         K.sync();
         nb_pad_sort(K, m, Mq, tid, nt);
-        const double rmax = nb_rank_max(K, m);
-        int b1 = 0, b2 = 0;
+        const NbRule R = nb_rule<OPTS>(K, m, nb, rank_dense, disc_mean, tid, nt, s_part);
+        unsigned long long seen = 0;
         for (int k = tid; k < m; k += nt) {
-            const int bin = nb_bin(K, m, rmax, nb_key<TSS>(nzval[a + k], gmean, rownew[rowval[a + k]], rsum32, rowval[a + k]));
-            b1 |= bin == 1;
-            b2 |= bin == 2;
+            const int bin = nb_bin(K, R, nb_key<TSS>(nzval[a + k], gmean, rownew[rowval[a + k]], rsum32, rowval[a + k]));
+            seen |= 1ull << bin;
             bins[a + k] = bin;
         }
-        if (b1) s_b1 = 1;
-        if (b2) s_b2 = 1;
-        __syncthreads();
-        if (tid == 0) two[q] = s_b1 && s_b2;
+        const bool all = nb_all_levels(seen, nb, tid, nt, s_wmask);
+        if (tid == 0) two[q] = all;
     }
 }
 
@@ -839,7 +993,8 @@ template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *
         return FW_OK;
     }
     if (c.K.binned) {
-        const auto binned = !c.K.tss ? csc_binned_kernel<V, false> : csc_binned_kernel<V, true>;  // (the key: nb_key)
+        const auto binned = c.O.plain() ? (!c.K.tss ? csc_binned_kernel<V, false, false> : csc_binned_kernel<V, true, false>)  // (the key: nb_key)
+                                        : (!c.K.tss ? csc_binned_kernel<V, false, true> : csc_binned_kernel<V, true, true>);
         int64_t mmax = 0;
         for (int j : c.cols) mmax = std::max(mmax, colptr[j + 1] - colptr[j]);
         NormBinShape B;
@@ -847,7 +1002,7 @@ template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *
         FW_HIP(nullptr, d_bins.alloc((size_t)nnz));
         FW_HIP(nullptr, d_two.alloc((size_t)pk));
         hipLaunchKernelGGL(binned, dim3(B.grid), dim3(B.threads), B.lds(), 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), c.d_cols.get(), pk, d_rownew.get(),
-                           d_g.get(), c.d_s32.get(), d_bins.get(), d_two.get(), B.M, B.keys.get());
+                           d_g.get(), c.d_s32.get(), d_bins.get(), d_two.get(), B.M, B.keys.get(), c.O.b, (int)c.O.dense, (int)c.O.mean);
         FW_HIP(nullptr, hipGetLastError());
         FW_HIP(nullptr, d_two.download(two));
     } else if (c.K.none_left) {  // FW_MI, presabs_norm!: two levels among the kept samples <=> an absence among them
@@ -876,11 +1031,12 @@ template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *
 // The CSC front-end for either value type (fn: the entry point's name, for the messages).
 template <typename V>
 int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval, const V *nzval,
-             int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
+             int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+             const fw_norm_opts *opts)
 {
     if (!colptr || !row_mask || !col_mask || !n_out || !p_out || !nnz_out || n <= 0 || p <= 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
     NormCall c{fn, kind, norm_kind(kind), n, row_mask, col_mask};
-    if (!c.K.known) return fw_fail(nullptr, FW_ERR_ARG, "%s: unknown kind %d", fn, kind);
+    if (int rc = norm_call_check(c, opts)) return rc;
     if ((c.K.i32 ? !out_i32 : !out_f32) || (kind != FW_FZ && (!out_colptr || !out_rowval))) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
     const long long nnz = colptr[p];
     if (colptr[0] != 0 || nnz < 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: colptr must run from 0 to nnz (column 0)", fn);
@@ -898,18 +1054,34 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
 
 }  // namespace
 
+extern "C" int fw_normalize_counts_csc_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                                            const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                                            uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                                            const fw_norm_opts *opts)
+{
+    return norm_csc<int32_t>(opts ? "fw_normalize_counts_csc_opts" : "fw_normalize_counts_csc", device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32,
+                             out_f32, row_mask, col_mask, n_out, p_out, nnz_out, opts);
+}
+
 extern "C" int fw_normalize_counts_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
                                        const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
                                        uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
 {
-    return norm_csc<int32_t>("fw_normalize_counts_csc", device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32, out_f32, row_mask,
-                             col_mask, n_out, p_out, nnz_out);
+    return fw_normalize_counts_csc_opts(device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32, out_f32, row_mask, col_mask, n_out, p_out, nnz_out, nullptr);
+}
+
+extern "C" int fw_normalize_abund_csc_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                                           const double *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                                           uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                                           const fw_norm_opts *opts)
+{
+    return norm_csc<double>(opts ? "fw_normalize_abund_csc_opts" : "fw_normalize_abund_csc", device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32,
+                            out_f32, row_mask, col_mask, n_out, p_out, nnz_out, opts);
 }
 
 extern "C" int fw_normalize_abund_csc(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
                                       const double *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
                                       uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
 {
-    return norm_csc<double>("fw_normalize_abund_csc", device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32, out_f32, row_mask,
-                            col_mask, n_out, p_out, nnz_out);
+    return fw_normalize_abund_csc_opts(device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32, out_f32, row_mask, col_mask, n_out, p_out, nnz_out, nullptr);
 }

@@ -38,6 +38,35 @@ inline NormKind norm_kind(int kind)
     return {false, false, false, false, -1, -1, nullptr};
 }
 
+// The options of the binned kinds (fw_norm_opts) as the kernels take them: b = n_bins - 1 non-zero bins, the dense instead of the tied
+// rank, the "mean" instead of the "median" rule.  The defaults are what the front-end computed before it had options.
+#define NORM_BINS_MAX 62  // n_bins - 1 <= 61: the levels 1 .. b are the bits of one 64-bit mask, and the engine takes at most 62 levels
+struct NormOpts {
+    int b = 2;
+    bool dense = false, mean = false;
+    bool plain() const { return b == 2 && !dense && !mean; }  // the defaults: the kernels' instantiation without options
+};
+
+// fw_norm_opts (nullptr: the defaults) against the kind -> nullptr and `out`, or the refusal in words that name the field.
+inline const char *norm_opts_check(const fw_norm_opts *o, const NormKind &K, NormOpts &out)
+{
+    out = NormOpts();
+    if (!o) return nullptr;
+    if (o->n_bins < 3 || o->n_bins > NORM_BINS_MAX) return "n_bins must lie in 3 .. 62 (two levels are the kind FW_MI)";
+    if (o->rank_method != FW_RANK_TIED && o->rank_method != FW_RANK_DENSE) return "rank_method must be FW_RANK_TIED or FW_RANK_DENSE";
+    if (o->disc_method != FW_DISC_MEDIAN && o->disc_method != FW_DISC_MEAN) return "disc_method must be FW_DISC_MEDIAN or FW_DISC_MEAN";
+    if (o->disc_method == FW_DISC_MEAN && o->n_bins > 3) return "disc_method FW_DISC_MEAN only works with 2 non-zero bins (n_bins = 3)";
+    if (!K.binned) {
+        if (o->n_bins != 3) return "n_bins applies to the binned kinds only (FW_MI_NZ, FW_NORM_TSS_BINNED)";
+        if (o->rank_method != FW_RANK_TIED) return "rank_method applies to the binned kinds only (FW_MI_NZ, FW_NORM_TSS_BINNED)";
+        if (o->disc_method != FW_DISC_MEDIAN) return "disc_method applies to the binned kinds only (FW_MI_NZ, FW_NORM_TSS_BINNED)";
+    }
+    out.b = o->n_bins - 1;
+    out.dense = o->rank_method == FW_RANK_DENSE;
+    out.mean = o->disc_method == FW_DISC_MEAN;
+    return nullptr;
+}
+
 // A refusal as a value (reason == nullptr: none).  sample >= 0: the Float32 sum of that sample is `reason` ("zero" / "infinite").
 struct NormRefusal {
     const char *reason = nullptr;

@@ -5,7 +5,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .preprocess import norm_check
+from .preprocess import bins_check, bins_kw, norm_check
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 FW_MI, FW_MI_NZ, FW_FZ, FW_FZ_NZ = 0, 1, 2, 3
@@ -18,6 +18,9 @@ _NORMS = {"tss": FW_NORM_TSS, "tss-nonzero-binned": FW_NORM_TSS_BINNED}
 # The element type of what a fw_normalize_* entry point writes for a `kind` (out_f32 | out_i32; csrc/fw_norm_host.h: norm_kind).
 NORM_OUT_DTYPE = {FW_FZ: np.float32, FW_FZ_NZ: np.float32, FW_NORM_TSS: np.float32, FW_MI: np.int32, FW_MI_NZ: np.int32,
                   FW_NORM_TSS_BINNED: np.int32}
+# fw_norm_opts: the options of the binned kinds as the *_opts entry points take them (include/flashweave_amd.h)
+FW_RANK = {"tied": 0, "dense": 1}
+FW_DISC = {"median": 0, "mean": 1}
 TSS_MIN, TSS_MAX = 2.0 ** -126, 2.0 ** 96  # positive real values a TSS norm takes: (float)x > 0, and fewer than 2^31 of them sum finitely
 
 TestResult = namedtuple("TestResult", "stat pval df suff_power")  # src/types.jl:140-145
@@ -36,6 +39,10 @@ class _Params(C.Structure):
                 ("max_k", C.c_int32), ("hps", C.c_int32), ("fdr", C.c_int32), ("dense_rules", C.c_int32),
                 ("n_obs_min", C.c_int64), ("max_tests", C.c_int64), ("alpha", C.c_double),
                 ("recursive_pcor", C.c_int32), ("no_cor_mat", C.c_int32)]
+
+
+class _NormOpts(C.Structure):  # fw_norm_opts
+    _fields_ = [("n_bins", C.c_int32), ("rank_method", C.c_int32), ("disc_method", C.c_int32)]
 
 
 class _TestResult(C.Structure):
@@ -160,6 +167,9 @@ def load_library():
     if hasattr(L, "fw_normalize_abund"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
         L.fw_normalize_abund.argtypes = L.fw_normalize_counts.argtypes
         L.fw_normalize_abund_csc.argtypes = L.fw_normalize_counts_csc.argtypes
+    if hasattr(L, "fw_normalize_counts_opts"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        for name in ("fw_normalize_counts", "fw_normalize_counts_csc", "fw_normalize_abund", "fw_normalize_abund_csc"):
+            getattr(L, name + "_opts").argtypes = getattr(L, name).argtypes + [C.POINTER(_NormOpts)]
     if hasattr(L, "fw_set_data_csc_f32_resident"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
         L.fw_set_data_csc_f32_resident.argtypes = [vp, vp, vp, vp]
         L.fw_data_resident_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -272,8 +282,27 @@ def tss_range_defect(values):
     return None
 
 
-def _normalize_csc(front_end, who, triple, test_name, device, norm=None):
-    """fw_normalize_counts_csc / fw_normalize_abund_csc (front_end) on the canonical triple -> (data, row_mask, col_mask)"""
+def _opts_arg(front_end, n_bins=3, rank_method="tied", disc_method="median"):
+    """The last argument of an *_opts entry point -- the options as a fw_norm_opts, the defaults spelled out too -- or nothing for an
+    entry point without options, which is never handed any."""
+    if not (front_end.argtypes and front_end.argtypes[-1] is C.POINTER(_NormOpts)):
+        assert not bins_kw(n_bins, rank_method, disc_method), "options need an *_opts entry point"
+        return ()
+    return (C.byref(_NormOpts(int(n_bins), FW_RANK[rank_method], FW_DISC[disc_method])),)
+
+
+def _opts_front_end(L, who, name, bins):
+    """The entry point `name`, or its *_opts sibling when any of the three options is away from its default (bins: bins_kw)."""
+    if not bins:
+        return getattr(L, name)
+    if not hasattr(L, name + "_opts"):
+        raise FlashWeaveError(-2, "%s: the loaded library has no %s_opts (an older build)" % (who, name))
+    return getattr(L, name + "_opts")
+
+
+def _normalize_csc(front_end, who, triple, test_name, device, norm=None, **bins):
+    """fw_normalize_counts_csc / fw_normalize_abund_csc or their *_opts siblings (front_end) on the canonical triple
+    -> (data, row_mask, col_mask)"""
     import scipy.sparse as sp
     L = load_library()
     colptr, rowval, nzval, (n, p) = triple
@@ -287,7 +316,7 @@ def _normalize_csc(front_end, who, triple, test_name, device, norm=None):
     of = np.zeros(n * p if kind == FW_FZ else max(nnz, 1), np.float32) if NORM_OUT_DTYPE[kind] is np.float32 else None
     oi = np.zeros(max(nnz, 1), np.int32) if NORM_OUT_DTYPE[kind] is np.int32 else None
     rc = front_end(device, kind, n, p, _ptr(colptr), _ptr(rowval), _ptr(nzval), _ptr(ocp), _ptr(orow), _ptr(oi), _ptr(of),
-                   _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), C.byref(nz))
+                   _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), C.byref(nz), *_opts_arg(front_end, **bins))
     if rc != 0:
         raise FlashWeaveError(rc, L.fw_last_error(None).decode())
     if kind == FW_FZ:
@@ -304,7 +333,7 @@ def _norm_kw(norm):
     return {} if norm is None else {"norm": norm}
 
 
-def normalize_counts(counts, test_name, device=0, norm=None):
+def normalize_counts(counts, test_name, device=0, norm=None, n_bins=3, rank_method="tied", disc_method="median"):
     """Normalisation front-end on the device (fw_normalize_counts): -> (data, row_mask, col_mask) like preprocess.normalize,
     for every test_name ("fz": clr_adapt, "fz_nz": clr_nz, "mi": binary, "mi_nz": binned_nz_clr).
     A scipy.sparse count table (or what as_csc returned) takes fw_normalize_counts_csc and stays sparse: data is then a
@@ -312,12 +341,19 @@ def normalize_counts(counts, test_name, device=0, norm=None):
     is 0) and a dense array for "fz"; the values are the bits the dense table gives.
     norm: "tss" (with test_name "fz") or "tss-nonzero-binned" (with "mi_nz") replaces the test's transform by total-sum scaling in
     Float32 / by the binned ranks of its non-zero values, as preprocess.normalize(norm=...) computes them, bit for bit; a sparse table
-    comes back sparse for both (Float32 / Int32)."""
+    comes back sparse for both (Float32 / Int32).
+    n_bins, rank_method ("tied" | "dense"), disc_method ("median" | "mean"): the options of the two binned modes ("mi_nz", and norm
+    "tss-nonzero-binned"), as preprocess.normalize takes and computes them: Int32 levels 0 .. n_bins - 1.  Away from their defaults
+    the call goes to fw_normalize_counts_opts / fw_normalize_counts_csc_opts; a value out of range, or an option given with a mode that
+    does not bin, raises ValueError naming it before anything is loaded."""
     if norm is not None:
         _front_end_kind("normalize_counts", test_name, norm)  # (an unknown or misplaced norm is refused before anything is loaded)
+    bins_check("normalize_counts", test_name, n_bins, rank_method, disc_method)
+    bins = bins_kw(n_bins, rank_method, disc_method)
     L = load_library()
     if is_sparse(counts) or isinstance(counts, CSC):  # (any other tuple is a dense table, as before)
-        return _normalize_csc(L.fw_normalize_counts_csc, "normalize_counts", as_csc(counts, np.int32), test_name, device, **_norm_kw(norm))
+        return _normalize_csc(_opts_front_end(L, "normalize_counts", "fw_normalize_counts_csc", bins), "normalize_counts", as_csc(counts, np.int32),
+                              test_name, device, **_norm_kw(norm), **bins)
     raw = np.asarray(counts)
     if raw.ndim != 2:
         raise ValueError("normalize_counts: counts must be a samples x OTUs matrix")
@@ -326,11 +362,13 @@ def normalize_counts(counts, test_name, device=0, norm=None):
             raise TypeError("normalize_counts: the device front-end takes integer counts (got non-integral %s values)" % raw.dtype)
     if raw.size and (raw.min() < 0 or raw.max() > np.iinfo(np.int32).max):
         raise ValueError("normalize_counts: counts must lie in [0, 2^31 - 1]")
-    return _normalize_dense(L.fw_normalize_counts, np.asfortranarray(raw.astype(np.int32)), test_name, device, **_norm_kw(norm))
+    return _normalize_dense(_opts_front_end(L, "normalize_counts", "fw_normalize_counts", bins), np.asfortranarray(raw.astype(np.int32)), test_name,
+                            device, **_norm_kw(norm), **bins)
 
 
-def _normalize_dense(front_end, x, test_name, device, norm=None):
-    """fw_normalize_counts / fw_normalize_abund (front_end) on the column-major table -> (data, row_mask, col_mask)"""
+def _normalize_dense(front_end, x, test_name, device, norm=None, **bins):
+    """fw_normalize_counts / fw_normalize_abund or their *_opts siblings (front_end) on the column-major table
+    -> (data, row_mask, col_mask)"""
     L = load_library()
     n, p = x.shape
     rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
@@ -338,7 +376,7 @@ def _normalize_dense(front_end, x, test_name, device, norm=None):
     kind = _front_end_kind("normalize", test_name, norm)
     of = np.zeros(n * p, np.float32) if NORM_OUT_DTYPE[kind] is np.float32 else None
     oi = np.zeros(n * p, np.int32) if NORM_OUT_DTYPE[kind] is np.int32 else None
-    rc = front_end(device, kind, n, p, _ptr(x), _ptr(of), _ptr(oi), _ptr(rm), _ptr(cm), C.byref(no), C.byref(po))
+    rc = front_end(device, kind, n, p, _ptr(x), _ptr(of), _ptr(oi), _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), *_opts_arg(front_end, **bins))
     if rc != 0:
         raise FlashWeaveError(rc, L.fw_last_error(None).decode())
     out = (of if of is not None else oi)[:no.value * po.value].reshape((no.value, po.value), order="F")
@@ -355,17 +393,20 @@ def abundance_defect(values):
     return None
 
 
-def normalize_abundances(table, test_name, device=0, norm=None):
+def normalize_abundances(table, test_name, device=0, norm=None, n_bins=3, rank_method="tied", disc_method="median"):
     """normalize_counts for a real-valued table -- relative abundances, percentages, coverage-normalised counts, counts beyond
     2^31 - 1 -- on the device (fw_normalize_abund, fw_normalize_abund_csc): -> (data, row_mask, col_mask) in the forms normalize_counts
     returns.  The values are taken as Float64 (a dense array of booleans, integers or floats is widened, Float32 exactly; a sparse
     table goes through as_csc(table, np.float64)); a table of integers gives the bits normalize_counts gives.  A NaN, an infinite or a
     negative value and a table that is not two-dimensional raise ValueError before any device call.
     norm: as for normalize_counts; every value is rounded to Float32 first, and a positive value outside [2^-126, 2^96] raises
-    ValueError before any device call."""
+    ValueError before any device call.
+    n_bins, rank_method, disc_method: as for normalize_counts (fw_normalize_abund_opts / fw_normalize_abund_csc_opts)."""
     who = "normalize_abundances"
     if norm is not None:
         _front_end_kind(who, test_name, norm)
+    bins_check(who, test_name, n_bins, rank_method, disc_method)
+    bins = bins_kw(n_bins, rank_method, disc_method)
     sparse = is_sparse(table) or isinstance(table, CSC)
     if sparse:
         triple = as_csc(table, np.float64)
@@ -385,8 +426,8 @@ def normalize_abundances(table, test_name, device=0, norm=None):
     if not hasattr(L, "fw_normalize_abund"):
         raise FlashWeaveError(-2, "%s: the loaded library has no fw_normalize_abund (an older build)" % who)
     if sparse:
-        return _normalize_csc(L.fw_normalize_abund_csc, who, triple, test_name, device, **_norm_kw(norm))
-    return _normalize_dense(L.fw_normalize_abund, values, test_name, device, **_norm_kw(norm))
+        return _normalize_csc(_opts_front_end(L, who, "fw_normalize_abund_csc", bins), who, triple, test_name, device, **_norm_kw(norm), **bins)
+    return _normalize_dense(_opts_front_end(L, who, "fw_normalize_abund", bins), values, test_name, device, **_norm_kw(norm), **bins)
 
 
 class Engine:

@@ -5,6 +5,7 @@ variables: variance / zero-read filters (:367-409), then
   "fz"    -> clr_adapt      adaptive pseudo-counts + centred log-ratio (:133-214)      -> Float32 dense
   "mi"    -> binary         presence/absence, columns with exactly 2 levels (:475-490) -> int {0,1}
   "mi_nz" -> binned_nz_clr  non-zero CLR, 2-bin median discretisation of the non-zeros (:492-521) -> int {0,1,2}
+                            (n_bins, rank_method, disc_method: other numbers of bins, dense ranks, the "mean" rule; discretize_nz)
 Computation is in Float64 like the reference (clrnorm converts to Matrix{Float64}, :330-341); `prec` only
 selects the output type of the continuous mode (convert_to_target_prec, misc.jl:54-62).
 The two total-sum-scaling modes (normalize(norm=...), TSS_NORMS) are the exception: like the reference they compute in
@@ -70,11 +71,67 @@ def _tiedrank(x):
     return rankdata(x, method="average")
 
 
-def discretize_nz(col, nz_mask, n_bins=3):
-    """discretize_nz + discretize (preprocessing.jl:238-291), disc_method = "median", rank_method = "tied"."""
+def _denserank(x):
+    from scipy.stats import rankdata
+    return rankdata(x, method="dense").astype(np.float64)
+
+
+def pairwise_mean(keys):
+    """The threshold of disc_method "mean", the one number the host and both device forms compute: the keys sorted ascending, padded
+    with +0.0 to the next power of two, added level by level (a[2i] + a[2i+1]), divided by their number.  Within rounding of the
+    reference's mean(x_vec) (preprocessing.jl:263), which leaves the order of its additions to Base."""
+    a = np.sort(np.asarray(keys, dtype=np.float64))
+    m, size = a.size, 1
+    while size < m:
+        size *= 2
+    a = np.concatenate([a, np.zeros(size - m)])
+    while a.size > 1:
+        a = a[0::2] + a[1::2]
+    return a[0] / m
+
+
+RANK_METHODS, DISC_METHODS = ("tied", "dense"), ("median", "mean")
+N_BINS_MAX = 62  # the engine takes variables of at most 62 levels (0 .. 61)
+
+
+def bins_check(who, test_name, n_bins=3, rank_method="tied", disc_method="median"):
+    """The three options of the binned modes (preprocessing.jl:217-291,412-416) against each other and against the test_name the
+    transform goes with ("mi_nz": binned_nz_clr and, with norm "tss-nonzero-binned", binned_nz_rows); anything else raises ValueError
+    naming the option.  -> True when all three are at their defaults."""
+    if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or not 3 <= n_bins <= N_BINS_MAX:
+        raise ValueError("%s: n_bins=%r is not supported: an integer in 3 .. %d (two levels are \"mi\" / \"pres-abs\"; the engine takes "
+                         "variables of at most %d levels)" % (who, n_bins, N_BINS_MAX, N_BINS_MAX))
+    if rank_method not in RANK_METHODS:
+        raise ValueError("%s: rank_method=%r is not a valid ranking method (%s)" % (who, rank_method, ", ".join(map(repr, RANK_METHODS))))
+    if disc_method not in DISC_METHODS:
+        raise ValueError("%s: disc_method=%r is not a valid discretization method (%s)" % (who, disc_method, ", ".join(map(repr, DISC_METHODS))))
+    if disc_method == "mean" and n_bins > 3:
+        raise ValueError("%s: disc_method='mean' only works with 2 non-zero bins (n_bins=3), got n_bins=%d" % (who, n_bins))
+    default = n_bins == 3 and rank_method == "tied" and disc_method == "median"
+    if not default and test_name != "mi_nz":
+        given = "n_bins=%r" % (n_bins,) if n_bins != 3 else "rank_method=%r" % (rank_method,) if rank_method != "tied" else "disc_method=%r" % (disc_method,)
+        raise ValueError("%s: %s applies to the binned modes only (test_name \"mi_nz\" / norm_mode \"clr-nonzero-binned\", "
+                         "\"tss-nonzero-binned\"), not to %r" % (who, given, test_name))
+    return default
+
+
+def bins_kw(n_bins=3, rank_method="tied", disc_method="median"):
+    """The three options as keywords for the next layer, only those away from their defaults: a call at the defaults is handed on as it
+    always was."""
+    given = dict(n_bins=n_bins, rank_method=rank_method, disc_method=disc_method)
+    return {k: v for k, v in given.items() if v != dict(n_bins=3, rank_method="tied", disc_method="median")[k]}
+
+
+def discretize_nz(col, nz_mask, n_bins=3, rank_method="tied", disc_method="median"):
+    """discretize_nz + discretize (preprocessing.jl:238-291) of the column's non-zero entries into n_bins - 1 levels 1 .. n_bins - 1,
+    zeros stay 0.  "median": the tied (average) or the dense rank r, level = floor((r / max r) / (1 / (n_bins - 1) + 1e-5)) + 1;
+    "mean" (n_bins = 3): level = 1 where the value is <= pairwise_mean of the non-zero entries, 2 above it."""
+    bins_check("discretize_nz", "mi_nz", n_bins, rank_method, disc_method)
     out = np.zeros(col.shape[0], dtype=np.int64)
-    if nz_mask.any():
-        r = _tiedrank(col[nz_mask])
+    if nz_mask.any() and disc_method == "mean":
+        out[nz_mask] = np.where(col[nz_mask] <= pairwise_mean(col[nz_mask]), 1, 2)
+    elif nz_mask.any():
+        r = _tiedrank(col[nz_mask]) if rank_method == "tied" else _denserank(col[nz_mask])
         r = r / r.max()
         step = (1.0 / (n_bins - 1)) + 1e-5
         out[nz_mask] = np.floor(r / step).astype(np.int64) + 1
@@ -149,7 +206,8 @@ def prepare_meta_block(md, mh, test_name, row_mask):
     return md[:, keep], [h for h, k in zip(mh, keep) if k]
 
 
-def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_header=None, make_onehot=True, normalizer=None, norm=None):
+def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_header=None, make_onehot=True, normalizer=None, norm=None,
+                        n_bins=3, rank_method="tied", disc_method="median"):
     """preprocess_data with a meta_mask (preprocessing.jl:412-563): OTU columns are normalised as in normalize(); meta
     variables are one-hot encoded, follow the row filters, are discretised into 2 bins for the discrete tests when they look
     continuous, are shifted by +1 for "fz_nz" if they hold zeros (zeros mean "absent" there), lose zero-variance columns
@@ -157,8 +215,11 @@ def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_head
     appended in CSC form as well: Int32 levels / Float32 values, a zero is an absent entry, the OTU part's stored zeros stay stored.
     norm (TSS_NORMS): the OTU columns take normalize(norm=...) -- a normalizer is expected to do the same -- and the meta variables
     the rules of the test_name the norm goes with: never shifted, discretised under "tss-nonzero-binned" only.
+    n_bins, rank_method, disc_method (the binned modes, see normalize): the OTU columns take them -- a normalizer is expected to do the
+    same -- and the meta variables do not: they go into 2 bins whatever n_bins is (preprocessing.jl:531-533).
     -> dict(data, header, meta_mask, row_mask)"""
     norm_check("normalize_with_meta", test_name, norm)
+    bins_check("normalize_with_meta", test_name, n_bins, rank_method, disc_method)
     if make_onehot:
         md, mh = onehot(meta, meta_header)
     else:
@@ -167,7 +228,8 @@ def normalize_with_meta(counts, test_name, meta, prec=32, header=None, meta_head
     if normalizer is not None:
         data, row_mask, col_mask = normalizer(counts, test_name)
     else:
-        data, row_mask, col_mask = normalize(counts, test_name, prec=prec, **({} if norm is None else {"norm": norm}))
+        data, row_mask, col_mask = normalize(counts, test_name, prec=prec, **({} if norm is None else {"norm": norm}),
+                                             **bins_kw(n_bins, rank_method, disc_method))
     md, mh = prepare_meta_block(md, mh, test_name, row_mask)
     if _is_csc(data):
         *otu, rows = _csc_parts(data)
@@ -211,14 +273,19 @@ def tss(data, prec=32):
         return X / s[:, None]
 
 
-def normalize(counts, test_name, prec=32, tie_anchor=False, norm=None):
+def normalize(counts, test_name, prec=32, tie_anchor=False, norm=None, n_bins=3, rank_method="tied", disc_method="median"):
     """-> (data, row_mask, col_mask).  row/col masks refer to the input matrix.  tie_anchor: see adaptive_clr ("fz" only).
     norm (TSS_NORMS, with the test_name it goes with) replaces the test's transform, under the same filters:
       "tss"                 tss() of the filtered table                                               -> Float{prec} dense
       "tss-nonzero-binned"  the ranks, bins and column rule of "mi_nz" with the tss() value as the key; the non-zero mask is taken
-                            before the division (a quotient may underflow to 0)                      -> Int32 {0,1,2}"""
+                            before the division (a quotient may underflow to 0)                      -> Int32 {0,1,2}
+    n_bins, rank_method ("tied" | "dense"), disc_method ("median" | "mean"): the options of the two binned modes ("mi_nz", and
+    "tss-nonzero-binned"), see discretize_nz; levels 0 .. n_bins - 1, and a column is kept iff its non-zero entries show exactly
+    n_bins - 1 distinct levels (preprocessing.jl:511-515).  Away from their defaults with any other mode: ValueError."""
     counts = np.asarray(counts)
     norm_check("normalize", test_name, norm)
+    bins_check("normalize", test_name, n_bins, rank_method, disc_method)
+    disc = dict(n_bins=n_bins, rank_method=rank_method, disc_method=disc_method)
     data, row_mask, col_mask = filter_by_variance(counts.astype(np.float64))
     cols = np.nonzero(col_mask)[0]
     if norm == "tss":
@@ -226,8 +293,8 @@ def normalize(counts, test_name, prec=32, tie_anchor=False, norm=None):
     if norm == "tss-nonzero-binned":
         nzm = data != 0
         c = tss(data, prec).astype(np.float64)  # (widening keeps order and ties)
-        d = np.stack([discretize_nz(c[:, j], nzm[:, j]) for j in range(c.shape[1])], axis=1)
-        km = np.array([len(np.unique(d[d[:, j] != 0, j])) == 2 for j in range(d.shape[1])])
+        d = np.stack([discretize_nz(c[:, j], nzm[:, j], **disc) for j in range(c.shape[1])], axis=1)
+        km = np.array([len(np.unique(d[d[:, j] != 0, j])) == n_bins - 1 for j in range(d.shape[1])])
         cm = np.zeros_like(col_mask)
         cm[cols[km]] = True
         return d[:, km].astype(np.int32), row_mask, cm
@@ -247,8 +314,8 @@ def normalize(counts, test_name, prec=32, tie_anchor=False, norm=None):
     if test_name == "mi_nz":
         nzm = data != 0
         c = clr_nz(data)
-        d = np.stack([discretize_nz(c[:, j], nzm[:, j]) for j in range(c.shape[1])], axis=1)
-        km = np.array([len(np.unique(d[d[:, j] != 0, j])) == 2 for j in range(d.shape[1])])
+        d = np.stack([discretize_nz(c[:, j], nzm[:, j], **disc) for j in range(c.shape[1])], axis=1)
+        km = np.array([len(np.unique(d[d[:, j] != 0, j])) == n_bins - 1 for j in range(d.shape[1])])
         cm = np.zeros_like(col_mask)
         cm[cols[km]] = True
         return d[:, km], row_mask, cm

@@ -433,6 +433,41 @@ int fw_normalize_abund_csc(int32_t device, int32_t kind, int32_t n, int32_t p, c
                            const double *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
                            uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out);
 
+/* The options of the two binned kinds (FW_MI_NZ, FW_NORM_TSS_BINNED): the reference's preprocess_kwargs n_bins, rank_method and
+ * disc_method (discretize, :217-291; preprocess_data, :412-416,492-521).  b = n_bins - 1 is the number of non-zero bins; in every
+ * kept column the keys of the non-zero entries (the clr_nz value, or the Float32 TSS quotient widened) are discretised in Float64:
+ *   FW_DISC_MEDIAN  r = the tied (average) rank (FW_RANK_TIED) or the dense rank (FW_RANK_DENSE: the distinct keys numbered 1 .. d
+ *                   in ascending order); level = floor((r / max r) / (1.0 / b + 1e-5)) + 1, in 1 .. b
+ *   FW_DISC_MEAN    (n_bins = 3 only) level = key <= mean ? 1 : 2, the mean being the pairwise sum of the column's keys sorted
+ *                   ascending and padded with +0.0 to the next power of two (a[2i] + a[2i+1], level by level), divided by their
+ *                   number: one number on every path, within rounding of the reference's mean(); rank_method is not looked at
+ * Zeros stay 0, and a column is kept iff its non-zero entries show exactly b distinct levels (:511-515).  Output: Int32 levels
+ * 0 .. b.  The defaults {3, FW_RANK_TIED, FW_DISC_MEDIAN} are what the four entry points above compute, to the bit.
+ * FW_ERR_ARG, the message naming the field, before any device call: n_bins outside 3 .. 62 (2 is FW_MI; the engine takes
+ * variables of at most 62 levels), an unknown rank_method or disc_method, FW_DISC_MEAN with n_bins > 3, and any field away from its
+ * default with a kind that does not bin. */
+#define FW_RANK_TIED 0
+#define FW_RANK_DENSE 1
+#define FW_DISC_MEDIAN 0
+#define FW_DISC_MEAN 1
+typedef struct fw_norm_opts {
+    int32_t n_bins, rank_method, disc_method;
+} fw_norm_opts;
+
+/* The four front-ends above with the options as a last argument (NULL: the defaults); the entry points above forward here with NULL. */
+int fw_normalize_counts_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *counts, float *out_f32, int32_t *out_i32,
+                             uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, const fw_norm_opts *opts);
+int fw_normalize_counts_csc_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                                 const int32_t *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                                 uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                                 const fw_norm_opts *opts);
+int fw_normalize_abund_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const double *values, float *out_f32, int32_t *out_i32,
+                            uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, const fw_norm_opts *opts);
+int fw_normalize_abund_csc_opts(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *colptr, const int32_t *rowval,
+                                const double *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
+                                uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                                const fw_norm_opts *opts);
+
 /* Device self-test of hand-written arithmetic sequences that replace a compiler-generated IEEE sequence and must return the
  * same bits.  which = FW_SELFTEST_DIV: the unscaled Float64 division of the NaN-free partial-correlation path (statfuns.jl:44-62
  * `/`) against the compiler's division on `cases` hashed operand pairs of that path's ranges; *mismatches = pairs that differ. */
