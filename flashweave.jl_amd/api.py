@@ -10,8 +10,8 @@ import numpy as np
 
 from . import io as fio
 from . import preprocess as pre
-from .engine import (CSC, Engine, abundance_defect, as_csc, is_sparse, normalize_abundances, normalize_counts, rejections_dict,
-                     tss_range_defect)
+from .engine import (CSC, Engine, abundance_defect, as_csc, is_device_tensor, is_sparse, normalize_abundances, normalize_counts,
+                     rejections_dict, tss_range_defect)
 
 
 class FWResult(dict):
@@ -43,12 +43,64 @@ def default_round_size(p):
 def _integral(a):
     """Count table the device front-end accepts: integral values in 0 .. 2^31 - 1 (fw_normalize_counts takes Int32); anything else
     -- relative abundances, negative entries, counts beyond Int32 -- goes to the host front-end (preprocess.py)."""
+    if is_device_tensor("_integral", a):
+        return _integral_tensor(a)
     if not a.size:
         return False
     if np.issubdtype(a.dtype, np.integer):
         return bool(a.min() >= 0 and a.max() < 2**31)
     return bool(np.issubdtype(a.dtype, np.floating) and np.all(np.isfinite(a)) and np.all(a == np.floor(a)) and
                 a.max() < 2**31 and a.min() >= 0)
+
+
+
+def _integral_tensor(t):
+    """_integral for a table in GPU memory, in torch ops on the device (booleans count as 0 / 1)"""
+    import torch
+    if not t.numel() or t.dtype.is_complex:
+        return False
+    if t.dtype.is_floating_point and not (bool(torch.isfinite(t).all()) and bool((t == torch.floor(t)).all())):
+        return False
+    return t.dtype == torch.bool or bool(float(t.min()) >= 0 and float(t.max()) < 2**31)
+
+
+def _tensor_refusals(who, t, device, normalize, abundances, meta_data=None, meta_mask=None, extra_data=None, prec=32, device_normalize=True,
+                     distributed=False, csc_resident=False):
+    """What a table in GPU memory (a torch tensor, engine.is_device_tensor) is not served with: each would need the table's bytes on
+    the host, and copying silently would defeat the point.  Every refusal names its option and the way out (tensor.cpu()), before any
+    library call; the last one looks at the values, with torch ops on the device."""
+    import torch
+
+    def no(option, why):
+        raise ValueError("%s: %s with a table in GPU memory is not supported: %s; pass tensor.cpu() instead" % (who, option, why))
+    if t.layout != torch.strided:
+        raise ValueError("%s: a sparse torch tensor is not supported: scipy.sparse is the sparse interface; build a scipy matrix from "
+                         "tensor.cpu() instead (or pass tensor.to_dense())" % who)
+    numeric = t.dtype.is_floating_point or t.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+    if t.dim() != 2 or not numeric:
+        raise ValueError("%s: a device tensor must be a 2-D samples x variables table of a numeric dtype (got %d dimensions, %s); "
+                         "pass tensor.cpu() instead if it is something else" % (who, t.dim(), t.dtype))
+    if meta_data is not None:
+        no("meta_data", "meta variables are prepared on the host")
+    if meta_mask is not None:
+        no("meta_mask", "meta variables are prepared on the host")
+    if extra_data is not None:
+        no("extra_data", "several tables are combined on the host")
+    if prec == 64:
+        no("prec=64", "the Float64 mode uploads from the host")
+    if not device_normalize:
+        no("device_normalize=False", "the host front-end reads host memory")
+    if distributed:
+        no("distributed=True", "the digest the ranks compare needs the table's bytes on the host")
+    if csc_resident:
+        no("csc_resident=True", "the CSC-resident layout is built from a scipy.sparse matrix")
+    if t.device.index != device:
+        raise ValueError("%s: device=%d while the tensor lives on %s: pass the device the table is on, or tensor.cpu() instead"
+                         % (who, device, t.device))
+    if normalize and not abundances and not _integral_tensor(t):
+        raise ValueError("%s: the tensor does not hold integral counts in 0 .. 2^31 - 1 and abundances=True is not given: pass "
+                         "abundances=True for a real-valued table in GPU memory, or tensor.cpu() instead for the host front-end" % who)
+
 
 _TEST_NAMES = ("fz", "fz_nz", "mi", "mi_nz")
 # normalize_data's norm_mode (preprocessing.jl:660-684) -> the test_name it stands for (four aliases) or goes with (the two TSS modes,
@@ -254,7 +306,8 @@ def _normalize_tables(data, header, extra, test_name, meta_data, meta_header, ma
     kw = dict({} if tss is None else {"norm": tss}, **(bins or {}))
     norm = None  # (None: the host front-end as it is)
     if on_device and abundances:  # (a dense table is handed over as the Float64 values the front-end reads; Float32 widens exactly)
-        norm = lambda c, t: normalize_abundances(c if isinstance(c, CSC) else np.asarray(c, dtype=np.float64), t, device=device, **kw)
+        norm = lambda c, t: normalize_abundances(c if (isinstance(c, CSC) or is_device_tensor("normalize_data", c)) else np.asarray(c, dtype=np.float64),
+                                                 t, device=device, **kw)
     elif on_device:
         norm = lambda c, t: normalize_counts(c, t, device=device, **kw)
     elif abundances:  # the host front-end with the anchor rule of the Float64 device front-end (preprocess.adaptive_clr)
@@ -353,7 +406,7 @@ def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extr
     as well?).  abundances (with normalize): a sparse block is made canonical as Float64 instead of as counts, and the value refusals
     come last.  -> _Tables; header is the caller's object when one was given and nothing was split off."""
     sparse = _any_sparse(data) if csc_tuple_is_sparse else is_sparse(data)
-    data = data if sparse else np.asarray(data)
+    data = data if (sparse or is_device_tensor(who, data)) else np.asarray(data)  # (a table in GPU memory stays where it is)
     mask = _meta_mask_vector(who, meta_mask, meta_data, data)
     if sparse:
         # a sparse table stays sparse from here to the device (fw_normalize_counts_csc, fw_set_data_csc_*); what would need the dense
@@ -529,6 +582,12 @@ def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data
     normalize=False (the discrete engine serves up to 62 levels).  ValueError naming the option, before any device call: n_bins no
     integer in 3 .. 62, an unknown rank_method or disc_method, disc_method="mean" with n_bins > 3, and any of the three away from its
     default with a mode that does not bin.
+    data may be a 2-D torch.Tensor in GPU memory (device.type "cuda", on GPU `device`): the device front-end borrows it
+    (fw_normalize_counts_dev, with abundances=True fw_normalize_abund_dev) and `data` of the result is a tensor on the same device, an
+    (n_out, p_out) view with strides (1, n_out), the bits of the numpy call; header and the two masks come back as always.  Every
+    norm_mode and the three binning options are served; meta_data, meta_mask, extra_data, prec=64, device_normalize=False, a
+    non-integral tensor without abundances=True, a tensor of another GPU, one that is not 2-D or not numeric and a sparse tensor raise a
+    ValueError that names the option and says to pass tensor.cpu() instead (see learn_network).
     -> dict(data, header, meta_mask, row_mask): row_mask over the input samples, data a scipy.sparse.csc_matrix for sparse tables
     (dense for "fz")."""
     who = "normalize_data"
@@ -549,6 +608,9 @@ def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data
     if prec not in (32, 64):
         raise ValueError("%s: prec=%r is not supported (32 or 64)" % (who, prec))
     pre.bins_check(who, test_name, n_bins, rank_method, disc_method)
+    if is_device_tensor(who, data):  # a table in GPU memory: what would need its bytes on the host is refused by name
+        _tensor_refusals(who, data, device, True, bool(abundances), meta_data=meta_data, meta_mask=meta_mask, extra_data=extra_data, prec=prec,
+                         device_normalize=device_normalize)
     # this entry point's rules of the table stage: an engine.CSC tuple is a sparse table, and a header always has the table's length
     t = _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec, device_normalize,
                         normalize=True, csc_tuple_is_sparse=True, strict_header=True, abundances=bool(abundances))
@@ -649,6 +711,15 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     infinite or a negative value in a table (named: data or extra_data[i]) raise ValueError naming abundances before any device call.
     Without the option a real-valued dense table goes to the host front-end and a sparse one is refused, as before.
     parameters["abundances"] is there (True) only when the option is on.
+    A table in GPU memory: data may be a 2-D torch.Tensor with device.type "cuda" on GPU `device`.  It never crosses to the host: the
+    front-end borrows it and writes into a device buffer (engine.normalize_counts / normalize_abundances: fw_normalize_*_dev), and the
+    engine builds its resident layout from that buffer on the device (Engine.set_data: fw_set_data_dense_*_dev); normalize=False hands
+    the tensor straight to the engine.  The result is the FWResult of tensor.cpu().numpy(), to the bit; counters["table_on_device"] and
+    parameters["table_on_device"] are there (True) only for such a call.  All four tests, abundances=True, header and every engine
+    option are served.  Refused with a ValueError that names the option and says to pass tensor.cpu() instead, before any library
+    call: meta_data, meta_mask, extra_data, prec=64, device_normalize=False, distributed=True, csc_resident=True, a non-integral tensor
+    without abundances=True, a tensor of another GPU than `device`, one that is not 2-D or not numeric, a sparse tensor.  A CPU tensor
+    is an array (np.asarray); any other device type raises ValueError.
     Path form (learning.jl:354-401): data may be a path (str / os.PathLike) or a list of paths, read with io.load_data (.tsv, .csv,
     BIOM 1.0 JSON; anything else raises what load_data raises): the first is the main table, the others become extra_data under their
     file headers; meta_data_path (second positional argument, as in the reference) is the main table's meta data file;
@@ -659,6 +730,13 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     if prec not in (32, 64):
         raise ValueError("learn_network: prec=%r is not supported (32 or 64; the reference's 16 and 128 are not served)" % (prec,))
     abundances = bool(abundances)  # (before the digest: ranks passing 1 and True make the same run)
+    on_gpu = is_device_tensor("learn_network", data)
+    if on_gpu:  # a table in GPU memory: what would need its bytes on the host is refused by name, before any library call
+        if abundances and not normalize:
+            raise ValueError("learn_network: abundances=True with normalize=False is not supported: the option chooses the front-end of a "
+                             "table that is normalised here, and a prepared matrix has nothing left to normalise")
+        _tensor_refusals("learn_network", data, device, normalize, abundances, meta_data=meta_data, meta_mask=meta_mask, extra_data=extra_data,
+                         prec=prec, device_normalize=device_normalize, distributed=distributed, csc_resident=csc_resident)
     # the mode keywords as the caller passed them, before any is resolved: what the ranks of a distributed run compare
     caller = dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=feed_forward, normalize=normalize,
                   hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec, round_size=round_size, make_onehot=make_onehot,
@@ -695,5 +773,7 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     parameters.update(extra_data=len(t.extra), meta_mask=t.n_marked, distributed=world, schedule=_schedule(run["round_size"], feed_forward, p))
     if abundances:
         parameters["abundances"] = True
+    if on_gpu:  # (the table never left the device: front-end and upload borrowed it there)
+        counters["table_on_device"] = parameters["table_on_device"] = True
     return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header), parameters=parameters,
                     counters=counters, rejections=net["rejections"])

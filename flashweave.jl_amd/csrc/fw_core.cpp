@@ -437,6 +437,54 @@ int fw_set_data_dense_i32(fw_ctx *c, const int32_t *data)
     return fw_set_data_csc_i32(c, colptr.data(), rowval.data(), nzval.data());
 }
 
+// ---- tables that already live in device memory (a torch tensor's data_ptr(), a ROCArray): nothing crosses to the host but the small
+// column records of the discrete scan.  The pointer is asked of the runtime before anything reads it; each call synchronises the
+// context's stream before it returns.
+int fw_set_data_dense_i32_dev(fw_ctx *c, const int32_t *d_data)
+{
+    CHECK_CTX(c);
+    if (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_i32_dev: context is not discrete");
+    if (!d_data) return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_i32_dev: NULL data");
+    if (!fw_is_dev_ptr(d_data, c->P.device))
+        return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_i32_dev: data is not device memory of device %d (fw_set_data_dense_i32 takes a host table)", c->P.device);
+    int rc = fwi_mi_upload_dev(c, d_data);
+    if (rc) return rc;
+    resolve_n_obs_min_discrete(c);
+    c->have_data = true;
+    c->have_level0 = false;
+    c->have_network = false;
+    return FW_OK;
+}
+
+int fw_set_data_dense_f32_dev(fw_ctx *c, const float *d_data)
+{
+    CHECK_CTX(c);
+    if (c->P.kind != FW_FZ && c->P.kind != FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_f32_dev: context is not FW_FZ / FW_FZ_NZ");
+    if (!d_data) return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_f32_dev: NULL data");
+    if (!fw_is_dev_ptr(d_data, c->P.device))
+        return fw_fail(c, FW_ERR_ARG, "fw_set_data_dense_f32_dev: data is not device memory of device %d (fw_set_data_dense_f32 takes a host matrix)", c->P.device);
+    if (c->f64) return fw_fail(c, FW_ERR_STATE, "fw_set_data_dense_f32_dev: the context is in Float64 mode (fw_set_data_dense_f64 / fw_set_cor_mat_f64 came first); precisions do not mix");
+    if (c->P.kind == FW_FZ_NZ) {
+        int rc = fwi_fznz_upload_dev(c, d_data);
+        if (rc) return rc;
+        c->have_data = true;
+        c->have_level0 = false;
+        c->have_network = false;
+        return FW_OK;
+    }
+    const size_t bytes = sizeof(float) * (size_t)c->P.n * c->P.p;
+    if (!c->d_data) FW_HIP(c, hipMalloc(&c->d_data, bytes));
+    FW_HIP(c, hipMemcpyAsync(c->d_data, d_data, bytes, hipMemcpyDeviceToDevice, c->stream));
+    FW_HIP(c, hipStreamSynchronize(c->stream));
+    c->f32_input = true;
+    c->have_data = true;
+    c->have_fzs_stat = false;
+    c->have_cor = false;
+    c->have_level0 = false;
+    c->have_network = false;
+    return FW_OK;
+}
+
 int fw_get_levels(const fw_ctx *c, int32_t *levels, int32_t *max_vals)
 {
     CHECK_CTX(c);

@@ -1525,6 +1525,42 @@ int fwi_fznz_upload(fw_ctx *ctx, const float *data)
     return FW_OK;
 }
 
+// fw_set_data_dense_f32_dev: the plane of a [p][n] matrix in device memory.  Wavefront g builds word g of the [p][W] plane: its 64
+// lanes load 64 consecutive rows of one column and the ballot of x != 0.0f -- the expression of the host loop above, so -0.0f is a
+// zero and a NaN is not -- is the word; the rows >= n of a column's last word come out zero.
+__global__ __launch_bounds__(256) void fznz_dev_plane_kernel(const float *__restrict__ x, int n, int W, unsigned long long words,
+                                                             unsigned long long *__restrict__ nzb)
+{
+    const unsigned long long g = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= words) return;  // (whole wavefronts leave: the ballot below sees all 64 lanes)
+    const int lane = threadIdx.x & 63;
+    const unsigned long long v = g / (unsigned)W;
+    const long long r = (long long)(g % (unsigned)W) * 64 + lane;
+    const float a = r < n ? x[(size_t)v * n + r] : 0.0f;
+    const unsigned long long nz = __ballot(a != 0.0f);
+    if (lane == 0) nzb[g] = nz;
+}
+
+int fwi_fznz_upload_dev(fw_ctx *ctx, const float *d_src)
+{
+    const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
+    const size_t bytes = sizeof(float) * (size_t)n * p;
+    const unsigned long long words = (unsigned long long)p * W;
+    fznz_drop_cscres(ctx);
+    if (!ctx->d_data) FW_HIP(ctx, hipMalloc(&ctx->d_data, bytes));
+    if (ctx->d_nzbits) (void)hipFree(ctx->d_nzbits);
+    ctx->d_nzbits = nullptr;
+    FW_HIP(ctx, hipMalloc((void **)&ctx->d_nzbits, sizeof(uint64_t) * words));
+    ctx->W = W;
+    FW_HIP(ctx, hipMemcpyAsync(ctx->d_data, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    hipLaunchKernelGGL(fznz_dev_plane_kernel, dim3((unsigned)((words + 3) / 4)), dim3(256), 0, ctx->stream, (const float *)ctx->d_data, n, W, words,
+                       (unsigned long long *)ctx->d_nzbits);
+    FW_HIP(ctx, hipGetLastError());
+    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cnt.kernel_launches += 1;
+    return FW_OK;
+}
+
 // fw_set_data_csc_f32: the CSC triple scattered on the device into the layout fwi_fznz_upload leaves (values [p][n], zero elsewhere,
 // and the plane of values != 0), one wavefront per column.  The column is checked first (fw_csc.h) and scattered only when it is
 // good, so no store leaves the layout.  Each plane word belongs to one lane, which finds the word's entries in the sorted run by

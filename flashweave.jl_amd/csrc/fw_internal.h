@@ -73,6 +73,19 @@ public:
     }
 };
 
+// A table the *_dev entry points borrow: device memory of `device`, asked of the runtime before anything reads it.  NULL, a host
+// pointer (pinned or not), managed memory and memory of another device are not.
+inline bool fw_is_dev_ptr(const void *q, int device)
+{
+    if (!q) return false;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, q) != hipSuccess) {
+        (void)hipGetLastError();  // (an unregistered host pointer: the error is the answer, not a state to keep)
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice && a.device == device;
+}
+
 // Job descriptor for the test_subsets kernels (device layout)
 struct FwJob {
     int32_t X;        // T
@@ -342,6 +355,7 @@ int fwi_fzs_segments_nz(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const in
 
 // ---- HE-S / fz_nz (fw_fz.hip) ----
 int fwi_fznz_upload(fw_ctx *ctx, const float *data);
+int fwi_fznz_upload_dev(fw_ctx *ctx, const float *d_src);  // the same layout from a [p][n] matrix in device memory: copy + plane kernel
 int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);  // the same layout from a CSC triple
 int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);  // plane + base + values != 0 (fw_cscres.h)
 int fwi_fznz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
@@ -363,6 +377,7 @@ int fwi_fznz_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t 
 
 // ---- discrete (fw_mi.hip) ----
 int fwi_mi_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const int32_t *nzval);
+int fwi_mi_upload_dev(fw_ctx *ctx, const int32_t *d_src);  // the same layouts from a [p][n] table in device memory: column scan + pack
 int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                   std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev);
 int fwi_mi_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff,

@@ -1281,6 +1281,7 @@ static int mig_dev_tables(fw_ctx *ctx, MiDev &P, int64_t wgs, int which /* 0: th
     P.gtab_words = (unsigned long long)ctx->mig_gtab_words;
     return FW_OK;
 }
+static int mig_finish(fw_ctx *ctx, int maxv_all, const unsigned char *vals, const int32_t *d_src);
 static int mig_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const int32_t *nzval)
 {
     const int n = ctx->P.n, p = ctx->P.p;
@@ -1301,6 +1302,21 @@ static int mig_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval,
         ctx->max_vals[v] = mx;
         maxv_all = std::max(maxv_all, mx);
     }
+    return mig_finish(ctx, maxv_all, vals.data(), nullptr);
+}
+
+// the byte matrix of the generic form from a [p][n] Int32 table in device memory (values checked: 0 .. MIG_MAX_L - 1)
+__global__ __launch_bounds__(256) void mi_dev_bytes_kernel(const int32_t *__restrict__ x, size_t cells, unsigned char *__restrict__ vals)
+{
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < cells; t += (size_t)gridDim.x * 256) vals[t] = (unsigned char)x[t];
+}
+
+// What follows levels / max_vals in the generic form, for both builds: the limits, the byte matrix -- copied from the host (vals) or
+// cast on the device from the caller's table (d_src, fw_set_data_dense_i32_dev) -- and the thresholds.
+static int mig_finish(fw_ctx *ctx, int maxv_all, const unsigned char *vals, const int32_t *d_src)
+{
+    const int n = ctx->P.n, p = ctx->P.p;
+    const size_t cells = (size_t)p * n;
     ctx->L = maxv_all + 1;
     ctx->mi_nxy = ctx->L;
     ctx->W = (n + 63) / 64;
@@ -1319,8 +1335,15 @@ static int mig_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval,
             (void)hipFree(*q);
             *q = nullptr;
         }
-    FW_HIP(ctx, hipMalloc((void **)&ctx->d_vals, vals.size()));
-    FW_HIP(ctx, hipMemcpy(ctx->d_vals, vals.data(), vals.size(), hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMalloc((void **)&ctx->d_vals, cells));
+    if (d_src) {
+        hipLaunchKernelGGL(mi_dev_bytes_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 65536)), dim3(256), 0, ctx->stream, d_src, cells, ctx->d_vals);
+        FW_HIP(ctx, hipGetLastError());
+        FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->cnt.kernel_launches += 1;
+    } else {
+        FW_HIP(ctx, hipMemcpy(ctx->d_vals, vals, cells, hipMemcpyHostToDevice));
+    }
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_levels, sizeof(int32_t) * p));
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_maxvals, sizeof(int32_t) * p));
     FW_HIP(ctx, hipMemcpy(ctx->d_levels, ctx->levels.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice));
@@ -1456,6 +1479,15 @@ static int mig_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t
     return FW_OK;
 }
 
+// The planes of the three-level form as the host scan of a CSC triple leaves them (nzb, hib), or the caller's [p][n] table in device
+// memory to pack them from (d_src); the per-column totals come from the host either way.
+struct MiPlaneSrc {
+    const uint64_t *nzb, *hib;
+    const int32_t *cnt_nz, *cnt_hi;
+    const int32_t *d_src;
+};
+static int mi_finish_planes(fw_ctx *ctx, int maxv_all, const MiPlaneSrc &S);
+
 int fwi_mi_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const int32_t *nzval)
 {
     const int n = ctx->P.n, p = ctx->P.p;
@@ -1499,6 +1531,119 @@ int fwi_mi_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, con
         maxv_all = std::max(maxv_all, (int)mx);
     }
     if (generic) return mig_upload(ctx, colptr, rowval, nzval);
+    return mi_finish_planes(ctx, maxv_all, MiPlaneSrc{nzb.data(), hib.data(), cnt_nz.data(), cnt_hi.data(), nullptr});
+}
+
+// ---- fw_set_data_dense_i32_dev: the same layouts from a [p][n] Int32 table in device memory, in two passes -------------------------
+// Pass 1, one workgroup per column: what the host needs to decide the form and to refuse as fwi_mi_upload refuses.  Only these p
+// records cross to the host.
+struct MiColRec {
+    unsigned long long mask;  // bit x: the column holds the value x (0 .. MIG_MAX_L - 1)
+    int32_t cnt_nz, cnt_hi;   // cells != 0, cells == 2 (in-range cells)
+    int32_t maxv;             // the largest in-range value
+    int32_t bad_row, bad_val; // the first row whose value is outside 0 .. MIG_MAX_L - 1 and that value; bad_row = n: none
+    int32_t pad;
+};
+static_assert(MIG_MAX_L <= 64, "MiColRec.mask holds one bit per value");
+
+__global__ __launch_bounds__(256) void mi_dev_scan_kernel(const int32_t *__restrict__ x, int n, MiColRec *__restrict__ rec)
+{
+    __shared__ unsigned long long s_mask[4];
+    __shared__ int s_nz[4], s_hi[4], s_bad[4];
+    const int v = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t *col = x + (size_t)v * n;
+    unsigned long long mask = 0;
+    int nz = 0, hi = 0, bad = n;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int32_t a = col[i];
+        if (a < 0 || a >= MIG_MAX_L) {
+            if (bad == n) bad = i;  // (rows ascend within a thread)
+        } else {
+            mask |= 1ull << a;
+            nz += a != 0;
+            hi += a == 2;
+        }
+    }
+    for (int o = 32; o; o >>= 1) {
+        mask |= __shfl_xor(mask, o);
+        nz += __shfl_xor(nz, o);
+        hi += __shfl_xor(hi, o);
+        bad = min(bad, __shfl_xor(bad, o));
+    }
+    if (lane == 0) s_mask[wave] = mask, s_nz[wave] = nz, s_hi[wave] = hi, s_bad[wave] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        MiColRec r;
+        r.mask = s_mask[0] | s_mask[1] | s_mask[2] | s_mask[3];
+        r.cnt_nz = s_nz[0] + s_nz[1] + s_nz[2] + s_nz[3];
+        r.cnt_hi = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
+        r.maxv = r.mask ? 63 - __clzll((long long)r.mask) : 0;
+        r.bad_row = min(min(s_bad[0], s_bad[1]), min(s_bad[2], s_bad[3]));
+        r.bad_val = r.bad_row < n ? col[r.bad_row] : 0;
+        r.pad = 0;
+        rec[v] = r;
+    }
+}
+
+// Pass 2 of the three-level form: wavefront g builds plane word g of the padded [p_pad][W] layout (+ the slack words): its 64 lanes load
+// 64 consecutive rows of one column, and the two ballots are the two words.  Words past the table -- the last word's rows >= n, the pad
+// columns, the slack -- come out zero, so the planes need no clearing.  hib: nullptr when no column holds a 2.
+__global__ __launch_bounds__(256) void mi_dev_pack_kernel(const int32_t *__restrict__ x, int n, int p, int W, unsigned long long words,
+                                                          unsigned long long *__restrict__ nzb, unsigned long long *__restrict__ hib)
+{
+    const unsigned long long g = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= words) return;  // (whole wavefronts leave: the ballots below see all 64 lanes)
+    const int lane = threadIdx.x & 63;
+    const unsigned long long v = g / (unsigned)W;
+    const long long r = (long long)(g % (unsigned)W) * 64 + lane;
+    int32_t a = 0;
+    if (v < (unsigned long long)p && r < n) a = x[(size_t)v * n + r];
+    const unsigned long long nz = __ballot(a != 0), hi = __ballot(a == 2);
+    if (lane == 0) {
+        nzb[g] = nz;
+        if (hib) hib[g] = hi;
+    }
+}
+
+int fwi_mi_upload_dev(fw_ctx *ctx, const int32_t *d_src)
+{
+    const int n = ctx->P.n, p = ctx->P.p;
+    if (ctx->P.max_k > MI_MAX_K) return fw_fail(ctx, FW_ERR_LIMIT, "discrete tests support max_k <= %d (got %d)", MI_MAX_K, ctx->P.max_k);
+    FwDevArray<MiColRec> d_rec;
+    std::vector<MiColRec> rec((size_t)p);
+    FW_HIP(ctx, d_rec.alloc((size_t)p));
+    hipLaunchKernelGGL(mi_dev_scan_kernel, dim3((unsigned)p), dim3(256), 0, ctx->stream, d_src, n, d_rec.get());
+    FW_HIP(ctx, hipGetLastError());
+    FW_HIP(ctx, hipMemcpyAsync(rec.data(), d_rec.get(), sizeof(MiColRec) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cnt.kernel_launches += 1;
+    std::vector<int32_t> cnt_nz(p, 0), cnt_hi(p, 0);
+    ctx->levels.assign(p, 0);
+    ctx->max_vals.assign(p, 0);
+    int maxv_all = 0;
+    bool generic = false;
+    ctx->mi_generic = false;
+    for (int v = 0; v < p; ++v) {  // (the lowest bad column and its first bad row: what the host scan meets first)
+        const MiColRec &r = rec[v];
+        if (r.bad_row < n)
+            return fw_fail(ctx, FW_ERR_LIMIT, "discrete values must be 0 .. %d (column %d holds %d); stored zeros are not allowed", MIG_MAX_L - 1, v, r.bad_val);
+        generic = generic || (r.mask >> 3) != 0;
+        // misc.jl:64-72 / :84-87: the distinct values of the column, the zero included
+        ctx->levels[v] = (int32_t)__builtin_popcountll(r.mask);
+        ctx->max_vals[v] = r.maxv;
+        cnt_nz[v] = r.cnt_nz;
+        cnt_hi[v] = r.cnt_hi;
+        maxv_all = std::max(maxv_all, (int)r.maxv);
+    }
+    if (generic) return mig_finish(ctx, maxv_all, nullptr, d_src);
+    return mi_finish_planes(ctx, maxv_all, MiPlaneSrc{nullptr, nullptr, cnt_nz.data(), cnt_hi.data(), d_src});
+}
+
+// What follows levels / max_vals in the three-level form, for both builds: the limits, the padded planes, the per-column records, the
+// tables and the thresholds.
+static int mi_finish_planes(fw_ctx *ctx, int maxv_all, const MiPlaneSrc &S)
+{
+    const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
     ctx->L = maxv_all + 1;  // types.jl:89,110
     if (ctx->L < 2) ctx->L = 2;
     ctx->mi_nxy = (ctx->L == 3 && ctx->P.kind == FW_MI) ? 3 : 2;
@@ -1517,12 +1662,21 @@ int fwi_mi_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, con
     // (rows padded to whole level-0 tiles plus one stage of slack words, zero: mi_level0_mfma_kernel stages without clamps)
     const size_t pb_alloc = sizeof(uint64_t) * ((size_t)((p + L0M_T - 1) / L0M_T * L0M_T) * W + L0M_WC);
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_nzbits, pb_alloc));
-    FW_HIP(ctx, hipMemset(ctx->d_nzbits, 0, pb_alloc));
-    FW_HIP(ctx, hipMemcpy(ctx->d_nzbits, nzb.data(), pb, hipMemcpyHostToDevice));
-    if (ctx->L > 2) {
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_hibits, pb_alloc));
-        FW_HIP(ctx, hipMemset(ctx->d_hibits, 0, pb_alloc));
-        FW_HIP(ctx, hipMemcpy(ctx->d_hibits, hib.data(), pb, hipMemcpyHostToDevice));
+    if (ctx->L > 2) FW_HIP(ctx, hipMalloc((void **)&ctx->d_hibits, pb_alloc));
+    if (S.d_src) {
+        const unsigned long long words = pb_alloc / sizeof(uint64_t);
+        hipLaunchKernelGGL(mi_dev_pack_kernel, dim3((unsigned)((words + 3) / 4)), dim3(256), 0, ctx->stream, S.d_src, n, p, W, words,
+                           (unsigned long long *)ctx->d_nzbits, (unsigned long long *)ctx->d_hibits);
+        FW_HIP(ctx, hipGetLastError());
+        FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->cnt.kernel_launches += 1;
+    } else {
+        FW_HIP(ctx, hipMemset(ctx->d_nzbits, 0, pb_alloc));
+        FW_HIP(ctx, hipMemcpy(ctx->d_nzbits, S.nzb, pb, hipMemcpyHostToDevice));
+        if (ctx->L > 2) {
+            FW_HIP(ctx, hipMemset(ctx->d_hibits, 0, pb_alloc));
+            FW_HIP(ctx, hipMemcpy(ctx->d_hibits, S.hib, pb, hipMemcpyHostToDevice));
+        }
     }
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_levels, sizeof(int32_t) * p));
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_maxvals, sizeof(int32_t) * p));
@@ -1564,8 +1718,8 @@ int fwi_mi_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, con
     }
     // d_firstnz doubles as storage for the per-column totals [cnt_nz | cnt_hi]
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_firstnz, sizeof(int32_t) * 2 * (size_t)p));
-    FW_HIP(ctx, hipMemcpy(ctx->d_firstnz, cnt_nz.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice));
-    FW_HIP(ctx, hipMemcpy(ctx->d_firstnz + p, cnt_hi.data(), sizeof(int32_t) * p, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(ctx->d_firstnz, S.cnt_nz, sizeof(int32_t) * p, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(ctx->d_firstnz + p, S.cnt_hi, sizeof(int32_t) * p, hipMemcpyHostToDevice));
     return FW_OK;
 }
 

@@ -484,6 +484,7 @@ struct NormCall {
     NormRows R;
     FwDevArray<int32_t> d_cols;
     FwDevArray<float> d_s32;
+    bool dev_out = false;  // the *_dev entry points: out_f32 / out_i32 are the caller's device buffers, written by the output kernels
 };
 
 dim3 norm_out_grid(int nk, int pk) { return dim3((nk + 255) / 256, std::min(pk, NORM_GRID_Y)); }
@@ -576,7 +577,8 @@ template <typename V> int dense_filters(NormCall &c, const V *d_x, int p)
     return norm_rows(c, NormVal<V>::tie_rel(pk), norm_reduce_chunks(n, rsum, rlog, rzero, rmin), s32);
 }
 
-// dense output: the kind's transform over the kept cells -> out_i32 | out_f32 (column-major, kept samples x the columns left in cols)
+// dense output: the kind's transform over the kept cells -> out_i32 | out_f32 (column-major, kept samples x the columns left in cols):
+// host buffers the result is downloaded into, or (c.dev_out) device buffers of n p elements the output kernels write themselves
 template <typename V> int dense_output(NormCall &c, const V *d_x, float *out_f32, int32_t *out_i32)
 {
     const int n = c.n, nk = (int)c.R.rows.size(), pk = (int)c.cols.size();
@@ -585,7 +587,12 @@ template <typename V> int dense_output(NormCall &c, const V *d_x, float *out_f32
     FwDevArray<float> d_of;
     std::vector<int32_t> two((size_t)pk);
     FW_HIP(nullptr, d_rows.upload(c.R.rows));
-    if (!c.K.i32) FW_HIP(nullptr, d_of.alloc((size_t)nk * pk));
+    float *of = out_f32;
+    int32_t *oi = out_i32;
+    if (!c.K.i32 && !c.dev_out) {
+        FW_HIP(nullptr, d_of.alloc((size_t)nk * pk));
+        of = d_of.get();
+    }
     if (c.K.i32 && !c.K.binned) {  // FW_MI: presabs_norm! + columns with exactly two levels among the kept samples
         FW_HIP(nullptr, d_two.alloc((size_t)pk));
         hipLaunchKernelGGL(norm_col_levels_kernel<V>, dim3(pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_two.get());
@@ -594,8 +601,11 @@ template <typename V> int dense_output(NormCall &c, const V *d_x, float *out_f32
         if (norm_keep_columns(two, c.cols, c.col_mask).empty()) return norm_none_left(c);
         const int pf = (int)c.cols.size();
         FW_HIP(nullptr, hipMemcpy(c.d_cols.get(), c.cols.data(), sizeof(int32_t) * pf, hipMemcpyHostToDevice));
-        FW_HIP(nullptr, d_oi.alloc((size_t)nk * pf));
-        hipLaunchKernelGGL(norm_binary_out_kernel<V>, norm_out_grid(nk, pf), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pf, d_oi.get());
+        if (!c.dev_out) {
+            FW_HIP(nullptr, d_oi.alloc((size_t)nk * pf));
+            oi = d_oi.get();
+        }
+        hipLaunchKernelGGL(norm_binary_out_kernel<V>, norm_out_grid(nk, pf), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pf, oi);
     } else if (c.K.binned) {  // every kept column is binned, then the columns that show both bins are gathered
         const auto binned = c.O.plain() ? (!c.K.tss ? norm_binned_kernel<V, false, false> : norm_binned_kernel<V, true, false>)  // (the key: nb_key)
                                         : (!c.K.tss ? norm_binned_kernel<V, false, true> : norm_binned_kernel<V, true, true>);
@@ -611,35 +621,49 @@ template <typename V> int dense_output(NormCall &c, const V *d_x, float *out_f32
         const int pf = (int)sel.size();
         if (pf == 0) return norm_none_left(c);
         FW_HIP(nullptr, d_sel.upload(sel));
-        FW_HIP(nullptr, d_oi.alloc((size_t)nk * pf));
-        hipLaunchKernelGGL(norm_gather_cols_kernel, norm_out_grid(nk, pf), dim3(256), 0, 0, d_tmp.get(), d_sel.get(), nk, pf, d_oi.get());
+        if (!c.dev_out) {
+            FW_HIP(nullptr, d_oi.alloc((size_t)nk * pf));
+            oi = d_oi.get();
+        }
+        hipLaunchKernelGGL(norm_gather_cols_kernel, norm_out_grid(nk, pf), dim3(256), 0, 0, d_tmp.get(), d_sel.get(), nk, pf, oi);
     } else if (c.K.tss) {
-        hipLaunchKernelGGL(norm_tss_out_kernel<V>, norm_out_grid(nk, pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, c.d_s32.get(), d_of.get());
+        hipLaunchKernelGGL(norm_tss_out_kernel<V>, norm_out_grid(nk, pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, c.d_s32.get(), of);
     } else {
         FW_HIP(nullptr, d_pseudo.upload(c.R.pseudo));
         FW_HIP(nullptr, d_g.upload(c.R.g));
-        hipLaunchKernelGGL(norm_clr_out_kernel<V>, norm_out_grid(nk, pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_pseudo.get(), d_g.get(), c.K.clr_mode, d_of.get());
+        hipLaunchKernelGGL(norm_clr_out_kernel<V>, norm_out_grid(nk, pk), dim3(256), 0, 0, d_x, n, d_rows.get(), nk, c.d_cols.get(), pk, d_pseudo.get(), d_g.get(), c.K.clr_mode, of);
     }
     FW_HIP(nullptr, hipGetLastError());
+    if (c.dev_out) {  // (the caller reads its buffer at once)
+        FW_HIP(nullptr, hipStreamSynchronize(0));
+        return FW_OK;
+    }
     if (c.K.i32) FW_HIP(nullptr, d_oi.download(out_i32, (size_t)nk * c.cols.size()));
     if (!c.K.i32) FW_HIP(nullptr, d_of.download(out_f32, (size_t)nk * c.cols.size()));
     return FW_OK;
 }
 
-// The dense front-end for either value type (fn: the entry point's name, for the messages).
+// The dense front-end for either value type (fn: the entry point's name, for the messages).  dev: the *_dev form -- counts and the
+// output buffer are device memory of `device` (asked of the runtime before anything reads them); the table is borrowed, not uploaded,
+// and the output is written in place, not downloaded.  The stages and their kernels are the same, so the bits are.
 template <typename V>
 int norm_dense(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const V *counts, float *out_f32, int32_t *out_i32,
-               uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, const fw_norm_opts *opts)
+               uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, const fw_norm_opts *opts, bool dev = false)
 {
     if (!counts || !row_mask || !col_mask || !n_out || !p_out || n <= 0 || p <= 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
     NormCall c{fn, kind, norm_kind(kind), n, row_mask, col_mask};
     if (int rc = norm_call_check(c, opts)) return rc;
     if (c.K.i32 ? !out_i32 : !out_f32) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
+    c.dev_out = dev;
+    if (dev && !fw_is_dev_ptr(counts, device)) return fw_fail(nullptr, FW_ERR_ARG, "%s: the table is not device memory of device %d", fn, device);
+    if (dev && !fw_is_dev_ptr(c.K.i32 ? (const void *)out_i32 : (const void *)out_f32, device))
+        return fw_fail(nullptr, FW_ERR_ARG, "%s: the output buffer is not device memory of device %d", fn, device);
     FwDevArray<V> d_x;
     FW_HIP(nullptr, hipSetDevice(device));
-    FW_HIP(nullptr, d_x.upload(counts, (size_t)n * p));
-    if (int rc = dense_filters(c, d_x.get(), p)) return rc;
-    if (int rc = dense_output(c, d_x.get(), out_f32, out_i32)) return rc;
+    if (!dev) FW_HIP(nullptr, d_x.upload(counts, (size_t)n * p));
+    const V *x = dev ? counts : d_x.get();
+    if (int rc = dense_filters(c, x, p)) return rc;
+    if (int rc = dense_output(c, x, out_f32, out_i32)) return rc;
     *n_out = (int32_t)c.R.rows.size();
     *p_out = (int32_t)c.cols.size();
     return FW_OK;
@@ -666,6 +690,21 @@ extern "C" int fw_normalize_abund_opts(int32_t device, int32_t kind, int32_t n, 
                                        const fw_norm_opts *opts)
 {
     return norm_dense<double>(opts ? "fw_normalize_abund_opts" : "fw_normalize_abund", device, kind, n, p, values, out_f32, out_i32, row_mask, col_mask, n_out, p_out, opts);
+}
+
+// The *_dev forms: the table and the output buffer in device memory (include/flashweave_amd.h); opts == NULL means the defaults.
+extern "C" int fw_normalize_counts_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *d_counts, float *d_out_f32,
+                                       int32_t *d_out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out,
+                                       const fw_norm_opts *opts)
+{
+    return norm_dense<int32_t>("fw_normalize_counts_dev", device, kind, n, p, d_counts, d_out_f32, d_out_i32, row_mask, col_mask, n_out, p_out, opts, true);
+}
+
+extern "C" int fw_normalize_abund_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const double *d_values, float *d_out_f32,
+                                      int32_t *d_out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out,
+                                      const fw_norm_opts *opts)
+{
+    return norm_dense<double>("fw_normalize_abund_dev", device, kind, n, p, d_values, d_out_f32, d_out_i32, row_mask, col_mask, n_out, p_out, opts, true);
 }
 
 extern "C" int fw_normalize_abund(int32_t device, int32_t kind, int32_t n, int32_t p, const double *values, float *out_f32,

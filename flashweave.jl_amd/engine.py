@@ -1,6 +1,7 @@
 """ctypes binding of include/flashweave_amd.h and the Python mirror of the reference's operator interface."""
 import ctypes as C
 import os
+import sys
 from collections import namedtuple
 
 import numpy as np
@@ -170,6 +171,11 @@ def load_library():
     if hasattr(L, "fw_normalize_counts_opts"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
         for name in ("fw_normalize_counts", "fw_normalize_counts_csc", "fw_normalize_abund", "fw_normalize_abund_csc"):
             getattr(L, name + "_opts").argtypes = getattr(L, name).argtypes + [C.POINTER(_NormOpts)]
+    if hasattr(L, "fw_set_data_dense_i32_dev"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        L.fw_set_data_dense_i32_dev.argtypes = [vp, vp]
+        L.fw_set_data_dense_f32_dev.argtypes = [vp, vp]
+        L.fw_normalize_counts_dev.argtypes = L.fw_normalize_counts.argtypes + [C.POINTER(_NormOpts)]
+        L.fw_normalize_abund_dev.argtypes = L.fw_normalize_counts_dev.argtypes
     if hasattr(L, "fw_set_data_csc_f32_resident"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
         L.fw_set_data_csc_f32_resident.argtypes = [vp, vp, vp, vp]
         L.fw_data_resident_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -216,6 +222,49 @@ def is_sparse(data):
         return False
     import scipy.sparse as sp
     return bool(sp.issparse(data))
+
+
+def is_device_tensor(who, data):
+    """True for a torch.Tensor in GPU memory (device.type "cuda": what PyTorch-ROCm calls a HIP device) -- the table then stays on the
+    device from here to the engine; False for anything else, a CPU tensor included (it keeps going through np.asarray).  A tensor of
+    any other device type (meta, xla, ...) has no bytes this library could take: ValueError."""
+    torch = sys.modules.get("torch")  # (a tensor exists only where torch has been imported: nothing is imported to ask)
+    if torch is None or not isinstance(data, torch.Tensor) or data.device.type == "cpu":
+        return False
+    if data.device.type != "cuda":
+        raise ValueError("%s: a torch.Tensor on a %r device is not supported: pass a tensor in GPU memory (device type \"cuda\") or "
+                         "a CPU tensor" % (who, data.device.type))
+    return True
+
+
+def _dev_table(who, t, device, dtype, numeric="biuf"):
+    """A 2-D GPU tensor as the *_dev entry points borrow it: `dtype`, column-major (strides (1, n): taken as it is, anything else
+    through t.t().contiguous()), on GPU `device`; the conversions run on the device and the producer's stream is drained before the
+    pointer is handed over.  -> the tensor to take data_ptr() of (keep it alive over the call)."""
+    import torch
+    if t.layout != torch.strided:
+        raise ValueError("%s: a sparse torch tensor is not supported: scipy.sparse is the sparse interface, pass tensor.to_dense() "
+                         "or a scipy matrix built from tensor.cpu()" % who)
+    kind = "b" if t.dtype == torch.bool else "f" if t.dtype.is_floating_point else "c" if t.dtype.is_complex else "i"
+    if t.dim() != 2 or kind not in numeric:
+        raise ValueError("%s: a device tensor must be a 2-D samples x variables table of a numeric dtype (got %d dimensions, %s)"
+                         % (who, t.dim(), t.dtype))
+    if t.device.index != device:
+        raise ValueError("%s: the tensor lives on %s while device=%d: pass the device the table is on (or tensor.cpu())" % (who, t.device, device))
+    n = t.shape[0]
+    t = t.detach()
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    if t.stride() != (1, n):
+        t = t.t().contiguous().t()
+    torch.cuda.current_stream(t.device).synchronize()
+    return t
+
+
+def _tensor_np_kind(v):
+    """numpy's dtype.kind of a torch tensor's elements, for the checks both array types share"""
+    import torch
+    return "b" if v.dtype == torch.bool else "f" if v.dtype.is_floating_point else "c" if v.dtype.is_complex else "i"
 
 
 class CSC(namedtuple("CSC", "colptr rowval nzval shape")):
@@ -274,6 +323,11 @@ def _front_end_kind(who, test_name, norm):
 def tss_range_defect(values):
     """What keeps real values out of a TSS norm, as words for a refusal, or None: a positive value outside [2^-126, 2^96] (as a
     Float32 it could vanish, or the Float32 sum of a sample could overflow)."""
+    if is_device_tensor("tss_range_defect", values):  # the same rule in torch ops on the device
+        pos = values[values > 0] if _tensor_np_kind(values) == "f" else values[:0]
+        if pos.numel() and (float(pos.min()) < TSS_MIN or float(pos.max()) > TSS_MAX):
+            return "a positive value outside [2^-126, 2^96] (%r)" % float(pos.min() if float(pos.min()) < TSS_MIN else pos.max())
+        return None
     v = np.asarray(values)
     if v.size and v.dtype.kind == "f":
         pos = v[v > 0]
@@ -345,11 +399,17 @@ def normalize_counts(counts, test_name, device=0, norm=None, n_bins=3, rank_meth
     n_bins, rank_method ("tied" | "dense"), disc_method ("median" | "mean"): the options of the two binned modes ("mi_nz", and norm
     "tss-nonzero-binned"), as preprocess.normalize takes and computes them: Int32 levels 0 .. n_bins - 1.  Away from their defaults
     the call goes to fw_normalize_counts_opts / fw_normalize_counts_csc_opts; a value out of range, or an option given with a mode that
-    does not bin, raises ValueError naming it before anything is loaded."""
+    does not bin, raises ValueError naming it before anything is loaded.
+    A 2-D torch.Tensor in GPU memory (device.type "cuda", on GPU `device`) is borrowed where it is (fw_normalize_counts_dev): the
+    checks above run as torch ops on the device, and data comes back as a tensor on that device -- an (n_out, p_out) view with
+    strides (1, n_out) of the output buffer, the bits the numpy table gives; the masks are numpy.  normalize_abundances likewise
+    (fw_normalize_abund_dev).  A CPU tensor is an array; any other device type raises ValueError."""
     if norm is not None:
         _front_end_kind("normalize_counts", test_name, norm)  # (an unknown or misplaced norm is refused before anything is loaded)
     bins_check("normalize_counts", test_name, n_bins, rank_method, disc_method)
     bins = bins_kw(n_bins, rank_method, disc_method)
+    if is_device_tensor("normalize_counts", counts):
+        return _normalize_counts_dev(counts, test_name, device, norm, bins)
     L = load_library()
     if is_sparse(counts) or isinstance(counts, CSC):  # (any other tuple is a dense table, as before)
         return _normalize_csc(_opts_front_end(L, "normalize_counts", "fw_normalize_counts_csc", bins), "normalize_counts", as_csc(counts, np.int32),
@@ -364,6 +424,42 @@ def normalize_counts(counts, test_name, device=0, norm=None, n_bins=3, rank_meth
         raise ValueError("normalize_counts: counts must lie in [0, 2^31 - 1]")
     return _normalize_dense(_opts_front_end(L, "normalize_counts", "fw_normalize_counts", bins), np.asfortranarray(raw.astype(np.int32)), test_name,
                             device, **_norm_kw(norm), **bins)
+
+
+def _normalize_counts_dev(counts, test_name, device, norm, bins):
+    """normalize_counts for a GPU tensor: the checks of the numpy path in torch ops on the device, then fw_normalize_counts_dev"""
+    import torch
+    who = "normalize_counts"
+    x = _dev_table(who, counts, device, counts.dtype)  # (the refusals of shape, dtype and device first; the values as they came)
+    if _tensor_np_kind(x) == "f":  # a silent cast would truncate relative abundances / floats to zero
+        if not bool(torch.isfinite(x).all()) or bool((x != torch.floor(x)).any()):
+            raise TypeError("normalize_counts: the device front-end takes integer counts (got non-integral %s values)" % x.dtype)
+    if x.numel() and (float(x.min()) < 0 or float(x.max()) > np.iinfo(np.int32).max):
+        raise ValueError("normalize_counts: counts must lie in [0, 2^31 - 1]")
+    return _normalize_dense_dev("fw_normalize_counts_dev", who, _dev_table(who, x, device, torch.int32), test_name, device, norm, bins)
+
+
+def _normalize_dense_dev(name, who, x, test_name, device, norm, bins):
+    """fw_normalize_counts_dev / fw_normalize_abund_dev on the column-major GPU tensor x -> (tensor, row_mask, col_mask): the tensor an
+    (n_out, p_out) view with strides (1, n_out) of the output buffer on x's device, the masks numpy"""
+    import torch
+    L = load_library()
+    if not hasattr(L, name):
+        raise FlashWeaveError(-2, "%s: the loaded library has no %s (an older build)" % (who, name))
+    n, p = x.shape
+    if n <= 0 or p <= 0:
+        raise ValueError("%s: counts must be a samples x OTUs matrix" % who)
+    rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
+    no, po = C.c_int32(0), C.c_int32(0)
+    kind = _front_end_kind("normalize", test_name, norm)
+    out = torch.empty(n * p, dtype=torch.float32 if NORM_OUT_DTYPE[kind] is np.float32 else torch.int32, device=x.device)
+    torch.cuda.current_stream(x.device).synchronize()
+    of, oi = (C.c_void_p(out.data_ptr()), None) if out.dtype == torch.float32 else (None, C.c_void_p(out.data_ptr()))
+    opts = C.byref(_NormOpts(int(bins.get("n_bins", 3)), FW_RANK[bins.get("rank_method", "tied")], FW_DISC[bins.get("disc_method", "median")])) if bins else None
+    rc = getattr(L, name)(device, kind, n, p, C.c_void_p(x.data_ptr()), of, oi, _ptr(rm), _ptr(cm), C.byref(no), C.byref(po), opts)
+    if rc != 0:
+        raise FlashWeaveError(rc, L.fw_last_error(None).decode())
+    return out[:no.value * po.value].view(po.value, no.value).t(), rm.astype(bool), cm.astype(bool)
 
 
 def _normalize_dense(front_end, x, test_name, device, norm=None, **bins):
@@ -385,6 +481,14 @@ def _normalize_dense(front_end, x, test_name, device, norm=None, **bins):
 
 def abundance_defect(values):
     """What keeps real values from being abundances, as words for a refusal, or None: a NaN, an infinite or a negative value."""
+    if is_device_tensor("abundance_defect", values):  # the same rule in torch ops on the device
+        import torch
+        kind = _tensor_np_kind(values)
+        if values.numel() and kind == "f" and not bool(torch.isfinite(values).all()):
+            return "a NaN or an infinite value"
+        if values.numel() and kind in "if" and float(values.min()) < 0:
+            return "a negative value"
+        return None
     v = np.asarray(values)
     if v.size and v.dtype.kind == "f" and not np.all(np.isfinite(v)):
         return "a NaN or an infinite value"
@@ -408,7 +512,11 @@ def normalize_abundances(table, test_name, device=0, norm=None, n_bins=3, rank_m
     bins_check(who, test_name, n_bins, rank_method, disc_method)
     bins = bins_kw(n_bins, rank_method, disc_method)
     sparse = is_sparse(table) or isinstance(table, CSC)
-    if sparse:
+    on_gpu = is_device_tensor(who, table)
+    if on_gpu:
+        import torch
+        values = _dev_table(who, table, device, torch.float64)
+    elif sparse:
         triple = as_csc(table, np.float64)
         values = triple.nzval
     else:
@@ -422,6 +530,8 @@ def normalize_abundances(table, test_name, device=0, norm=None, n_bins=3, rank_m
     defect = tss_range_defect(values) if norm is not None else None
     if defect:
         raise ValueError("%s: norm=%r: the table holds %s" % (who, norm, defect))
+    if on_gpu:
+        return _normalize_dense_dev("fw_normalize_abund_dev", who, values, test_name, device, norm, bins)
     L = load_library()
     if not hasattr(L, "fw_normalize_abund"):
         raise FlashWeaveError(-2, "%s: the loaded library has no fw_normalize_abund (an older build)" % who)
@@ -462,6 +572,7 @@ class Engine:
         if rc != 0:
             raise FlashWeaveError(rc, self.L.fw_last_error(None).decode())
         self.max_k = max_k
+        self.device = int(device)
         self._cb = None
 
     # -- plumbing ------------------------------------------------------------------------------------
@@ -491,7 +602,13 @@ class Engine:
         values (fw_set_data_csc_f32: zeros = absences, nothing is densified on the host); mi / mi_nz: integer n x p (dense
         ndarray), a scipy.sparse matrix or a (colptr, rowval, nzval) CSC triple with 0-based rows.
         csc_resident=True (fz_nz with sparse input or a triple only, else ValueError): the data stays sparse on the device as well
-        (fw_set_data_csc_f32_resident: plane + base + the values != 0 instead of the n x p matrix); results are the same bits."""
+        (fw_set_data_csc_f32_resident: plane + base + the values != 0 instead of the n x p matrix); results are the same bits.
+        A 2-D torch.Tensor in GPU memory (device.type "cuda", on this engine's device) never leaves the device: it is converted
+        there (float32 for fz / fz_nz, int32 for mi / mi_nz; column-major) and the resident layout is built from it on the device
+        (fw_set_data_dense_f32_dev / fw_set_data_dense_i32_dev), the same bits as the upload of tensor.cpu().numpy().  Not served,
+        ValueError: csc_resident=True, prec=64, a sparse tensor, a tensor of another GPU.  A CPU tensor goes through np.asarray."""
+        if is_device_tensor("Engine.set_data", data):
+            return self._set_data_dev(data, csc_resident)
         if csc_resident:
             if self.test_name != "fz_nz":
                 raise ValueError("Engine.set_data: csc_resident=True is served for test_name \"fz_nz\" only (got %r)" % (self.test_name,))
@@ -527,6 +644,19 @@ class Engine:
             d = np.asfortranarray(np.asarray(data, dtype=np.int32))
             assert d.shape == (self.n, self.p)
             self._ck(self.L.fw_set_data_dense_i32(self.h, _ptr(d)))
+
+    def _set_data_dev(self, t, csc_resident):
+        import torch
+        who = "Engine.set_data"
+        if csc_resident:
+            raise ValueError("Engine.set_data: csc_resident=True takes a scipy.sparse matrix or a CSC triple, not a device tensor")
+        if self.prec == 64:
+            raise ValueError("Engine.set_data: prec=64 is not served for a device tensor (Float64 mode uploads from the host): pass tensor.cpu()")
+        self._need("fw_set_data_dense_i32_dev", "a device tensor")
+        continuous = self.test_name in ("fz", "fz_nz")
+        d = _dev_table(who, t, self.device, torch.float32 if continuous else torch.int32)
+        assert tuple(d.shape) == (self.n, self.p)
+        self._ck((self.L.fw_set_data_dense_f32_dev if continuous else self.L.fw_set_data_dense_i32_dev)(self.h, C.c_void_p(d.data_ptr())))
 
     def data_resident_bytes(self):
         """fz_nz: bytes of device memory the context holds for the data (fw_data_resident_bytes) -- 4 n p + 8 p W dense-resident,

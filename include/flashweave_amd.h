@@ -197,6 +197,22 @@ int fw_set_data_csc_i32(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowva
  * the same packed device layout, i.e. evaluated with the SPARSE-path semantics (levels_z rules). */
 int fw_set_data_dense_i32(fw_ctx *ctx, const int32_t *data);
 
+/* Tables that already live in device memory (a torch tensor's data_ptr(), a ROCArray's pointer): column-major [p][n] on the
+ * context's device.  The pointer is asked of the runtime (hipPointerGetAttributes) before anything reads it: NULL, a host pointer
+ * and memory of another device give FW_ERR_ARG without a dereference.  The table is borrowed for the call only; the call
+ * synchronises before it returns, so the caller may free or reuse the buffer at once.  Work of the caller's own streams that
+ * produces the table must be complete before the call.
+ * fw_set_data_dense_i32_dev (FW_MI / FW_MI_NZ): the resident layouts of fw_set_data_csc_i32 built on the device in two passes -- a
+ * column scan (range check, the values seen, the totals), of which only p small records reach the host, which picks the form, fills
+ * levels / max_vals and refuses as fw_set_data_dense_i32 refuses the same table (same code, same message: the lowest bad column and
+ * the value at its first bad row); then the pack: one wavefront per plane word, the two ballots of 64 consecutive rows being the two
+ * plane words (three-level form), or a cast to the byte matrix (generic form).  The host never holds n x p cells.
+ * fw_set_data_dense_f32_dev (FW_FZ / FW_FZ_NZ): a device-to-device copy into the resident matrix and, for FW_FZ_NZ, the plane of
+ * x != 0.0f by the same ballot scheme (-0.0f is an absence, a NaN is not, as in fw_set_data_dense_f32); FW_ERR_STATE in Float64 mode.
+ * Either leaves the context in the state its host sibling leaves for the same table, to the bit. */
+int fw_set_data_dense_i32_dev(fw_ctx *ctx, const int32_t *d_data);
+int fw_set_data_dense_f32_dev(fw_ctx *ctx, const float *d_data);
+
 int fw_get_levels(const fw_ctx *ctx, int32_t *levels, int32_t *max_vals); /* p entries each */
 
 /* FW_FZ: supply a precomputed Pearson matrix (p x p, Float32) instead of computing it on the device --
@@ -467,6 +483,20 @@ int fw_normalize_abund_csc_opts(int32_t device, int32_t kind, int32_t n, int32_t
                                 const double *nzval, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32,
                                 uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
                                 const fw_norm_opts *opts);
+
+/* The dense front-ends on a table that already lives in device memory: d_counts / d_values is column-major [p][n] on `device` and is
+ * borrowed, not uploaded; the output goes into the caller's device buffer of n p elements (d_out_f32 or d_out_i32 by kind, as above:
+ * kept samples x kept columns, column-major, at its start) instead of being downloaded.  Both pointers are asked of the runtime
+ * before anything reads them (FW_ERR_ARG for NULL, a host pointer, memory of another device).  The masks, the counts and opts stay on
+ * the host; opts == NULL means the defaults.  The same kernels run in the same order as in fw_normalize_counts_opts /
+ * fw_normalize_abund_opts, so the same bits come out; the small per-row and per-column statistics go through the host as they do
+ * there.  Device memory besides the two buffers: the binned kinds' temporary of n p Int32.  The call synchronises before it returns. */
+int fw_normalize_counts_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const int32_t *d_counts, float *d_out_f32,
+                            int32_t *d_out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out,
+                            const fw_norm_opts *opts);
+int fw_normalize_abund_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const double *d_values, float *d_out_f32,
+                           int32_t *d_out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out,
+                           const fw_norm_opts *opts);
 
 /* Device self-test of hand-written arithmetic sequences that replace a compiler-generated IEEE sequence and must return the
  * same bits.  which = FW_SELFTEST_DIV: the unscaled Float64 division of the NaN-free partial-correlation path (statfuns.jl:44-62
