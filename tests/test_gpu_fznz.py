@@ -1,6 +1,9 @@
 """GPU parity tests of the HE-S ("fz_nz", zero-ignoring Fisher-z) HIP path against the CPU oracle, through the C ABI.
-The device sums run sequentially over the rows in Float64, like the oracle's: correlations, partial correlations and
-edge weights are compared bit-exact; p-values within 1e-12 relative (device log/erfc)."""
+The device sums run in Float64 in a fixed order that the oracle follows: sequentially over the rows at level 0,
+in univariate jobs and for more than 16 384 samples; in every other job as 64 interleaved partial sums over the rows of the view,
+combined in a fixed tree (fznz_tree64 / the oracle's fz_nz_tree64).  Correlations, partial correlations and edge weights are
+compared bit-exact; p-values within 1e-12 relative (device log/erfc).  One shape, 400 x 250: the switches of the sample count, the
+view size and the list length are crossed in tests/test_gpu_fznz_edges.py."""
 import numpy as np
 import pytest
 
