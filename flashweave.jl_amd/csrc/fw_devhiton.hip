@@ -2355,6 +2355,27 @@ __global__ __launch_bounds__(256) void dh_tmat_build_kernel(const DhTgt *__restr
         }
 }
 
+// The record of ranks [start, end) of target x's job on candidate Y against the list of acc_len entries at acc_off: what the segment
+// body reads about a job, the target's local matrix included where it has one (dh_fill_one, dh_fz_light_kernel)
+__device__ __forceinline__ FwSeg dh_seg_record(const DhTgt &x, const DhArrays &A, int32_t Y, long long acc_off, int acc_len, int32_t pad,
+                                               unsigned long long start, unsigned long long end)
+{
+    FwSeg sg;
+    sg.X = x.T;
+    sg.Y = Y;
+    sg.acc_off = acc_off;
+    sg.acc_len = acc_len;
+    sg.pad = pad;
+    sg.start = start;
+    sg.end = end;
+    const bool has_tm = A.tmat != nullptr && x.tm_off >= 0;
+    sg.tm = has_tm ? (uint64_t)(A.tmat + x.tm_off) : 0ull;
+    sg.tm_ids = has_tm ? (uint64_t)(A.nb_idx + x.nb_off) : 0ull;
+    sg.tm_m = has_tm ? x.nb_n + 1 : 0;
+    sg.pad1 = 0;
+    return sg;
+}
+
 // segment record s of the coming launch (one thread)
 __device__ __forceinline__ void dh_fill_one(const unsigned int s, const DhTgt *__restrict__ tg, int ntg, DhGlobal *__restrict__ g,
                                             const long long *__restrict__ seg0, const DhArrays &A, FwSeg *__restrict__ segs, int d1,
@@ -2383,23 +2404,14 @@ __device__ __forceinline__ void dh_fill_one(const unsigned int s, const DhTgt *_
         }
     }
     const bool acc_mode = slot > 0u && x.spmode == 1;  // list = accepted + [current candidate], first window of its own enumeration
-    FwSeg sg;
-    sg.X = x.T;
-    sg.Y = cands[x.pos + (int)slot];
-    sg.acc_off = DH_ACC_OFF(x, x.phase == 1 ? (x.cur + (int)slot) % d1 : x.cur, d1);
-    sg.acc_len = x.na + (acc_mode ? 1 : 0);
-    if (sg.acc_len > FW_TAB_A) g->any_big = 1u;  // same value from every writer
-    sg.pad = act[(size_t)g->act_sel * ntg + lo - 1];  // fz_nz: the job's record slot = the target's index in the run (dh_nz_recs_kernel)
+    const int acc_len = x.na + (acc_mode ? 1 : 0);
+    if (acc_len > FW_TAB_A) g->any_big = 1u;  // same value from every writer
     const unsigned long long lo_r = acc_mode ? 0ull : x.jnext;
-    sg.start = lo_r + k * seglen;
+    const unsigned long long start = lo_r + k * seglen;
     const unsigned long long hi_r = lo_r + (slot > 0u ? x.jwin2 : x.jwin);
-    sg.end = sg.start + seglen < hi_r ? sg.start + seglen : hi_r;
-    const bool has_tm = A.tmat != nullptr && x.tm_off >= 0;
-    sg.tm = has_tm ? (uint64_t)(A.tmat + x.tm_off) : 0ull;
-    sg.tm_ids = has_tm ? (uint64_t)(A.nb_idx + x.nb_off) : 0ull;
-    sg.tm_m = has_tm ? x.nb_n + 1 : 0;
-    sg.pad1 = 0;
-    segs[s] = sg;
+    // (pad -- fz_nz: the job's record slot = the target's index in the run, dh_nz_recs_kernel)
+    segs[s] = dh_seg_record(x, A, cands[x.pos + (int)slot], DH_ACC_OFF(x, x.phase == 1 ? (x.cur + (int)slot) % d1 : x.cur, d1), acc_len,
+                            act[(size_t)g->act_sel * ntg + lo - 1], start, start + seglen < hi_r ? start + seglen : hi_r);
 }
 __global__ __launch_bounds__(256) void dh_fill_kernel(const DhTgt *__restrict__ tg, int ntg, DhGlobal *__restrict__ g,
                                                       const long long *__restrict__ seg0, const DhArrays A,
@@ -2485,6 +2497,82 @@ __global__ __launch_bounds__(256) void dh_nz_recs_kernel(const DhTgt *__restrict
     } else {
         r->pad = 1;
     }
+}
+
+// ---- light Fisher-z targets: one resident workgroup per target, no device rounds ---------------------------------------------------
+// A target with a handful of level-0 neighbours is a chain of a few dozen jobs of a few hundred tests each; through the rounds above
+// every link of that chain costs a device-wide dependency (segment kernel -> step -> plan -> fill), ~50 us for work that fills a
+// fraction of one workgroup (cfg3: nine of the ten feed-forward rounds, 21-25 dependent rounds each).  Targets of a round are
+// independent and such a target's longest enumeration is shorter than one segment, so here a workgroup runs its target's whole HITON-PC
+// in the reference's own order -- no window, no look-ahead, no other workgroup to wait for -- the way dh_mi_target_kernel runs the
+// discrete kinds.  Wave 0 is the state machine of dh_step_dev (dh_advance, dh_commit, the same per-target counters); all four
+// wavefronts run a job as ONE segment [0, N) through the segment kernel's own body, so statistic, p-value, first stop and the "later
+// wins ties" maximum are those of the rounds bit for bit.  The host decides which targets are light (dh_is_light, from static sizes);
+// the others leave at once and go through DhRounds afterwards.
+__host__ __device__ inline bool dh_is_light(int deg, int cap, int light_deg) { return light_deg > 0 && deg <= light_deg && cap <= light_deg; }
+
+__shared__ DhTgt dh_lt_x;    // the workgroup's target between two jobs
+__shared__ FwSeg dh_lt_seg;  // the job all four wavefronts run next
+__shared__ int dh_lt_go;     // ... 0: none (the target has finished, or hit one of the bounds below and stays unfinished)
+
+__global__ __launch_bounds__(256, 4) void dh_fz_light_kernel(DhTgt *__restrict__ tg, int ntg, int light_deg, const DhArrays A,
+                                                             FwSegOut *__restrict__ so, const DhParams P, const float *__restrict__ cor, int p,
+                                                             double zscale, const double *__restrict__ thr)
+{
+    const int t = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63;
+    if (t >= ntg || !dh_is_light(tg[t].nb_n, tg[t].cap, light_deg)) return;  // (workgroup-uniform)
+    const int d1 = P.spec_depth + 1;
+    // every job consumes an interleaving candidate (at most cap) or a member of TPC (at most one per candidate): a hard bound on the
+    // loop.  A target that would pass it, or whose list would not fit the table variant, is left unfinished: the rounds take it
+    // up where a slot has any, and the host reports unfinished targets as FW_ERR_DEVICE (dh_download, dh_sched_finish)
+    const int job_max = 2 * tg[t].cap;
+    for (int job = 0;; ++job) {
+        if (tid < 64) {  // wave 0, all lanes in lock-step as in dh_step_dev
+            DhTgt x = job == 0 ? tg[t] : dh_lt_x;
+            if (job > 0) {  // the finished job: one record, one window (dh_step_dev's commit of a whole enumeration)
+                const DhMerge M = dh_merge(so, (long long)t, 1, lane);
+                const double r_stat = M.stop ? M.stat : (M.p != -2.0 ? M.stat : 0.0);
+                const double r_p = M.stop ? M.p : (M.p < 0.0 ? 0.0 : M.p);
+                (x.phase == 0 ? x.r_first0 : x.r_first1) += 1u;
+                x.c_ref += M.stop ? M.nt : x.jN;
+                x.c_calls += 1ull;
+                x.c_eval += M.ev;
+                x.c_eval_short += x.na <= FW_HK_A ? M.ev : 0ull;
+                x.na_max = x.na > x.na_max ? x.na : x.na_max;
+                x.c_alg += dh_alg_bytes(x.na, M.ev, P.max_k, P.disc_bytes_per_col);
+                dh_commit(x, A, lane, d1, r_stat, r_p, M.stop ? M.pow : 1, P.alpha, P.elim_mode != 0);
+            }
+            bool go = x.phase != 2 && dh_advance(x, A, lane, d1, P.elim_mode == 2);
+            go = go && job < job_max && x.na <= FW_TAB_A;
+            if (go) x.jN = dh_enum_size(x.na, P.max_k, P.max_tests);
+            if (lane == 0) {
+                dh_lt_x = x;
+                dh_lt_go = go ? 1 : 0;
+                if (go)
+                    dh_lt_seg = dh_seg_record(x, A, (x.phase == 0 ? A.cand0 + x.cand_off : A.tpc_key + x.co)[x.pos], DH_ACC_OFF(x, x.cur, d1),
+                                              x.na, t, 0ull, x.jN);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the list wave 0 wrote, the record in LDS
+        __syncthreads();
+        if (!dh_lt_go) break;
+        FwSeg sg = dh_lt_seg;  // (the body takes a workgroup-uniform record: out of LDS it is, but the compiler has to be told)
+        sg.X = __builtin_amdgcn_readfirstlane(sg.X);
+        sg.Y = __builtin_amdgcn_readfirstlane(sg.Y);
+        sg.acc_off = (int64_t)mi_rfl64((unsigned long long)sg.acc_off);
+        sg.acc_len = __builtin_amdgcn_readfirstlane(sg.acc_len);
+        sg.pad = __builtin_amdgcn_readfirstlane(sg.pad);
+        sg.start = mi_rfl64(sg.start);
+        sg.end = mi_rfl64(sg.end);
+        sg.tm = mi_rfl64(sg.tm);
+        sg.tm_ids = mi_rfl64(sg.tm_ids);
+        sg.tm_m = __builtin_amdgcn_readfirstlane(sg.tm_m);
+        fz_seg_body<false, false, true>(cor, p, sg, A.acc + sg.acc_off, false, so + t, P.max_k, P.alpha, zscale, P.max_tests, thr,
+                                        (const FwNzJob *)nullptr, 0ll);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the record, whichever thread wrote it
+        __syncthreads();
+    }
+    if (tid == 0) tg[t] = dh_lt_x;
 }
 
 // ---- the whole feed-forward schedule on the device (fwi_devhiton_mi_schedule, fwi_devhiton_fz_schedule) ------------------------------
@@ -2595,25 +2683,59 @@ __global__ __launch_bounds__(256) void dh_sched_pack_kernel(const DhTgt *__restr
                                                          int32_t *__restrict__ o_t, int32_t *__restrict__ o_u, double *__restrict__ o_s,
                                                          double *__restrict__ o_p, unsigned long long *__restrict__ tot, double *__restrict__ alg)
 {
-    const int t = (int)(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (t >= nt) return;
-    const DhTgt &x = tg[t];
-    const int npc = x.npc;
-    unsigned long long base = 0ull;
-    if (lane == 0) {
-        if (npc > 0) base = atomicAdd(&tot[0], (unsigned long long)npc);
-        if (x.c_ref) atomicAdd(&tot[1], x.c_ref);
-        if (x.c_calls) atomicAdd(&tot[2], x.c_calls);
-        if (x.c_eval) atomicAdd(&tot[3], x.c_eval);
-        if (x.phase != 2) atomicAdd(&tot[4], 1ull);
-        if (x.c_alg != 0.0) atomicAdd(alg, x.c_alg);
+    // (one set of atomics per target, six on one line for each of cfg3's 10 000 targets, was 0.6 ms per pass: the totals are taken by
+    // one thread per target and reduced per wavefront first -- one ticket and one set of atomics per 64 targets)
+    __shared__ unsigned long long s_base[256];
+    const int tid = (int)threadIdx.x, lane = tid & 63, t = (int)blockIdx.x * 256 + tid;
+    unsigned long long npc = 0ull, ref = 0ull, calls = 0ull, ev = 0ull, unfinished = 0ull;
+    double al = 0.0;
+    if (t < nt) {
+        const DhTgt &x = tg[t];
+        npc = (unsigned long long)x.npc;
+        ref = x.c_ref;
+        calls = x.c_calls;
+        ev = x.c_eval;
+        unfinished = x.phase != 2 ? 1ull : 0ull;
+        al = x.c_alg;
     }
-    base = mi_rfl64(base);
-    for (int i = lane; i < npc; i += 64) {
-        o_t[base + i] = x.T;
-        o_u[base + i] = pc_key[x.co + i];
-        o_s[base + i] = pc_stat[x.co + i];
-        o_p[base + i] = pc_p[x.co + i];
+    unsigned long long incl = npc;  // entries of the wavefront's targets up to and including this one
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ref += __shfl_xor(ref, o);
+        calls += __shfl_xor(calls, o);
+        ev += __shfl_xor(ev, o);
+        unfinished += __shfl_xor(unfinished, o);
+        al += __shfl_xor(al, o);
+    }
+    unsigned long long wbase = 0ull;
+    if (lane == 63) {
+        if (incl) wbase = atomicAdd(&tot[0], incl);
+        if (ref) atomicAdd(&tot[1], ref);
+        if (calls) atomicAdd(&tot[2], calls);
+        if (ev) atomicAdd(&tot[3], ev);
+        if (unfinished) atomicAdd(&tot[4], unfinished);
+        if (al != 0.0) atomicAdd(alg, al);
+    }
+    s_base[tid] = __shfl(wbase, 63) + incl - npc;
+    __syncthreads();
+    // the lists as before: a wavefront per target, here the 64 targets of its own totals one after the other
+    for (int j = 0; j < 64; ++j) {
+        const int u = tid - lane + j, tu = (int)blockIdx.x * 256 + u;
+        if (tu >= nt) break;
+        const DhTgt &x = tg[tu];
+        const unsigned long long base = s_base[u];
+        const int n = x.npc;
+        for (int i = lane; i < n; i += 64) {
+            o_t[base + i] = x.T;
+            o_u[base + i] = pc_key[x.co + i];
+            o_s[base + i] = pc_stat[x.co + i];
+            o_p[base + i] = pc_p[x.co + i];
+        }
     }
 }
 
@@ -2762,7 +2884,8 @@ static DhPolicy dh_policy(const fw_ctx *c, int ntg)
     y.spec_depth = c->P.kind == FW_FZ ? std::min(std::max(spec_env >= 0 ? spec_env : spec_dflt, 0), DH_MAX_SPEC) : 0;
     // discrete kinds: persistent wavefronts + boards (dh_mi_target_kernel); FW_MI_ROUNDS=1 keeps the level-synchronous rounds over
     // the segment kernels (the path of the ABI's fw_test_subsets_batch) for comparison.  Fisher-z always runs as rounds (a
-    // persistent-workgroup variant was built in r02, lost 140 vs 58 ms on the heavy rounds, and was removed in r03).
+    // persistent-workgroup variant was built in r02, lost 140 vs 58 ms on the heavy rounds, and was removed in r03); its light targets
+    // alone go through one workgroup each first (dh_fz_light_kernel, dh_light_prepass).
     static const bool mi_rounds = fw_mi_rounds();
     // (more than 65 535 samples: 32-bit cell counts -- r04: the persistent kernel has a 32-bit-count form too, PRE = 2)
     y.nzk = c->P.kind == FW_FZ_NZ;
@@ -3064,6 +3187,7 @@ struct DhRun {
     // what the launches report
     double timed_s = 0.0;
     long timed_n = 0, launches_n = 0;
+    long light_n = 0;  // launches of dh_fz_light_kernel (dh_light_prepass): a launch of the segment body that is one kernel, not four
     std::vector<float> log_ms;  // FW_DH_LOG: segment-kernel time of launch i (planned by plan #i)
     unsigned max_a_seen = 0;    // longest accepted list reported so far (lags by up to two batches)
     unsigned max_ab_seen = 0;   // ... and the largest accepted + whitelisted-to-come
@@ -3490,8 +3614,35 @@ static void dh_count_run(const DhRun &R, long extra_kernels)
     fw_ctx *c = R.c;
     std::lock_guard<std::mutex> lk(dh_cnt_mu);
     if (R.timed_n > 0) c->cnt.t_dev_subsets_s += R.timed_s * (double)R.launches_n / (double)R.timed_n;
-    c->cnt.subsets_launches += R.launches_n;
-    c->cnt.kernel_launches += (R.y.per_target ? R.launches_n : (R.y.nzk ? 7 : 4) * R.launches_n) + extra_kernels;
+    c->cnt.subsets_launches += R.launches_n + R.light_n;
+    c->cnt.kernel_launches += (R.y.per_target ? R.launches_n : (R.y.nzk ? 7 : 4) * R.launches_n) + R.light_n + extra_kernels;
+}
+
+// Light targets (dh_fz_light_kernel): the largest level-0 degree the pre-pass of a run serves, 0: none.  Fisher-z on the Float32
+// matrix with max_k <= 3 and no rejection log; everything else keeps the rounds.  At most FW_TAB_A / 2: a pool can hold every
+// candidate twice (whitelist duplicates) and must still take the table variant of the segment body.  Read per call (the tests switch it
+// inside a live process).  Default 32, by the sweep of profiles/r15_light_targets.txt
+static int dh_light_deg(const fw_ctx *c, const DhPolicy &y)
+{
+    if (c->P.kind != FW_FZ || c->f64 || !c->d_cor || c->P.max_k < 1 || c->P.max_k > 3 || c->d_rej_run || y.per_target) return 0;
+    return std::min(std::max(fw_knob_int(knob::FW_DH_LIGHT_DEG, 32), 0), FW_TAB_A / 2);
+}
+
+// The pre-pass in front of DhRounds, for the round loop and the slots of the schedule alike: one launch finishes the n_light light
+// targets of the run (the kernel tells them from the others by the same rule, dh_is_light), so that DhRounds -- whose first step kernel
+// finds them finished and whose first compaction drops them -- runs on what is left, or not at all.  R.D.tg, R.A (local matrices
+// included) and R.P are in place; the launch goes to the run's stream, in front of its rounds.
+static int dh_light_prepass(DhRun &R, int light_deg, int n_light)
+{
+    if (n_light == 0) return FW_OK;
+    fw_ctx *c = R.c;
+    double zscale = 0.0;
+    if (int rc = fwi_fz_thresholds(c, R.st, &zscale)) return rc;
+    hipLaunchKernelGGL(dh_fz_light_kernel, dim3((unsigned)R.ntg), dim3(256), 0, R.st, R.D.tg, R.ntg, light_deg, R.A, R.D.s.so, R.P,
+                       (const float *)c->d_cor, c->P.p, zscale, (const double *)c->d_thr);
+    FW_HIP(c, hipGetLastError());
+    R.light_n = 1;
+    return FW_OK;
 }
 
 // One round of targets on the device.  in: T ids, interleaving candidates and (sorted) whitelists per target;
@@ -3512,7 +3663,15 @@ int fwi_devhiton_run(fw_ctx *c, const std::vector<FwDhTarget> &in, std::vector<F
     DhEvents E(R.st, 2 * 2 * DH_BATCH, 2);
     if (!E.ok) return fw_fail(c, FW_ERR_DEVICE, "device HITON: hipEventCreate failed");
     const double th1 = fwi_now_s();
-    rc = R.y.per_target ? dh_run_persistent(R, E) : DhRounds(R, E).run();
+    if (R.y.per_target) {
+        rc = dh_run_persistent(R, E);
+    } else {
+        const int light_deg = dh_light_deg(c, R.y);
+        int n_light = 0;
+        for (const DhTgt &x : R.tg) n_light += dh_is_light(x.nb_n, x.cap, light_deg) ? 1 : 0;
+        rc = dh_light_prepass(R, light_deg, n_light);
+        if (!rc && n_light < ntg) rc = DhRounds(R, E).run();  // (a run of light targets alone: no round, no batch, no record to wait for)
+    }
     dh_count_run(R, 0);
     if (rc) return rc;
     const double th2 = fwi_now_s();
@@ -3597,7 +3756,7 @@ static void dh_sched_append(fw_ctx *c, hipStream_t st, const DhSchedState &S, co
 // results of a schedule: packed on the device (dh_sched_pack_kernel, enqueued behind the last round on st) ...
 static int dh_sched_pack(fw_ctx *c, hipStream_t st, const DhSchedState &S, int nt)
 {
-    hipLaunchKernelGGL(dh_sched_pack_kernel, dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, st, (const DhTgt *)S.tg, nt, (const int32_t *)S.lists.pc_key,
+    hipLaunchKernelGGL(dh_sched_pack_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, (const DhTgt *)S.tg, nt, (const int32_t *)S.lists.pc_key,
                        (const double *)S.lists.pc_stat, (const double *)S.lists.pc_p, S.ot, S.ou, S.os, S.op, S.tot, (double *)(S.tot + 5));
     FW_HIP(c, hipGetLastError());
     return FW_OK;
@@ -3786,6 +3945,7 @@ struct DhFzBarrier {
 // a chain's share of one round of the schedule
 struct DhFzSlot {
     int base = 0, ntg = 0, max_cap = 0;
+    int n_light = 0;  // targets of the slot that the pre-pass finishes (dh_light_prepass)
     unsigned max_ns = 0;
     size_t tm_floats = 0;
 };
@@ -3835,11 +3995,13 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
             for (int q = 0; q < K; ++q) {
                 if (s[q].ntg == 0) continue;
                 const DhPolicy y = dh_policy(c, s[q].ntg);
+                const int light_deg = dh_light_deg(c, y);
                 z.d1 = (size_t)y.spec_depth + 1;
                 for (int t = 0; t < s[q].ntg; ++t) {
                     const int T = slot_T[(size_t)(s[q].base + t)];
                     const int deg = (int)(c->nb_off[T + 1] - c->nb_off[T]);
                     s[q].max_cap = std::max(s[q].max_cap, deg);
+                    s[q].n_light += dh_is_light(deg, deg, light_deg) ? 1 : 0;  // (dh_sched_init_kernel: capacity = degree)
                     slot_tm[(size_t)(s[q].base + t)] = dh_tm_off(c, y, deg, s[q].tm_floats);
                 }
                 s[q].max_ns = dh_max_ns(y, s[q].ntg);
@@ -3901,7 +4063,9 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
         hipLaunchKernelGGL(dh_fz_round_begin_kernel, dim3((unsigned)s.ntg), dim3(256), 0, sq, Rn.D.tg, s.ntg, (const unsigned int *)D.S.wl_cnt, D.S.lists.wl,
                            cb.g, cb.seg0, cb.act, d_wl_max);
         FW_HIP(c, hipGetLastError());
-        if (feed_forward && r > 0) {
+        // a slot of light targets alone never enters DhRounds: no batch, and no whitelist word, which only DhRounds' in-lane bound reads
+        const bool rounds = s.n_light < s.ntg;
+        if (rounds && feed_forward && r > 0) {
             FW_HIP(c, hipMemcpyAsync(h_wl_max, d_wl_max, sizeof(unsigned int), hipMemcpyDeviceToHost, sq));
             FW_HIP(c, hipEventRecord(X.ev_end[(size_t)q * 3 + 2], sq));
         }
@@ -3911,11 +4075,12 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
             FW_HIP(c, hipGetLastError());
         }
         Rn.P = dh_make_params(c, s.ntg, Rn.y.spec_depth, Rn.y.spec0_depth);
-        if (feed_forward && r > 0) {  // the exact longest whitelist, before the round's first batch is enqueued
+        int rc = dh_light_prepass(Rn, dh_light_deg(c, Rn.y), s.n_light);
+        if (!rc && rounds && feed_forward && r > 0) {  // the exact longest whitelist, before the round's first batch is enqueued
             FW_HIP(c, hipEventSynchronize(X.ev_end[(size_t)q * 3 + 2]));
             Rn.max_wl = (int)*h_wl_max;
         }
-        int rc = DhRounds(Rn, E).run();
+        if (!rc && rounds) rc = DhRounds(Rn, E).run();
         const bool append = !rc && feed_forward && r + 1 < nrounds;
         // besides the kernels of every round of the segment kernel, what this round of targets launches: the round-begin kernel, the
         // local matrices and the append where they run
@@ -3949,7 +4114,7 @@ int fwi_devhiton_fz_schedule(fw_ctx *c, const int32_t *sched, int nt, int R, boo
     }
     if (bar.rc) return bar.rc;
     const double th2 = fwi_now_s();
-    // ---- results (every chain has retired its last batch: the device is idle) ----
+    // ---- results (every chain has retired its last batch and synchronised its stream: the device is idle) ----
     if (int rc = dh_sched_pack(c, st, D.S, nt)) return rc;
     unsigned long long htot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (int rc = dh_sched_totals(c, st, D.S, htot)) return rc;

@@ -59,6 +59,7 @@
     X(FW_SEG_A, "launches of fewer ranks than this use a third of FW_SEG_TARGET (fz); default 8000000")                                                                   \
     X(FW_SEG_B, "... fewer than this, two thirds; default 12000000")                                                                                                      \
     X(FW_SEG_GRID, "cap on the striding workgroups of the segment kernel (positive); default 2048 (fz, max_k <= 3) / FW_SEG_TARGET + 512")                                \
+    X(FW_DH_LIGHT_DEG, "largest level-0 degree of a target that one workgroup runs from start to end (fz, max_k <= 3), clamped to FW_TAB_A / 2, 0: off; default 32")      \
     X(FW_FZ_TMAT, "smallest degree of a target that gets a local correlation matrix, 0: none; default 16 (max_k > 3: 1)")                                                 \
     X(FW_DH_BATCH, "rounds per batch (positive, at most 16); default 4 up to 1 024 targets, else 16")                                                                     \
     X(FW_DH_TIME_EVERY, "one segment launch in this many is timed with events (positive); default 4")                                                                     \
