@@ -1,6 +1,6 @@
-// Context lifecycle, data hand-over, level-0 host logic (Benjamini-Hochberg + neighbour lists) and the
-// extern "C" entry points of include/flashweave_amd.h.  Device work lives in fw_fz.hip / fw_mi.hip,
-// the HITON-PC host driver in fw_hiton.cpp.
+// Context lifecycle, data hand-over, the staged level 0 (host-only pieces: fw_level0_host.h), the per-pair and per-job batch entry
+// points and the rest of the extern "C" surface of include/flashweave_amd.h.  Device work lives in fw_fz.hip / fw_mi.hip, the host job
+// pool in fw_pool.cpp, the HITON-PC host driver in fw_hiton.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "fw_internal.h"
+#include "fw_level0_host.h"
 
 static thread_local std::string g_create_err;
 
@@ -591,12 +592,17 @@ int fw_level0_sharded(fw_ctx *c, int32_t rank, int32_t world_size, fw_allgather_
     return fw_level0_impl(c, nnz_out, rank, world_size, allgather, user);
 }
 
-static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_allgather_fn allgather, void *user,
-                          const fw_dev_exchange *xdev)
+// What one fw_level0 call carries from stage to stage: the significant pairs on the host (host exchange, host epilogue) and / or as
+// the kernels left them in device memory, and the number of reliable tests BH divides by.
+struct L0Run {
+    std::vector<int32_t> pi, pj;
+    std::vector<double> stat, pval;
+    int64_t m = 0;
+    FwL0Dev dev;
+};
+
+static int l0_precheck(fw_ctx *c)
 {
-    CHECK_CTX(c);
-    const double t0 = fwi_now_s();
-    const int p = c->P.p;
     if (c->P.kind == FW_FZ && !c->P.no_cor_mat) {
         if (!c->have_cor) {
             int rc = c->f64 ? fwi_fz64_compute_cor(c) : fwi_fz_compute_cor(c);
@@ -609,205 +615,141 @@ static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_a
         return fw_fail(c, FW_ERR_NOBS,
                        "Dataset has an insufficient number of observations, need at least %lld ('n_obs_min') for reliable tests",
                        (long long)c->n_obs_min_eff);
-    std::vector<int32_t> pi, pj;
-    std::vector<double> stat, pval;
-    int64_t m = 0;
-    // BH + neighbour lists run on the device (fw_bh.hip); FW_HOST_BH=1 keeps the host restatement below, which
-    // tests/test_gpu_*.py use to cross-check the two
-    const bool host_bh = fw_knob_int(knob::FW_HOST_BH, 0) == 1;
-    FwL0Dev dev;
-    FwL0Dev *devp = host_bh ? nullptr : &dev;
-    // Target-sharded runs: for the discrete kinds, whose pair screen is the expensive part of level 0
-    // (cfg4: 73 of 140 ms), every rank screens its share of the pair tiles and the significant pairs are all-gathered; the
-    // Fisher-z kinds screen a resident matrix in well under a millisecond per 10^8 pairs and stay replicated.  BH and the
-    // neighbour lists are then built redundantly on every rank from the same merged list (their result does not depend
-    // on the order of the list).
-    const bool sharded = world > 1 && (c->P.kind == FW_MI || c->P.kind == FW_MI_NZ);
-    c->l0_rank = sharded ? rank : 0;
-    c->l0_world = sharded ? world : 1;
-    int rc = (c->P.kind == FW_FZ)      ? (c->f64 ? fwi_fz64_level0(c, pi, pj, stat, pval, &m, devp) : fwi_fz_level0(c, pi, pj, stat, pval, &m, devp))
-             : (c->P.kind == FW_FZ_NZ) ? fwi_fznz_level0(c, pi, pj, stat, pval, &m, devp)
-                                       : fwi_mi_level0(c, pi, pj, stat, pval, &m, (sharded && !xdev) ? nullptr : devp);
+    return FW_OK;
+}
+
+// The pair screen of the context's kind; a sharded run screens this rank's share of the pair tiles.  want_dev: leave the pairs in
+// device memory (r.dev) instead of the host vectors.
+static int l0_screen(fw_ctx *c, L0Run &r, int rank, int world, bool want_dev)
+{
+    FwL0Dev *devp = want_dev ? &r.dev : nullptr;
+    c->l0_rank = rank;
+    c->l0_world = world;
+    int rc = (c->P.kind == FW_FZ)      ? (c->f64 ? fwi_fz64_level0(c, r.pi, r.pj, r.stat, r.pval, &r.m, devp) : fwi_fz_level0(c, r.pi, r.pj, r.stat, r.pval, &r.m, devp))
+             : (c->P.kind == FW_FZ_NZ) ? fwi_fznz_level0(c, r.pi, r.pj, r.stat, r.pval, &r.m, devp)
+                                       : fwi_mi_level0(c, r.pi, r.pj, r.stat, r.pval, &r.m, devp);
     c->l0_rank = 0;
     c->l0_world = 1;
-    if (rc) return rc;
-    if (sharded && xdev) {
-        // payload stays on the device: pack -> caller's collective -> unpack (fw_xchg.hip).  m = sum_r m_r - (W - 1) * npairs
-        // (every rank reports npairs minus ITS unreliable pairs)
-        if (host_bh) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded_dev: FW_HOST_BH=1 is a single-rank debugging mode");
-        FwL0Dev merged;
-        int64_t msum = 0;
-        if ((rc = fwi_l0_exchange_dev(c, xdev, world, dev, m, &merged, &msum))) return rc;
-        dev = merged;
-        m = msum - (int64_t)(world - 1) * ((int64_t)p * (p - 1) / 2);
-    } else if (sharded) {
-        // one extra record carries this rank's count of reliable tests: m = sum_r m_r - (W - 1) * npairs (every rank reports
-        // npairs minus ITS unreliable pairs)
-        pi.push_back(-1);
-        pj.push_back(rank);
-        stat.push_back((double)m);
-        pval.push_back(0.0);
-        int64_t ntot = 0;
-        const int32_t *ai = nullptr, *aj = nullptr;
-        const double *as = nullptr, *ap = nullptr;
-        rc = allgather(user, (int64_t)pi.size(), pi.data(), pj.data(), stat.data(), pval.data(), &ntot, &ai, &aj, &as, &ap);
-        if (rc) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded: allgather callback failed (%d)", rc);
-        std::vector<int32_t> qi, qj;
-        std::vector<double> qs, qp;
-        qi.reserve((size_t)ntot);
-        qj.reserve((size_t)ntot);
-        qs.reserve((size_t)ntot);
-        qp.reserve((size_t)ntot);
-        const int64_t npairs = (int64_t)p * (p - 1) / 2;
-        int64_t msum = 0;
-        int nrec = 0;
-        for (int64_t t = 0; t < ntot; ++t) {
-            if (ai[t] < 0) {
-                msum += (int64_t)as[t];
-                ++nrec;
-                continue;
-            }
-            qi.push_back(ai[t]);
-            qj.push_back(aj[t]);
-            qs.push_back(as[t]);
-            qp.push_back(ap[t]);
-        }
-        if (nrec != world) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded: %d of %d ranks reported", nrec, world);
-        m = msum - (int64_t)(world - 1) * npairs;
-        pi.swap(qi);
-        pj.swap(qj);
-        stat.swap(qs);
-        pval.swap(qp);
-        if (!host_bh) {  // back to the device for the BH / neighbour-list epilogue
-            const size_t k = pi.size();
-            if ((rc = fw_dev_reserve(c, c->d_tmp1, (k + 1) * 2 * sizeof(int32_t)))) return rc;
-            if ((rc = fw_dev_reserve(c, c->d_tmp2, (k + 1) * 2 * sizeof(double)))) return rc;
-            int32_t *oi = (int32_t *)c->d_tmp1.ptr, *oj = oi + k;
-            double *os = (double *)c->d_tmp2.ptr, *op = os + k;
-            if (k) {
-                FW_HIP(c, hipMemcpyAsync(oi, pi.data(), k * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                FW_HIP(c, hipMemcpyAsync(oj, pj.data(), k * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                FW_HIP(c, hipMemcpyAsync(os, stat.data(), k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-                FW_HIP(c, hipMemcpyAsync(op, pval.data(), k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-                FW_HIP(c, hipStreamSynchronize(c->stream));
-            }
-            dev = FwL0Dev{};
-            dev.i = oi;
-            dev.j = oj;
-            dev.stat64 = os;
-            dev.pval = op;
-            dev.k = k;
-        }
+    return rc;
+}
+
+// Sharded exchange through the caller's host all-gather: one extra record carries this rank's count of reliable tests
+static int l0_exchange_host(fw_ctx *c, L0Run &r, int rank, int world, fw_allgather_fn allgather, void *user)
+{
+    r.pi.push_back(-1);
+    r.pj.push_back(rank);
+    r.stat.push_back((double)r.m);
+    r.pval.push_back(0.0);
+    int64_t ntot = 0;
+    const int32_t *ai = nullptr, *aj = nullptr;
+    const double *as = nullptr, *ap = nullptr;
+    int rc = allgather(user, (int64_t)r.pi.size(), r.pi.data(), r.pj.data(), r.stat.data(), r.pval.data(), &ntot, &ai, &aj, &as, &ap);
+    if (rc) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded: allgather callback failed (%d)", rc);
+    L0Run all;
+    const int nrec = fw_l0_split_gathered(ntot, ai, aj, as, ap, world, (int64_t)c->P.p * (c->P.p - 1) / 2, all.pi, all.pj, all.stat, all.pval, &all.m);
+    if (nrec != world) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded: %d of %d ranks reported", nrec, world);
+    r = std::move(all);
+    return FW_OK;
+}
+
+// Sharded exchange with the payload on the device: pack -> caller's collective -> unpack (fw_xchg.hip), the same rule for m
+static int l0_exchange_dev(fw_ctx *c, L0Run &r, int world, const fw_dev_exchange *xdev)
+{
+    FwL0Dev merged;
+    int64_t msum = 0;
+    if (int rc = fwi_l0_exchange_dev(c, xdev, world, r.dev, r.m, &merged, &msum)) return rc;
+    r.dev = merged;
+    r.m = msum - (int64_t)(world - 1) * ((int64_t)c->P.p * (c->P.p - 1) / 2);
+    return FW_OK;
+}
+
+// The host's merged pairs back to the device (d_tmp1 / d_tmp2) for the device epilogue
+static int l0_upload(fw_ctx *c, L0Run &r)
+{
+    const size_t k = r.pi.size();
+    if (int rc = fw_dev_reserve(c, c->d_tmp1, (k + 1) * 2 * sizeof(int32_t))) return rc;
+    if (int rc = fw_dev_reserve(c, c->d_tmp2, (k + 1) * 2 * sizeof(double))) return rc;
+    int32_t *oi = (int32_t *)c->d_tmp1.ptr, *oj = oi + k;
+    double *os = (double *)c->d_tmp2.ptr, *op = os + k;
+    if (k) {
+        FW_HIP(c, hipMemcpyAsync(oi, r.pi.data(), k * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        FW_HIP(c, hipMemcpyAsync(oj, r.pj.data(), k * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        FW_HIP(c, hipMemcpyAsync(os, r.stat.data(), k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        FW_HIP(c, hipMemcpyAsync(op, r.pval.data(), k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        FW_HIP(c, hipStreamSynchronize(c->stream));
     }
-    if (!host_bh) {
-        const double t_bh0 = fwi_now_s();
-        if ((rc = fwi_bh_csr_device(c, dev, m))) return rc;
-        c->cnt.t_level0_host_s += fwi_now_s() - t_bh0;  // here: the device epilogue incl. its device-to-host copies
-        c->have_level0 = true;
-        c->have_network = false;
-        c->cnt.level0_tests += (int64_t)p * (p - 1) / 2;
-        c->cnt.t_level0_s += fwi_now_s() - t0;
-        if (nnz_out) *nnz_out = c->nb_off[p];
-        return FW_OK;
-    }
+    r.dev = FwL0Dev{};
+    r.dev.i = oi;
+    r.dev.j = oj;
+    r.dev.stat64 = os;
+    r.dev.pval = op;
+    r.dev.k = k;
+    return FW_OK;
+}
+
+// BH + neighbour lists on the device (fw_bh.hip); the time includes its device-to-host copies
+static int l0_epilogue_dev(fw_ctx *c, const L0Run &r)
+{
+    const double t0 = fwi_now_s();
+    if (int rc = fwi_bh_csr_device(c, r.dev, r.m)) return rc;
+    c->cnt.t_level0_host_s += fwi_now_s() - t0;
+    return FW_OK;
+}
+
+// FW_HOST_BH=1: the host restatement (fw_level0_host.h); the lists then live on the host only
+static void l0_epilogue_host(fw_ctx *c, L0Run &r)
+{
     c->d_nb_off = nullptr;
     c->d_nb_idx = nullptr;
     c->d_nb_stat = c->d_nb_p = nullptr;
     c->d_cand = nullptr;
     c->nb_host_valid = true;
-    const size_t k = pi.size();
-    const double t_host0 = fwi_now_s();
-    if (c->P.fdr && k > 0) {
-        // statfuns.jl:326-350.  Ascending sort by p: LSD radix sort on the IEEE bit pattern (p >= 0 -> order preserving).
-        // Ties need no stable order: the backward cumulative minimum gives every member of a tie group the same value.
-        std::vector<uint64_t> key(k), key2(k);
-        std::vector<uint32_t> val(k), val2(k);
-        for (size_t t = 0; t < k; ++t) {
-            uint64_t u;
-            memcpy(&u, &pval[t], 8);
-            key[t] = u;
-            val[t] = (uint32_t)t;
-        }
-        std::vector<uint32_t> hist(65536);
-        for (int pass = 0; pass < 4; ++pass) {
-            const int sh = 16 * pass;
-            std::fill(hist.begin(), hist.end(), 0u);
-            for (size_t t = 0; t < k; ++t) hist[(key[t] >> sh) & 0xFFFF]++;
-            uint32_t run = 0;
-            for (size_t d = 0; d < 65536; ++d) {
-                const uint32_t h = hist[d];
-                hist[d] = run;
-                run += h;
-            }
-            for (size_t t = 0; t < k; ++t) {
-                const uint32_t dst = hist[(key[t] >> sh) & 0xFFFF]++;
-                key2[dst] = key[t];
-                val2[dst] = val[t];
-            }
-            key.swap(key2);
-            val.swap(val2);
-        }
-        const double md = (double)m;
-        double next_adj = 0.0;
-        for (size_t i = k; i-- > 0;) {
-            double pv;
-            memcpy(&pv, &key[i], 8);
-            double adj = pv * md / (double)(i + 1);
-            if (i == k - 1)
-                adj = std::min(adj, 1.0);
-            else
-                adj = std::min(next_adj, adj);
-            next_adj = adj;
-            pval[val[i]] = adj;
-        }
-    }
-    // neighbour lists (tests.jl:372-388): adj p < alpha, partners ascending.  Two stable counting sorts give the
-    // (X ascending, Y ascending) pair order of the reference's condensed arrays; appending in that order yields
-    // ascending partner lists for both endpoints.
-    std::vector<uint32_t> keep;
-    keep.reserve(k);
-    for (size_t t = 0; t < k; ++t)
-        if (pval[t] < c->P.alpha) keep.push_back((uint32_t)t);
-    const size_t kk = keep.size();
-    std::vector<uint32_t> byj(kk), byij(kk);
-    {
-        std::vector<uint32_t> cnt((size_t)p + 1, 0);
-        for (uint32_t t : keep) cnt[pj[t] + 1]++;
-        for (int v = 0; v < p; ++v) cnt[v + 1] += cnt[v];
-        for (uint32_t t : keep) byj[cnt[pj[t]]++] = t;
-        std::fill(cnt.begin(), cnt.end(), 0u);
-        for (uint32_t t : byj) cnt[pi[t] + 1]++;
-        for (int v = 0; v < p; ++v) cnt[v + 1] += cnt[v];
-        for (uint32_t t : byj) byij[cnt[pi[t]]++] = t;
-    }
-    c->nb_off.assign((size_t)p + 1, 0);
-    for (uint32_t t : byij) {
-        c->nb_off[pi[t] + 1]++;
-        c->nb_off[pj[t] + 1]++;
-    }
-    for (int v = 0; v < p; ++v) c->nb_off[v + 1] += c->nb_off[v];
-    const int64_t tot = c->nb_off[p];
-    c->nb_idx.assign((size_t)tot, 0);
-    c->nb_stat.assign((size_t)tot, 0.0);
-    c->nb_p.assign((size_t)tot, 0.0);
-    std::vector<int64_t> fill(c->nb_off.begin(), c->nb_off.end() - 1);
-    for (uint32_t t : byij) {
-        const int X = pi[t], Y = pj[t];
-        const int64_t a = fill[X]++, b = fill[Y]++;
-        c->nb_idx[a] = Y;
-        c->nb_stat[a] = stat[t];
-        c->nb_p[a] = pval[t];
-        c->nb_idx[b] = X;
-        c->nb_stat[b] = stat[t];
-        c->nb_p[b] = pval[t];
-    }
-    c->cnt.t_level0_host_s += fwi_now_s() - t_host0;
+    const double t0 = fwi_now_s();
+    if (c->P.fdr) fw_bh_adjust(r.pval, r.m);
+    fw_nb_csr(c->P.p, r.pi, r.pj, r.stat, r.pval, c->P.alpha, c->nb_off, c->nb_idx, c->nb_stat, c->nb_p);
+    c->cnt.t_level0_host_s += fwi_now_s() - t0;
+}
+
+static int l0_finish(fw_ctx *c, double t_start, int64_t *nnz_out)
+{
     c->have_level0 = true;
     c->have_network = false;
-    c->cnt.level0_tests += (int64_t)p * (p - 1) / 2;
-    c->cnt.t_level0_s += fwi_now_s() - t0;
-    if (nnz_out) *nnz_out = tot;
+    c->cnt.level0_tests += (int64_t)c->P.p * (c->P.p - 1) / 2;
+    c->cnt.t_level0_s += fwi_now_s() - t_start;
+    if (nnz_out) *nnz_out = c->nb_off[c->P.p];
     return FW_OK;
+}
+
+// Target-sharded runs: for the discrete kinds, whose pair screen is the expensive part of level 0 (cfg4: 73 of
+// 140 ms), every rank screens its share of the pair tiles and the significant pairs are all-gathered; the Fisher-z kinds screen a
+// resident matrix in well under a millisecond per 10^8 pairs and stay replicated.  BH and the neighbour lists are then built
+// redundantly on every rank from the same merged list (their result does not depend on the order of the list).
+static int fw_level0_impl(fw_ctx *c, int64_t *nnz_out, int rank, int world, fw_allgather_fn allgather, void *user,
+                          const fw_dev_exchange *xdev)
+{
+    CHECK_CTX(c);
+    const double t0 = fwi_now_s();
+    if (int rc = l0_precheck(c)) return rc;
+    // BH + neighbour lists run on the device (fw_bh.hip); FW_HOST_BH=1 keeps the host restatement, which tests/test_gpu_*.py use to
+    // cross-check the two
+    const bool host_bh = fw_knob_int(knob::FW_HOST_BH, 0) == 1;
+    const bool sharded = world > 1 && (c->P.kind == FW_MI || c->P.kind == FW_MI_NZ);
+    const bool via_host = sharded && !xdev;  // the pairs cross the host all-gather: the screen leaves them on the host
+    L0Run r;
+    if (int rc = l0_screen(c, r, sharded ? rank : 0, sharded ? world : 1, !host_bh && !via_host)) return rc;
+    if (sharded && xdev) {
+        if (host_bh) return fw_fail(c, FW_ERR_ARG, "fw_level0_sharded_dev: FW_HOST_BH=1 is a single-rank debugging mode");
+        if (int rc = l0_exchange_dev(c, r, world, xdev)) return rc;
+    } else if (sharded) {
+        if (int rc = l0_exchange_host(c, r, rank, world, allgather, user)) return rc;
+        if (!host_bh)
+            if (int rc = l0_upload(c, r)) return rc;
+    }
+    if (host_bh)
+        l0_epilogue_host(c, r);
+    else if (int rc = l0_epilogue_dev(c, r))
+        return rc;
+    return l0_finish(c, t0, nnz_out);
 }
 
 int fw_level0_get(const fw_ctx *c, int64_t *off, int32_t *idx, double *stat, double *adj_p)
@@ -895,467 +837,6 @@ int fw_test_batch(fw_ctx *c, int64_t m, const int32_t *X, const int32_t *Y, cons
 }
 
 }  // extern "C"
-
-// ---- progressive, segment-parallel evaluation of test_subsets jobs -------------------------------------
-// A job's subsets are ranked in the reference's enumeration order.  Ranks are evaluated in windows that grow
-// geometrically (256, 1k, 4k, ... ranks); each window is cut into segments, one workgroup per segment, and the
-// per-segment outputs are merged IN RANK ORDER on the host: the first stopping rank ends the job exactly where the
-// sequential reference would have stopped (tests.jl:326-336); otherwise the (p, rank) maximum with "later wins
-// ties" is carried forward (tests.jl:338-341).  Speculation is bounded by the window growth factor.
-static uint64_t binom_sat(int64_t m, int t)
-{
-    if (t < 0 || m < t) return 0;
-    const uint64_t SAT = 1ull << 62;
-    long double r = 1.0L;
-    for (int i = 1; i <= t; ++i) r = r * (long double)(m - t + i) / (long double)i;
-    if (r > (t > 5 ? 2.0e18L : 3.6e18L)) return SAT;  // the intermediate v * (m - t + i) is up to t * C(m, t): stay below 2^64 / 5 (t = 6, 7: the device's fz_binom_sat7 bound)
-    uint64_t v = 1;
-    for (int i = 1; i <= t; ++i) v = v * (uint64_t)(m - t + i) / (uint64_t)i;  // exact: product of i consecutive ints / i!
-    return v;
-}
-
-// lexicographic unranking (same order as the device code): rank -> subset size and positions
-static void unrank_host(uint64_t r, int a, int max_k, int *s_out, int *pos)
-{
-    int s = max_k;
-    while (s > 1) {
-        const uint64_t cnt = binom_sat(a, s);
-        if (r < cnt) break;
-        r -= cnt;
-        --s;
-    }
-    *s_out = s;
-    int prev = -1;
-    for (int d = 0; d < s; ++d) {
-        const int t = s - d;
-        int c = prev + 1;
-        for (;;) {
-            const uint64_t with_c = binom_sat(a - 1 - c, t - 1);
-            if (r < with_c) break;
-            r -= with_c;
-            ++c;
-        }
-        pos[d] = c;
-        prev = c;
-    }
-}
-
-// geometric growth of the evaluation window of a job (speculation bound vs number of latency-bound rounds);
-// FW_WINDOW_GROWTH is a tuning knob for profiling runs
-static uint64_t fw_window_growth(size_t n_live, uint64_t launched_ranks)
-{
-    static const long forced = [] {
-        const long v = (long)fw_knob_u64(knob::FW_WINDOW_GROWTH, 0ull);
-        return (v >= 2 && v <= 64) ? v : 0l;
-    }();
-    if (forced) return (uint64_t)forced;
-    // many jobs in flight: launches are full, keep speculation tight (x4); few jobs: the round latency dominates
-    // and a wider window (x16) saves rounds (measured on cfg3: 3236 -> 2024 launches for +9 % evaluated tests);
-    // a launch that does not even fill the GPU (a few thousand workgroups of 256 ranks) costs the same whether its
-    // windows are 16 or 256 times larger: grow faster there, the extra speculative tests are free
-    static const uint64_t small = fw_small_launch();  // default 1 << 22; cfg3 sweep: 0 -> 630 ms, 1M 613, 4M 569, 8M 588, 64M 582
-    if (launched_ranks < small) return 256;
-    return n_live > 2048 ? 4 : 16;
-}
-
-static void no_power_result(const fw_ctx *c, const int32_t *acc, int a, FwJobOut &o)
-{
-    // tests.jl:254-262: every test lacks power -> the first one is returned (0, 1, 0, false)
-    o = FwJobOut{};
-    o.stat = 0.0;
-    o.pval = 1.0;
-    o.num_tests = 1;
-    o.evaluated = 0;
-    o.status = FW_SUBSETS_STOPPED;
-    const int s = std::min<int>(c->P.max_k, a);
-    o.n_zs = s;
-    for (int q = 0; q < s; ++q) o.zs[q] = acc[q];
-}
-
-int fwi_pool_add(fw_ctx *c, FwPool &pool, int32_t X, int32_t Y, const int32_t *acc, int a, int64_t tag)
-{
-    FwPoolJob j;
-    j.X = X;
-    j.Y = Y;
-    j.tag = tag;
-    j.acc.assign(acc, acc + a);
-    uint64_t N = 0;
-    for (int s = c->P.max_k; s >= 1; --s) {
-        N += binom_sat(a, s);
-        if (N > (1ull << 62)) N = 1ull << 62;
-    }
-    const uint64_t mt = c->P.max_tests > 0 ? (uint64_t)c->P.max_tests : 0;
-    if (mt && mt < N) N = mt;
-    j.N = N;
-    j.next = 0;
-    // first window: fz 256 ranks (one test per lane of one workgroup), 16384 once |accepted| >= 64 -- a job that large
-    // either stops within the first few tests or runs for tens of thousands, so small first windows are wasted round
-    // trips (cfg3: 1731 -> 1154 launches per pass, +4 % evaluated tests, 0.527 -> 0.50 s); discrete: 16
-    static const uint64_t w0_big = fw_knob_u64(knob::FW_W0_BIG, 16384ull);
-    j.width = (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) ? (a >= 64 ? w0_big : 256ull) : 16ull;
-    j.best_p = -1.0;
-    j.best_stat = 0.0;
-    j.best_rank = 0;
-    j.best_df = 0;
-    j.done = false;
-    j.out = FwJobOut{};
-    pool.live.push_back(std::move(j));
-    return FW_OK;
-}
-
-static void finish_job(const fw_ctx *c, FwPoolJob &j, bool want_zs)
-{
-    j.done = true;
-    j.out.n_zs = 0;
-    if (!want_zs || j.no_zs) return;  // the HITON driver never looks at the conditioning set of the returned result
-    int s = 0, pos[FW_MAX_K] = {0};
-    unrank_host(j.best_rank, (int)j.acc.size(), c->P.max_k, &s, pos);  // conditioning set of the returned result
-    j.out.n_zs = s;
-    for (int q = 0; q < FW_MAX_K; ++q) j.out.zs[q] = q < s ? j.acc[pos[q]] : 0;
-    j.done = true;
-}
-
-// One window of every live job = one kernel launch on the pool's own stream.  fwi_pool_launch only enqueues;
-// fwi_pool_collect waits for it and merges.  Two pools can therefore overlap: the host merges / re-posts one
-// while the GPU evaluates the other.
-int fwi_pool_launch(fw_ctx *c, FwPool &pool)
-{
-    pool.ns = 0;
-    pool.inflight = false;
-    if (pool.owner_epoch) {  // drop jobs whose owner's accepted set has changed since they were posted
-        size_t w = 0;
-        for (size_t ji = 0; ji < pool.live.size(); ++ji) {
-            FwPoolJob &j = pool.live[ji];
-            if (j.epoch != (*pool.owner_epoch)[(size_t)j.tag]) {
-                pool.dropped_evaluated += j.out.evaluated;
-                pool.dropped_alg_bytes += fwi_alg_bytes(c, (int)j.acc.size(), j.out.evaluated);
-                continue;
-            }
-            if (w != ji) pool.live[w] = std::move(j);
-            ++w;
-        }
-        pool.live.resize(w);
-    }
-    if (pool.live.empty()) return FW_OK;
-    const bool stream = c->P.kind == FW_FZ && !c->P.recursive_pcor;  // one wavefront per test on the sample columns (fw_fzs.hip)
-    const bool fz = (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) && !stream;  // one lane per test on a correlation matrix
-    const bool nzs = c->P.kind == FW_FZ_NZ;
-    if (c->P.kind == FW_FZ && c->P.n < c->n_obs_min_eff) {  // no device work: fwi_pool_collect fills the results
-        pool.inflight = true;
-        return FW_OK;
-    }
-    if (stream) {  // job matrices kept across the rounds of this pool (ctx->d_arena): a new pool, or an arena another pool used, starts empty
-        if (pool.gram_epoch == 0 || pool.gram_epoch != c->gram_epoch || pool.gram_top * sizeof(double) > ((size_t)4 << 30)) {
-            pool.gram_epoch = ++c->gram_epoch;
-            pool.gram_top = 0;
-        }
-    }
-    const double tb0 = fwi_now_s();
-    FwPoolBuf &pb = c->pb[pool.buf];
-    // window of every live job, then a segment length that yields a few thousand workgroups
-    uint64_t total = 0, acc_total = 0;
-    size_t n_launch = 0;
-    for (FwPoolJob &j : pool.live) {
-        j.launched = !j.hold;
-        if (!j.launched) continue;
-        ++n_launch;
-        total += std::min(j.width, j.N - j.next);
-        acc_total += j.acc.size();
-    }
-    pool.launched_ranks = total;
-    if (n_launch == 0) return FW_OK;  // everything is on hold: nothing to do this round
-    // fz: one lane per test (256-rank granularity); discrete: one wavefront per test (4-rank granularity)
-    const uint64_t q = fz ? 256 : 4, smin = fz ? 256 : 8, smax = fz ? 8192 : 256;
-    static const uint64_t seg_target = fw_seg_target();  // workgroups per launch the segment length aims for
-    const uint64_t seg_tgt = seg_target ? seg_target : (fz ? 3072 : 4096);  // fz: runs of up to 32 ranks per lane
-    uint64_t seglen = (total / seg_tgt + q - 1) / q * q;
-    seglen = std::max<uint64_t>(smin, std::min<uint64_t>(seglen, smax));
-    size_t ns = 0;
-    for (const FwPoolJob &j : pool.live)
-        if (j.launched) ns += (size_t)((std::min(j.width, j.N - j.next) + seglen - 1) / seglen);
-    // Accepted lists live in a device arena for as long as their job does: a job uploads its list once, with its
-    // first window, not with every window (at cfg3 the lists of ~1500 live jobs are ~1 MB per round).  The arena is a
-    // bump allocator; when it is full every live job is re-staged from offset 0.
-    int rc;
-    size_t new_ints = 0;
-    for (const FwPoolJob &j : pool.live)
-        if (j.launched && j.acc_dev_off < 0) new_ints += j.acc.size();
-    if (pool.arena_top + new_ints > pb.d_acc.cap / sizeof(int32_t) || pool.arena_top == 0) {
-        size_t live_ints = 0;
-        for (FwPoolJob &j : pool.live) {
-            j.acc_dev_off = -1;
-            live_ints += j.acc.size();
-        }
-        if ((rc = fw_dev_reserve(c, pb.d_acc, std::max<size_t>(4 * live_ints, (size_t)1 << 20) * sizeof(int32_t)))) return rc;
-        pool.arena_top = 0;
-        new_ints = acc_total;
-    }
-    const size_t in_bytes = ns * sizeof(FwSeg) + std::max<size_t>(new_ints, 1) * sizeof(int32_t);
-    if ((rc = fw_pin_reserve(c, pb.h_in, in_bytes))) return rc;
-    if ((rc = fw_pin_reserve(c, pb.h_out, ns * sizeof(FwSegOut)))) return rc;
-    if ((rc = fw_dev_reserve(c, pb.d_in, ns * sizeof(FwSeg)))) return rc;
-    // results: one 64-byte record per workgroup, written straight into pinned host memory (posted PCIe writes) -- saves
-    // the device-to-host copy of every round; FW_ZC_OUT=0 stages them through device memory instead (profiling knob)
-    static const bool zc_out = fw_knob_on(knob::FW_ZC_OUT);
-    if (!zc_out && (rc = fw_dev_reserve(c, pb.d_out, ns * sizeof(FwSegOut)))) return rc;
-    FwSegOut *dout = zc_out ? (FwSegOut *)pb.h_out.ptr : (FwSegOut *)pb.d_out.ptr;
-    FwSeg *segs = (FwSeg *)pb.h_in.ptr;
-    int32_t *hacc = (int32_t *)((char *)pb.h_in.ptr + ns * sizeof(FwSeg));
-    pool.seg_job.resize(ns);
-    pool.nzrecs.clear();
-    size_t arena_floats = 0;
-    size_t si = 0, ns_tab = 0;
-    size_t staged = 0;
-    // fz / fz_nz with max_k <= 3: segments of jobs with at most FW_TAB_A accepted variables come first (table kernel)
-    static const bool no_tab = fw_knob_set(knob::FW_NO_TAB);  // profiling knob: force the in-lane caching kernel
-    const bool no_hk = fw_no_hk();  // profiling / test knob: generic size-4/5 kernel for every job
-    const bool hk = c->P.max_k > 3;  // max_k 4-5: level-2 table kernel up to FW_HK_A accepted variables (plain fz only)
-    const bool split = fz && !no_tab && (!hk || (c->P.kind == FW_FZ && !stream && !no_hk));
-    const size_t tab_a = hk ? (size_t)FW_HK_A : (size_t)FW_TAB_A;
-    // record of every launched job in pool.nzrecs: with `split` the records are pushed in two passes (short lists first), i.e. NOT in
-    // pool.live order -- the re-layout below must follow this map, not a running counter
-    std::vector<size_t> job_rec(pool.live.size(), (size_t)-1);
-    for (int pass = 0; pass < (split ? 2 : 1); ++pass) {
-        for (size_t ji = 0; ji < pool.live.size(); ++ji) {
-            FwPoolJob &j = pool.live[ji];
-            if (!j.launched) continue;
-            if (split && (j.acc.size() <= tab_a) != (pass == 0)) continue;
-            if (j.acc_dev_off < 0) {
-                memcpy(hacc + staged, j.acc.data(), j.acc.size() * sizeof(int32_t));
-                j.acc_dev_off = (int64_t)(pool.arena_top + staged);
-                staged += j.acc.size();
-            }
-            const int64_t aoff = j.acc_dev_off;
-            const uint64_t lo = j.next, hi = lo + std::min(j.width, j.N - lo);
-            for (uint64_t sgs = lo; sgs < hi; sgs += seglen) {
-                FwSeg sg{};
-                sg.X = j.X;
-                sg.Y = j.Y;
-                sg.acc_off = aoff;
-                sg.acc_len = (int32_t)j.acc.size();
-                sg.start = sgs;
-                sg.end = std::min(hi, sgs + seglen);
-                sg.pad = (int32_t)pool.nzrecs.size();  // fz_nz: index of the job's record in this launch
-                segs[si] = sg;
-                pool.seg_job[si] = (int64_t)ji;
-                ++si;
-            }
-            if (nzs || stream) {  // per-job record: fz_nz sub-matrix / recursive_pcor = 0 job-local correlation matrix
-                job_rec[ji] = pool.nzrecs.size();
-                FwNzJob r{};
-                r.X = j.X;
-                r.Y = j.Y;
-                r.acc_off = aoff;
-                r.acc_len = (int32_t)j.acc.size();
-                r.m = r.acc_len + 2;
-                if (stream) {
-                    // the matrix of a job stays in the arena while the job lives: a job that takes several windows (pool rounds) has it
-                    // computed once (whole cfg3: fzs_gram_kernel was 30 % of the kernel time with one computation per round)
-                    if (j.gram_off < 0 || j.gram_epoch != pool.gram_epoch) {
-                        j.gram_off = (int64_t)pool.gram_top;
-                        j.gram_epoch = pool.gram_epoch;
-                        pool.gram_top += (size_t)r.m * r.m;
-                        r.nR = 1;  // to be computed in this launch
-                        c->cnt.gram_jobs += 1;  // (the job-matrix form's own algorithmic unit, fw_counters)
-                        c->cnt.gram_alg_bytes += (double)r.m * (double)c->P.n * 4.0;
-                        c->cnt.gram_alg_flops += 2.0 * (double)c->P.n * 0.5 * (double)r.m * (double)(r.m - 1);
-                    }
-                    r.cor_off = (long long)j.gram_off;
-                    arena_floats = pool.gram_top;
-                } else {
-                    r.cor_off = (long long)arena_floats;
-                    arena_floats += (size_t)r.m * r.m;
-                }
-                pool.nzrecs.push_back(r);
-            }
-        }
-        if (split && pass == 0) ns_tab = si;
-    }
-    if (stream && pool.gram_top * sizeof(double) > c->d_arena.cap) {
-        // the arena has to grow and loses its contents: every matrix of this launch is computed again at fresh offsets (the jobs
-        // that sit this round out are caught by the epoch)
-        pool.gram_epoch = ++c->gram_epoch;
-        pool.gram_top = 0;
-        for (size_t ji = 0; ji < pool.live.size(); ++ji) {
-            FwPoolJob &j = pool.live[ji];
-            if (!j.launched) continue;
-            FwNzJob &r = pool.nzrecs[job_rec[ji]];
-            j.gram_off = (int64_t)pool.gram_top;
-            j.gram_epoch = pool.gram_epoch;
-            r.cor_off = (long long)j.gram_off;
-            if (r.nR == 0) {  // a cached matrix that is computed again: counted like the ones the first loop scheduled
-                c->cnt.gram_jobs += 1;
-                c->cnt.gram_alg_bytes += (double)r.m * (double)c->P.n * 4.0;
-                c->cnt.gram_alg_flops += 2.0 * (double)c->P.n * 0.5 * (double)r.m * (double)(r.m - 1);
-            }
-            r.nR = 1;
-            pool.gram_top += (size_t)r.m * r.m;
-        }
-        arena_floats = pool.gram_top;
-    }
-    const double tb1 = fwi_now_s();
-    c->cnt.t_host_build_s += tb1 - tb0;
-    FW_HIP(c, hipMemcpyAsync(pb.d_in.ptr, pb.h_in.ptr, ns * sizeof(FwSeg), hipMemcpyHostToDevice, pb.launch_stream));
-    if (staged)
-        FW_HIP(c, hipMemcpyAsync((int32_t *)pb.d_acc.ptr + pool.arena_top, hacc, staged * sizeof(int32_t), hipMemcpyHostToDevice,
-                                 pb.launch_stream));
-    pool.arena_top += staged;
-    const FwSeg *dsegs = (const FwSeg *)pb.d_in.ptr;
-    const int32_t *dacc = (const int32_t *)pb.d_acc.ptr;
-    if (nzs) {
-        const bool f64 = !c->P.recursive_pcor;  // fz_nz without a matrix: Float64 view correlations, conditioned as StatsBase.partialcor does
-        rc = fwi_fznz_submatrices(c, (int64_t)pool.nzrecs.size(), pool.nzrecs.data(), arena_floats, dacc, pb.launch_stream, f64);
-        if (rc) return rc;
-        if (f64) {
-            int m_max = 2;
-            for (const FwNzJob &r : pool.nzrecs) m_max = std::max(m_max, (int)r.m);
-            rc = fwi_fzs_segments_nz(c, (int64_t)ns, dsegs, dacc, dout, pb, m_max);
-        } else {
-            rc = fwi_fznz_segments(c, (int64_t)ns, (int64_t)ns_tab, dsegs, dacc, dout, pb);
-        }
-    } else {
-        rc = stream ? fwi_fzs_segments(c, (int64_t)ns, dsegs, dacc, dout, pb, pool.nzrecs.data(), (int64_t)pool.nzrecs.size(), arena_floats)
-             : c->f64 ? fwi_fz64_segments(c, (int64_t)ns, dsegs, dacc, dout, pb)
-             : fz   ? fwi_fz_segments(c, (int64_t)ns, (int64_t)ns_tab, dsegs, dacc, dout, pb)
-                : fwi_mi_segments(c, (int64_t)ns, dsegs, dacc, dout, pb);
-    }
-    if (rc) return rc;
-    if (stream && arena_floats * sizeof(double) > ((size_t)8 << 30))
-        pool.gram_epoch = 0;  // fwi_fzs_segments streamed this launch instead (matrices beyond its arena limit): nothing was cached
-    if (!zc_out)
-        FW_HIP(c, hipMemcpyAsync(pb.h_out.ptr, pb.d_out.ptr, ns * sizeof(FwSegOut), hipMemcpyDeviceToHost, pb.launch_stream));
-    FW_HIP(c, hipEventRecord(pb.evd, pb.launch_stream));
-    pool.ns = ns;
-    pool.inflight = true;
-    pool.t_launch = fwi_now_s();
-    c->cnt.t_host_launch_s += pool.t_launch - tb1;
-    return FW_OK;
-}
-
-int fwi_pool_collect(fw_ctx *c, FwPool &pool, std::vector<FwPoolJob> &finished)
-{
-    if (!pool.inflight) return FW_OK;
-    pool.inflight = false;
-    if (c->P.kind == FW_FZ && c->P.n < c->n_obs_min_eff) {
-        for (FwPoolJob &j : pool.live) {
-            no_power_result(c, j.acc.data(), (int)j.acc.size(), j.out);
-            j.done = true;
-            finished.push_back(std::move(j));
-        }
-        pool.live.clear();
-        return FW_OK;
-    }
-    FwPoolBuf &pb = c->pb[pool.buf];
-    const double tb1 = fwi_now_s();
-    FW_HIP(c, hipEventSynchronize(pb.evd));
-    const double tb2 = fwi_now_s();
-    c->cnt.t_host_wait_s += tb2 - tb1;
-    float ms = 0.0f;
-    FW_HIP(c, hipEventElapsedTime(&ms, pb.ev0, pb.ev1));
-    c->cnt.t_dev_subsets_s += 1e-3 * (double)ms;
-    {  // FW_TRACE_ROUNDS=<file>: one line per pool round (profiling aid; see profiles/README.md)
-        static FILE *tf = [] {
-            const char *e = fw_knob_str(knob::FW_TRACE_ROUNDS);
-            return e ? fopen(e, "w") : (FILE *)nullptr;
-        }();
-        static double t_prev = 0.0;
-        if (tf) {
-            unsigned long long ev_sum = 0;
-            for (size_t q = 0; q < pool.ns; ++q) ev_sum += ((const FwSegOut *)pb.h_out.ptr)[q].evaluated;
-            fprintf(tf, "%zu %zu %.1f %.1f %.1f %llu\n", pool.live.size(), pool.ns, 1e3 * (double)ms, 1e6 * (tb2 - tb1),
-                    t_prev > 0.0 ? 1e6 * (tb2 - t_prev) : 0.0, ev_sum);
-            fflush(tf);
-        }
-        t_prev = tb2;
-    }
-    c->cnt.kernel_launches += 1;
-    c->cnt.subsets_launches += 1;
-    const size_t ns = pool.ns;
-    const FwSegOut *so = (const FwSegOut *)pb.h_out.ptr;
-    // in-order merge (segments of a job are contiguous and in rank order)
-    for (size_t s = 0; s < ns; ++s) {
-        FwPoolJob &j = pool.live[(size_t)pool.seg_job[s]];
-        j.out.evaluated += (int64_t)so[s].evaluated;
-        if (j.done) continue;  // a later (speculative) segment of a job that already stopped
-        if (so[s].stop_rank != FW_RANK_NONE) {
-            j.out.stat = so[s].stop_stat;
-            j.out.pval = so[s].stop_pval;
-            j.out.df = so[s].stop_df;
-            j.out.suff_power = so[s].stop_power;
-            j.out.status = FW_SUBSETS_STOPPED;
-            j.out.num_tests = (int64_t)(so[s].stop_rank + 1);
-            j.best_rank = so[s].stop_rank;
-            j.done = true;
-            if (so[s].stop_df == -2) {  // fz_nz: too few rows with T != 0 and candidate != 0 -> no test at all
-                j.out.df = 0;
-                j.out.num_tests = 0;
-                j.no_zs = true;
-            }
-        } else if (so[s].best_pval >= j.best_p) {
-            j.best_p = so[s].best_pval;
-            j.best_stat = so[s].best_stat;
-            j.best_rank = so[s].best_rank;
-            j.best_df = so[s].best_df;
-        }
-    }
-    size_t w = 0;
-    const uint64_t growth = fw_window_growth(pool.live.size(), pool.launched_ranks);
-    for (size_t ji = 0; ji < pool.live.size(); ++ji) {
-        FwPoolJob &j = pool.live[ji];
-        if (!j.done && j.launched) {
-            j.next += std::min(j.width, j.N - j.next);
-            j.width *= growth;
-            if (j.next >= j.N) {
-                j.out.stat = j.best_stat;
-                j.out.pval = j.best_p < 0.0 ? 0.0 : j.best_p;
-                j.out.df = j.best_df;
-                j.out.suff_power = 1;
-                j.out.status = FW_SUBSETS_ALL_SIG;
-                j.out.num_tests = (int64_t)j.N;
-                j.done = true;
-            }
-        }
-        if (j.done) {
-            finish_job(c, j, pool.want_zs);
-            {  // FW_TRACE_JOBS=<file>: |accepted|, evaluated tests, reference-order tests, status per finished job
-                static FILE *jf = [] {
-                    const char *e = fw_knob_str(knob::FW_TRACE_JOBS);
-                    return e ? fopen(e, "w") : (FILE *)nullptr;
-                }();
-                if (jf) fprintf(jf, "%zu %lld %lld %d\n", j.acc.size(), (long long)j.out.evaluated, (long long)j.out.num_tests, j.out.status);
-            }
-            finished.push_back(std::move(j));
-        } else {
-            if (w != ji) pool.live[w] = std::move(j);
-            ++w;
-        }
-    }
-    pool.live.resize(w);
-    c->cnt.t_host_merge_s += fwi_now_s() - tb2;
-    return FW_OK;
-}
-
-int fwi_pool_round(fw_ctx *c, FwPool &pool, std::vector<FwPoolJob> &finished)
-{
-    int rc = fwi_pool_launch(c, pool);
-    if (rc) return rc;
-    return fwi_pool_collect(c, pool, finished);
-}
-
-int fwi_subsets_dispatch(fw_ctx *c, int64_t m, const FwJob *jobs, const int32_t *acc, int64_t acc_total, FwJobOut *out)
-{
-    (void)acc_total;
-    FwPool pool;
-    pool.want_zs = true;
-    for (int64_t i = 0; i < m; ++i) fwi_pool_add(c, pool, jobs[i].X, jobs[i].Y, acc + jobs[i].acc_off, jobs[i].acc_len, i);
-    std::vector<FwPoolJob> fin;
-    while (!pool.live.empty()) {
-        int rc = fwi_pool_round(c, pool, fin);
-        if (rc) return rc;
-    }
-    for (FwPoolJob &j : fin) out[j.tag] = j.out;
-    return FW_OK;
-}
 
 static double binom_d(int n, int k)
 {

@@ -90,7 +90,7 @@ struct DhParams {
     double alpha;
     int max_k;
     long long max_tests;
-    unsigned long long small_launch, w0_big, w0_small;  // window policy (fw_core.cpp: fwi_pool_add / fw_window_growth)
+    unsigned long long small_launch, w0_big, w0_small;  // window policy (fw_pool_host.h: fw_pool_first_window / fw_pool_growth)
     unsigned int seg_q, seg_min;                        // segment length granularity / minimum (fz 256 / 256, discrete 4 / 8)
     double disc_bytes_per_col;                          // discrete kinds: n * b / 8 (algorithmic bytes per column), else 0
     int elim_full;                                      // elimination-phase jobs start with the full enumeration as their window

@@ -575,7 +575,7 @@ __global__ __launch_bounds__(256) void fz_subsets_slow_kernel(const float *__res
         }
         int pos[FW_MAX_K];
         for (int q = 0; q < FW_MAX_K; ++q) pos[q] = 0;
-        {   // position d = the first c whose block of C(a - 1 - c, s - d - 1) subsets holds the rank (the scan of unrank_host)
+        {   // position d = the first c whose block of C(a - 1 - c, s - d - 1) subsets holds the rank (the scan of fw_pool_unrank)
             int prev = -1;
             for (int d = 0; d < s; ++d) {
                 int c = prev + 1;

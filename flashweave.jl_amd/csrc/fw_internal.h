@@ -17,6 +17,7 @@
 
 #include "../../include/flashweave_amd.h"
 #include "fw_graph.h"  // host-only: FwDirected, FwNetwork, FwHostWorkers, fwi_now_s
+#include "fw_pool_host.h"  // host-only: FwJob, FwJobOut, FwSeg, FwSegOut, FW_RANK_NONE, the job pool's rules
 
 struct FwDevBuf {
     void *ptr = nullptr;
@@ -86,50 +87,10 @@ inline bool fw_is_dev_ptr(const void *q, int device)
     return a.type == hipMemoryTypeDevice && a.device == device;
 }
 
-// Job descriptor for the test_subsets kernels (device layout)
-struct FwJob {
-    int32_t X;        // T
-    int32_t Y;        // candidate
-    int64_t acc_off;  // offset into the flat accepted array
-    int32_t acc_len;  // |accepted|
-    int32_t pad;
-};
-
-// Device-side result of one job (mirrors fw_subsets_result without frac)
 // Conditioning sets of 6 and 7 variables (ABI 6: FW_MAX_K = 7; tests.jl:311-343 has no cap) take general-form kernels through the host job
 // pool; every table kernel, the device rounds and the persistent discrete kernel size their arrays for FW_MAX_K_FAST.
 #define FW_MAX_K_FAST 5
 
-struct FwJobOut {
-    double stat;
-    double pval;
-    int64_t num_tests;  // reference-equivalent count
-    int64_t evaluated;  // tests evaluated by the kernel (speculation included)
-    int32_t df;
-    int32_t suff_power;
-    int32_t status;
-    int32_t n_zs;
-    int32_t zs[FW_MAX_K];
-    int32_t pad[3];
-};
-
-// One segment of a job: ranks [start, end) of the job's subset enumeration (device layout)
-struct FwSeg {
-    int32_t X;
-    int32_t Y;
-    int64_t acc_off;
-    int32_t acc_len;
-    int32_t pad;
-    uint64_t start;
-    uint64_t end;
-    // r06, fz device rounds: the target's LOCAL correlation matrix -- (tm_m x tm_m) Float32 over [T, its level-0 neighbours in ascending id
-    // order], a copy of those entries of the p x p matrix (fw_devhiton.hip: dh_tmat_build_kernel) -- and the sorted ids; 0: none (host pool,
-    // light targets): the kernel gathers from the p x p matrix
-    uint64_t tm, tm_ids;
-    int32_t tm_m, pad1;
-};
-
-#define FW_RANK_NONE (~0ull)
 #define FW_TAB_A 512  // fz / fz_nz: largest |accepted| served by the LDS-table kernel (csrc/fw_fz.hip, FZ_TAB_CAP)
 #ifndef FW_HK_A
 #define FW_HK_A 88    // fz, max_k 4-5: largest |accepted| served by the level-2 table kernel (one (z1, z2) table <= FZ_HK_CAP)
@@ -149,21 +110,6 @@ struct FwNzJob {
     double zscale;      // sqrt(nR - 3) / 2, 0 if nR <= 3          (device-computed)
     double rxy;         // unrounded Float64 pair correlation of (X, Y) over R, statfuns.jl:114 (device-computed)
     double thr[4];      // |r| significance thresholds for this nR (device-computed)
-};
-
-// Device-side result of one segment.  The conditioning sets are recovered on the host from the ranks.
-struct FwSegOut {
-    uint64_t stop_rank;  // first rank in the segment that ends the job (non-significant or max_tests), else FW_RANK_NONE
-    double stop_stat;
-    double stop_pval;
-    uint64_t best_rank;  // last rank attaining the maximum p in the segment (valid when there was no stop)
-    double best_stat;
-    double best_pval;
-    int32_t stop_df;
-    int32_t stop_power;
-    int32_t best_df;
-    int32_t pad;
-    uint64_t evaluated;
 };
 
 // per-pool staging: own stream + events so that two pools can be in flight (host merges one while the GPU runs the other)
@@ -387,25 +333,19 @@ int fwi_mi_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32_
 // algorithmic bytes of the first `evaluated` tests of a job with |accepted| = a (enumeration order: sizes max_k..1)
 double fwi_alg_bytes(const fw_ctx *ctx, int a, int64_t evaluated);
 
-// ---- asynchronous job pool (fw_core.cpp): every round evaluates one window of every live job in ONE launch ----
-struct FwPoolJob {
+// ---- asynchronous job pool (fw_pool.cpp; records and rules: fw_pool_host.h): every round evaluates one window of every live job in ONE launch ----
+struct FwPoolJob : FwJobRun {
     int32_t X = 0, Y = 0;
     int64_t tag = 0;     // caller's id (driver: target slot)
     int32_t aux = 0;     // driver: candidate index
     int32_t epoch = 0;   // driver: accepted-set epoch of the owner when the job was posted (stale jobs are dropped)
     bool hold = false;     // driver: do not launch further windows for now (speculative job past its first window)
     bool launched = false; // set by fwi_pool_launch for the jobs that are part of the pending window
-    bool no_zs = false;    // the returned result has no conditioning set (fz_nz job without a test)
     std::vector<int32_t> acc;
     int64_t acc_dev_off = -1;  // offset (ints) of this job's accepted list in the pool buffer's device arena, -1 = not uploaded
     int64_t gram_off = -1;     // recursive_pcor = 0: offset (doubles) of the job's correlation matrix in ctx->d_arena, valid while
     uint64_t gram_epoch = 0;   // ... gram_epoch == ctx->gram_epoch (the arena was neither reallocated nor reset since)
-    uint64_t N = 0, next = 0, width = 0;
-    double best_p = -1.0, best_stat = 0.0;
-    uint64_t best_rank = 0;
-    int32_t best_df = 0;
-    bool done = false;
-    FwJobOut out{};
+    int32_t rec = -1;          // fz_nz, recursive_pcor = 0: index of the job's record in pool.nzrecs of the pending launch
 };
 struct FwPool {
     std::vector<FwPoolJob> live;
@@ -471,6 +411,6 @@ int fwi_fz_thresholds(fw_ctx *ctx, hipStream_t stream, double *zscale);  // ensu
 int fwi_fz_segments_dev(fw_ctx *ctx, unsigned grid, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns,
                         bool any_big, const unsigned *d_big, hipStream_t stream);
 
-// ---- host driver (fw_hiton.cpp) ----
+// ---- test_subsets batches through the job pool (fw_pool.cpp) ----
 int fwi_subsets_dispatch(fw_ctx *ctx, int64_t m, const FwJob *jobs_host, const int32_t *acc_host, int64_t acc_total,
                          FwJobOut *out_host);

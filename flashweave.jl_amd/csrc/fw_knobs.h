@@ -34,12 +34,12 @@
     X(FW_L0_MFMA, "discrete level 0 on the matrix cores: 0 never, 2 wherever defined; default 1 (mi_nz from 1 024 variables on)")                                         \
     X(FW_MI_ROWK, "row-count form of the discrete test core, 99: popcount form only; default 2")                                                                          \
     X(FW_MI_ROW4, "0: one subset per wavefront step, 2: four per step up to MI4_N samples; default 1 (four up to 2 048 samples)")                                         \
-    /* ---- host job pool (fw_core.cpp, fw_hiton.cpp) ---- */                                                                                                             \
-    X(FW_WINDOW_GROWTH, "2..64: fixed growth factor of a job's evaluation window; default 0 (by launch size, see fw_window_growth)")                                      \
+    /* ---- host job pool (fw_pool.cpp, fw_hiton.cpp) ---- */                                                                                                             \
+    X(FW_WINDOW_GROWTH, "2..64: fixed growth factor of a job's evaluation window; default 0 (by launch size, see fw_pool_growth)")                                        \
     X(FW_SMALL_LAUNCH, "ranks below which a launch counts as small and windows grow x256; default 4194304")                                                               \
     X(FW_W0_BIG, "first window of a job with 64 accepted variables or more; default 16384 (device rounds, fz max_k <= 3: 32768, see dh_make_params)")                     \
     X(FW_W0_SMALL, "first window of a smaller job in the device rounds (positive, fz only); default per kind / max_k, see dh_make_params")                                \
-    X(FW_SEG_TARGET, "workgroups per launch the segment length aims for (positive); default per kind / max_k, see dh_policy and pool_round")                              \
+    X(FW_SEG_TARGET, "workgroups per launch the segment length aims for (positive); default per kind / max_k, see dh_policy / fw_pool_seglen")                            \
     X(FW_SPEC_DEPTH, "candidates the host pool tests ahead per target; default 8")                                                                                        \
     X(FW_SPEC_TARGETS, "... in rounds of at most this many targets; default 512")                                                                                         \
     /* ---- device rounds: windows and look-ahead (dh_make_params, dh_policy in fw_devhiton.hip) ---- */                                                                  \

@@ -6,7 +6,7 @@ tests/test_gpu_fz.py::_check_subsets does (status, num_tests, Zs, stat exact; pv
 
 WHEN THE SCREEN RUNS AT ALL.  The fast loop needs a chunk that lies wholly inside the size-3 enumeration (`ilv`: cend <= C(a, 3)), and the
 screen needs a bound to compare with, i.e. a lane that has ALREADY taken an exact test in the same segment: runs of R >= 2 ranks per lane.
-A chunk is min(segment, 256 R) ranks, R = ceil(len / 256) <= 64; the host (fwi_pool_add / fwi_pool_launch, fw_core.cpp) cuts a job's window
+A chunk is min(segment, 256 R) ranks, R = ceil(len / 256) <= 64; the host (fwi_pool_add / fwi_pool_launch, fw_pool.cpp) cuts a job's window
 (first 256 ranks, 16 384 from 64 accepted variables on; everything that is left afterwards in these small launches) into segments of
     seglen = clamp(ceil256(ranks of the launch / 3072), 256, 8192),
 so (a) alone in a launch, a job has segments of 256 ranks whatever its length: R = 1, one test per lane, and the screen only ever meets a
@@ -34,6 +34,7 @@ import pytest
 import flashweave_jl_amd as fw
 from oracle import oracle as O
 from tests import screen_model as M
+from tests.pool_plan import _job_ranks, _plan
 from tests.util import GOLDEN, rel
 
 pytestmark = pytest.mark.gpu
@@ -42,31 +43,7 @@ f32, f64 = np.float32, np.float64
 N_OBS = 300  # sure range of |stat| at alpha = 0.01: about (0.149, 0.973)
 
 
-# ---- the host's segmenting, restated (fw_core.cpp: fwi_pool_add, fwi_pool_launch, fw_window_growth) ---------------------------------
-def _job_ranks(a, max_tests=10_000_000):
-    return min(math.comb(a, 3) + math.comb(a, 2) + a, max_tests)
-
-
-def _plan(alens, max_tests=10_000_000):
-    """Launches of a batch whose jobs all run to their last rank -> [(seglen, [(job, lo, hi)])]."""
-    N = [_job_ranks(a, max_tests) for a in alens]
-    nxt = [0] * len(alens)
-    width = [16384 if a >= 64 else 256 for a in alens]
-    out = []
-    while True:
-        live = [i for i in range(len(alens)) if nxt[i] < N[i]]
-        if not live:
-            return out
-        wins = [(i, nxt[i], nxt[i] + min(width[i], N[i] - nxt[i])) for i in live]
-        total = sum(h - l for _, l, h in wins)
-        seglen = max(256, min(8192, -(-(total // 3072) // 256) * 256))
-        out.append((seglen, wins))
-        growth = 256 if total < (1 << 22) else (4 if len(live) > 2048 else 16)
-        for i, _, h in wins:
-            nxt[i] = h
-            width[i] *= growth
-
-
+# ---- the host's segmenting: tests/pool_plan.py restates fw_pool_host.h / fw_pool.cpp (tests/test_pool_host_cpu.py holds the two together) ----
 def _screen_segments(alens, max_tests=10_000_000):
     """Segments of the batch that lie wholly inside the size-3 enumeration with runs of R >= 2 ranks per lane -> (count, smallest R, largest R)."""
     n, rs = 0, []
