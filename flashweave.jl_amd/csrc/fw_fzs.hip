@@ -6,8 +6,13 @@
 // from HBM / L2 in ONE pass of 16-byte loads (lane l holds samples 4l .. 4l+3 of every 256-sample row).  r03 rewrite of the r02
 // kernel (two passes of 4-byte loads, 213-244 VGPRs, X and Y re-read for every subset of a job):
 //   * column means and sums of squared deviations (Float64) are computed ONCE per data upload (fzs_colstat_kernel), so a test
-//     needs only the cross products, and  sum (x_a - mu_a)(x_b - mu_b) = sum x_a (x_b - mu_b)  (the dropped term is mu_a times the
-//     rounding residue of a centred sum: < 1e-14 relative) -- one conversion + one FMA per element and pair;
+//     needs only the cross products  sum (x_a - mu_a)(x_b - mu_b), BOTH factors centred -- one conversion and one subtraction per
+//     element, one FMA per element and pair.  (Up to r06 the first factor was left as it is: sum x_a (x_b - mu_b) differs from the
+//     centred sum by mu_a times the rounding residue of sum (x_b - mu_b), which is harmless only while |mu_a| is about sigma_a.  On
+//     columns at 1 000 sigma the statistic was 1.3e-10 off, at 30 000 sigma 1.5e-7, and a variable conditioned on itself or on its
+//     exact copy came out as +-1 with p = 0 instead of NaN -- DESIGN.md section 4.7 has the measurements.)
+//     A sum of squared deviations is accumulated in the same order as a cross product of the form that reads it, so two columns
+//     that hold the same values correlate at exactly 1, as StatsBase's identical sums make them;
 //   * inside a test_subsets job the workgroup keeps the X and Y columns in LDS (n <= 2048: 16 KB) and every wavefront their cross
 //     product for all the subsets it evaluates: a test streams its k conditioning columns only;
 //   * the (k+2) x (k+2) correlation matrix is then conditioned on Z_k, ..., Z_1 (the unrolled recursion of StatsBase._partialcor,
@@ -25,12 +30,15 @@
 #include "fw_unrank.h"
 
 #define FZS_MAXM (FW_MAX_K_FAST + 2)
+#define FZS_ST 3     // doubles per column in FzsDev::st
+#define FZS_SS_LANE 1  // sum of squared deviations, lane l adds samples l, l + 64, ... (the generic loops)
+#define FZS_SS_ROW 2   // lane l adds samples 4l .. 4l+3 of every 256-sample row (the float4 loops); n % 4 != 0: a copy of FZS_SS_LANE
 
 namespace {
 
 struct FzsDev {
     const float *data;  // n x p column-major
-    const double *st;   // per column {mean, sum of squared deviations}
+    const double *st;   // per column FZS_ST doubles: {mean, sum of squared deviations in steps of 64 samples, the same in 16-byte rows}
     int n, p;
     double zscale;      // sqrt(n - 3) / 2, 0 if n <= 3
     long long n_obs_min;
@@ -75,8 +83,9 @@ __device__ __forceinline__ double fzs_uniform(double v)
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-// per column: {mean, sum of squared deviations} in Float64, one wavefront per column (two passes over the column: it is read from
-// L2 the second time).  Once per data upload.
+// per column: {mean, sum of squared deviations (twice)} in Float64, one wavefront per column (the column is read from L2 after the
+// first pass).  Once per data upload.  The sum of squares is formed in both orders the cross products use -- fma(d, d, q) over a
+// lane's samples, then the wave sum -- so that a column and its exact copy give S_ab == S_aa == S_bb to the bit in either form.
 __global__ __launch_bounds__(256) void fzs_colstat_kernel(const float *__restrict__ data, int n, int p, double *__restrict__ st)
 {
     const int col = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -91,9 +100,25 @@ __global__ __launch_bounds__(256) void fzs_colstat_kernel(const float *__restric
         q = fma(d, d, q);
     }
     q = fzs_wave_sum(q);
+    double q4 = q;
+    if ((n & 3) == 0) {  // (uniform)
+        const float4 *c4 = (const float4 *)c;
+        const int n4 = n >> 2;
+        q4 = 0.0;
+        for (int r = lane; r < n4; r += 64) {
+            const float4 x = c4[r];
+            const double dx = (double)x.x - mu, dy = (double)x.y - mu, dz = (double)x.z - mu, dw = (double)x.w - mu;
+            q4 = fma(dx, dx, q4);
+            q4 = fma(dy, dy, q4);
+            q4 = fma(dz, dz, q4);
+            q4 = fma(dw, dw, q4);
+        }
+        q4 = fzs_wave_sum(q4);
+    }
     if (lane == 0) {
-        st[2 * (size_t)col] = mu;
-        st[2 * (size_t)col + 1] = q;
+        st[FZS_ST * (size_t)col] = mu;
+        st[FZS_ST * (size_t)col + FZS_SS_LANE] = q;
+        st[FZS_ST * (size_t)col + FZS_SS_ROW] = q4;
     }
 }
 
@@ -103,7 +128,7 @@ __global__ __launch_bounds__(256) void fzs_colstat_kernel(const float *__restric
 template <int T>
 struct FzsXY {
     const float4 *lx, *ly;  // LDS copies (T > 0)
-    double sxy;             // sum x (y - mu_y)
+    double sxy;             // sum (x - mu_x) (y - mu_y)
     const float *cx, *cy;   // the columns in global memory
     double mux, muy, ssx, ssy;
     int vx, vy;             // the variables
@@ -120,10 +145,11 @@ __device__ __forceinline__ void fzs_load_xy(const FzsDev &P, int X, int Y, FzsXY
     H.vy = Y;
     H.cx = P.data + (size_t)X * P.n;
     H.cy = P.data + (size_t)Y * P.n;
-    H.mux = P.st[2 * (size_t)X];
-    H.ssx = P.st[2 * (size_t)X + 1];
-    H.muy = P.st[2 * (size_t)Y];
-    H.ssy = P.st[2 * (size_t)Y + 1];
+    constexpr int SSO = T > 0 ? FZS_SS_ROW : FZS_SS_LANE;
+    H.mux = P.st[FZS_ST * (size_t)X];
+    H.ssx = P.st[FZS_ST * (size_t)X + SSO];
+    H.muy = P.st[FZS_ST * (size_t)Y];
+    H.ssy = P.st[FZS_ST * (size_t)Y + SSO];
     H.lx = (const float4 *)lds;
     H.ly = (const float4 *)(lds + FZS_LDS_N);
     double s = 0.0;
@@ -131,13 +157,13 @@ __device__ __forceinline__ void fzs_load_xy(const FzsDev &P, int X, int Y, FzsXY
         const int n4 = P.n >> 2;
         for (int q = lane; q < n4; q += 64) {
             const float4 x = H.lx[q], y = H.ly[q];
-            s = fma((double)x.x, (double)y.x - H.muy, s);
-            s = fma((double)x.y, (double)y.y - H.muy, s);
-            s = fma((double)x.z, (double)y.z - H.muy, s);
-            s = fma((double)x.w, (double)y.w - H.muy, s);
+            s = fma((double)x.x - H.mux, (double)y.x - H.muy, s);
+            s = fma((double)x.y - H.mux, (double)y.y - H.muy, s);
+            s = fma((double)x.z - H.mux, (double)y.z - H.muy, s);
+            s = fma((double)x.w - H.mux, (double)y.w - H.muy, s);
         }
     } else {
-        for (int i = lane; i < P.n; i += 64) s = fma((double)H.cx[i], (double)H.cy[i] - H.muy, s);
+        for (int i = lane; i < P.n; i += 64) s = fma((double)H.cx[i] - H.mux, (double)H.cy[i] - H.muy, s);
     }
     H.sxy = fzs_uniform(fzs_wave_sum(s));
 }
@@ -234,10 +260,10 @@ __device__ __forceinline__ void fzs_stream(const FzsDev &P, const FzsXY<T> &H, c
     for (int j = 0; j < K; ++j) {
         const int v = j < k ? zs[j] : zs[0];
         col[j] = P.data + (size_t)v * P.n;
-        mu[j] = P.st[2 * (size_t)v];
-        ss[2 + j] = P.st[2 * (size_t)v + 1];
+        mu[j] = P.st[FZS_ST * (size_t)v];
+        ss[2 + j] = P.st[FZS_ST * (size_t)v + (T > 0 ? FZS_SS_ROW : FZS_SS_LANE)];
     }
-    // cross products S[a][b], a < b, b >= 2:  sum x_a (z_b - mu_b)   (S[0][1] is the job's)
+    // cross products S[a][b], a < b, b >= 2:  sum (x_a - mu_a) (z_b - mu_b)   (S[0][1] is the job's)
     double S[M][M];
 #pragma unroll
     for (int a = 0; a < M; ++a)
@@ -245,18 +271,14 @@ __device__ __forceinline__ void fzs_stream(const FzsDev &P, const FzsXY<T> &H, c
         for (int b = 0; b < M; ++b) S[a][b] = 0.0;
 #define FZS_ACC(xv, yv, zsel)                                                             \
     {                                                                                     \
-        double zr[K > 0 ? K : 1], zd[K > 0 ? K : 1];                                      \
-        _Pragma("unroll") for (int j = 0; j < K; ++j)                                    \
-        {                                                                                 \
-            zr[j] = (double)(zsel(j));                                                    \
-            zd[j] = zr[j] - mu[j];                                                        \
-        }                                                                                 \
-        const double xd = (double)(xv), yd = (double)(yv);                                \
+        double zd[K > 0 ? K : 1];                                                         \
+        _Pragma("unroll") for (int j = 0; j < K; ++j) zd[j] = (double)(zsel(j)) - mu[j]; \
+        const double xd = (double)(xv) - H.mux, yd = (double)(yv) - H.muy;                \
         _Pragma("unroll") for (int j = 0; j < K; ++j) if (j < k)                         \
         {                                                                                 \
             S[0][2 + j] = fma(xd, zd[j], S[0][2 + j]);                                    \
             S[1][2 + j] = fma(yd, zd[j], S[1][2 + j]);                                    \
-            _Pragma("unroll") for (int i = 0; i < K; ++i) if (i < j) S[2 + i][2 + j] = fma(zr[i], zd[j], S[2 + i][2 + j]); \
+            _Pragma("unroll") for (int i = 0; i < K; ++i) if (i < j) S[2 + i][2 + j] = fma(zd[i], zd[j], S[2 + i][2 + j]); \
         }                                                                                 \
     }
     if (T > 0) {
@@ -603,7 +625,7 @@ __global__ __launch_bounds__(256, FZS_SEG_OCC) void fzs_subsets_seg_kernel(FzsDe
 // Every test of a (X, Y | subsets of the accepted list) job conditions a sub-matrix of ONE matrix: the Float64 correlations of
 // {X, Y} u accepted.  Streaming the columns per test (above) computes each of them C(a, k - 1) times over; this kernel computes
 // them once per job (the matrix stays in the launch arena while the job's pool lives) -- one workgroup per job, one wavefront per 4 x 4 tile of pairs (8 columns in 16-byte loads feed
-// 16 sums x 4 samples), the same sum  x_i (x_j - mu_j), i < j in job order (X, Y, accepted positions), as the streamed form, the
+// 16 sums x 4 samples), the same sum  (x_i - mu_i) (x_j - mu_j), i < j in job order (X, Y, accepted positions), as the streamed form, the
 // same DPP wave sums -- and the segment kernel (GRAM) then only gathers and conditions: tests/s go from 3.7e8 (streamed, itself
 // 1.8 x the nominal HBM rate) to the rate of the conditioning arithmetic.  Row-major m x m doubles per job in the launch's arena.
 __global__ __launch_bounds__(256) void fzs_gram_kernel(FzsDev P, const FwNzJob *__restrict__ recs, const int32_t *__restrict__ accflat,
@@ -624,7 +646,7 @@ __global__ __launch_bounds__(256) void fzs_gram_kernel(FzsDev P, const FwNzJob *
         }
         const int tj = ti + rem;
         const float *ci[4], *cj[4];
-        double muj[4], ssi[4], ssj[4];
+        double mui[4], muj[4], ssi[4], ssj[4];
         int idi[4], idj[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -637,9 +659,10 @@ __global__ __launch_bounds__(256) void fzs_gram_kernel(FzsDev P, const FwNzJob *
             idj[q] = vj;
             ci[q] = P.data + (size_t)vi * P.n;
             cj[q] = P.data + (size_t)vj * P.n;
-            ssi[q] = P.st[2 * (size_t)vi + 1];
-            muj[q] = P.st[2 * (size_t)vj];
-            ssj[q] = P.st[2 * (size_t)vj + 1];
+            mui[q] = P.st[FZS_ST * (size_t)vi];
+            ssi[q] = P.st[FZS_ST * (size_t)vi + FZS_SS_ROW];  // (the order of the loop below: a copy of FZS_SS_LANE when n % 4 != 0)
+            muj[q] = P.st[FZS_ST * (size_t)vj];
+            ssj[q] = P.st[FZS_ST * (size_t)vj + FZS_SS_ROW];
         }
         double S[4][4];
 #pragma unroll
@@ -652,7 +675,7 @@ __global__ __launch_bounds__(256) void fzs_gram_kernel(FzsDev P, const FwNzJob *
         _Pragma("unroll") for (int b = 0; b < 4; ++b) d[b] = (double)(YS(b)) - muj[b]; \
         _Pragma("unroll") for (int a = 0; a < 4; ++a)                       \
         {                                                                    \
-            const double xa = (double)(XS(a));                               \
+            const double xa = (double)(XS(a)) - mui[a];                      \
             _Pragma("unroll") for (int b = 0; b < 4; ++b) S[a][b] = fma(xa, d[b], S[a][b]); \
         }                                                                    \
     }
@@ -741,7 +764,7 @@ FzsDev fzs_dev(const fw_ctx *ctx)
 int fzs_ensure_stat(fw_ctx *ctx, hipStream_t st)
 {
     if (ctx->have_fzs_stat) return FW_OK;
-    if (!ctx->d_fzs_stat) FW_HIP(ctx, hipMalloc((void **)&ctx->d_fzs_stat, sizeof(double) * 2 * (size_t)ctx->P.p));
+    if (!ctx->d_fzs_stat) FW_HIP(ctx, hipMalloc((void **)&ctx->d_fzs_stat, sizeof(double) * FZS_ST * (size_t)ctx->P.p));
     hipLaunchKernelGGL(fzs_colstat_kernel, dim3((unsigned)((ctx->P.p + 3) / 4)), dim3(256), 0, st, (const float *)ctx->d_data, ctx->P.n, ctx->P.p,
                        ctx->d_fzs_stat);
     FW_HIP(ctx, hipGetLastError());

@@ -152,7 +152,7 @@ struct fw_ctx {
     int cor_rows_rank = -1, cor_rows_world = 0;  // what the last fw_compute_cor_mat_rows computed: rank / world / rows per rank
     int64_t cor_rows_per_rank = 0;               // (fw_cor_mat_allgather_comm checks its arguments against them)
     double *d_thr = nullptr;  // |r| significance thresholds of the segment kernel (fz_thresholds_kernel)
-    double *d_fzs_stat = nullptr;  // recursive_pcor = 0: per column {mean, sum of squared deviations} in Float64 (fw_fzs.hip)
+    double *d_fzs_stat = nullptr;  // recursive_pcor = 0: per column {mean, sum of squared deviations in both summation orders} in Float64 (fw_fzs.hip, FZS_ST)
     uint64_t gram_epoch = 0;       // recursive_pcor = 0: bumped whenever the job-matrix arena loses its contents (new pool, reallocation, reset)
     bool have_fzs_stat = false;
     int n_pad = 0, p_pad = 0;

@@ -104,8 +104,9 @@ def test_test_subsets_and_network_stream(ctx):
 
 def test_test_subsets_streams_without_a_correlation_matrix():
     # recursive_pcor = 0 needs the DATA only: fw_test_subsets_batch must not ask for a resident Pearson matrix (r02 gated both
-    # entry points on it).  Also the generic form of the kernel: n = 346 is not a multiple of 4, so X and Y are streamed too
-    # (no 16-byte rows, nothing held in registers).
+    # entry points on it).  n = 346 is not a multiple of 4: with FW_FZS_GRAM at its default the jobs take the Gram form, whose matrix
+    # kernel then runs its generic loop (4-byte loads).  The streamed form without 16-byte rows (T = 0) is run by
+    # tests/test_gpu_fzs_edges.py, which switches the knob off at such n.
     raw = np.loadtxt(GOLDEN + "/HMP_SRA_gut_small.tsv", delimiter="\t", skiprows=1, usecols=range(1, 51))
     clr, _, _ = pre.normalize(raw, "fz", prec=32)
     data = np.asfortranarray(clr)
