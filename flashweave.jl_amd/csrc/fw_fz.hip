@@ -491,8 +491,9 @@ __global__ __launch_bounds__(256, HIGHK ? ((TAB || LOCAL) ? FW_HIGHK_OCC : FW_HI
         // routing by list length (workgroup-uniform); HIGHK without the flag word: the generic variant takes every segment
         // (per-job matrices, device rounds of fz_nz: the size-3 table / in-lane pair routes the same way; max_k 4-5 has one variant)
         if (ns_dev && (!LOCAL || (!HIGHK && big_dev)) && (!HIGHK || big_dev) && ((segs[s].acc_len <= (HIGHK ? FZ_HK_A : FZ_TAB_A)) != TAB)) continue;
-        fz_seg_body<HIGHK, LOCAL, TAB>(cor_g, p_g, segs[s], accflat + segs[s].acc_off, false, out + s, max_k, alpha, zscale_g, max_tests, thr_g, recs,
-                                       n_obs_min);
+        // (size-3 table kernel: a segment that stays inside the size-3 table form takes the lean body, see fz_seg3_lean_ok)
+        fz_seg_body<HIGHK, LOCAL, TAB, TAB && !HIGHK && !LOCAL && FW_FZ_LEAN3 != 0>(cor_g, p_g, segs[s], accflat + segs[s].acc_off, false, out + s, max_k, alpha,
+                                                                                     zscale_g, max_tests, thr_g, recs, n_obs_min);
         __syncthreads();  // the LDS state of the body is reused by the next segment
     }
 }

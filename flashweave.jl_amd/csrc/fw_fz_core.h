@@ -685,10 +685,526 @@ __device__ __forceinline__ double fz_l1t_stat(const float *__restrict__ cor, int
 // FZ_L3_CAP: positions (over all sub-blocks of a chunk): 31 KB; with the level-1 table and the list 48 KB -> three workgroups per CU
 #define FZ_L3_DIR 64   // sub-blocks per chunk
 
+// ---- pieces of fz_seg3_lean_body (below): fz_seg_body's own text of the same steps stays as it is -- moving it into these helpers
+// changed the register allocation of the per-job-matrix table kernel (profiles/lean_size3_body.txt) ----
+// (i, j, k + 64 already added) -> the position 64 ranks ahead: row (i, j) holds k = j + 1 .. a - 1, the overflow is carried into the next
+// rows; returns the lowest position index that changed (2: k only, 1: j, 0: i)
+__device__ __forceinline__ int fz_tab3_carry(int a, int &i, int &j, int &k)
+{
+    int chg = 2;
+    while (k > a - 1) {
+        const int over = k - a;
+        if (++j > a - 2) {
+            ++i;
+            j = i + 1;
+            chg = 0;
+        } else if (chg > 1) {
+            chg = 1;
+        }
+        k = j + 1 + over;
+    }
+    return chg;
+}
+
+// the cheap screen's guards and its comparison with the bound scr_T (derivation: "cheap screen" in fz_seg_body); false on every NaN
+__device__ __forceinline__ bool fz_tab3_screen(float c32, const float4 tj, const float4 tk, float rj1, float rk1, const float2 rj2, double A2j,
+                                               float scr_T)
+{
+    const float e1s = c32 - tk.z * tj.z;
+    const float d1s = rk1 * rj1;
+    const float inv1 = __builtin_amdgcn_rcpf(d1s);
+    const float Fs = e1s * inv1;
+    const float dl = fmaf(4.8e-5f, inv1, 7.4e-5f);
+    const float gs = fmaf(-Fs, Fs, 1.0f);
+    const float nDs = fmaf(-tj.x, Fs, tk.x), nEs = fmaf(-tj.y, Fs, tk.y);
+    const float rg = rj2.x * gs;
+    const float Pb = fmaf(-nDs, nDs, rj2.x * rg), Pc = fmaf(-nEs, nEs, rj2.y * rj2.y * gs);
+    const float Nm = fmaf(-nDs, nEs, (float)A2j * rg * rj2.y);
+    const float Nlo = fabsf(Nm) - dl;
+    return d1s > 0.01f && gs > 0.02f && Pb > dl && Pc > dl && Nlo > 0.0f && Nlo * Nlo > scr_T * ((Pb + dl) * (Pc + dl));
+}
+
+// the record of a segment that ends at a stop / that ran to its end
+__device__ __forceinline__ void fz_rec_stop(FwSegOut *out_rec, unsigned long long first, double stop_stat, double stop_p, unsigned long long evaluated)
+{
+    FwSegOut o;
+    o.stop_rank = first;
+    o.stop_stat = stop_stat;
+    o.stop_pval = stop_p;
+    o.best_rank = 0;
+    o.best_stat = 0.0;
+    o.best_pval = -1.0;
+    o.stop_df = 0;
+    o.stop_power = 1;
+    o.best_df = 0;
+    o.pad = 0;
+    o.evaluated = evaluated;
+    *out_rec = o;
+}
+__device__ __forceinline__ void fz_rec_best(FwSegOut *out_rec, unsigned long long best_rank, double best_stat, double best_pval, unsigned long long evaluated)
+{
+    FwSegOut o;
+    o.stop_rank = FW_RANK_NONE;
+    o.stop_stat = 0.0;
+    o.stop_pval = 0.0;
+    o.best_rank = best_rank;
+    o.best_stat = best_stat;
+    o.best_pval = best_pval;
+    o.stop_df = 0;
+    o.stop_power = 1;
+    o.best_df = 0;
+    o.pad = 0;
+    o.evaluated = evaluated;
+    *out_rec = o;
+}
+
+// ---- lean body of the size-3 table kernel: segments that can never leave the size-3 table form ----
+// A segment that lies wholly inside the size-3 enumeration of a list the table takes, holds no cap and gathers with a 32-bit index runs
+// every one of its chunks interleaved, from the table, through the fast test of fz_seg_body.  fz_seg3_lean_body is that segment and nothing
+// else: the same chunks, table entries, lane <-> rank mapping, gather one step ahead, screen, reductions and record -- the same device
+// functions on the same operands in the same order within a test -- but the step every lane passes is a loop of its own that carries
+// only what it reads, the rare wave-iteration in which a lane deviates (an unclean entry, a test not significant for sure or beyond the
+// normal range of p, a stop in front of it, a tie) is evaluated by the general size-3 table test in a block outside that loop, and the
+// prologue holds no state of sizes 1 and 2.  It works in the LDS arrays of the fz_seg_body instance that calls it (FzLean3Lds): LDS does
+// not grow.  -DFW_FZ_LEAN3=0 routes every segment to fz_seg_body (A/B knob; what the tests of the lean body compare against).
+#ifndef FW_FZ_LEAN3
+#define FW_FZ_LEAN3 1
+#endif
+#ifndef FW_CORT_TAB3
+#define FW_CORT_TAB3 1  // the size-3 table kernel gathers the transposed entry (see CORT in fz_seg_body)
+#endif
+struct FzLean3Lds {
+    int *acc;
+    float4 *tab;
+    float *tab_r1;
+    float2 *tab_r2;
+    double *tab_a2;
+    int *blk;
+    unsigned int *cstop, *scrq, *evc;
+    unsigned long long *stop, *br, *best_rank;
+    double *bx, *bps, *best_x, *best_ps, *best_stat;
+};
+
+// workgroup-uniform, decided from the segment and the kernel arguments before any LDS is written
+__device__ __forceinline__ bool fz_seg3_lean_ok(const FwSeg &seg, int p_g, int max_k, long long max_tests)
+{
+#if !FW_FZ_LEAN3 || !FW_FZ_FASTLOOP || !FW_FZ_INTERLEAVE
+    return false;
+#endif
+    const int a = seg.acc_len;
+    if (max_k < 3 || a < 3 || a > FZ_TAB_A) return false;
+    if (seg.end > (unsigned long long)fw_binom32(a, 3)) return false;                // every chunk interleaved, with its table
+    if (max_tests > 0 && seg.end >= (unsigned long long)max_tests) return false;    // no chunk holds the cap
+    return (seg.tm != 0ull ? seg.tm_m : p_g) <= 46000;                               // p^2 < 2^31: 32-bit element index
+}
+
+__device__ __forceinline__ void fz_seg3_lean_body(const float *__restrict__ cor_g, int p_g, const FwSeg seg /* workgroup-uniform */,
+                                                  const int32_t *__restrict__ gacc, FwSegOut *out_rec, double alpha, double zscale,
+                                                  const double *__restrict__ thr, const FzLean3Lds L)
+{
+    const int a = seg.acc_len;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < a; i += 256) L.acc[i] = gacc[i];
+    const float *cor = cor_g;
+    int p = p_g, X = seg.X, Y = seg.Y;
+    if (seg.tm != 0ull) {  // the target's local matrix: ids become indices in [T, its neighbours ascending] (see fz_seg_body)
+        int32_t *s_ids = (int32_t *)L.tab;
+        const int32_t *ids = (const int32_t *)seg.tm_ids;
+        const int nid = seg.tm_m - 1;
+        for (int i = tid; i < nid; i += 256) s_ids[i] = ids[i];
+        __syncthreads();
+        auto local_of = [&](int v) -> int {
+            if (v == seg.X) return 0;
+            int lo = 0, hi = nid - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (s_ids[mid] < v)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            if (nid <= 0 || s_ids[lo] != v) __builtin_trap();
+            return lo + 1;
+        };
+        for (int i = tid; i < a; i += 256) L.acc[i] = local_of(L.acc[i]);
+        X = 0;
+        Y = local_of(seg.Y);
+        cor = cor_g + (((long long)seg.tm - (long long)(unsigned long long)cor_g) >> 2);
+        p = seg.tm_m;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        *L.best_x = FZ_X_NONE;
+        *L.best_ps = 0.0;
+        *L.best_stat = 0.0;
+        *L.best_rank = 0;
+        *L.cstop = 0xffffffffu;
+        *L.scrq = 0x7f7fffffu;
+    }
+    // the squared thresholds of the screened test (thr[5..7], see fz_seg_body); the thresholds on |r| itself are read where the block
+    // outside the loop needs them
+    const double h2_pos = thr[5], h2_neg = thr[6], s2 = thr[7];
+    const float scr_h2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)(h2_pos > h2_neg ? h2_pos : h2_neg) * 1.00001f)));
+    __syncthreads();
+#define LCORV(u, v) cor[(size_t)(u) * p + (v)]
+#if FW_CORT_TAB3 || defined(FW_CORT_TRANSPOSED)
+#define LCORT(u, v) LCORV(v, u)
+#else
+#define LCORT(u, v) LCORV(u, v)
+#endif
+#if FW_CORT_TAB3
+#define LCORT32(u, v) cor[(unsigned int)(v) * (unsigned int)p + (unsigned int)(u)]
+#else
+#define LCORT32(u, v) cor[(unsigned int)(u) * (unsigned int)p + (unsigned int)(v)]
+#endif
+    const float cXY = LCORV(X, Y);
+    const unsigned long long NONE = FW_RANK_NONE;
+    const unsigned long long len = seg.end - seg.start;
+    const int R = (int)((len + 255) / 256 < FW_RUN_MAX3 ? (len + 255) / 256 : FW_RUN_MAX3);
+    unsigned long long evaluated = 0;
+
+    unsigned long long cnext = seg.start;
+    for (unsigned long long cbase = seg.start; cbase < seg.end; cbase = cnext) {
+        unsigned long long cend = cbase + 256ull * R;
+        cend = cend < seg.end ? cend : seg.end;
+        int Rc = R, tb_i0, tb_E;
+        for (;;) {  // the z1-blocks [i0, i1] this chunk touches; a chunk whose blocks do not fit the table is halved
+            if (tid == 0 || tid == 64) {
+                int q[FW_MAX_K_FAST];
+                fw_unrank_comb32((uint32_t)(tid == 0 ? cbase : cend - 1ull), a, 3, q);
+                L.blk[tid == 0 ? 0 : 1] = q[0];
+            }
+            __syncthreads();
+            const int i0 = L.blk[0], i1 = L.blk[1];
+            tb_E = fz_tab_off(i1 + 1, i0, a);
+            tb_i0 = i0;
+            if (tb_E <= FZ_TAB_CAP) break;
+            if (Rc <= FW_RUN_MAX) __builtin_trap();
+            __syncthreads();
+            Rc = (Rc + 1) / 2;
+            cend = cbase + 256ull * Rc;
+        }
+        cnext = cend;
+        // interleaved: wavefront w owns the 64 Rc ranks behind cbase + w 64 Rc, lane l every 64th of them (ranks relative to the chunk)
+        const unsigned int clen = (unsigned int)(cend - cbase);
+        const unsigned int r0rel = (unsigned int)wave * 64u * (unsigned int)Rc + (unsigned int)lane;
+        unsigned int r1rel = (unsigned int)(wave + 1) * 64u * (unsigned int)Rc;
+        r1rel = r1rel < clen ? r1rel : clen;
+        for (int e = tid; e < tb_E; e += 256) {  // the table (see FZ_TAB_A): the entries of fz_seg_body
+            int i = tb_i0, rem = e;
+            while (rem >= a - 1 - i) {
+                rem -= a - 1 - i;
+                ++i;
+            }
+            const int z1 = L.acc[i], zv = L.acc[i + 1 + rem];
+            const float cXz1 = LCORV(X, z1), cYz1 = LCORV(Y, z1), cvz1 = LCORT(zv, z1);
+            const TV A1 = pc_l1(cXY, cXz1, cYz1);
+            const TV LX = pc_l1(LCORV(X, zv), cXz1, cvz1);
+            const TV LY = pc_l1(LCORV(Y, zv), cYz1, cvz1);
+            const double a2 = pc_l2(A1, LX, LY);
+            L.tab_a2[e] = a2;
+            const bool clean = LX.v == LX.v && LY.v == LY.v && a2 == a2;
+            const float fx = (float)LX.v, fy = (float)LY.v;
+            L.tab_r1[e] = sqrtf(1.0f - cvz1 * cvz1);
+            L.tab_r2[e] = make_float2(sqrtf(1.0f - fx * fx), sqrtf(1.0f - fy * fy));
+            L.tab[e] = make_float4((float)LX.v, (float)LY.v, cvz1,
+                                   __int_as_float(zv | (LX.f32 ? (1 << 30) : 0) | (LY.f32 ? (1 << 29) : 0) | (clean ? (1 << 28) : 0)));
+        }
+        __syncthreads();
+        // lane-local results (fz_seg_body's, ranks relative to the chunk)
+        unsigned int my_stop_rel = 0xffffffffu, my_brel = 0, my_done = 0;
+        double stop_stat = 0.0, stop_p = 0.0;
+        double my_bx = FZ_X_NONE, my_bps = 0.0, my_bev = 0.0, my_bxb = 1.0, my_bxc = 1.0;
+        if (r0rel < r1rel) {
+            int pos[FW_MAX_K_FAST];
+#pragma unroll
+            for (int q = 0; q < FW_MAX_K_FAST; ++q) pos[q] = 0;
+            fw_unrank_comb32((uint32_t)cbase + r0rel, a, 3, pos);
+            int pi = pos[0], pj = pos[1], pk = pos[2];
+            int boff = fz_tab_off(pi, tb_i0, a) - pi - 1;
+            unsigned int rrel = r0rel;
+            // the matrix entry of the first test; every later one is fetched during the test in front of it
+            float pf_c32 = LCORT32(__float_as_int(L.tab[boff + pk].w) & FZ_TAB_ZMASK, __float_as_int(L.tab[boff + pj].w) & FZ_TAB_ZMASK);
+            for (;;) {
+                // what the iteration that leaves the inner loop hands to the block behind it
+                float4 tj, tk;
+                float rj1, rk1, c32, F1f;
+                float2 rj2;
+                double A2j, dF, f_ev, f_xb, f_xc;
+                bool f1ok, e_clean, f_nostop, hasN, fin;
+                int ni, nj, nk, nboff;
+                for (;;) {  // ---- the step every lane passes ----
+                    ++my_done;
+                    const int ej = boff + pj, ek = boff + pk;
+                    tj = L.tab[ej];
+                    rj1 = L.tab_r1[ej];
+                    rj2 = L.tab_r2[ej];
+                    A2j = L.tab_a2[ej];
+                    tk = L.tab[ek];
+                    rk1 = L.tab_r1[ek];
+                    const int fj = __float_as_int(tj.w), fk = __float_as_int(tk.w);
+                    c32 = pf_c32;
+                    // the next test of this lane (64 ranks ahead): its position, and its matrix entry on the way while this one is evaluated
+                    hasN = rrel + 64u < r1rel;
+                    ni = pi;
+                    nj = pj;
+                    nk = pk + (hasN ? 64 : 0);
+                    const int nchg = fz_tab3_carry(a, ni, nj, nk);
+                    nboff = boff;
+                    if (nchg <= 0) nboff = fz_tab_off(ni, tb_i0, a) - ni - 1;
+                    const int nfj = __float_as_int(L.tab[nboff + nj].w), nfk = __float_as_int(L.tab[nboff + nk].w);
+                    if (hasN) pf_c32 = LCORT32(nfk & FZ_TAB_ZMASK, nfj & FZ_TAB_ZMASK);
+                    f_nostop = !(__hip_atomic_load(L.cstop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < rrel);
+                    e_clean = (((fj & fk) >> 28) & 7) == 7;
+                    fin = false;
+#if FW_FZ_SCREEN
+                    {   // the cheap screen: bounds and guards derived in fz_seg_body
+                        const unsigned int sq_bits = __hip_atomic_load(L.scrq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (sq_bits != 0x7f7fffffu) {
+                            const float scr_T = fmaxf(__uint_as_float(sq_bits), scr_h2) * 1.0002f;
+                            const bool s_ok = e_clean && fz_tab3_screen(c32, tj, tk, rj1, rk1, rj2, A2j, scr_T) && f_nostop;
+                            if (__all(s_ok)) {
+                                if (!hasN) {
+                                    fin = true;
+                                    break;
+                                }
+                                pi = ni;
+                                pj = nj;
+                                pk = nk;
+                                boff = nboff;
+                                rrel += 64u;
+                                continue;
+                            }
+                        }
+                    }
+#endif
+                    F1f = pc_l1_rf(c32, tk.z, tj.z, rk1, rj1, f1ok);
+                    const double F1v = (double)F1f;
+                    dF = fz_sqrt_unit(1.0 - F1v * F1v);
+                    const double D2 = pc_l2_all32_d1_nn(tk.x, tj.x, F1f, (double)rj2.x, dF);
+                    const double E2 = pc_l2_all32_d1_nn(tk.y, tj.y, F1f, (double)rj2.y, dF);
+                    f_ev = round5_f64_nn(A2j - D2 * E2);
+                    f_xb = 1.0 - D2 * D2;
+                    f_xc = 1.0 - E2 * E2;
+                    const double f_m2 = f_xb * f_xc, f_e2 = f_ev * f_ev;
+                    const bool f_sure = f_e2 > (f_ev < 0.0 ? h2_neg : h2_pos) * f_m2 && f_e2 < s2 * f_m2;
+                    const double f_lhs = f_e2 * (my_bxb * my_bxc), f_rhs = (my_bev * my_bev) * f_m2;
+                    const bool f_take = my_bx > FZ_X_SUB || f_lhs < f_rhs * (1.0 - 1e-11);
+                    const bool f_tie = !f_take && f_lhs <= f_rhs * (1.0 + 1e-11);
+                    if (!__all(e_clean && f1ok && f_sure && f_nostop && !f_tie)) break;  // a lane deviates: the block below
+                    if (f_take) {
+                        my_bx = FZ_X_LAZY;
+                        my_bps = 0.0;
+                        my_brel = rrel;
+                        my_bev = f_ev;
+                        my_bxb = f_xb;
+                        my_bxc = f_xc;
+#if FW_FZ_SCREEN
+                        (void)__hip_atomic_fetch_min(L.scrq, __float_as_uint(((float)f_e2 / ((float)f_xb * (float)f_xc)) * 1.00001f), __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+#endif
+                    }
+                    if (!hasN) {
+                        fin = true;
+                        break;
+                    }
+                    pi = ni;
+                    pj = nj;
+                    pk = nk;
+                    boff = nboff;
+                    rrel += 64u;
+                }
+                if (fin) break;
+                // ---- a lane of this wave-iteration deviates: the general size-3 table test of fz_seg_body with its stop and maximum-p
+                // tail, on the values the iteration has already taken (nothing of it has been committed) ----
+                double stat = 0.0;
+                const bool screened = __all(e_clean && f1ok);  // no Float64 literal and no NaN among the inputs: (f_ev, f_xb, f_xc) stand
+                if (!screened) {
+                    const int fj = __float_as_int(tj.w), fk = __float_as_int(tk.w);
+                    const TV F1 = pc_l1_r(c32, tk.z, tj.z, rk1, rj1);
+                    const TV D1{(double)tk.x, ((fk >> 30) & 1) != 0}, Bj{(double)tj.x, ((fj >> 30) & 1) != 0};
+                    const TV E1{(double)tk.y, ((fk >> 29) & 1) != 0}, Cj{(double)tj.y, ((fj >> 29) & 1) != 0};
+                    const double D2 = pc_l2_d2(D1, Bj, F1, dF);
+                    const double E2 = pc_l2_d2(E1, Cj, F1, dF);
+                    stat = pc_l3(A2j, D2, E2);
+                }
+                double e2, m2 = 1.0;
+                bool sure = false;
+                if (screened) {
+                    m2 = f_xb * f_xc;
+                    e2 = f_ev * f_ev;
+                    sure = e2 > (f_ev < 0.0 ? h2_neg : h2_pos) * m2 && e2 < s2 * m2;
+                    if (!sure) stat = fz_l3_finish(f_ev, f_xb, f_xc);
+                } else {
+                    e2 = stat * stat;
+                }
+                const double av = fabs(stat);
+                if (!sure) {
+                    const bool negr = stat < 0.0;
+                    bool sig;
+                    if (av > (negr ? thr[3] : thr[1]))
+                        sig = true;
+                    else if (av < (negr ? thr[2] : thr[0]))
+                        sig = false;
+                    else
+                        sig = fz_pval_slow(stat, zscale) < alpha;  // inside the guard band (or NaN): exact
+                    if (!sig) {
+                        my_stop_rel = rrel;
+                        stop_stat = stat;
+                        stop_p = fz_pval_slow(stat, zscale);
+                        (void)__hip_atomic_fetch_min(L.cstop, rrel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        break;
+                    }
+                }
+                if (__hip_atomic_load(L.cstop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < rrel) break;
+                // tests.jl:338 `pval >= lowest.pval`: the three-way decision of fz_seg_body on the squares
+                bool exact = false, lazy_take = false;
+                if (sure || av < thr[4]) {
+                    if (my_bx == FZ_X_NONE || my_bx > FZ_X_SUB) {
+                        lazy_take = true;
+                    } else {
+                        const double lhs = e2 * (my_bxb * my_bxc), rhs = (my_bev * my_bev) * m2;
+                        if (lhs < rhs * (1.0 - 1e-11))
+                            lazy_take = true;
+                        else
+                            exact = lhs <= rhs * (1.0 + 1e-11);
+                    }
+                } else {
+                    exact = true;
+                }
+                if (lazy_take) {
+                    my_bx = FZ_X_LAZY;
+                    my_bps = 0.0;
+                    my_brel = rrel;
+                    my_bev = sure ? f_ev : stat;
+                    my_bxb = sure ? f_xb : 1.0;
+                    my_bxc = sure ? f_xc : 1.0;
+                }
+                if (exact) {
+                    if (sure) stat = fz_l3_finish(f_ev, f_xb, f_xc);
+                    if (my_bx == FZ_X_LAZY) {
+                        if (my_bxb != 1.0 || my_bxc != 1.0) {
+                            my_bev = fz_l3_finish(my_bev, my_bxb, my_bxc);
+                            my_bxb = my_bxc = 1.0;
+                        }
+                        my_bx = fz_xkey_slow(my_bev, zscale);
+                    }
+                    const double xz = fz_xkey_slow(stat, zscale);
+                    bool take;
+                    double ps = 0.0;
+                    if (xz > FZ_X_SUB) {
+                        ps = fz_pval_slow(stat, zscale);  // exact (possibly subnormal / zero) p
+                        take = (my_bx == FZ_X_NONE) || (my_bx > FZ_X_SUB && ps >= my_bps);
+                    } else {
+                        take = (my_bx == FZ_X_NONE) || (my_bx > FZ_X_SUB) || (xz <= my_bx);
+                    }
+                    if (take) {
+                        my_bx = xz;
+                        my_bps = ps;
+                        my_brel = rrel;
+                        my_bev = stat;
+                        my_bxb = my_bxc = 1.0;
+                    }
+                }
+                if (!hasN) break;
+                pi = ni;
+                pj = nj;
+                pk = nk;
+                boff = nboff;
+                rrel += 64u;
+            }
+        }
+        // ---- end of the chunk: fz_seg_body's reductions ----
+        if (my_bx != FZ_X_NONE && (my_bxb != 1.0 || my_bxc != 1.0)) my_bev = fz_l3_finish(my_bev, my_bxb, my_bxc);
+        const double my_bstat = my_bev;
+        if (my_bx == FZ_X_LAZY) my_bx = fz_xkey_slow(my_bstat, zscale);
+        const unsigned long long my_stop = my_stop_rel == 0xffffffffu ? NONE : cbase + my_stop_rel, my_br = my_bx == FZ_X_NONE ? 0ull : cbase + my_brel;
+        unsigned long long ws = my_stop;
+        if (!FW_FZ_CHEAPRED || __any(my_stop != NONE)) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long t = __shfl_xor(ws, o);
+                ws = t < ws ? t : ws;
+            }
+        }
+        double bx = (my_bx == FZ_X_NONE) ? FZ_X_NONE : (my_bx > FZ_X_SUB ? FZ_X_SUBKEY : my_bx);
+        double bps = my_bps;
+        unsigned long long br = my_br;
+        bool reduced = false;
+        if (FW_FZ_CHEAPRED) {
+            double mn = bx;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mn = __builtin_fmin(mn, __shfl_xor(mn, o));
+            const unsigned long long eq = __ballot(bx == mn);
+            if (mn == FZ_X_NONE) {
+                reduced = true;
+            } else if (mn != FZ_X_SUBKEY && __popcll(eq) == 1) {
+                const int src = __ffsll((long long)eq) - 1;
+                bx = mn;
+                bps = __shfl(bps, src);
+                br = __shfl(br, src);
+                reduced = true;
+            }
+        }
+        if (!reduced) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ox = __shfl_xor(bx, o), ops = __shfl_xor(bps, o);
+                const unsigned long long orr = __shfl_xor(br, o);
+                if (fz_key_better(ox, ops, orr, bx, bps, br)) {
+                    bx = ox;
+                    bps = ops;
+                    br = orr;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) my_done += __shfl_xor(my_done, o);
+        if (lane == 0) {
+            L.evc[wave] = my_done;
+            L.stop[wave] = ws;
+            L.bx[wave] = bx;
+            L.bps[wave] = bps;
+            L.br[wave] = br;
+        }
+        __syncthreads();
+        unsigned long long first = L.stop[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) first = L.stop[w] < first ? L.stop[w] : first;
+        evaluated += (unsigned long long)(L.evc[0] + L.evc[1] + L.evc[2] + L.evc[3]);
+        if (first != NONE) {
+            if (my_stop == first) fz_rec_stop(out_rec, first, stop_stat, stop_p, evaluated);
+            return;
+        }
+        double cbx = L.bx[0], cbps = L.bps[0];
+        unsigned long long cbr = L.br[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (fz_key_better(L.bx[w], L.bps[w], L.br[w], cbx, cbps, cbr)) {
+                cbx = L.bx[w];
+                cbps = L.bps[w];
+                cbr = L.br[w];
+            }
+        if (my_bx != FZ_X_NONE && my_br == cbr && cbx != FZ_X_NONE &&
+            (*L.best_x == FZ_X_NONE || !fz_key_better(*L.best_x, *L.best_ps, 0ull, cbx, cbps, 1ull))) {
+            *L.best_x = cbx;
+            *L.best_ps = cbps;
+            *L.best_stat = my_bstat;
+            *L.best_rank = my_br;
+        }
+        __syncthreads();
+    }
+#undef LCORV
+#undef LCORT
+#undef LCORT32
+    if (tid == 0) fz_rec_best(out_rec, *L.best_rank, *L.best_stat, (*L.best_x == FZ_X_NONE) ? -1.0 : fz_pval_slow(*L.best_stat, zscale), evaluated);
+}
+
 // HIGHK: subsets of size 4-5 possible; LOCAL: per-job matrices (fz_nz); TAB: size-3 subsets through the LDS table
 // (the host routes only segments of jobs with |accepted| <= FZ_TAB_A to a TAB launch); HIGHK && TAB: subsets of 4 and 5
 // variables through the level-2 tables above (jobs with |accepted| <= FZ_HK_A), sizes <= 3 through the in-lane forms
-template <bool HIGHK, bool LOCAL, bool TAB>
+// LEAN (size-3 table kernel only): a segment that fz_seg3_lean_ok admits runs fz_seg3_lean_body in this instance's LDS arrays
+template <bool HIGHK, bool LOCAL, bool TAB, bool LEAN = false>
 __device__ __forceinline__ void fz_seg_body(const float *__restrict__ cor_g, int p_g, const FwSeg seg /* workgroup-uniform */,
                                             const int32_t *__restrict__ gacc /* the job's accepted list */,
                                             const bool remote_acc /* list written through by another workgroup: sc1 loads */,
@@ -755,6 +1271,14 @@ __device__ __forceinline__ void fz_seg_body(const float *__restrict__ cor_g, int
     __shared__ double s_tab_a2[TAB3 ? FZ_TAB_CAP : 1]; // rho(X, Y | z1, v)
     __shared__ int s_blk[2];
 
+    if constexpr (LEAN && TAB3 && !LOCAL) {
+        if (!remote_acc && fz_seg3_lean_ok(seg, p_g, max_k, max_tests)) {  // workgroup-uniform
+            const FzLean3Lds L{s_acc, s_tab, s_tab_r1, s_tab_r2, s_tab_a2, s_blk, &s_cstop, &s_scrq, s_evc, s_stop, s_br, &s_best_rank,
+                               s_bx,  s_bps, &s_best_x, &s_best_ps, &s_best_stat};
+            fz_seg3_lean_body(cor_g, p_g, seg, gacc, out_rec, alpha, zscale_g, thr_g, L);
+            return;
+        }
+    }
 #ifdef FW_FZ_FASTDBG
     const unsigned long long dbg_t0 = __builtin_amdgcn_s_memtime();
     unsigned long long dbg_t1 = 0, dbg_tab = 0, dbg_loop = 0, dbg_red = 0;
