@@ -58,6 +58,63 @@ int fw_pin_reserve(fw_ctx *ctx, FwPinned &b, size_t bytes)
     return FW_OK;
 }
 
+int fwi_l0_handover(fw_ctx *ctx, const int32_t *oi, const int32_t *oj, const double *stat64, const float *stat32, const double *op, size_t k,
+                    std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat, std::vector<double> &pval, FwL0Dev *dev)
+{
+    pi.assign(dev ? 0 : k, 0);
+    pj.assign(pi.size(), 0);
+    stat.assign(pi.size(), 0.0);
+    pval.assign(pi.size(), 0.0);
+    if (dev) {  // results stay on the device for fwi_bh_csr_device
+        *dev = FwL0Dev{oi, oj, stat64, stat32, op, k};
+        return FW_OK;
+    }
+    if (k == 0) return FW_OK;
+    std::vector<float> rr(stat32 ? k : 0);
+    FW_HIP(ctx, hipMemcpy(pi.data(), oi, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FW_HIP(ctx, hipMemcpy(pj.data(), oj, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    FW_HIP(ctx, stat32 ? hipMemcpy(rr.data(), stat32, k * sizeof(float), hipMemcpyDeviceToHost)
+                       : hipMemcpy(stat.data(), stat64, k * sizeof(double), hipMemcpyDeviceToHost));
+    FW_HIP(ctx, hipMemcpy(pval.data(), op, k * sizeof(double), hipMemcpyDeviceToHost));
+    if (stat32) std::copy(rr.begin(), rr.end(), stat.begin());
+    return FW_OK;
+}
+
+int fwi_batch_upload(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff, const int32_t *zflat, FwBatch &b)
+{
+    const int64_t nz = zoff[m];
+    int rc;
+    if ((rc = fw_dev_reserve(ctx, ctx->d_jobs, (size_t)m * 2 * sizeof(int32_t) + (size_t)(m + 1) * sizeof(int64_t)))) return rc;
+    if ((rc = fw_dev_reserve(ctx, ctx->d_acc, (size_t)(nz > 0 ? nz : 1) * sizeof(int32_t)))) return rc;
+    if ((rc = fw_dev_reserve(ctx, ctx->d_out, (size_t)m * sizeof(fw_test_result)))) return rc;
+    b.dz = (long long *)ctx->d_jobs.ptr;
+    b.dX = (int32_t *)(b.dz + m + 1);
+    b.dY = b.dX + m;
+    b.dzflat = (const int32_t *)ctx->d_acc.ptr;
+    b.dout = (fw_test_result *)ctx->d_out.ptr;
+    FW_HIP(ctx, hipMemcpyAsync(b.dz, zoff, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    FW_HIP(ctx, hipMemcpyAsync(b.dX, X, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    FW_HIP(ctx, hipMemcpyAsync(b.dY, Y, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (nz > 0) FW_HIP(ctx, hipMemcpyAsync(ctx->d_acc.ptr, zflat, (size_t)nz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    b.kmax = 0;
+    for (int64_t t = 0; t < m; ++t) b.kmax = std::max<int>(b.kmax, (int)(zoff[t + 1] - zoff[t]));
+    return FW_OK;
+}
+
+int fwi_batch_finish(fw_ctx *ctx, int64_t m, fw_test_result *out)
+{
+    FW_HIP(ctx, hipGetLastError());
+    FW_HIP(ctx, hipMemcpyAsync(out, ctx->d_out.ptr, (size_t)m * sizeof(fw_test_result), hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cnt.kernel_launches += 1;
+    return FW_OK;
+}
+
+void fw_fill_no_power(fw_test_result *out, int64_t m)
+{
+    for (int64_t t = 0; t < m; ++t) out[t] = fw_test_result{0.0, 1.0, 0, 0};
+}
+
 extern "C" {
 
 int fw_abi_version(void) { return FW_ABI_VERSION; }
@@ -786,7 +843,7 @@ int fw_test_batch(fw_ctx *c, int64_t m, const int32_t *X, const int32_t *Y, cons
         // the matrix path (level 0 computes the matrix anyway)
         if (!c->have_data) return fw_fail(c, FW_ERR_STATE, "fw_test_batch: no data uploaded");
         if ((int64_t)c->P.n < c->n_obs_min_eff) {
-            for (int64_t t = 0; t < m; ++t) out[t] = fw_test_result{0.0, 1.0, 0, 0};
+            fw_fill_no_power(out, m);
             return FW_OK;
         }
         std::vector<int64_t> iu, ic;
@@ -828,7 +885,7 @@ int fw_test_batch(fw_ctx *c, int64_t m, const int32_t *X, const int32_t *Y, cons
     if (!c->have_data) return fw_fail(c, FW_ERR_STATE, "fw_test_batch: no data uploaded");
     if (c->P.kind == FW_FZ_NZ) {
         if ((int64_t)c->P.n < c->n_obs_min_eff) {  // tests.jl:11 / :254 on the full row count
-            for (int64_t t = 0; t < m; ++t) out[t] = fw_test_result{0.0, 1.0, 0, 0};
+            fw_fill_no_power(out, m);
             return FW_OK;
         }
         return fwi_fznz_test_batch(c, m, X, Y, zoff, zflat, out);

@@ -667,12 +667,23 @@ __global__ __launch_bounds__(256) void fz_subsets_slow_kernel(const float *__res
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
-static int fz_ensure_thresholds(fw_ctx *ctx, hipStream_t stream);
-
 static double fz_zscale(const fw_ctx *ctx)
 {
     const long long sf = (long long)ctx->P.n - 3;  // len_z = 0 always (tests.jl:156,256)
     return sf > 0 ? std::sqrt((double)sf) / 2.0 : 0.0;
+}
+
+static int fz_ensure_thresholds(fw_ctx *ctx, hipStream_t stream)
+{
+    if (!ctx->d_thr) {
+        const int flags = fw_knob_int(knob::FW_FZ_DBG, 0);
+        FW_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(fz_dbg_flags), &flags, sizeof(int)));
+        FW_HIP(ctx, hipMalloc((void **)&ctx->d_thr, 12 * sizeof(double)));
+        hipLaunchKernelGGL(fz_thresholds_kernel, dim3(1), dim3(64), 0, stream, ctx->P.alpha, fz_zscale(ctx), ctx->d_thr);
+        FW_HIP(ctx, hipGetLastError());
+        FW_HIP(ctx, hipStreamSynchronize(stream));  // another stream may use it next
+    }
+    return FW_OK;
 }
 
 int fwi_fz_compute_cor(fw_ctx *ctx)
@@ -736,26 +747,20 @@ int fwi_fz_compute_cor_rows(fw_ctx *ctx, int rank, int world, int64_t *row0, int
 int fwi_fz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                   std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev)
 {
-    if (dev) *dev = FwL0Dev{};
     const int p = ctx->P.p;
     const long long npairs = (long long)p * (p - 1) / 2;
     if (ctx->P.n < ctx->n_obs_min_eff) {  // tests.jl:11 -> every test lacks power -> all NaN
-        pi.clear();
-        pj.clear();
-        stat.clear();
-        pval.clear();
         *m_reliable = 0;
-        return FW_OK;
+        return fwi_l0_handover(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0, pi, pj, stat, pval, dev);
     }
-    {
-        int rc0 = fz_ensure_thresholds(ctx, ctx->stream);
-        if (rc0) return rc0;
-    }
-    unsigned long long cap = (unsigned long long)std::min<long long>(npairs, 4ll << 20);
-    if (cap < ctx->l0_cap_hint) cap = ctx->l0_cap_hint;  // a repeated call does not overflow (and re-run the kernel) again
-    if (cap == 0) cap = 1;
-    FzL0Counters h{};
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    if (int rc0 = fz_ensure_thresholds(ctx, ctx->stream)) return rc0;
+    FzL0Counters h1{}, h{};
+    int32_t *oi = nullptr, *oj = nullptr;
+    float *orr = nullptr;
+    double *op = nullptr;
+    bool centred = false;
+    // two stages: the screen counts into n.first; the exact test of the screened pairs, into a buffer as large, into n.second
+    const int rc = fwi_l0_attempts(ctx, npairs, 4ll << 20, "fz level-0: compaction buffer", [&](unsigned long long cap, FwL0Counts &n) -> int {
         int rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp0, 2 * sizeof(FzL0Counters)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, cap * (2 * sizeof(int32_t) + sizeof(float))))) return rc;
@@ -763,22 +768,23 @@ int fwi_fz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
         if ((rc = fw_dev_reserve(ctx, ctx->d_jobs, cap * (2 * sizeof(int32_t) + sizeof(float))))) return rc;
         FW_HIP(ctx, hipMemsetAsync(ctx->d_tmp0.ptr, 0, 2 * sizeof(FzL0Counters), ctx->stream));
         FzL0Counters *d_c1 = (FzL0Counters *)ctx->d_tmp0.ptr, *d_c2 = d_c1 + 1;
-        int32_t *oi = (int32_t *)ctx->d_tmp1.ptr;
-        int32_t *oj = oi + cap;
-        float *orr = (float *)(oj + cap);
-        double *op = (double *)ctx->d_tmp2.ptr;
+        oi = (int32_t *)ctx->d_tmp1.ptr;
+        oj = oi + cap;
+        orr = (float *)(oj + cap);
+        op = (double *)ctx->d_tmp2.ptr;
         int32_t *ci = (int32_t *)ctx->d_jobs.ptr;
         int32_t *cj = ci + cap;
         float *cr = (float *)(cj + cap);
         if (ctx->P.no_cor_mat) {  // dense_cor = false: centred columns -> MFMA tiles -> screen, no matrix
-            const int n = ctx->P.n;
-            ctx->n_pad = (n + GEMM_BK - 1) / GEMM_BK * GEMM_BK;
+            const int n_obs = ctx->P.n;
+            ctx->n_pad = (n_obs + GEMM_BK - 1) / GEMM_BK * GEMM_BK;
             ctx->p_pad = (p + GEMM_BM - 1) / GEMM_BM * GEMM_BM;
             if (!ctx->d_xc) FW_HIP(ctx, hipMalloc(&ctx->d_xc, sizeof(float) * (size_t)ctx->n_pad * ctx->p_pad));
             if (!ctx->d_sd) FW_HIP(ctx, hipMalloc(&ctx->d_sd, sizeof(float) * (size_t)ctx->p_pad));
-            if (attempt == 0)
-                hipLaunchKernelGGL(fz_center_kernel, dim3(ctx->p_pad), dim3(256), 0, ctx->stream, ctx->d_data, ctx->d_xc, ctx->d_sd, n, p,
+            if (!centred)
+                hipLaunchKernelGGL(fz_center_kernel, dim3(ctx->p_pad), dim3(256), 0, ctx->stream, ctx->d_data, ctx->d_xc, ctx->d_sd, n_obs, p,
                                    ctx->n_pad);
+            centred = true;
             const int T = ctx->p_pad / GEMM_BM;
             hipLaunchKernelGGL(fz_cor_gemm_kernel<true>, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, ctx->stream, ctx->d_xc, ctx->d_sd,
                                (float *)nullptr, p, ctx->n_pad, T, 0, 0, (const double *)ctx->d_thr, d_c1, cap, ci, cj, cr);
@@ -788,14 +794,11 @@ int fwi_fz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
                                cj, cr);
         }
         FW_HIP(ctx, hipGetLastError());
-        FzL0Counters h1{};
         FW_HIP(ctx, hipMemcpyAsync(&h1, d_c1, sizeof(h1), hipMemcpyDeviceToHost, ctx->stream));
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (h1.n_sig > ctx->l0_cap_hint) ctx->l0_cap_hint = h1.n_sig;
-        if (h1.n_sig > cap) {  // more screened pairs than the buffer holds: retry with the exact count
-            cap = h1.n_sig;
-            continue;
-        }
+        ctx->cnt.kernel_launches += 1;
+        n.first = h1.n_sig;
+        if (h1.n_sig > cap) return FW_OK;  // more screened pairs than the buffer holds
         if (h1.n_sig)
             hipLaunchKernelGGL(fz_level0_exact_kernel, dim3((unsigned)((h1.n_sig + 255) / 256)), dim3(256), 0, ctx->stream,
                                (const int32_t *)ci, (const int32_t *)cj, (const float *)cr, h1.n_sig, ctx->P.alpha, fz_zscale(ctx),
@@ -803,78 +806,26 @@ int fwi_fz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
         FW_HIP(ctx, hipGetLastError());
         FW_HIP(ctx, hipMemcpyAsync(&h, d_c2, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        h.n_nan = h1.n_nan;
-        ctx->cnt.kernel_launches += 2;
-        if (h.n_sig <= cap) {
-            const size_t k = (size_t)h.n_sig;
-            if (dev) {  // results stay on the device for fwi_bh_csr_device
-                dev->i = oi;
-                dev->j = oj;
-                dev->stat32 = orr;
-                dev->pval = op;
-                dev->k = k;
-                *m_reliable = npairs - (long long)h.n_nan;
-                return FW_OK;
-            }
-            pi.resize(k);
-            pj.resize(k);
-            stat.resize(k);
-            pval.resize(k);
-            std::vector<float> rr(k);
-            if (k) {
-                FW_HIP(ctx, hipMemcpy(pi.data(), oi, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-                FW_HIP(ctx, hipMemcpy(pj.data(), oj, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-                FW_HIP(ctx, hipMemcpy(rr.data(), orr, k * sizeof(float), hipMemcpyDeviceToHost));
-                FW_HIP(ctx, hipMemcpy(pval.data(), op, k * sizeof(double), hipMemcpyDeviceToHost));
-            }
-            for (size_t t = 0; t < k; ++t) stat[t] = (double)rr[t];
-            *m_reliable = npairs - (long long)h.n_nan;
-            return FW_OK;
-        }
-        cap = h.n_sig;
-    }
-    return fw_fail(ctx, FW_ERR_DEVICE, "fz level-0: compaction buffer overflow twice");
+        ctx->cnt.kernel_launches += 1;
+        n.second = h.n_sig;
+        return FW_OK;
+    });
+    if (rc) return rc;
+    *m_reliable = npairs - (long long)h1.n_nan;
+    return fwi_l0_handover(ctx, oi, oj, nullptr, orr, op, (size_t)h.n_sig, pi, pj, stat, pval, dev);
 }
 
 int fwi_fz_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff,
                       const int32_t *zflat, fw_test_result *out)
 {
     if (m == 0) return FW_OK;
-    const int64_t nz = zoff[m];
-    int rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_jobs, (size_t)m * 2 * sizeof(int32_t) + (size_t)(m + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_acc, (size_t)(nz > 0 ? nz : 1) * sizeof(int32_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_out, (size_t)m * sizeof(fw_test_result)))) return rc;
-    long long *dz = (long long *)ctx->d_jobs.ptr;
-    int32_t *dX = (int32_t *)(dz + m + 1);
-    int32_t *dY = dX + m;
-    FW_HIP(ctx, hipMemcpyAsync(dz, zoff, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dX, X, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dY, Y, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (nz > 0)
-        FW_HIP(ctx, hipMemcpyAsync(ctx->d_acc.ptr, zflat, (size_t)nz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    int kmax = 0;
-    for (int64_t t = 0; t < m; ++t) kmax = std::max<int>(kmax, (int)(zoff[t + 1] - zoff[t]));
-    if (kmax > FW_MAX_K_FAST)
-        hipLaunchKernelGGL(fz_test_batch_kernel<true>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_cor,
-                           ctx->P.p, (long long)m, dX, dY, dz, (const int32_t *)ctx->d_acc.ptr, fz_zscale(ctx),
-                           (fw_test_result *)ctx->d_out.ptr);
-    else
-        hipLaunchKernelGGL(fz_test_batch_kernel<false>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_cor,
-                           ctx->P.p, (long long)m, dX, dY, dz, (const int32_t *)ctx->d_acc.ptr, fz_zscale(ctx),
-                           (fw_test_result *)ctx->d_out.ptr);
-    FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipMemcpyAsync(out, ctx->d_out.ptr, (size_t)m * sizeof(fw_test_result), hipMemcpyDeviceToHost, ctx->stream));
-    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cnt.kernel_launches += 1;
-    const bool power = ctx->P.n >= ctx->n_obs_min_eff;  // tests.jl:254 / :111
-    if (!power)
-        for (int64_t t = 0; t < m; ++t) {
-            out[t].stat = 0.0;
-            out[t].pval = 1.0;
-            out[t].df = 0;
-            out[t].suff_power = 0;
-        }
+    FwBatch b;
+    if (int rc = fwi_batch_upload(ctx, m, X, Y, zoff, zflat, b)) return rc;
+    const auto kernel = b.kmax > FW_MAX_K_FAST ? fz_test_batch_kernel<true> : fz_test_batch_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const float *)ctx->d_cor, ctx->P.p, (long long)m,
+                       (const int32_t *)b.dX, (const int32_t *)b.dY, (const long long *)b.dz, b.dzflat, fz_zscale(ctx), b.dout);
+    if (int rc = fwi_batch_finish(ctx, m, out)) return rc;
+    if (ctx->P.n < ctx->n_obs_min_eff) fw_fill_no_power(out, m);  // tests.jl:254 / :111
     return FW_OK;
 }
 
@@ -896,19 +847,6 @@ extern "C" void fwi_fz_fastdbg_print()
                 c[8], c[14], (double)c[9] / c[8], (double)c[10] / c[8], (double)c[11] / c[8], (double)c[12] / c[8], (double)c[13] / c[8]);
 }
 #endif
-static int fz_ensure_thresholds(fw_ctx *ctx, hipStream_t stream)
-{
-    if (!ctx->d_thr) {
-        const int flags = fw_knob_int(knob::FW_FZ_DBG, 0);
-        FW_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(fz_dbg_flags), &flags, sizeof(int)));
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_thr, 12 * sizeof(double)));
-        hipLaunchKernelGGL(fz_thresholds_kernel, dim3(1), dim3(64), 0, stream, ctx->P.alpha, fz_zscale(ctx), ctx->d_thr);
-        FW_HIP(ctx, hipGetLastError());
-        FW_HIP(ctx, hipStreamSynchronize(stream));  // another stream may use it next
-    }
-    return FW_OK;
-}
-
 // Device-driven rounds (fw_devhiton.hip): a fixed grid over an unsorted segment list whose live length is *d_ns.
 int fwi_fz_thresholds(fw_ctx *ctx, hipStream_t stream, double *zscale)
 {
@@ -916,30 +854,70 @@ int fwi_fz_thresholds(fw_ctx *ctx, hipStream_t stream, double *zscale)
     return fz_ensure_thresholds(ctx, stream);
 }
 
+// What a launch of fz_subsets_seg_kernel is given besides the context's max_k, alpha and max_tests.
+struct FzSegArgs {
+    const float *cor;  // the p x p matrix; LOCAL: the arena of the job-local matrices
+    int p;             // (LOCAL: 0)
+    const FwSeg *segs;
+    const int32_t *acc;
+    FwSegOut *out;
+    double zscale;              // LOCAL: 0, every job record carries its own
+    const double *thr;          // ... and its own thresholds
+    const FwNzJob *recs;        // LOCAL only
+    long long n_obs_min;        // LOCAL only
+    const unsigned *d_ns, *d_big;  // device rounds: live length of the list, "a long accepted list exists"; null when the host drives
+    FzSegArgs from(int64_t s0) const  // the same launch over segments s0..
+    {
+        FzSegArgs a = *this;
+        a.segs += s0;
+        a.out += s0;
+        return a;
+    }
+};
+static FzSegArgs fz_seg_args(const fw_ctx *ctx, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns, const unsigned *d_big)
+{
+    return FzSegArgs{ctx->d_cor, ctx->P.p, d_segs, d_acc, d_out, fz_zscale(ctx), ctx->d_thr, nullptr, 0ll, d_ns, d_big};
+}
+static FzSegArgs fznz_seg_args(const fw_ctx *ctx, const float *d_arena, const FwNzJob *d_recs, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out,
+                               const unsigned *d_ns, const unsigned *d_big)
+{
+    return FzSegArgs{d_arena, 0, d_segs, d_acc, d_out, 0.0, nullptr, d_recs, (long long)ctx->n_obs_min_eff, d_ns, d_big};
+}
+
+template <bool HIGHK, bool LOCAL, bool TAB> static void fz_seg_launch(const fw_ctx *ctx, unsigned grid, hipStream_t stream, const FzSegArgs &a)
+{
+    hipLaunchKernelGGL((fz_subsets_seg_kernel<HIGHK, LOCAL, TAB>), dim3(grid), dim3(256), 0, stream, a.cor, a.p, a.segs, a.acc, a.out, ctx->P.max_k,
+                       ctx->P.alpha, a.zscale, (long long)ctx->P.max_tests, a.thr, a.recs, a.n_obs_min, a.d_ns, a.d_big);
+}
+// The host job pool's sorted list: segments [0, nseg_tab) belong to jobs whose accepted list the table variant serves (HIGHK: at most
+// FZ_HK_A entries, level-2 table; else at most FZ_TAB_A), the rest go to the other variant (HIGHK: generic form; else in-lane caching).
+template <bool HIGHK, bool LOCAL>
+static void fz_seg_launch_sorted(const fw_ctx *ctx, int64_t nseg, int64_t nseg_tab, hipStream_t stream, const FzSegArgs &a)
+{
+    if (nseg_tab > 0) fz_seg_launch<HIGHK, LOCAL, true>(ctx, (unsigned)nseg_tab, stream, a);
+    if (nseg > nseg_tab) fz_seg_launch<HIGHK, LOCAL, false>(ctx, (unsigned)(nseg - nseg_tab), stream, a.from(nseg_tab));
+}
+// Device rounds without HIGHK: the table variant on the whole grid, and where an accepted list may exceed FZ_TAB_A the in-lane variant
+// on a few striding workgroups (such lists are rare).  Both stride the list and pick their segments by length.
+template <bool LOCAL> static void fz_seg_launch_dev3(const fw_ctx *ctx, unsigned grid, bool any_big, hipStream_t stream, const FzSegArgs &a)
+{
+    fz_seg_launch<false, LOCAL, true>(ctx, grid, stream, a);
+    if (any_big) fz_seg_launch<false, LOCAL, false>(ctx, grid < 512u ? grid : 512u, stream, a);
+}
+
 int fwi_fz_segments_dev(fw_ctx *ctx, unsigned grid, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns,
                         bool any_big, const unsigned *d_big, hipStream_t stream)
 {
-    int rc = fz_ensure_thresholds(ctx, stream);
-    if (rc) return rc;
-    const unsigned grid_big = grid < 512u ? grid : 512u;  // accepted sets beyond FZ_TAB_A are rare: few striding workgroups
+    if (int rc = fz_ensure_thresholds(ctx, stream)) return rc;
+    const FzSegArgs a = fz_seg_args(ctx, d_segs, d_acc, d_out, d_ns, d_big);
     if (ctx->P.max_k > 3) {
-        // level-2 table variant for |accepted| <= FZ_HK_A, generic variant for the longer lists (both stride the list)
+        // level-2 table variant for |accepted| <= FZ_HK_A, generic variant for the longer lists (both stride the list); without the
+        // first, the second gets no flag word and takes every segment
         const bool no_hk = fw_no_hk();  // profiling / test knob (read per call)
-        if (!no_hk)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<true, false, true>), dim3(grid), dim3(256), 0, stream, ctx->d_cor, ctx->P.p, d_segs,
-                               d_acc, d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests, ctx->d_thr,
-                               (const FwNzJob *)nullptr, 0ll, d_ns, d_big);
-        hipLaunchKernelGGL((fz_subsets_seg_kernel<true, false, false>), dim3(grid), dim3(256), 0, stream, ctx->d_cor,
-                           ctx->P.p, d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests,
-                           ctx->d_thr, (const FwNzJob *)nullptr, 0ll, d_ns, no_hk ? (const unsigned *)nullptr : d_big);
+        if (!no_hk) fz_seg_launch<true, false, true>(ctx, grid, stream, a);
+        fz_seg_launch<true, false, false>(ctx, grid, stream, no_hk ? fz_seg_args(ctx, d_segs, d_acc, d_out, d_ns, nullptr) : a);
     } else {
-        hipLaunchKernelGGL((fz_subsets_seg_kernel<false, false, true>), dim3(grid), dim3(256), 0, stream, ctx->d_cor, ctx->P.p, d_segs,
-                           d_acc, d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests, ctx->d_thr,
-                           (const FwNzJob *)nullptr, 0ll, d_ns, d_big);
-        if (any_big)  // some accepted set may exceed FZ_TAB_A
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<false, false, false>), dim3(grid_big), dim3(256), 0, stream, ctx->d_cor, ctx->P.p,
-                               d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests,
-                               ctx->d_thr, (const FwNzJob *)nullptr, 0ll, d_ns, d_big);
+        fz_seg_launch_dev3<false>(ctx, grid, any_big, stream, a);
     }
     FW_HIP(ctx, hipGetLastError());
     return FW_OK;
@@ -950,36 +928,15 @@ int fwi_fz_segments(fw_ctx *ctx, int64_t nseg, int64_t nseg_tab, const FwSeg *d_
 {
     if (nseg == 0) return FW_OK;
     FW_HIP(ctx, hipEventRecord(pb.ev0, pb.launch_stream));
-    {
-        int rc = fz_ensure_thresholds(ctx, pb.launch_stream);
-        if (rc) return rc;
-    }
-    if (ctx->P.max_k > FW_MAX_K_FAST) {  // conditioning sets of 6 and 7 variables: the general form for every segment
-        hipLaunchKernelGGL(fz_subsets_slow_kernel<false>, dim3((unsigned)nseg), dim3(256), 0, pb.launch_stream, ctx->d_cor, ctx->P.p, d_segs, d_acc,
-                           d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests, (const FwNzJob *)nullptr, 0ll);
-    } else if (ctx->P.max_k > 3) {
-        // segments [0, nseg_tab) belong to jobs with |accepted| <= FZ_HK_A: level-2 table kernel; the rest: generic form
-        if (nseg_tab > 0)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<true, false, true>), dim3((unsigned)nseg_tab), dim3(256), 0, pb.launch_stream,
-                               ctx->d_cor, ctx->P.p, d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx),
-                               (long long)ctx->P.max_tests, ctx->d_thr, (const FwNzJob *)nullptr, 0ll, (const unsigned *)nullptr, (const unsigned *)nullptr);
-        if (nseg > nseg_tab)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<true, false, false>), dim3((unsigned)(nseg - nseg_tab)), dim3(256), 0,
-                               pb.launch_stream, ctx->d_cor, ctx->P.p, d_segs + nseg_tab, d_acc, d_out + nseg_tab, ctx->P.max_k,
-                               ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests, ctx->d_thr, (const FwNzJob *)nullptr,
-                               0ll, (const unsigned *)nullptr, (const unsigned *)nullptr);
-    } else {
-        // segments [0, nseg_tab) belong to jobs with |accepted| <= FZ_TAB_A: table kernel; the rest: in-lane caching
-        if (nseg_tab > 0)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<false, false, true>), dim3((unsigned)nseg_tab), dim3(256), 0, pb.launch_stream,
-                               ctx->d_cor, ctx->P.p, d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, fz_zscale(ctx),
-                               (long long)ctx->P.max_tests, ctx->d_thr, (const FwNzJob *)nullptr, 0ll, (const unsigned *)nullptr, (const unsigned *)nullptr);
-        if (nseg > nseg_tab)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<false, false, false>), dim3((unsigned)(nseg - nseg_tab)), dim3(256), 0,
-                               pb.launch_stream, ctx->d_cor, ctx->P.p, d_segs + nseg_tab, d_acc, d_out + nseg_tab, ctx->P.max_k,
-                               ctx->P.alpha, fz_zscale(ctx), (long long)ctx->P.max_tests, ctx->d_thr, (const FwNzJob *)nullptr,
-                               0ll, (const unsigned *)nullptr, (const unsigned *)nullptr);
-    }
+    if (int rc = fz_ensure_thresholds(ctx, pb.launch_stream)) return rc;
+    const FzSegArgs a = fz_seg_args(ctx, d_segs, d_acc, d_out, nullptr, nullptr);
+    if (ctx->P.max_k > FW_MAX_K_FAST)  // conditioning sets of 6 and 7 variables: the general form for every segment
+        hipLaunchKernelGGL(fz_subsets_slow_kernel<false>, dim3((unsigned)nseg), dim3(256), 0, pb.launch_stream, a.cor, a.p, a.segs, a.acc, a.out,
+                           ctx->P.max_k, ctx->P.alpha, a.zscale, (long long)ctx->P.max_tests, a.recs, a.n_obs_min);
+    else if (ctx->P.max_k > 3)
+        fz_seg_launch_sorted<true, false>(ctx, nseg, nseg_tab, pb.launch_stream, a);
+    else
+        fz_seg_launch_sorted<false, false>(ctx, nseg, nseg_tab, pb.launch_stream, a);
     FW_HIP(ctx, hipGetLastError());
     FW_HIP(ctx, hipEventRecord(pb.ev1, pb.launch_stream));
     return FW_OK;
@@ -1755,21 +1712,19 @@ int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32
 int fwi_fznz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                     std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev)
 {
-    if (dev) *dev = FwL0Dev{};
     const int p = ctx->P.p;
     const long long npairs = (long long)p * (p - 1) / 2;
-    unsigned long long cap = (unsigned long long)std::min<long long>(npairs, 4ll << 20);
-    if (cap < ctx->l0_cap_hint) cap = ctx->l0_cap_hint;
-    if (cap == 0) cap = 1;
     FzL0Counters h{};
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    int32_t *oi = nullptr, *oj = nullptr;
+    double *os = nullptr, *op = nullptr;
+    const int rc = fwi_l0_attempts(ctx, npairs, 4ll << 20, "fz_nz level-0: compaction buffer", [&](unsigned long long cap, FwL0Counts &n) -> int {
         int rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp0, sizeof(FzL0Counters)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, cap * 2 * sizeof(int32_t)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp2, cap * 2 * sizeof(double)))) return rc;
         FW_HIP(ctx, hipMemsetAsync(ctx->d_tmp0.ptr, 0, sizeof(FzL0Counters), ctx->stream));
-        int32_t *oi = (int32_t *)ctx->d_tmp1.ptr, *oj = oi + cap;
-        double *os = (double *)ctx->d_tmp2.ptr, *op = os + cap;
+        oi = (int32_t *)ctx->d_tmp1.ptr, oj = oi + cap;
+        os = (double *)ctx->d_tmp2.ptr, op = os + cap;
         dim3 grid((p + 15) / 16, (p + 15) / 16);
         if (ctx->csc_resident)
             hipLaunchKernelGGL(fznz_level0_kernel<true>, grid, dim3(256), 0, ctx->stream, (const float *)ctx->d_cvals,
@@ -1783,34 +1738,12 @@ int fwi_fznz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> 
         FW_HIP(ctx, hipMemcpyAsync(&h, ctx->d_tmp0.ptr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->cnt.kernel_launches += 1;
-        if (h.n_sig > ctx->l0_cap_hint) ctx->l0_cap_hint = h.n_sig;
-        if (h.n_sig <= cap) {
-            const size_t k = (size_t)h.n_sig;
-            if (dev) {
-                dev->i = oi;
-                dev->j = oj;
-                dev->stat64 = os;
-                dev->pval = op;
-                dev->k = k;
-                *m_reliable = npairs - (long long)h.n_nan;
-                return FW_OK;
-            }
-            pi.resize(k);
-            pj.resize(k);
-            stat.resize(k);
-            pval.resize(k);
-            if (k) {
-                FW_HIP(ctx, hipMemcpy(pi.data(), oi, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-                FW_HIP(ctx, hipMemcpy(pj.data(), oj, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-                FW_HIP(ctx, hipMemcpy(stat.data(), os, k * sizeof(double), hipMemcpyDeviceToHost));
-                FW_HIP(ctx, hipMemcpy(pval.data(), op, k * sizeof(double), hipMemcpyDeviceToHost));
-            }
-            *m_reliable = npairs - (long long)h.n_nan;
-            return FW_OK;
-        }
-        cap = h.n_sig;
-    }
-    return fw_fail(ctx, FW_ERR_DEVICE, "fz_nz level-0: compaction buffer overflow twice");
+        n.first = h.n_sig;
+        return FW_OK;
+    });
+    if (rc) return rc;
+    *m_reliable = npairs - (long long)h.n_nan;
+    return fwi_l0_handover(ctx, oi, oj, os, nullptr, op, (size_t)h.n_sig, pi, pj, stat, pval, dev);
 }
 
 // erfc^-1(alpha) by bisection on the host's erfc (-1: alpha >= 1 or not a probability, the kernel bisects per job instead)
@@ -1911,18 +1844,10 @@ int fwi_fznz_submatrices_dev(fw_ctx *ctx, int nslots, FwNzJob *d_recs, const int
 int fwi_fznz_segments_dev(fw_ctx *ctx, unsigned grid, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns,
                           bool any_big, const unsigned *d_big, const FwNzJob *d_recs, const float *d_arena, hipStream_t stream)
 {
-    if (ctx->P.max_k > 3) {
-        hipLaunchKernelGGL((fz_subsets_seg_kernel<true, true, false>), dim3(grid), dim3(256), 0, stream, d_arena, 0, d_segs, d_acc, d_out, ctx->P.max_k,
-                           ctx->P.alpha, 0.0, (long long)ctx->P.max_tests, (const double *)nullptr, d_recs, (long long)ctx->n_obs_min_eff, d_ns,
-                           (const unsigned *)nullptr);
-    } else {
-        hipLaunchKernelGGL((fz_subsets_seg_kernel<false, true, true>), dim3(grid), dim3(256), 0, stream, d_arena, 0, d_segs, d_acc, d_out, ctx->P.max_k,
-                           ctx->P.alpha, 0.0, (long long)ctx->P.max_tests, (const double *)nullptr, d_recs, (long long)ctx->n_obs_min_eff, d_ns, d_big);
-        if (any_big)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<false, true, false>), dim3(grid < 512u ? grid : 512u), dim3(256), 0, stream, d_arena, 0, d_segs,
-                               d_acc, d_out, ctx->P.max_k, ctx->P.alpha, 0.0, (long long)ctx->P.max_tests, (const double *)nullptr, d_recs,
-                               (long long)ctx->n_obs_min_eff, d_ns, d_big);
-    }
+    if (ctx->P.max_k > 3)  // one variant, no flag word
+        fz_seg_launch<true, true, false>(ctx, grid, stream, fznz_seg_args(ctx, d_arena, d_recs, d_segs, d_acc, d_out, d_ns, nullptr));
+    else
+        fz_seg_launch_dev3<true>(ctx, grid, any_big, stream, fznz_seg_args(ctx, d_arena, d_recs, d_segs, d_acc, d_out, d_ns, d_big));
     FW_HIP(ctx, hipGetLastError());
     return FW_OK;
 }
@@ -1932,27 +1857,14 @@ int fwi_fznz_segments(fw_ctx *ctx, int64_t nseg, int64_t nseg_tab, const FwSeg *
 {
     if (nseg == 0) return FW_OK;
     FW_HIP(ctx, hipEventRecord(pb.ev0, pb.launch_stream));
+    const FzSegArgs a = fznz_seg_args(ctx, (const float *)ctx->d_arena.ptr, (const FwNzJob *)ctx->d_nzrecs.ptr, d_segs, d_acc, d_out, nullptr, nullptr);
     if (ctx->P.max_k > FW_MAX_K_FAST)  // conditioning sets of 6 and 7 variables: the general form on the job-local matrices
-        hipLaunchKernelGGL(fz_subsets_slow_kernel<true>, dim3((unsigned)nseg), dim3(256), 0, pb.launch_stream, (const float *)ctx->d_arena.ptr, 0, d_segs,
-                           d_acc, d_out, ctx->P.max_k, ctx->P.alpha, 0.0, (long long)ctx->P.max_tests, (const FwNzJob *)ctx->d_nzrecs.ptr,
-                           (long long)ctx->n_obs_min_eff);
+        hipLaunchKernelGGL(fz_subsets_slow_kernel<true>, dim3((unsigned)nseg), dim3(256), 0, pb.launch_stream, a.cor, a.p, a.segs, a.acc, a.out,
+                           ctx->P.max_k, ctx->P.alpha, a.zscale, (long long)ctx->P.max_tests, a.recs, a.n_obs_min);
     else if (ctx->P.max_k > 3)
-        hipLaunchKernelGGL((fz_subsets_seg_kernel<true, true, false>), dim3((unsigned)nseg), dim3(256), 0, pb.launch_stream,
-                           (const float *)ctx->d_arena.ptr, 0, d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, 0.0,
-                           (long long)ctx->P.max_tests, (const double *)nullptr, (const FwNzJob *)ctx->d_nzrecs.ptr,
-                           (long long)ctx->n_obs_min_eff, (const unsigned *)nullptr, (const unsigned *)nullptr);
-    else {
-        if (nseg_tab > 0)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<false, true, true>), dim3((unsigned)nseg_tab), dim3(256), 0, pb.launch_stream,
-                               (const float *)ctx->d_arena.ptr, 0, d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, 0.0,
-                               (long long)ctx->P.max_tests, (const double *)nullptr, (const FwNzJob *)ctx->d_nzrecs.ptr,
-                               (long long)ctx->n_obs_min_eff, (const unsigned *)nullptr, (const unsigned *)nullptr);
-        if (nseg > nseg_tab)
-            hipLaunchKernelGGL((fz_subsets_seg_kernel<false, true, false>), dim3((unsigned)(nseg - nseg_tab)), dim3(256), 0,
-                               pb.launch_stream, (const float *)ctx->d_arena.ptr, 0, d_segs + nseg_tab, d_acc, d_out + nseg_tab,
-                               ctx->P.max_k, ctx->P.alpha, 0.0, (long long)ctx->P.max_tests, (const double *)nullptr,
-                               (const FwNzJob *)ctx->d_nzrecs.ptr, (long long)ctx->n_obs_min_eff, (const unsigned *)nullptr, (const unsigned *)nullptr);
-    }
+        fz_seg_launch<true, true, false>(ctx, (unsigned)nseg, pb.launch_stream, a);
+    else
+        fz_seg_launch_sorted<false, true>(ctx, nseg, nseg_tab, pb.launch_stream, a);
     FW_HIP(ctx, hipGetLastError());
     FW_HIP(ctx, hipEventRecord(pb.ev1, pb.launch_stream));
     return FW_OK;
@@ -1986,11 +1898,7 @@ int fwi_fznz_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t 
     hipLaunchKernelGGL(fznz_single_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream,
                        (const FwNzJob *)ctx->d_nzrecs.ptr, (const float *)ctx->d_arena.ptr, (long long)m,
                        (long long)ctx->n_obs_min_eff, (fw_test_result *)ctx->d_out.ptr, f64 ? (const double *)ctx->d_arena.ptr : (const double *)nullptr);
-    FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipMemcpyAsync(out, ctx->d_out.ptr, (size_t)m * sizeof(fw_test_result), hipMemcpyDeviceToHost, ctx->stream));
-    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cnt.kernel_launches += 1;
-    return FW_OK;
+    return fwi_batch_finish(ctx, m, out);
 }
 
 

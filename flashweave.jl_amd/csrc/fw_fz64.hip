@@ -466,93 +466,50 @@ int fwi_fz64_compute_cor(fw_ctx *ctx)
 int fwi_fz64_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat, std::vector<double> &pval,
                     int64_t *m_reliable, FwL0Dev *dev)
 {
-    if (dev) *dev = FwL0Dev{};
     const int p = ctx->P.p;
     const long long npairs = (long long)p * (p - 1) / 2;
-    pi.clear();
-    pj.clear();
-    stat.clear();
-    pval.clear();
     if (ctx->P.n < ctx->n_obs_min_eff) {  // tests.jl:11 -> every test lacks power -> all NaN
         *m_reliable = 0;
-        return FW_OK;
+        return fwi_l0_handover(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0, pi, pj, stat, pval, dev);
     }
     double zscale = 0.0;
     if (int rc = fwi_fz_thresholds(ctx, ctx->stream, &zscale)) return rc;
-    unsigned long long cap = (unsigned long long)std::min<long long>(npairs, 4ll << 20);
-    if (cap < ctx->l0_cap_hint) cap = ctx->l0_cap_hint;
-    if (cap == 0) cap = 1;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    Fz64L0Counters h{};
+    int32_t *oi = nullptr, *oj = nullptr;
+    double *os = nullptr, *op = nullptr;
+    const int rc = fwi_l0_attempts(ctx, npairs, 4ll << 20, "Float64 fz level-0: compaction buffer", [&](unsigned long long cap, FwL0Counts &n) -> int {
         int rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp0, sizeof(Fz64L0Counters)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, cap * 2 * sizeof(int32_t)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp2, cap * 2 * sizeof(double)))) return rc;
         FW_HIP(ctx, hipMemsetAsync(ctx->d_tmp0.ptr, 0, sizeof(Fz64L0Counters), ctx->stream));
-        int32_t *oi = (int32_t *)ctx->d_tmp1.ptr, *oj = oi + cap;
-        double *os = (double *)ctx->d_tmp2.ptr, *op = os + cap;
+        oi = (int32_t *)ctx->d_tmp1.ptr, oj = oi + cap;
+        os = (double *)ctx->d_tmp2.ptr, op = os + cap;
         dim3 grid((p + FZ64_L0_COLS - 1) / FZ64_L0_COLS, (p + FZ64_L0_ROWS - 1) / FZ64_L0_ROWS);
         hipLaunchKernelGGL(fz64_level0_kernel, grid, dim3(256), 0, ctx->stream, (const double *)ctx->d_cor64, p, (const double *)ctx->d_thr,
                            ctx->P.alpha, zscale, (Fz64L0Counters *)ctx->d_tmp0.ptr, cap, oi, oj, os, op);
         FW_HIP(ctx, hipGetLastError());
-        Fz64L0Counters h{};
         FW_HIP(ctx, hipMemcpyAsync(&h, ctx->d_tmp0.ptr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->cnt.kernel_launches += 1;
-        if (h.n_sig > ctx->l0_cap_hint) ctx->l0_cap_hint = h.n_sig;
-        if (h.n_sig > cap) {  // more significant pairs than the buffer holds: once more with the exact count
-            cap = h.n_sig;
-            continue;
-        }
-        const size_t k = (size_t)h.n_sig;
-        *m_reliable = npairs - (long long)h.n_nan;
-        if (dev) {  // results stay on the device for fwi_bh_csr_device
-            dev->i = oi;
-            dev->j = oj;
-            dev->stat64 = os;
-            dev->pval = op;
-            dev->k = k;
-            return FW_OK;
-        }
-        pi.resize(k);
-        pj.resize(k);
-        stat.resize(k);
-        pval.resize(k);
-        if (k) {
-            FW_HIP(ctx, hipMemcpy(pi.data(), oi, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-            FW_HIP(ctx, hipMemcpy(pj.data(), oj, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-            FW_HIP(ctx, hipMemcpy(stat.data(), os, k * sizeof(double), hipMemcpyDeviceToHost));
-            FW_HIP(ctx, hipMemcpy(pval.data(), op, k * sizeof(double), hipMemcpyDeviceToHost));
-        }
+        n.first = h.n_sig;
         return FW_OK;
-    }
-    return fw_fail(ctx, FW_ERR_DEVICE, "Float64 fz level-0: compaction buffer overflow twice");
+    });
+    if (rc) return rc;
+    *m_reliable = npairs - (long long)h.n_nan;
+    return fwi_l0_handover(ctx, oi, oj, os, nullptr, op, (size_t)h.n_sig, pi, pj, stat, pval, dev);
 }
 
 int fwi_fz64_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff, const int32_t *zflat,
                         fw_test_result *out)
 {
     if (m == 0) return FW_OK;
-    const int64_t nz = zoff[m];
-    int rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_jobs, (size_t)m * 2 * sizeof(int32_t) + (size_t)(m + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_acc, (size_t)(nz > 0 ? nz : 1) * sizeof(int32_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_out, (size_t)m * sizeof(fw_test_result)))) return rc;
-    long long *dz = (long long *)ctx->d_jobs.ptr;
-    int32_t *dX = (int32_t *)(dz + m + 1);
-    int32_t *dY = dX + m;
-    FW_HIP(ctx, hipMemcpyAsync(dz, zoff, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dX, X, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dY, Y, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (nz > 0) FW_HIP(ctx, hipMemcpyAsync(ctx->d_acc.ptr, zflat, (size_t)nz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    FwBatch b;
+    if (int rc = fwi_batch_upload(ctx, m, X, Y, zoff, zflat, b)) return rc;
     hipLaunchKernelGGL(fz64_test_batch_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const double *)ctx->d_cor64, ctx->P.p,
-                       (long long)m, (const int32_t *)dX, (const int32_t *)dY, (const long long *)dz, (const int32_t *)ctx->d_acc.ptr,
-                       fz64_zscale(ctx), (fw_test_result *)ctx->d_out.ptr);
-    FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipMemcpyAsync(out, ctx->d_out.ptr, (size_t)m * sizeof(fw_test_result), hipMemcpyDeviceToHost, ctx->stream));
-    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cnt.kernel_launches += 1;
-    if (ctx->P.n < ctx->n_obs_min_eff)  // tests.jl:254 / :111
-        for (int64_t t = 0; t < m; ++t) out[t] = fw_test_result{0.0, 1.0, 0, 0};
+                       (long long)m, (const int32_t *)b.dX, (const int32_t *)b.dY, (const long long *)b.dz, b.dzflat, fz64_zscale(ctx), b.dout);
+    if (int rc = fwi_batch_finish(ctx, m, out)) return rc;
+    if (ctx->P.n < ctx->n_obs_min_eff) fw_fill_no_power(out, m);  // tests.jl:254 / :111
     return FW_OK;
 }
 

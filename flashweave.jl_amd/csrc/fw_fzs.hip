@@ -25,6 +25,7 @@
 // Algorithmic bytes: B_fzS(k, n) = (k + 2) * n * 4 + 32 per test (variant S): what a test that shares nothing
 // with its neighbours streams.  With X / Y held, the bytes really requested are k * n * 4 per test.
 #include <cmath>
+#include <type_traits>
 
 #include "fw_internal.h"
 #include "fw_unrank.h"
@@ -776,6 +777,41 @@ int fzs_ensure_stat(fw_ctx *ctx, hipStream_t st)
 // X / Y columns in LDS: n a multiple of 4 (16-byte rows) and at most FZS_LDS_N samples
 bool fzs_hold_xy(const fw_ctx *ctx) { return ctx->P.n % 4 == 0 && ctx->P.n <= 2048; }
 
+// The instantiation of the fzs_* kernels: f receives (K, T, GRAM) as integral constants -- K = 3 or FW_MAX_K_FAST conditioning variables
+// at most, T = 8: the X / Y columns held in LDS (fzs_hold_xy), GRAM: the job-local matrices, which exist with T = 0 only.
+template <int K, class F> void fzs_dispatch_k(bool hold_xy, bool gram, F &f)
+{
+    using KK = std::integral_constant<int, K>;
+    if (gram)
+        f(KK{}, std::integral_constant<int, 0>{}, std::true_type{});
+    else if (hold_xy)
+        f(KK{}, std::integral_constant<int, 8>{}, std::false_type{});
+    else
+        f(KK{}, std::integral_constant<int, 0>{}, std::false_type{});
+}
+template <class F> void fzs_dispatch(int kmax, bool hold_xy, bool gram, F &&f)
+{
+    if (kmax <= 3)
+        fzs_dispatch_k<3>(hold_xy, gram, f);
+    else
+        fzs_dispatch_k<FW_MAX_K_FAST>(hold_xy, gram, f);
+}
+
+// One launch of the segment kernel on the pool buffer's stream, between its two events; lds_m: rows of a job matrix the LDS copy holds
+int fzs_seg_launch(fw_ctx *ctx, const FzsDev &P, bool hold_xy, bool gram, int lds_m, int64_t nseg, const FwSeg *d_segs, const int32_t *d_acc,
+                   FwSegOut *d_out, FwPoolBuf &pb)
+{
+    const size_t lds = gram ? (size_t)lds_m * lds_m * sizeof(double) : 0;
+    fzs_dispatch(ctx->P.max_k, hold_xy, gram, [&](auto k, auto t, auto g) {
+        hipLaunchKernelGGL((fzs_subsets_seg_kernel<decltype(k)::value, decltype(t)::value, decltype(g)::value>), dim3((unsigned)nseg), dim3(256), lds,
+                           pb.launch_stream, P, d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests,
+                           (const FwNzJob *)ctx->d_nzrecs.ptr, (const double *)ctx->d_arena.ptr, lds_m);
+    });
+    FW_HIP(ctx, hipGetLastError());
+    FW_HIP(ctx, hipEventRecord(pb.ev1, pb.launch_stream));
+    return FW_OK;
+}
+
 }  // namespace
 
 int fwi_fzs_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff, const int32_t *zflat,
@@ -784,36 +820,16 @@ int fwi_fzs_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *
     if (m == 0) return FW_OK;
     if (ctx->csc_resident) return fw_fail(ctx, FW_ERR_LIMIT, "recursive_pcor = 0 is not served on the CSC-resident layout (fw_set_data_csc_f32_resident)");
     if (!ctx->d_data) return fw_fail(ctx, FW_ERR_STATE, "recursive_pcor = 0 needs the data matrix on the device (fw_set_data_dense_f32)");
-    const int64_t nz = zoff[m];
-    int kmax = 0;
-    for (int64_t t = 0; t < m; ++t) kmax = std::max<int>(kmax, (int)(zoff[t + 1] - zoff[t]));
+    FwBatch b;
     int rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_jobs, (size_t)m * 2 * sizeof(int32_t) + (size_t)(m + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_acc, (size_t)(nz > 0 ? nz : 1) * sizeof(int32_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_out, (size_t)m * sizeof(fw_test_result)))) return rc;
-    long long *dz = (long long *)ctx->d_jobs.ptr;
-    int32_t *dX = (int32_t *)(dz + m + 1), *dY = dX + m;
-    FW_HIP(ctx, hipMemcpyAsync(dz, zoff, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dX, X, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dY, Y, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (nz > 0) FW_HIP(ctx, hipMemcpyAsync(ctx->d_acc.ptr, zflat, (size_t)nz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid((unsigned)((m + 3) / 4));
+    if ((rc = fwi_batch_upload(ctx, m, X, Y, zoff, zflat, b))) return rc;
     if ((rc = fzs_ensure_stat(ctx, ctx->stream))) return rc;
     const FzsDev P = fzs_dev(ctx);
-#define FZS_BATCH(KK, TT)                                                                                                    \
-    hipLaunchKernelGGL((fzs_test_batch_kernel<KK, TT>), grid, dim3(256), 0, ctx->stream, P, (long long)m, dX, dY, dz,        \
-                       (const int32_t *)ctx->d_acc.ptr, (fw_test_result *)ctx->d_out.ptr)
-    if (fzs_hold_xy(ctx)) {
-        if (kmax <= 3) FZS_BATCH(3, 8); else FZS_BATCH(FW_MAX_K_FAST, 8);
-    } else {
-        if (kmax <= 3) FZS_BATCH(3, 0); else FZS_BATCH(FW_MAX_K_FAST, 0);
-    }
-#undef FZS_BATCH
-    FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipMemcpyAsync(out, ctx->d_out.ptr, (size_t)m * sizeof(fw_test_result), hipMemcpyDeviceToHost, ctx->stream));
-    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cnt.kernel_launches += 1;
-    return FW_OK;
+    fzs_dispatch(b.kmax, fzs_hold_xy(ctx), false, [&](auto k, auto t, auto) {
+        hipLaunchKernelGGL((fzs_test_batch_kernel<decltype(k)::value, decltype(t)::value>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, P,
+                           (long long)m, (const int32_t *)b.dX, (const int32_t *)b.dY, (const long long *)b.dz, b.dzflat, b.dout);
+    });
+    return fwi_batch_finish(ctx, m, out);
 }
 
 int fwi_fzs_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, FwPoolBuf &pb,
@@ -843,22 +859,7 @@ int fwi_fzs_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32
                            (double *)ctx->d_arena.ptr);
         ctx->cnt.kernel_launches += 1;
     }
-    const size_t lds = gram ? (size_t)lds_m * lds_m * sizeof(double) : 0;
-#define FZS_SEG(KK, TT, GG)                                                                                                        \
-    hipLaunchKernelGGL((fzs_subsets_seg_kernel<KK, TT, GG>), dim3((unsigned)nseg), dim3(256), lds, pb.launch_stream, P, d_segs, d_acc, \
-                       d_out, ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, (const FwNzJob *)ctx->d_nzrecs.ptr,         \
-                       (const double *)ctx->d_arena.ptr, lds_m)
-    if (gram) {
-        if (ctx->P.max_k <= 3) FZS_SEG(3, 0, true); else FZS_SEG(FW_MAX_K_FAST, 0, true);
-    } else if (fzs_hold_xy(ctx)) {
-        if (ctx->P.max_k <= 3) FZS_SEG(3, 8, false); else FZS_SEG(FW_MAX_K_FAST, 8, false);
-    } else {
-        if (ctx->P.max_k <= 3) FZS_SEG(3, 0, false); else FZS_SEG(FW_MAX_K_FAST, 0, false);
-    }
-#undef FZS_SEG
-    FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipEventRecord(pb.ev1, pb.launch_stream));
-    return FW_OK;
+    return fzs_seg_launch(ctx, P, fzs_hold_xy(ctx), gram, lds_m, nseg, d_segs, d_acc, d_out, pb);
 }
 
 // fz_nz without a matrix (fw_params.recursive_pcor = 0 with FW_FZ_NZ; the reference's FzTestCond with an empty cor_mat on the row views
@@ -878,17 +879,5 @@ int fwi_fzs_segments_nz(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const in
     P.zscale = 0.0;
     P.n_obs_min = ctx->n_obs_min_eff;
     P.nzjobs = 1;
-    const int lds_m = std::min(m_max, 80);
-    const size_t lds = (size_t)lds_m * lds_m * sizeof(double);
-    if (ctx->P.max_k <= 3)
-        hipLaunchKernelGGL((fzs_subsets_seg_kernel<3, 0, true>), dim3((unsigned)nseg), dim3(256), lds, pb.launch_stream, P, d_segs, d_acc, d_out,
-                           ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, (const FwNzJob *)ctx->d_nzrecs.ptr,
-                           (const double *)ctx->d_arena.ptr, lds_m);
-    else
-        hipLaunchKernelGGL((fzs_subsets_seg_kernel<FW_MAX_K_FAST, 0, true>), dim3((unsigned)nseg), dim3(256), lds, pb.launch_stream, P, d_segs, d_acc,
-                           d_out, ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, (const FwNzJob *)ctx->d_nzrecs.ptr,
-                           (const double *)ctx->d_arena.ptr, lds_m);
-    FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipEventRecord(pb.ev1, pb.launch_stream));
-    return FW_OK;
+    return fzs_seg_launch(ctx, P, false, true, std::min(m_max, 80), nseg, d_segs, d_acc, d_out, pb);
 }

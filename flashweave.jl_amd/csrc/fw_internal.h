@@ -18,6 +18,7 @@
 #include "../../include/flashweave_amd.h"
 #include "fw_graph.h"  // host-only: FwDirected, FwNetwork, FwHostWorkers, fwi_now_s
 #include "fw_pool_host.h"  // host-only: FwJob, FwJobOut, FwSeg, FwSegOut, FW_RANK_NONE, the job pool's rules
+#include "fw_stage_host.h"  // host-only: the level-0 capacity policy (fw_l0_first_cap, fw_l0_attempts)
 
 struct FwDevBuf {
     void *ptr = nullptr;
@@ -271,6 +272,31 @@ int fw_pin_reserve(fw_ctx *ctx, FwPinned &b, size_t bytes);
             return fw_fail(ctx, e__ == hipErrorOutOfMemory ? FW_ERR_NOMEM : FW_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, \
                            hipGetErrorString(e__), __FILE__, __LINE__);                          \
     } while (0)
+
+// ---- what the kinds' back-ends share (fw_core.cpp; the capacity policy itself: fw_stage_host.h) ----
+// The attempts of a level-0 driver on the context's hint; run(cap, counts) is one attempt, `what` names the buffer in the error.
+template <class Run> int fwi_l0_attempts(fw_ctx *ctx, long long pairs, long long limit, const char *what, Run &&run)
+{
+    std::string overflow;
+    const int rc = fw_l0_attempts(fw_l0_first_cap(pairs, limit, ctx->l0_cap_hint), ctx->l0_cap_hint, what, overflow, run);
+    return overflow.empty() ? rc : fw_fail(ctx, rc, "%s", overflow.c_str());
+}
+// The k significant pairs of a level-0 driver, handed over: left where they are for fwi_bh_csr_device (dev != null; the vectors end
+// empty) or downloaded into the vectors.  The statistic is Float64 (stat64) or Float32 (stat32, widened on the host), the other null.
+int fwi_l0_handover(fw_ctx *ctx, const int32_t *oi, const int32_t *oj, const double *stat64, const float *stat32, const double *op, size_t k,
+                    std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat, std::vector<double> &pval, FwL0Dev *dev);
+// Staging of an explicit-test batch (fw_test_batch) on ctx->stream: zoff | X | Y in ctx->d_jobs, zflat in ctx->d_acc, room for the m
+// results in ctx->d_out.  fwi_batch_finish after the launches: launch error, results to `out`, synchronise, count the batch.
+struct FwBatch {
+    long long *dz = nullptr;
+    int32_t *dX = nullptr, *dY = nullptr;
+    const int32_t *dzflat = nullptr;
+    fw_test_result *dout = nullptr;
+    int kmax = 0;  // the batch's largest conditioning set
+};
+int fwi_batch_upload(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff, const int32_t *zflat, FwBatch &b);
+int fwi_batch_finish(fw_ctx *ctx, int64_t m, fw_test_result *out);
+void fw_fill_no_power(fw_test_result *out, int64_t m);  // tests.jl:11 / :254: too few observations, every test {0, 1, 0, 0}
 
 // ---- fz (fw_fz.hip) ----
 int fwi_fz_compute_cor(fw_ctx *ctx);

@@ -1263,7 +1263,6 @@ static MiDev mi_dev(const fw_ctx *ctx)
 // zero included); L = maximum(max_vals) + 1 for every table of the context (types.jl:89,110).  The conditional tests run through the
 // same batch / segment kernels as the bit-plane forms (template value L = 0), HITON-PC through the host job pool, level 0 through
 // mig_level0_kernel (one wavefront per pair).  Limits: values <= 7, L^max_k (L^2 + 1) <= MIG_TAB32 words of LDS per wavefront.
-static double host_igamc(double a, double x);
 #define MIG_GTAB_MAX (64ll << 20)          // words of one device-memory table
 #define MIG_GTAB_BYTES (1ll << 30)         // device memory the tables of ONE launch may take: launches are cut to fit
 // workgroups (of four wavefronts, one table each) a launch of the generic form may hold: all of them with LDS tables, else what fits
@@ -1424,13 +1423,11 @@ static int mig_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t
     const long long npairs = (long long)p * (p - 1) / 2;
     const long long q0 = npairs * ctx->l0_rank / ctx->l0_world, q1 = npairs * (ctx->l0_rank + 1) / ctx->l0_world;
     const MiDev P = mi_dev(ctx);
-    unsigned long long cap = (unsigned long long)std::max<long long>(std::min<long long>(q1 - q0, 1ll << 22), 1);
-    if (cap < ctx->l0_cap_hint) cap = ctx->l0_cap_hint;
     MiL0Counters h{};
-    int rc;
     int32_t *oi = nullptr, *oj = nullptr;
     double *os = nullptr, *op = nullptr;
-    for (int attempt = 0;; ++attempt) {
+    const int rc = fwi_l0_attempts(ctx, q1 - q0, 1ll << 22, "discrete level-0 (generic form): result buffer", [&](unsigned long long cap, FwL0Counts &n) -> int {
+        int rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp0, sizeof(MiL0Counters)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, cap * 2 * sizeof(int32_t)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp2, cap * 2 * sizeof(double)))) return rc;
@@ -1446,37 +1443,12 @@ static int mig_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t
         FW_HIP(ctx, hipMemcpyAsync(&h, ctx->d_tmp0.ptr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->cnt.kernel_launches += 1;
-        if (h.n_sig > ctx->l0_cap_hint) ctx->l0_cap_hint = h.n_sig;
-        if (h.n_sig <= cap) break;
-        if (attempt == 1) return fw_fail(ctx, FW_ERR_DEVICE, "discrete level-0 (generic form): result buffer overflow twice");
-        cap = h.n_sig;
-    }
-    *m_reliable = npairs - (long long)h.n_unreliable;  // (sharded runs: this rank's share; fw_level0_sharded adds the ranks' counts up)
-    const size_t k = (size_t)h.n_sig;
-    pi.clear();
-    pj.clear();
-    stat.clear();
-    pval.clear();
-    if (dev) {
-        *dev = FwL0Dev{};
-        dev->i = oi;
-        dev->j = oj;
-        dev->stat64 = os;
-        dev->pval = op;
-        dev->k = k;
+        n.first = h.n_sig;
         return FW_OK;
-    }
-    pi.resize(k);
-    pj.resize(k);
-    stat.resize(k);
-    pval.resize(k);
-    if (k) {
-        FW_HIP(ctx, hipMemcpy(pi.data(), oi, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        FW_HIP(ctx, hipMemcpy(pj.data(), oj, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        FW_HIP(ctx, hipMemcpy(stat.data(), os, k * sizeof(double), hipMemcpyDeviceToHost));
-        FW_HIP(ctx, hipMemcpy(pval.data(), op, k * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return FW_OK;
+    });
+    if (rc) return rc;
+    *m_reliable = npairs - (long long)h.n_unreliable;  // (sharded runs: this rank's share; fw_level0_sharded adds the ranks' counts up)
+    return fwi_l0_handover(ctx, oi, oj, os, nullptr, op, (size_t)h.n_sig, pi, pj, stat, pval, dev);
 }
 
 // The planes of the three-level form as the host scan of a CSC triple leaves them (nzb, hib), or the caller's [p][n] table in device
@@ -1768,7 +1740,6 @@ static double host_igamc(double a, double x)
 int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                   std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev)
 {
-    if (dev) *dev = FwL0Dev{};
     if (ctx->mi_generic) return mig_level0(ctx, pi, pj, stat, pval, m_reliable, dev);
     const int p = ctx->P.p;
     const long long npairs = (long long)p * (p - 1) / 2;
@@ -1831,12 +1802,10 @@ int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
     const MiDev P = mi_dev(ctx);
     // ---- kernel 1: popcounts + exact reliability/df + Float32 screen -> candidate records ----
     static const int l0_dbg = fw_knob_int(knob::FW_L0_DBG, 0);  // profiling only (invalid results)
-    unsigned long long cap_c = (unsigned long long)std::min<long long>(npairs, 8ll << 20);
-    if (cap_c < ctx->l0_cap_hint) cap_c = ctx->l0_cap_hint;  // a repeated call does not overflow (and re-run the kernel) again
-    if (cap_c == 0) cap_c = 1;
     MiL0Counters h1{};
     double *d_gthr = nullptr;
-    for (int attempt = 0;; ++attempt) {
+    rc = fwi_l0_attempts(ctx, npairs, 8ll << 20, "discrete level-0: candidate buffer", [&](unsigned long long cap_c, FwL0Counts &nc) -> int {
+        int rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_tmp0, 2 * sizeof(MiL0Counters) + 8 * sizeof(double) + 8 * sizeof(unsigned long long)))) return rc;
         if ((rc = fw_dev_reserve(ctx, ctx->d_jobs, cap_c * sizeof(MiCand)))) return rc;
         FW_HIP(ctx, hipMemsetAsync(ctx->d_tmp0.ptr, 0, 2 * sizeof(MiL0Counters), ctx->stream));
@@ -1876,19 +1845,14 @@ int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
             fprintf(stderr, "[fw] mi_level0_mfma_kernel, shader cycles per tile (%llu tiles): staging + matrix loop %.0f, first pass %.0f, second pass %.0f, queue %.0f; pairs for the second pass per tile %.0f\n",
                     hp[4], hp[0] / nt, hp[1] / nt, hp[2] / nt, hp[3] / nt, hp[5] / nt);
         }
-        if (h1.n_sig > ctx->l0_cap_hint) ctx->l0_cap_hint = h1.n_sig;
-        if (h1.n_sig <= cap_c) break;
-        if (attempt == 1) return fw_fail(ctx, FW_ERR_DEVICE, "discrete level-0: candidate buffer overflow twice");
-        cap_c = h1.n_sig;
-    }
+        nc.first = h1.n_sig;
+        return FW_OK;
+    });
+    if (rc) return rc;
     const unsigned long long ncand = h1.n_sig;
     *m_reliable = npairs - (long long)h1.n_unreliable;
     if (fw_l0_verbose()) fprintf(stderr, "[fw] discrete level-0: pairs %lld reliable %lld candidates %llu\n", npairs, (long long)*m_reliable, ncand);
-    pi.clear();
-    pj.clear();
-    stat.clear();
-    pval.clear();
-    if (ncand == 0) return FW_OK;
+    if (ncand == 0) return fwi_l0_handover(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0, pi, pj, stat, pval, dev);
     // ---- kernel 2: exact Float64 statistic + p-value of the candidates ----
     MiL0Counters *d_cnt2 = (MiL0Counters *)ctx->d_tmp0.ptr + 1;
     if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, ncand * 2 * sizeof(int32_t)))) return rc;
@@ -1904,47 +1868,70 @@ int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &p
     FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cnt.kernel_launches += 1;
     *m_reliable -= (long long)h2.n_unreliable;  // pairs the screening kernel handed over unscreened (mi_pair_epilogue)
-    const size_t k = (size_t)h2.n_sig;
-    if (dev) {  // results stay on the device for fwi_bh_csr_device
-        dev->i = oi;
-        dev->j = oj;
-        dev->stat64 = os;
-        dev->pval = op;
-        dev->k = k;
-        return FW_OK;
-    }
-    pi.resize(k);
-    pj.resize(k);
-    stat.resize(k);
-    pval.resize(k);
-    if (k) {
-        FW_HIP(ctx, hipMemcpy(pi.data(), oi, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        FW_HIP(ctx, hipMemcpy(pj.data(), oj, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        FW_HIP(ctx, hipMemcpy(stat.data(), os, k * sizeof(double), hipMemcpyDeviceToHost));
-        FW_HIP(ctx, hipMemcpy(pval.data(), op, k * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    return FW_OK;
+    return fwi_l0_handover(ctx, oi, oj, os, nullptr, op, (size_t)h2.n_sig, pi, pj, stat, pval, dev);
+}
+
+// ---- which instantiation of the conditional-test kernels (mi_test_batch_kernel, mi_subsets_seg_kernel) ----
+// L = 0: the generic form, which has the one instantiation <0, 2, false, false>; else the context's levels and cells per stratum side.
+// BIG: the large LDS table for conditioning sets beyond FW_MAX_K_FAST, where the caller may use it (fwi_mi_big_limits; it has no PRE
+// and no WIDE form).  WIDE: 32-bit cell counts and tables (fw_mi_core.h), and then no PRE.  kmax: the largest conditioning set the
+// launch can meet.
+struct MiVariant {
+    int L, NXY;
+    bool PRE, WIDE, BIG;
+};
+static MiVariant mi_variant(const fw_ctx *ctx, int kmax, bool may_big)
+{
+    if (ctx->mi_generic) return {0, 2, false, false, false};
+    const int L = ctx->L == 2 ? 2 : 3, NXY = (ctx->L == 2 || ctx->mi_nxy == 2) ? 2 : 3;
+    if (may_big && kmax > FW_MAX_K_FAST) return {L, NXY, false, false, true};
+    const bool wide = ctx->P.n > 65535;
+    return {L, NXY, !wide && ctx->P.n <= MI_PRE_N && kmax <= MI_PRE_K, wide, false};
+}
+template <int L_, int NXY_, bool PRE_, bool WIDE_, bool BIG_> struct MiTag {
+    static constexpr int L = L_, NXY = NXY_;
+    static constexpr bool PRE = PRE_, WIDE = WIDE_, BIG = BIG_;
+};
+// f(MiTag<...>{}) for the variant: exactly the instantiations named here exist
+template <int L, int NXY, class F> static void mi_dispatch_ln(const MiVariant &v, F &f)
+{
+    if (v.BIG)
+        f(MiTag<L, NXY, false, false, true>{});
+    else if (v.WIDE)
+        f(MiTag<L, NXY, false, true, false>{});
+    else if (v.PRE)
+        f(MiTag<L, NXY, true, false, false>{});
+    else
+        f(MiTag<L, NXY, false, false, false>{});
+}
+template <class F> static void mi_dispatch(const MiVariant &v, F &&f)
+{
+    if (v.L == 0)
+        f(MiTag<0, 2, false, false, false>{});
+    else if (v.L == 2)
+        mi_dispatch_ln<2, 2>(v, f);
+    else if (v.NXY == 2)
+        mi_dispatch_ln<3, 2>(v, f);
+    else
+        mi_dispatch_ln<3, 3>(v, f);
+}
+
+static void mi_seg_launch(const fw_ctx *ctx, const MiVariant &v, const MiDev &P, unsigned grid, hipStream_t stream, const FwSeg *d_segs,
+                          const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns, int need_p)
+{
+    mi_dispatch(v, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((mi_subsets_seg_kernel<T::L, T::NXY, T::PRE, T::WIDE, T::BIG>), dim3(grid), dim3(256), 0, stream, P, d_segs, d_acc, d_out,
+                           ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, d_ns, need_p);
+    });
 }
 
 // Device-driven rounds (fw_devhiton.hip)
 int fwi_mi_segments_dev(fw_ctx *ctx, unsigned grid, const FwSeg *d_segs, const int32_t *d_acc, FwSegOut *d_out, const unsigned *d_ns,
                         hipStream_t stream)
 {
-#define MI_SEG_LAUNCH(LL, NN, PP, WW)                                                                                                  \
-    hipLaunchKernelGGL((mi_subsets_seg_kernel<LL, NN, PP, WW>), dim3(grid), dim3(256), 0, stream, mi_dev_subsets(ctx), d_segs, d_acc, d_out, \
-                       ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, d_ns, 0 /* HITON-PC never reads a rejected test's p */)
-    const bool pre = ctx->P.n <= MI_PRE_N && ctx->P.max_k <= MI_PRE_K;
-    const bool wide = ctx->P.n > 65535;  // 32-bit cell counts and tables (fw_mi_core.h)
-    if (ctx->mi_generic) {
-        MI_SEG_LAUNCH(0, 2, false, false);
-    } else if (ctx->L == 2) {
-        if (wide) MI_SEG_LAUNCH(2, 2, false, true); else if (pre) MI_SEG_LAUNCH(2, 2, true, false); else MI_SEG_LAUNCH(2, 2, false, false);
-    } else if (ctx->mi_nxy == 2) {
-        if (wide) MI_SEG_LAUNCH(3, 2, false, true); else if (pre) MI_SEG_LAUNCH(3, 2, true, false); else MI_SEG_LAUNCH(3, 2, false, false);
-    } else {
-        if (wide) MI_SEG_LAUNCH(3, 3, false, true); else if (pre) MI_SEG_LAUNCH(3, 3, true, false); else MI_SEG_LAUNCH(3, 3, false, false);
-    }
-#undef MI_SEG_LAUNCH
+    mi_seg_launch(ctx, mi_variant(ctx, ctx->P.max_k, false), mi_dev_subsets(ctx), grid, stream, d_segs, d_acc, d_out, d_ns,
+                  0 /* HITON-PC never reads a rejected test's p */);
     FW_HIP(ctx, hipGetLastError());
     return FW_OK;
 }
@@ -1971,20 +1958,9 @@ int fwi_mi_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y
     for (int64_t t = 0; t < m; ++t)
         if (zoff[t + 1] - zoff[t] > MI_MAX_K)
             return fw_fail(ctx, FW_ERR_LIMIT, "discrete tests support at most %d conditioning variables", MI_MAX_K);
-    const int64_t nz = zoff[m];
+    FwBatch b;
     int rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_jobs, (size_t)m * 2 * sizeof(int32_t) + (size_t)(m + 1) * sizeof(int64_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_acc, (size_t)(nz > 0 ? nz : 1) * sizeof(int32_t)))) return rc;
-    if ((rc = fw_dev_reserve(ctx, ctx->d_out, (size_t)m * sizeof(fw_test_result)))) return rc;
-    long long *dz = (long long *)ctx->d_jobs.ptr;
-    int32_t *dX = (int32_t *)(dz + m + 1), *dY = dX + m;
-    FW_HIP(ctx, hipMemcpyAsync(dz, zoff, (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dX, X, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipMemcpyAsync(dY, Y, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (nz > 0)
-        FW_HIP(ctx, hipMemcpyAsync(ctx->d_acc.ptr, zflat, (size_t)nz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    int kmax = 0;
-    for (int64_t t = 0; t < m; ++t) kmax = std::max<int>(kmax, (int)(zoff[t + 1] - zoff[t]));
+    if ((rc = fwi_batch_upload(ctx, m, X, Y, zoff, zflat, b))) return rc;
     MiDev Pd = mi_dev(ctx);
     static const bool prof = fw_knob_set(knob::FW_MI_PROF);
     if (prof) {
@@ -1992,38 +1968,23 @@ int fwi_mi_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y
         FW_HIP(ctx, hipMemsetAsync(ctx->d_tmp0.ptr, 0, (size_t)m * 8 * sizeof(unsigned long long), ctx->stream));
         Pd.prof = (unsigned long long *)ctx->d_tmp0.ptr;
     }
-#define MI_TB_LAUNCH(LL, NN, PP, WW)                                                                                                         \
-    hipLaunchKernelGGL((mi_test_batch_kernel<LL, NN, PP, WW>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, Pd, \
-                       (long long)m, dX, dY, dz, (const int32_t *)ctx->d_acc.ptr, (fw_test_result *)ctx->d_out.ptr)
-    const bool pre = ctx->P.n <= MI_PRE_N && kmax <= MI_PRE_K;  // the batch's own largest conditioning set decides here
-    const bool wide = ctx->P.n > 65535;
-    if (kmax > FW_MAX_K_FAST && !ctx->mi_generic) {  // conditioning sets of 6 and 7 variables: the large table
-        if (int rcb = fwi_mi_big_limits(ctx, kmax)) return rcb;
-#define MI_TB_LAUNCH_BIG(LL, NN)                                                                                                             \
-    hipLaunchKernelGGL((mi_test_batch_kernel<LL, NN, false, false, true>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, Pd, \
-                       (long long)m, dX, dY, dz, (const int32_t *)ctx->d_acc.ptr, (fw_test_result *)ctx->d_out.ptr)
-        if (ctx->L == 2) MI_TB_LAUNCH_BIG(2, 2); else if (ctx->mi_nxy == 2) MI_TB_LAUNCH_BIG(3, 2); else MI_TB_LAUNCH_BIG(3, 3);
-#undef MI_TB_LAUNCH_BIG
-    } else if (ctx->mi_generic) {
-        // (tables in device memory: launches of as many workgroups as fit the table budget, one after the other on the stream)
-        const int64_t wgs_all = (m + 3) / 4, wgs_max = mig_launch_wgs(ctx, wgs_all);
-        if ((rc = mig_dev_tables(ctx, Pd, wgs_max, 0))) return rc;
+    // (the batch's own largest conditioning set decides; 6 and 7 variables: the large table)
+    if (b.kmax > FW_MAX_K_FAST && !ctx->mi_generic)
+        if ((rc = fwi_mi_big_limits(ctx, b.kmax))) return rc;
+    // generic form with its tables in device memory: launches of as many workgroups as fit the table budget, one after the other on
+    // the stream; every other form: one launch
+    const int64_t wgs_all = (m + 3) / 4, wgs_max = mig_launch_wgs(ctx, wgs_all);
+    if ((rc = mig_dev_tables(ctx, Pd, wgs_max, 0))) return rc;
+    mi_dispatch(mi_variant(ctx, b.kmax, true), [&](auto tag) {
+        using T = decltype(tag);
         for (int64_t w0 = 0; w0 < wgs_all; w0 += wgs_max) {
             const int64_t t0 = 4 * w0, mc = std::min<int64_t>(m - t0, 4 * wgs_max);
-            hipLaunchKernelGGL((mi_test_batch_kernel<0, 2, false, false>), dim3((unsigned)((mc + 3) / 4)), dim3(256), 0, ctx->stream, Pd, (long long)mc, dX + t0,
-                               dY + t0, dz + t0, (const int32_t *)ctx->d_acc.ptr, (fw_test_result *)ctx->d_out.ptr + t0);
+            hipLaunchKernelGGL((mi_test_batch_kernel<T::L, T::NXY, T::PRE, T::WIDE, T::BIG>), dim3((unsigned)((mc + 3) / 4)), dim3(256), 0, ctx->stream,
+                               Pd, (long long)mc, (const int32_t *)b.dX + t0, (const int32_t *)b.dY + t0, (const long long *)b.dz + t0, b.dzflat,
+                               b.dout + t0);
         }
-    } else if (ctx->L == 2) {
-        if (wide) MI_TB_LAUNCH(2, 2, false, true); else if (pre) MI_TB_LAUNCH(2, 2, true, false); else MI_TB_LAUNCH(2, 2, false, false);
-    } else if (ctx->mi_nxy == 2) {
-        if (wide) MI_TB_LAUNCH(3, 2, false, true); else if (pre) MI_TB_LAUNCH(3, 2, true, false); else MI_TB_LAUNCH(3, 2, false, false);
-    } else {
-        if (wide) MI_TB_LAUNCH(3, 3, false, true); else if (pre) MI_TB_LAUNCH(3, 3, true, false); else MI_TB_LAUNCH(3, 3, false, false);
-    }
-#undef MI_TB_LAUNCH
-    FW_HIP(ctx, hipGetLastError());
-    FW_HIP(ctx, hipMemcpyAsync(out, ctx->d_out.ptr, (size_t)m * sizeof(fw_test_result), hipMemcpyDeviceToHost, ctx->stream));
-    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    });
+    if ((rc = fwi_batch_finish(ctx, m, out))) return rc;
     if (prof) {
         std::vector<unsigned long long> hv((size_t)m * 8);
         FW_HIP(ctx, hipMemcpy(hv.data(), ctx->d_tmp0.ptr, hv.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -2034,7 +1995,6 @@ int fwi_mi_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y
         fprintf(stderr, "[fw] mi test phases, shader cycles per test: counting %.0f, occupancy/power %.0f, MI terms %.0f (of %.0f%% with power), p-value %.0f\n",
                 h[0] / nt, h[1] / nt, h[2] / nm, 100.0 * nm / nt, h[3] / nt);
     }
-    ctx->cnt.kernel_launches += 1;
     return FW_OK;
 }
 
@@ -2042,32 +2002,14 @@ int fwi_mi_segments(fw_ctx *ctx, int64_t nseg, const FwSeg *d_segs, const int32_
 {
     if (nseg == 0) return FW_OK;
     FW_HIP(ctx, hipEventRecord(pb.ev0, pb.launch_stream));
-#define MI_SEG_LAUNCH(LL, NN, PP, WW)                                                                                                       \
-    hipLaunchKernelGGL((mi_subsets_seg_kernel<LL, NN, PP, WW>), dim3((unsigned)nseg), dim3(256), 0, pb.launch_stream, mi_dev_subsets(ctx), d_segs, \
-                       d_acc, d_out, ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, (const unsigned *)nullptr, 1)
-    const bool pre = ctx->P.n <= MI_PRE_N && ctx->P.max_k <= MI_PRE_K;
-    const bool wide = ctx->P.n > 65535;  // 32-bit cell counts and tables (fw_mi_core.h)
-    if (ctx->P.max_k > FW_MAX_K_FAST && !ctx->mi_generic) {  // conditioning sets of 6 and 7 variables: the large table (fwi_mi_big_limits holds)
-#define MI_SEG_LAUNCH_BIG(LL, NN)                                                                                                           \
-    hipLaunchKernelGGL((mi_subsets_seg_kernel<LL, NN, false, false, true>), dim3((unsigned)nseg), dim3(256), 0, pb.launch_stream, mi_dev_subsets(ctx), \
-                       d_segs, d_acc, d_out, ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, (const unsigned *)nullptr, 1)
-        if (ctx->L == 2) MI_SEG_LAUNCH_BIG(2, 2); else if (ctx->mi_nxy == 2) MI_SEG_LAUNCH_BIG(3, 2); else MI_SEG_LAUNCH_BIG(3, 3);
-#undef MI_SEG_LAUNCH_BIG
-    } else if (ctx->mi_generic) {
-        MiDev Pg = mi_dev_subsets(ctx);
-        const int64_t wgs_max = mig_launch_wgs(ctx, nseg);
-        if (int rcg = mig_dev_tables(ctx, Pg, wgs_max, &pb == &ctx->pb[1] ? 2 : 1)) return rcg;
-        for (int64_t s0 = 0; s0 < nseg; s0 += wgs_max)
-            hipLaunchKernelGGL((mi_subsets_seg_kernel<0, 2, false, false>), dim3((unsigned)std::min<int64_t>(wgs_max, nseg - s0)), dim3(256), 0, pb.launch_stream, Pg,
-                               d_segs + s0, d_acc, d_out + s0, ctx->P.max_k, ctx->P.alpha, (long long)ctx->P.max_tests, (const unsigned *)nullptr, 1);
-    } else if (ctx->L == 2) {
-        if (wide) MI_SEG_LAUNCH(2, 2, false, true); else if (pre) MI_SEG_LAUNCH(2, 2, true, false); else MI_SEG_LAUNCH(2, 2, false, false);
-    } else if (ctx->mi_nxy == 2) {
-        if (wide) MI_SEG_LAUNCH(3, 2, false, true); else if (pre) MI_SEG_LAUNCH(3, 2, true, false); else MI_SEG_LAUNCH(3, 2, false, false);
-    } else {
-        if (wide) MI_SEG_LAUNCH(3, 3, false, true); else if (pre) MI_SEG_LAUNCH(3, 3, true, false); else MI_SEG_LAUNCH(3, 3, false, false);
-    }
-#undef MI_SEG_LAUNCH
+    // (conditioning sets of 6 and 7 variables: the large table, fwi_mi_big_limits holds.)  Generic form with its tables in device
+    // memory: launches of as many workgroups as fit the table budget; every other form: one launch
+    MiDev P = mi_dev_subsets(ctx);
+    const MiVariant v = mi_variant(ctx, ctx->P.max_k, true);
+    const int64_t wgs_max = mig_launch_wgs(ctx, nseg);
+    if (int rc = mig_dev_tables(ctx, P, wgs_max, &pb == &ctx->pb[1] ? 2 : 1)) return rc;
+    for (int64_t s0 = 0; s0 < nseg; s0 += wgs_max)
+        mi_seg_launch(ctx, v, P, (unsigned)std::min<int64_t>(wgs_max, nseg - s0), pb.launch_stream, d_segs + s0, d_acc, d_out + s0, nullptr, 1);
     FW_HIP(ctx, hipGetLastError());
     FW_HIP(ctx, hipEventRecord(pb.ev1, pb.launch_stream));
     return FW_OK;
