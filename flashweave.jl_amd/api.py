@@ -10,8 +10,8 @@ import numpy as np
 
 from . import io as fio
 from . import preprocess as pre
-from .engine import (CSC, Engine, abundance_defect, as_csc, is_device_tensor, is_sparse, normalize_abundances, normalize_counts,
-                     rejections_dict, tss_range_defect)
+from .engine import (CSC, Engine, abundance_defect, as_csc, is_device_tensor, is_sparse, is_sparse_csc_tensor, normalize_abundances,
+                     normalize_counts, rejections_dict, tss_range_defect)
 
 
 class FWResult(dict):
@@ -57,6 +57,7 @@ def _integral(a):
 def _integral_tensor(t):
     """_integral for a table in GPU memory, in torch ops on the device (booleans count as 0 / 1)"""
     import torch
+    t = t.values() if is_sparse_csc_tensor(t) else t  # (a sparse CSC tensor: its stored values; the absent cells are zeros)
     if not t.numel() or t.dtype.is_complex:
         return False
     if t.dtype.is_floating_point and not (bool(torch.isfinite(t).all()) and bool((t == torch.floor(t)).all())):
@@ -68,14 +69,15 @@ def _tensor_refusals(who, t, device, normalize, abundances, meta_data=None, meta
                      distributed=False, csc_resident=False):
     """What a table in GPU memory (a torch tensor, engine.is_device_tensor) is not served with: each would need the table's bytes on
     the host, and copying silently would defeat the point.  Every refusal names its option and the way out (tensor.cpu()), before any
-    library call; the last one looks at the values, with torch ops on the device."""
+    library call; the last one looks at the values, with torch ops on the device.  A sparse CSC tensor is the sparse table of this
+    path and gets the same refusals but csc_resident=True (served, for fz_nz); every other sparse layout is refused."""
     import torch
 
     def no(option, why):
         raise ValueError("%s: %s with a table in GPU memory is not supported: %s; pass tensor.cpu() instead" % (who, option, why))
-    if t.layout != torch.strided:
+    if t.layout not in (torch.strided, torch.sparse_csc):
         raise ValueError("%s: a sparse torch tensor is not supported: scipy.sparse is the sparse interface; build a scipy matrix from "
-                         "tensor.cpu() instead (or pass tensor.to_dense())" % who)
+                         "tensor.cpu() instead (or pass tensor.to_dense()); of the sparse layouts only tensor.to_sparse_csc() is taken" % who)
     numeric = t.dtype.is_floating_point or t.dtype in (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
     if t.dim() != 2 or not numeric:
         raise ValueError("%s: a device tensor must be a 2-D samples x variables table of a numeric dtype (got %d dimensions, %s); "
@@ -92,7 +94,7 @@ def _tensor_refusals(who, t, device, normalize, abundances, meta_data=None, meta
         no("device_normalize=False", "the host front-end reads host memory")
     if distributed:
         no("distributed=True", "the digest the ranks compare needs the table's bytes on the host")
-    if csc_resident:
+    if csc_resident and t.layout == torch.strided:
         no("csc_resident=True", "the CSC-resident layout is built from a scipy.sparse matrix")
     if t.device.index != device:
         raise ValueError("%s: device=%d while the tensor lives on %s: pass the device the table is on, or tensor.cpu() instead"
@@ -286,7 +288,7 @@ def _extra_tables(who, data, extra_data, test_name, normalize, n_named=None, abu
 def _abundance_refusals(who, data, extra):
     """abundances=True: every table of real values (the OTU block where a meta_mask split the table) holds finite values >= 0."""
     for name, tab in [("data", data)] + [("extra_data[%d]" % i, t) for i, (t, _) in enumerate(extra)]:
-        defect = abundance_defect(tab.nzval if isinstance(tab, CSC) else tab)
+        defect = abundance_defect(tab.nzval if isinstance(tab, CSC) else tab.values() if is_sparse_csc_tensor(tab) else tab)
         if defect:
             raise ValueError("%s: abundances=True: %s holds %s; abundances are finite and >= 0" % (who, name, defect))
 
@@ -405,7 +407,8 @@ def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extr
     (is an engine.CSC tuple a sparse table?) and strict_header (is a header of another length than the table refused without a mask
     as well?).  abundances (with normalize): a sparse block is made canonical as Float64 instead of as counts, and the value refusals
     come last.  -> _Tables; header is the caller's object when one was given and nothing was split off."""
-    sparse = _any_sparse(data) if csc_tuple_is_sparse else is_sparse(data)
+    dev_csc = is_sparse_csc_tensor(data) and is_device_tensor(who, data)  # a sparse table in GPU memory: canonical as it comes, never touched here
+    sparse = (_any_sparse(data) if csc_tuple_is_sparse else is_sparse(data)) or dev_csc
     data = data if (sparse or is_device_tensor(who, data)) else np.asarray(data)  # (a table in GPU memory stays where it is)
     mask = _meta_mask_vector(who, meta_mask, meta_data, data)
     if sparse:
@@ -416,7 +419,7 @@ def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extr
         raise ValueError("%s: a header of %d names for %d columns%s" % (who, len(header), _shape(data)[1], "" if strict_header else
                          ": with a meta_mask the header names all columns of data, the meta ones included"))
     if mask is None or not normalize:
-        data = _canonical_csc(who, data, test_name, normalize, abundances) if sparse else data
+        data = _canonical_csc(who, data, test_name, normalize, abundances) if (sparse and not dev_csc) else data
         if mask is not None:  # the prepared matrix is taken as it is; its marked columns are only looked at
             _finite_meta(who, pre._csc_take_cols(*data[:3], np.nonzero(mask)[0])[2] if sparse else data[:, mask])
         extra = _extra_tables(who, data, extra_data, test_name, normalize, abundances=abundances)  # (refused by name before any device call)
@@ -446,7 +449,7 @@ def _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense
         if test_name != "fz_nz":
             raise ValueError("learn_network: csc_resident=True is served for sensitive=True, heterogeneous=True (fz_nz) only; the discrete "
                              "kinds are bit-packed already and the plain fz test needs the dense matrix")
-        if not is_sparse(data):
+        if not (is_sparse(data) or (is_sparse_csc_tensor(data) and is_device_tensor("learn_network", data))):
             raise ValueError("learn_network: csc_resident=True needs sparse data (a scipy.sparse matrix); a dense table is not "
                              "converted silently")
         if not recursive_pcor:
@@ -482,7 +485,7 @@ def _matrix(t, test_name, normalize, prec, device_normalize, device, abundances=
                                                          [None] * len(t.extra) + [t.mask], [everyone] * (len(t.extra) + 1))
         meta_mask = None if t.mask is None else [bool(v) for v in combined_mask]
     else:  # the prepared matrix as it is: dense, or Int32 CSC for mi / mi_nz, Float32 CSC for fz_nz
-        mat = tuple(t.data[:3]) if t.sparse else t.data
+        mat = tuple(t.data[:3]) if (t.sparse and not is_sparse_csc_tensor(t.data)) else t.data
     return mat, header, meta_mask, on_device, time.perf_counter() - t0
 
 
@@ -541,7 +544,7 @@ def _tss_range_refusals(who, norm_mode, data, extra):
     """A TSS norm_mode on tables of real values: every positive value lies in [2^-126, 2^96], so that it does not vanish as a Float32
     and the Float32 sum of a sample (fewer than 2^31 terms) stays finite."""
     for name, tab in [("data", data)] + [("extra_data[%d]" % i, t) for i, (t, _) in enumerate(extra)]:
-        defect = tss_range_defect(tab.nzval if isinstance(tab, CSC) else tab)
+        defect = tss_range_defect(tab.nzval if isinstance(tab, CSC) else tab.values() if is_sparse_csc_tensor(tab) else tab)
         if defect:
             raise ValueError("%s: norm_mode=%r with abundances=True: %s holds %s" % (who, norm_mode, name, defect))
 
@@ -587,7 +590,9 @@ def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data
     (n_out, p_out) view with strides (1, n_out), the bits of the numpy call; header and the two masks come back as always.  Every
     norm_mode and the three binning options are served; meta_data, meta_mask, extra_data, prec=64, device_normalize=False, a
     non-integral tensor without abundances=True, a tensor of another GPU, one that is not 2-D or not numeric and a sparse tensor raise a
-    ValueError that names the option and says to pass tensor.cpu() instead (see learn_network).
+    ValueError that names the option and says to pass tensor.cpu() instead (see learn_network).  A sparse CSC tensor in GPU memory
+    (layout torch.sparse_csc, canonical: see learn_network) is the sparse table of that path: `data` comes back as a sparse CSC tensor
+    on the same device over the front-end's output buffers (a dense tensor for "fz"), the bits of the scipy call.
     -> dict(data, header, meta_mask, row_mask): row_mask over the input samples, data a scipy.sparse.csc_matrix for sparse tables
     (dense for "fz")."""
     who = "normalize_data"
@@ -720,6 +725,18 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     call: meta_data, meta_mask, extra_data, prec=64, device_normalize=False, distributed=True, csc_resident=True, a non-integral tensor
     without abundances=True, a tensor of another GPU than `device`, one that is not 2-D or not numeric, a sparse tensor.  A CPU tensor
     is an array (np.asarray); any other device type raises ValueError.
+    A sparse table in GPU memory: a 2-D tensor with layout torch.sparse_csc (what torch.sparse_csc_tensor builds over a canonical
+    scipy triple moved to the GPU) is the sparse form of that path, for every test, abundances=True included.  Its three arrays are
+    borrowed where they lie (fw_normalize_counts_csc_dev / fw_normalize_abund_csc_dev write the output triple into device buffers,
+    fw_set_data_csc_i32_dev / fw_set_data_csc_f32_dev / fw_set_data_csc_f32_resident_dev build the resident layout from them); of the
+    table only the p + 1 column pointers and the front-end's small per-column and per-row records reach the host.  The result is the
+    FWResult of the same table as a scipy.sparse.csc_matrix, to the bit, with counters["sparse_input"], counters["table_on_device"]
+    and parameters["table_on_device"] all True.  It gets the refusals of a dense device tensor -- the same option names, the same way
+    out -- except csc_resident=True, which is served for fz_nz as for scipy, and the sparse refusal of sensitive=True,
+    heterogeneous=False, normalize=False.  Unlike a scipy matrix it is not made canonical (no duplicates summed, stored zeros
+    dropped or rows sorted on the device): it must be canonical already, and one that is not raises FlashWeaveError naming the column
+    (ValueError when the column pointers themselves do not run from 0 to the number of entries); for fz_nz with normalize=False a
+    stored 0.0 is an absence.  Every other sparse layout (COO, CSR, BSR, BSC) stays refused: tensor.to_sparse_csc() converts.
     Path form (learning.jl:354-401): data may be a path (str / os.PathLike) or a list of paths, read with io.load_data (.tsv, .csv,
     BIOM 1.0 JSON; anything else raises what load_data raises): the first is the main table, the others become extra_data under their
     file headers; meta_data_path (second positional argument, as in the reference) is the main table's meta data file;

@@ -543,6 +543,59 @@ int fw_set_data_dense_f32_dev(fw_ctx *c, const float *d_data)
     return FW_OK;
 }
 
+// ---- CSC triples that already live in device memory (a sparse torch tensor's three arrays): borrowed where they lie.  Every pointer
+// is asked of the runtime, then the p + 1 column pointers are downloaded and checked, before any kernel reads rowval or nzval.  The
+// kernels, the state rules and the refusals are those of the host forms.
+int fw_set_data_csc_i32_dev(fw_ctx *c, const int64_t *d_colptr, const int32_t *d_rowval, const int32_t *d_nzval, int64_t nnz)
+{
+    CHECK_CTX(c);
+    if (c->P.kind == FW_FZ || c->P.kind == FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_csc_i32_dev: context is not discrete");
+    if (int rc = fwi_csc_dev_ptrs(c, "fw_set_data_csc_i32_dev", c->P.device, d_colptr, d_rowval, d_nzval, nnz)) return rc;
+    std::vector<int64_t> colptr;
+    if (int rc = fwi_csc_dev_colptr(c, "fw_set_data_csc_i32_dev", d_colptr, c->P.p, nnz, colptr)) return rc;
+    int rc = fwi_mi_upload_csc_dev(c, d_colptr, d_rowval, d_nzval, nnz);  // (a refused triple leaves the context as it was)
+    if (rc) return rc;
+    resolve_n_obs_min_discrete(c);
+    c->have_data = true;
+    c->have_level0 = false;
+    c->have_network = false;
+    return FW_OK;
+}
+
+int fw_set_data_csc_f32_dev(fw_ctx *c, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, int64_t nnz)
+{
+    CHECK_CTX(c);
+    if (c->P.kind != FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_csc_f32_dev: context is not FW_FZ_NZ");
+    if (int rc = fwi_csc_dev_ptrs(c, "fw_set_data_csc_f32_dev", c->P.device, d_colptr, d_rowval, d_nzval, nnz)) return rc;
+    std::vector<int64_t> colptr;
+    if (int rc = fwi_csc_dev_colptr(c, "fw_set_data_csc_f32_dev", d_colptr, c->P.p, nnz, colptr)) return rc;
+    c->have_data = false;  // (a triple refused from here on leaves the resident layout half written, as in fw_set_data_csc_f32)
+    c->have_level0 = false;
+    c->have_network = false;
+    int rc = fwi_fznz_upload_csc_dev(c, d_colptr, d_rowval, d_nzval, nnz);
+    if (rc) return rc;
+    c->have_data = true;
+    return FW_OK;
+}
+
+int fw_set_data_csc_f32_resident_dev(fw_ctx *c, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, int64_t nnz)
+{
+    CHECK_CTX(c);
+    if (c->P.kind != FW_FZ_NZ) return fw_fail(c, FW_ERR_ARG, "fw_set_data_csc_f32_resident_dev: context is not FW_FZ_NZ");
+    if (!c->P.recursive_pcor)
+        return fw_fail(c, FW_ERR_LIMIT, "fw_set_data_csc_f32_resident_dev: recursive_pcor = 0 is not served on the CSC-resident layout (its kernels "
+                                        "stream whole dense columns); use fw_set_data_csc_f32_dev");
+    if (int rc = fwi_csc_dev_ptrs(c, "fw_set_data_csc_f32_resident_dev", c->P.device, d_colptr, d_rowval, d_nzval, nnz)) return rc;
+    std::vector<int64_t> colptr;
+    if (int rc = fwi_csc_dev_colptr(c, "fw_set_data_csc_f32_resident_dev", d_colptr, c->P.p, nnz, colptr)) return rc;
+    int rc = fwi_fznz_upload_csc_resident_dev(c, d_colptr, d_rowval, d_nzval, nnz);  // (a refused triple leaves the context as it was)
+    if (rc) return rc;
+    c->have_data = true;
+    c->have_level0 = false;
+    c->have_network = false;
+    return FW_OK;
+}
+
 int fw_get_levels(const fw_ctx *c, int32_t *levels, int32_t *max_vals)
 {
     CHECK_CTX(c);

@@ -1,5 +1,6 @@
-// Structure check of a CSC triple on the device, shared by the two entry points that take one from the caller and read it in
-// kernels (fw_normalize_counts_csc in fw_norm.hip, fw_set_data_csc_f32 in fw_fz.hip): one wavefront per column, one pass.
+// Structure check of a CSC triple on the device, shared by the entry points that take one from the caller and read it in kernels
+// (fw_normalize_*_csc and their _dev forms in fw_norm.hip, fw_set_data_csc_f32* and their _dev forms in fw_fz.hip; fw_set_data_csc_i32_dev
+// in fw_mi.hip takes the column range from here and looks at rows and values in one loop of its own): one wavefront per column, one pass.
 // A column is good when colptr[j] <= colptr[j+1] lie in 0 .. nnz and its rows are 0 <= row < n, strictly ascending.  Nothing
 // outside [0, nnz) is read, so a broken colptr cannot make the check itself fault.
 #ifndef FW_CSC_H
@@ -23,18 +24,23 @@ __device__ inline int fw_wave_or(int v)
     return v;
 }
 
+// *a, *b = the entry range of column j, empty when colptr is broken (-> false): 0 <= colptr[j] <= colptr[j+1] <= nnz.
+__device__ inline bool fw_csc_column_range(const int64_t *__restrict__ colptr, int j, long long nnz, long long *a, long long *b)
+{
+    const long long lo = colptr[j], hi = colptr[j + 1];
+    const bool good = lo >= 0 && lo <= hi && hi <= nnz;
+    *a = good ? lo : 0;
+    *b = good ? hi : 0;
+    return good;
+}
+
 // Flags of column j over the whole wavefront (every lane returns the same value); *a, *b = the column's entry range, empty when
 // colptr is broken.
 __device__ inline int fw_csc_check_column(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval, int j, int n,
                                           long long nnz, int lane, long long *a, long long *b)
 {
-    const long long lo = colptr[j], hi = colptr[j + 1];
-    if (lo < 0 || hi < lo || hi > nnz) {
-        *a = *b = 0;
-        return FW_CSC_BAD_COLPTR;
-    }
-    *a = lo;
-    *b = hi;
+    if (!fw_csc_column_range(colptr, j, nnz, a, b)) return FW_CSC_BAD_COLPTR;
+    const long long lo = *a, hi = *b;
     int bad = 0;
     for (long long e = lo + lane; e < hi; e += 64) {
         const int32_t r = rowval[e];

@@ -1551,19 +1551,44 @@ __global__ __launch_bounds__(256) void fznz_csc_scatter_kernel(const int64_t *__
     }
 }
 
-int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval)
+// the dense-resident buffers of a CSC upload: whatever the CSC-resident layout held goes, the matrix stays or is allocated, the plane is new
+static int fznz_csc_dense_alloc(fw_ctx *ctx)
 {
     const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
-    const long long nnz = colptr[p];
-    if (colptr[0] != 0 || nnz < 0) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32: colptr must run from 0 to nnz (column 0)");
-    const size_t bytes = sizeof(float) * (size_t)n * p;
     fznz_drop_cscres(ctx);
-    if (!ctx->d_data) FW_HIP(ctx, hipMalloc(&ctx->d_data, bytes));
+    if (!ctx->d_data) FW_HIP(ctx, hipMalloc(&ctx->d_data, sizeof(float) * (size_t)n * p));
     if (ctx->d_nzbits) (void)hipFree(ctx->d_nzbits);
     ctx->d_nzbits = nullptr;
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_nzbits, sizeof(uint64_t) * (size_t)p * W));
     ctx->W = W;
+    return FW_OK;
+}
+
+// clear + scatter of a triple in device memory -- staged in d_tmp1 (fw_set_data_csc_f32) or the caller's own (fw_set_data_csc_f32_dev) --
+// and the refusal of its first bad column (fn: the entry point's name, for the message); d_stat: p Int32 of scratch
+static int fznz_csc_scatter(fw_ctx *ctx, const char *fn, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, long long nnz, int32_t *d_stat)
+{
+    const int n = ctx->P.n, p = ctx->P.p, W = ctx->W;
+    FW_HIP(ctx, hipMemsetAsync(ctx->d_data, 0, sizeof(float) * (size_t)n * p, ctx->stream));
+    hipLaunchKernelGGL(fznz_csc_scatter_kernel, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, ctx->stream, d_colptr, d_rowval, d_nzval, n, p, W, nnz, (float *)ctx->d_data,
+                       (unsigned long long *)ctx->d_nzbits, d_stat);
+    FW_HIP(ctx, hipGetLastError());
+    std::vector<int32_t> colstat((size_t)p);
+    FW_HIP(ctx, hipMemcpyAsync(colstat.data(), d_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cnt.kernel_launches += 1;
+    for (int j = 0; j < p; ++j)
+        if (colstat[j]) return fw_fail(ctx, FW_ERR_ARG, "%s: column %d: %s", fn, j, fw_csc_reason(colstat[j]));
+    return FW_OK;
+}
+
+int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval)
+{
+    const int p = ctx->P.p;
+    const long long nnz = colptr[p];
+    if (colptr[0] != 0 || nnz < 0) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32: colptr must run from 0 to nnz (column 0)");
     int rc;
+    if ((rc = fznz_csc_dense_alloc(ctx))) return rc;
     const size_t o_row = ((sizeof(int64_t) * ((size_t)p + 1)) + 255) & ~(size_t)255, o_val = o_row + ((sizeof(int32_t) * (size_t)nnz + 255) & ~(size_t)255),
                  o_stat = o_val + ((sizeof(float) * (size_t)nnz + 255) & ~(size_t)255);
     if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, o_stat + sizeof(int32_t) * (size_t)p))) return rc;
@@ -1573,17 +1598,17 @@ int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowva
         FW_HIP(ctx, hipMemcpyAsync(B + o_row, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
         FW_HIP(ctx, hipMemcpyAsync(B + o_val, nzval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
     }
-    FW_HIP(ctx, hipMemsetAsync(ctx->d_data, 0, bytes, ctx->stream));
-    hipLaunchKernelGGL(fznz_csc_scatter_kernel, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row),
-                       (const float *)(B + o_val), n, p, W, nnz, (float *)ctx->d_data, (unsigned long long *)ctx->d_nzbits, (int32_t *)(B + o_stat));
-    FW_HIP(ctx, hipGetLastError());
-    std::vector<int32_t> colstat((size_t)p);
-    FW_HIP(ctx, hipMemcpyAsync(colstat.data(), B + o_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
-    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cnt.kernel_launches += 1;
-    for (int j = 0; j < p; ++j)
-        if (colstat[j]) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32: column %d: %s", j, fw_csc_reason(colstat[j]));
-    return FW_OK;
+    return fznz_csc_scatter(ctx, "fw_set_data_csc_f32", (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val), nnz, (int32_t *)(B + o_stat));
+}
+
+// fw_set_data_csc_f32_dev: the same scatter on the caller's triple where it lies (checked: fwi_csc_dev_ptrs, fwi_csc_dev_colptr); only
+// the p column flags are staged
+int fwi_fznz_upload_csc_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, long long nnz)
+{
+    int rc;
+    if ((rc = fznz_csc_dense_alloc(ctx))) return rc;
+    if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, sizeof(int32_t) * (size_t)ctx->P.p))) return rc;
+    return fznz_csc_scatter(ctx, "fw_set_data_csc_f32_dev", d_colptr, d_rowval, d_nzval, nnz, (int32_t *)ctx->d_tmp1.ptr);
 }
 
 // fw_set_data_csc_f32_resident: the CSC-resident layout of fw_cscres.h built on the device from the staged triple, in three steps.
@@ -1644,17 +1669,47 @@ __global__ __launch_bounds__(256) void fznz_cscres_compact_kernel(const int64_t 
     }
 }
 
+static int fznz_cscres_build(fw_ctx *ctx, const char *fn, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, long long nnz, int32_t *d_stat,
+                             unsigned long long *d_tot);
+
 int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval)
 {
-    const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
+    const int p = ctx->P.p;
     const long long nnz = colptr[p];
     if (colptr[0] != 0 || nnz < 0) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32_resident: colptr must run from 0 to nnz (column 0)");
-    const size_t cells = (size_t)p * W;
     int rc;
-    // staging: the triple, the column flags and the 64-bit total (d_tmp1); the scan's scratch (d_tmp2)
+    // staging: the triple, the column flags and the 64-bit total (d_tmp1)
     const size_t o_row = ((sizeof(int64_t) * ((size_t)p + 1)) + 255) & ~(size_t)255, o_val = o_row + ((sizeof(int32_t) * (size_t)nnz + 255) & ~(size_t)255),
                  o_stat = o_val + ((sizeof(float) * (size_t)nnz + 255) & ~(size_t)255), o_tot = o_stat + ((sizeof(int32_t) * (size_t)p + 255) & ~(size_t)255);
     if ((rc = fw_dev_reserve(ctx, ctx->d_tmp1, o_tot + sizeof(unsigned long long)))) return rc;
+    char *B = (char *)ctx->d_tmp1.ptr;
+    FW_HIP_MEM(ctx, hipMemcpyAsync(B, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz > 0) {
+        FW_HIP_MEM(ctx, hipMemcpyAsync(B + o_row, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+        FW_HIP_MEM(ctx, hipMemcpyAsync(B + o_val, nzval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return fznz_cscres_build(ctx, "fw_set_data_csc_f32_resident", (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val), nnz, (int32_t *)(B + o_stat),
+                             (unsigned long long *)(B + o_tot));
+}
+
+// fw_set_data_csc_f32_resident_dev: the same three steps on the caller's triple where it lies (checked: fwi_csc_dev_ptrs,
+// fwi_csc_dev_colptr); only the column flags and the total are staged
+int fwi_fznz_upload_csc_resident_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, long long nnz)
+{
+    const size_t o_tot = (sizeof(int32_t) * (size_t)ctx->P.p + 255) & ~(size_t)255;
+    if (int rc = fw_dev_reserve(ctx, ctx->d_tmp1, o_tot + sizeof(unsigned long long))) return rc;
+    char *B = (char *)ctx->d_tmp1.ptr;
+    return fznz_cscres_build(ctx, "fw_set_data_csc_f32_resident_dev", d_colptr, d_rowval, d_nzval, nnz, (int32_t *)B, (unsigned long long *)(B + o_tot));
+}
+
+// plane, scan and compact on a triple in device memory -- staged in d_tmp1 or the caller's own -- and the install (fn: the entry point's
+// name, for the messages); d_stat: p Int32 of scratch, d_tot: the 64-bit total; the scan's scratch lives in d_tmp2
+static int fznz_cscres_build(fw_ctx *ctx, const char *fn, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, long long nnz, int32_t *d_stat,
+                             unsigned long long *d_tot)
+{
+    const int n = ctx->P.n, p = ctx->P.p, W = (n + 63) / 64;
+    const size_t cells = (size_t)p * W;
+    int rc;
     size_t scan_bytes = 0;
     FW_HIP(ctx, (rocprim::exclusive_scan(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, cells, rocprim::plus<uint32_t>(), ctx->stream)));
     if ((rc = fw_dev_reserve(ctx, ctx->d_tmp2, std::max<size_t>(scan_bytes, 1)))) return rc;
@@ -1665,33 +1720,25 @@ int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32
     FwDevArray<float> vals;
     FW_HIP_MEM(ctx, plane.alloc(cells));
     FW_HIP_MEM(ctx, base.alloc(cells));
-    char *B = (char *)ctx->d_tmp1.ptr;
-    FW_HIP_MEM(ctx, hipMemcpyAsync(B, colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (nnz > 0) {
-        FW_HIP_MEM(ctx, hipMemcpyAsync(B + o_row, rowval, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-        FW_HIP_MEM(ctx, hipMemcpyAsync(B + o_val, nzval, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    }
-    FW_HIP_MEM(ctx, hipMemsetAsync(B + o_tot, 0, sizeof(unsigned long long), ctx->stream));
+    FW_HIP_MEM(ctx, hipMemsetAsync(d_tot, 0, sizeof(unsigned long long), ctx->stream));
     const dim3 grid((unsigned)((p + 3) / 4));
-    hipLaunchKernelGGL(fznz_cscres_plane_kernel, grid, dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val),
-                       n, p, W, nnz, plane.get(), base.get(), (int32_t *)(B + o_stat), (unsigned long long *)(B + o_tot));
+    hipLaunchKernelGGL(fznz_cscres_plane_kernel, grid, dim3(256), 0, ctx->stream, d_colptr, d_rowval, d_nzval, n, p, W, nnz, plane.get(), base.get(), d_stat, d_tot);
     FW_HIP_MEM(ctx, hipGetLastError());
     std::vector<int32_t> colstat((size_t)p);
     unsigned long long nvals = 0;
-    FW_HIP_MEM(ctx, hipMemcpyAsync(colstat.data(), B + o_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
-    FW_HIP_MEM(ctx, hipMemcpyAsync(&nvals, B + o_tot, sizeof(nvals), hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP_MEM(ctx, hipMemcpyAsync(colstat.data(), d_stat, sizeof(int32_t) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP_MEM(ctx, hipMemcpyAsync(&nvals, d_tot, sizeof(nvals), hipMemcpyDeviceToHost, ctx->stream));
     FW_HIP_MEM(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cnt.kernel_launches += 1;
     for (int j = 0; j < p; ++j)
-        if (colstat[j]) return fw_fail(ctx, FW_ERR_ARG, "fw_set_data_csc_f32_resident: column %d: %s", j, fw_csc_reason(colstat[j]));
-    if (nvals >= (1ull << 32))
-        return fw_fail(ctx, FW_ERR_LIMIT, "fw_set_data_csc_f32_resident: %llu values != 0 exceed the 32-bit positions of the CSC-resident layout", nvals);
+        if (colstat[j]) return fw_fail(ctx, FW_ERR_ARG, "%s: column %d: %s", fn, j, fw_csc_reason(colstat[j]));
+    if (nvals >= (1ull << 32)) return fw_fail(ctx, FW_ERR_LIMIT, "%s: %llu values != 0 exceed the 32-bit positions of the CSC-resident layout", fn, nvals);
     // (vals holds at least one float: position 0 stands in for an absent entry in fw_cscres_word_value)
     FW_HIP_MEM(ctx, vals.alloc((size_t)std::max<unsigned long long>(nvals, 1)));
     if (nvals == 0) FW_HIP_MEM(ctx, hipMemsetAsync(vals.get(), 0, sizeof(float), ctx->stream));
     FW_HIP_MEM(ctx, (rocprim::exclusive_scan(ctx->d_tmp2.ptr, scan_bytes, (const uint32_t *)base.get(), base.get(), 0u, cells, rocprim::plus<uint32_t>(), ctx->stream)));
-    hipLaunchKernelGGL(fznz_cscres_compact_kernel, grid, dim3(256), 0, ctx->stream, (const int64_t *)B, (const int32_t *)(B + o_row), (const float *)(B + o_val), p,
-                       W, (const unsigned long long *)plane.get(), (const uint32_t *)base.get(), vals.get(), nvals);
+    hipLaunchKernelGGL(fznz_cscres_compact_kernel, grid, dim3(256), 0, ctx->stream, d_colptr, d_rowval, d_nzval, p, W, (const unsigned long long *)plane.get(),
+                       (const uint32_t *)base.get(), vals.get(), nvals);
     FW_HIP_MEM(ctx, hipGetLastError());
     FW_HIP_MEM(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cnt.kernel_launches += 2;

@@ -273,6 +273,28 @@ int fw_pin_reserve(fw_ctx *ctx, FwPinned &b, size_t bytes);
                            hipGetErrorString(e__), __FILE__, __LINE__);                          \
     } while (0)
 
+// ---- a CSC triple the *_csc_*_dev entry points borrow (fw_norm.hip, fw_core.cpp): colptr[p + 1] Int64, rowval[nnz] Int32, nzval[nnz] ----
+// Every pointer is asked of the runtime before anything reads it (rowval / nzval only when there are entries).
+inline int fwi_csc_dev_ptrs(const fw_ctx *ctx, const char *fn, int device, const void *colptr, const void *rowval, const void *nzval, long long nnz)
+{
+    if (nnz < 0) return fw_fail(ctx, FW_ERR_ARG, "%s: nnz = %lld", fn, nnz);
+    if (!colptr || (nnz > 0 && (!rowval || !nzval))) return fw_fail(ctx, FW_ERR_ARG, "%s: NULL array", fn);
+    if (!fw_is_dev_ptr(colptr, device) || (nnz > 0 && (!fw_is_dev_ptr(rowval, device) || !fw_is_dev_ptr(nzval, device))))
+        return fw_fail(ctx, FW_ERR_ARG, "%s: the triple is not device memory of device %d (the entry point without _dev takes host arrays)", fn, device);
+    return FW_OK;
+}
+// The p + 1 column pointers, downloaded and checked before any kernel reads rowval or nzval: they run monotonically from 0 to nnz, so
+// every column's range lies inside the two arrays of nnz entries.  What the kernels' own column check (fw_csc.h) would say, said first.
+inline int fwi_csc_dev_colptr(const fw_ctx *ctx, const char *fn, const int64_t *d_colptr, int p, long long nnz, std::vector<int64_t> &colptr)
+{
+    colptr.resize((size_t)p + 1);
+    FW_HIP(ctx, hipMemcpy(colptr.data(), d_colptr, sizeof(int64_t) * ((size_t)p + 1), hipMemcpyDeviceToHost));
+    if (colptr[0] != 0 || colptr[p] != nnz) return fw_fail(ctx, FW_ERR_ARG, "%s: colptr must run from 0 to nnz (column 0)", fn);
+    for (int j = 0; j < p; ++j)
+        if (colptr[j + 1] < colptr[j]) return fw_fail(ctx, FW_ERR_ARG, "%s: column %d: colptr is not monotone within 0 .. nnz", fn, j);
+    return FW_OK;
+}
+
 // ---- what the kinds' back-ends share (fw_core.cpp; the capacity policy itself: fw_stage_host.h) ----
 // The attempts of a level-0 driver on the context's hint; run(cap, counts) is one attempt, `what` names the buffer in the error.
 template <class Run> int fwi_l0_attempts(fw_ctx *ctx, long long pairs, long long limit, const char *what, Run &&run)
@@ -330,6 +352,9 @@ int fwi_fznz_upload(fw_ctx *ctx, const float *data);
 int fwi_fznz_upload_dev(fw_ctx *ctx, const float *d_src);  // the same layout from a [p][n] matrix in device memory: copy + plane kernel
 int fwi_fznz_upload_csc(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);  // the same layout from a CSC triple
 int fwi_fznz_upload_csc_resident(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const float *nzval);  // plane + base + values != 0 (fw_cscres.h)
+// the two CSC uploads on a triple that lies in device memory (pointers and column pointers checked by the entry point): nothing is staged
+int fwi_fznz_upload_csc_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, long long nnz);
+int fwi_fznz_upload_csc_resident_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, long long nnz);
 int fwi_fznz_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                     std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev);
 int fwi_fznz_submatrices(fw_ctx *ctx, int64_t njobs, const FwNzJob *recs_host, size_t arena_floats, const int32_t *d_acc,
@@ -350,6 +375,7 @@ int fwi_fznz_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t 
 // ---- discrete (fw_mi.hip) ----
 int fwi_mi_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const int32_t *nzval);
 int fwi_mi_upload_dev(fw_ctx *ctx, const int32_t *d_src);  // the same layouts from a [p][n] table in device memory: column scan + pack
+int fwi_mi_upload_csc_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const int32_t *d_nzval, long long nnz);  // ... from a CSC triple in device memory
 int fwi_mi_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t> &pj, std::vector<double> &stat,
                   std::vector<double> &pval, int64_t *m_reliable, FwL0Dev *dev);
 int fwi_mi_test_batch(fw_ctx *ctx, int64_t m, const int32_t *X, const int32_t *Y, const int64_t *zoff,

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "fw_csc.h"
 #include "fw_mi_core.h"
 #include "fw_unrank.h"
 
@@ -1262,7 +1263,7 @@ static MiDev mi_dev(const fw_ctx *ctx)
 // One byte per (variable, sample); levels / max_vals as misc.jl:64-97 computes them (distinct values of the column, the implicit
 // zero included); L = maximum(max_vals) + 1 for every table of the context (types.jl:89,110).  The conditional tests run through the
 // same batch / segment kernels as the bit-plane forms (template value L = 0), HITON-PC through the host job pool, level 0 through
-// mig_level0_kernel (one wavefront per pair).  Limits: values <= 7, L^max_k (L^2 + 1) <= MIG_TAB32 words of LDS per wavefront.
+// mig_level0_kernel (one wavefront per pair).  Limits: values <= MIG_MAX_L - 1, L^max_k (L^2 + 1) <= MIG_TAB32 words of LDS per wavefront.
 #define MIG_GTAB_MAX (64ll << 20)          // words of one device-memory table
 #define MIG_GTAB_BYTES (1ll << 30)         // device memory the tables of ONE launch may take: launches are cut to fit
 // workgroups (of four wavefronts, one table each) a launch of the generic form may hold: all of them with LDS tables, else what fits
@@ -1280,7 +1281,14 @@ static int mig_dev_tables(fw_ctx *ctx, MiDev &P, int64_t wgs, int which /* 0: th
     P.gtab_words = (unsigned long long)ctx->mig_gtab_words;
     return FW_OK;
 }
-static int mig_finish(fw_ctx *ctx, int maxv_all, const unsigned char *vals, const int32_t *d_src);
+// a checked CSC triple in device memory (fw_set_data_csc_i32_dev): the third source of the layouts, next to the host scan's arrays and
+// the caller's dense [p][n] table
+struct MiCscDev {
+    const int64_t *colptr;
+    const int32_t *rowval, *nzval;
+    long long nnz;
+};
+static int mig_finish(fw_ctx *ctx, int maxv_all, const unsigned char *vals, const int32_t *d_src, const MiCscDev *csc = nullptr);
 static int mig_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const int32_t *nzval)
 {
     const int n = ctx->P.n, p = ctx->P.p;
@@ -1310,9 +1318,25 @@ __global__ __launch_bounds__(256) void mi_dev_bytes_kernel(const int32_t *__rest
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < cells; t += (size_t)gridDim.x * 256) vals[t] = (unsigned char)x[t];
 }
 
-// What follows levels / max_vals in the generic form, for both builds: the limits, the byte matrix -- copied from the host (vals) or
-// cast on the device from the caller's table (d_src, fw_set_data_dense_i32_dev) -- and the thresholds.
-static int mig_finish(fw_ctx *ctx, int maxv_all, const unsigned char *vals, const int32_t *d_src)
+// the byte matrix of the generic form from a checked CSC triple in device memory: one wavefront per column over its stored entries, on
+// a matrix cleared before (rows in 0 .. n-1, values in 1 .. MIG_MAX_L - 1: mi_csc_scan_kernel found no defect; a row outside is skipped)
+__global__ __launch_bounds__(256) void mi_csc_bytes_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                           const int32_t *__restrict__ nzval, int n, int p, long long nnz, unsigned char *__restrict__ vals)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= p) return;
+    const long long a = colptr[j], b = colptr[j + 1];
+    if (a < 0 || b < a || b > nnz) return;
+    for (long long e = a + lane; e < b; e += 64) {
+        const int32_t r = rowval[e];
+        if ((unsigned)r < (unsigned)n) vals[(size_t)j * n + r] = (unsigned char)nzval[e];
+    }
+}
+
+// What follows levels / max_vals in the generic form, for every build: the limits, the byte matrix -- copied from the host (vals), cast
+// on the device from the caller's table (d_src, fw_set_data_dense_i32_dev) or cleared and scattered from the caller's triple (csc,
+// fw_set_data_csc_i32_dev) -- and the thresholds.
+static int mig_finish(fw_ctx *ctx, int maxv_all, const unsigned char *vals, const int32_t *d_src, const MiCscDev *csc)
 {
     const int n = ctx->P.n, p = ctx->P.p;
     const size_t cells = (size_t)p * n;
@@ -1335,7 +1359,13 @@ static int mig_finish(fw_ctx *ctx, int maxv_all, const unsigned char *vals, cons
             *q = nullptr;
         }
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_vals, cells));
-    if (d_src) {
+    if (csc) {
+        FW_HIP(ctx, hipMemsetAsync(ctx->d_vals, 0, cells, ctx->stream));
+        hipLaunchKernelGGL(mi_csc_bytes_kernel, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, ctx->stream, csc->colptr, csc->rowval, csc->nzval, n, p, csc->nnz, ctx->d_vals);
+        FW_HIP(ctx, hipGetLastError());
+        FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->cnt.kernel_launches += 1;
+    } else if (d_src) {
         hipLaunchKernelGGL(mi_dev_bytes_kernel, dim3((unsigned)std::min<size_t>((cells + 255) / 256, 65536)), dim3(256), 0, ctx->stream, d_src, cells, ctx->d_vals);
         FW_HIP(ctx, hipGetLastError());
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1452,11 +1482,13 @@ static int mig_level0(fw_ctx *ctx, std::vector<int32_t> &pi, std::vector<int32_t
 }
 
 // The planes of the three-level form as the host scan of a CSC triple leaves them (nzb, hib), or the caller's [p][n] table in device
-// memory to pack them from (d_src); the per-column totals come from the host either way.
+// memory to pack them from (d_src), or the caller's checked CSC triple in device memory (csc); the per-column totals come from the host
+// every time.
 struct MiPlaneSrc {
     const uint64_t *nzb, *hib;
     const int32_t *cnt_nz, *cnt_hi;
     const int32_t *d_src;
+    const MiCscDev *csc;
 };
 static int mi_finish_planes(fw_ctx *ctx, int maxv_all, const MiPlaneSrc &S);
 
@@ -1503,7 +1535,7 @@ int fwi_mi_upload(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, con
         maxv_all = std::max(maxv_all, (int)mx);
     }
     if (generic) return mig_upload(ctx, colptr, rowval, nzval);
-    return mi_finish_planes(ctx, maxv_all, MiPlaneSrc{nzb.data(), hib.data(), cnt_nz.data(), cnt_hi.data(), nullptr});
+    return mi_finish_planes(ctx, maxv_all, MiPlaneSrc{nzb.data(), hib.data(), cnt_nz.data(), cnt_hi.data(), nullptr, nullptr});
 }
 
 // ---- fw_set_data_dense_i32_dev: the same layouts from a [p][n] Int32 table in device memory, in two passes -------------------------
@@ -1608,10 +1640,153 @@ int fwi_mi_upload_dev(fw_ctx *ctx, const int32_t *d_src)
         maxv_all = std::max(maxv_all, (int)r.maxv);
     }
     if (generic) return mig_finish(ctx, maxv_all, nullptr, d_src);
-    return mi_finish_planes(ctx, maxv_all, MiPlaneSrc{nullptr, nullptr, cnt_nz.data(), cnt_hi.data(), d_src});
+    return mi_finish_planes(ctx, maxv_all, MiPlaneSrc{nullptr, nullptr, cnt_nz.data(), cnt_hi.data(), d_src, nullptr});
 }
 
-// What follows levels / max_vals in the three-level form, for both builds: the limits, the padded planes, the per-column records, the
+// ---- fw_set_data_csc_i32_dev: the same layouts from a CSC triple in device memory, in the two passes of fwi_mi_upload_dev ------------
+// Pass 1, one wavefront per column, one pass over its entries: the column's range (fw_csc.h), then every entry's row and value.  The
+// record says what fwi_mi_upload's scan of the column would have met first -- a row out of range or not above its predecessor
+// (FW_ERR_ARG), or a stored zero / a value outside 1 .. MIG_MAX_L - 1 (FW_ERR_LIMIT) -- and, for a good column, what the host needs to
+// pick the form.  Only these p records cross to the host.  Nothing outside [0, nnz) is read.
+enum { MI_CSC_GOOD = 0, MI_CSC_BAD_COLPTR = 1, MI_CSC_BAD_ROW = 2, MI_CSC_BAD_VALUE = 3 };
+struct MiCscRec {
+    unsigned long long mask;  // bit x: a stored entry holds the value x (1 .. MIG_MAX_L - 1)
+    long long bad_at;         // offset in the column of its first defective entry, -1: none
+    int32_t cnt_nz, cnt_hi;   // stored entries, stored entries == 2
+    int32_t maxv;             // the largest in-range value
+    int32_t bad_kind;         // MI_CSC_*: the column pointers, else the entry at bad_at -- its row is looked at first, as on the host
+    int32_t bad_val;          // the value of the entry at bad_at
+};
+
+__global__ __launch_bounds__(256) void mi_csc_scan_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                          const int32_t *__restrict__ nzval, int n, int p, long long nnz, MiCscRec *__restrict__ rec)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= p) return;
+    long long a, b;
+    const bool good_colptr = fw_csc_column_range(colptr, j, nnz, &a, &b);
+    const long long len = b - a;
+    unsigned long long mask = 0;
+    int hi = 0;
+    long long bad_at = len;  // (of this lane: its entries ascend, so the first defect it meets is its lowest)
+    int bad_kind = MI_CSC_GOOD, bad_val = 0;
+    for (long long e = a + lane; e < b; e += 64) {
+        const int32_t r = rowval[e], x = nzval[e];
+        const bool bad_row = r < 0 || r >= n || (e > a && rowval[e - 1] >= r), bad_value = x < 1 || x >= MIG_MAX_L;
+        if ((bad_row || bad_value) && bad_kind == MI_CSC_GOOD) {
+            bad_at = e - a;
+            bad_kind = bad_row ? MI_CSC_BAD_ROW : MI_CSC_BAD_VALUE;
+            bad_val = x;
+        }
+        if (!bad_value) {
+            mask |= 1ull << x;
+            hi += x == 2;
+        }
+    }
+    for (int o = 32; o; o >>= 1) {
+        mask |= __shfl_xor(mask, o, 64);
+        hi += __shfl_xor(hi, o, 64);
+        const long long at = __shfl_xor(bad_at, o, 64);
+        const int kind = __shfl_xor(bad_kind, o, 64), val = __shfl_xor(bad_val, o, 64);
+        if (at < bad_at) bad_at = at, bad_kind = kind, bad_val = val;
+    }
+    if (lane == 0) {
+        MiCscRec r;
+        r.mask = mask;
+        r.bad_at = bad_at < len ? bad_at : -1;
+        r.cnt_nz = (int32_t)len;
+        r.cnt_hi = hi;
+        r.maxv = mask ? 63 - __clzll((long long)mask) : 0;
+        r.bad_kind = good_colptr ? bad_kind : MI_CSC_BAD_COLPTR;
+        r.bad_val = bad_val;
+        rec[j] = r;
+    }
+}
+
+// Pass 2 of the three-level form (every stored value is 1 or 2): one wavefront per column of the padded [p_pad][W] layout, one more for
+// the slack words.  Each lane owns plane word w of its column: it finds the word's entries in the sorted run by binary search and writes
+// the nz and hi words whole -- the scheme of fznz_csc_scatter_kernel: no atomics, and the planes need no clearing.  Pad columns and the
+// slack come out zero, as mi_dev_pack_kernel leaves them.  Whatever the triple holds, a column's stores go to its own words only.
+// hib: nullptr when no column holds a 2.
+__global__ __launch_bounds__(256) void mi_csc_pack_kernel(const int64_t *__restrict__ colptr, const int32_t *__restrict__ rowval,
+                                                          const int32_t *__restrict__ nzval, int p, int p_pad, int W, long long nnz,
+                                                          unsigned long long *__restrict__ nzb, unsigned long long *__restrict__ hib)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j > p_pad) return;
+    if (j == p_pad) {
+        if (lane < L0M_WC) {
+            nzb[(size_t)p_pad * W + lane] = 0;
+            if (hib) hib[(size_t)p_pad * W + lane] = 0;
+        }
+        return;
+    }
+    long long a = 0, b = 0;
+    if (j < p) {
+        a = colptr[j], b = colptr[j + 1];
+        if (a < 0 || b < a || b > nnz) a = b = 0;
+    }
+    for (int w = lane; w < W; w += 64) {
+        const long long r0 = (long long)w * 64;
+        long long lo = a, up = b;  // first entry with row >= 64 w
+        while (lo < up) {
+            const long long mid = (lo + up) >> 1;
+            if (rowval[mid] < r0)
+                lo = mid + 1;
+            else
+                up = mid;
+        }
+        unsigned long long nz = 0, hi = 0;
+        for (long long e = lo; e < b && rowval[e] < r0 + 64; ++e) {
+            const unsigned long long bit = 1ull << (rowval[e] & 63);
+            nz |= bit;
+            if (nzval[e] == 2) hi |= bit;
+        }
+        nzb[(size_t)j * W + w] = nz;
+        if (hib) hib[(size_t)j * W + w] = hi;
+    }
+}
+
+// (the pointers and the column pointers are checked by the entry point: fwi_csc_dev_ptrs, fwi_csc_dev_colptr)
+int fwi_mi_upload_csc_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const int32_t *d_nzval, long long nnz)
+{
+    const int n = ctx->P.n, p = ctx->P.p;
+    if (ctx->P.max_k > MI_MAX_K) return fw_fail(ctx, FW_ERR_LIMIT, "discrete tests support max_k <= %d (got %d)", MI_MAX_K, ctx->P.max_k);
+    FwDevArray<MiCscRec> d_rec;
+    std::vector<MiCscRec> rec((size_t)p);
+    FW_HIP(ctx, d_rec.alloc((size_t)p));
+    hipLaunchKernelGGL(mi_csc_scan_kernel, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, ctx->stream, d_colptr, d_rowval, d_nzval, n, p, nnz, d_rec.get());
+    FW_HIP(ctx, hipGetLastError());
+    FW_HIP(ctx, hipMemcpyAsync(rec.data(), d_rec.get(), sizeof(MiCscRec) * (size_t)p, hipMemcpyDeviceToHost, ctx->stream));
+    FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->cnt.kernel_launches += 1;
+    // (levels / max_vals of the context change only once the triple is known to be good: a refused one leaves the context as it was)
+    std::vector<int32_t> levels(p, 0), max_vals(p, 0), cnt_nz(p, 0), cnt_hi(p, 0);
+    int maxv_all = 0;
+    bool generic = false;
+    for (int v = 0; v < p; ++v) {  // (the lowest bad column and its first bad entry: what the host scan meets first)
+        const MiCscRec &r = rec[v];
+        if (r.bad_kind == MI_CSC_BAD_COLPTR) return fw_fail(ctx, FW_ERR_ARG, "colptr not monotone at column %d", v);
+        if (r.bad_kind == MI_CSC_BAD_ROW) return fw_fail(ctx, FW_ERR_ARG, "row indices of column %d are not sorted / in range", v);
+        if (r.bad_kind == MI_CSC_BAD_VALUE)
+            return fw_fail(ctx, FW_ERR_LIMIT, "discrete values must be 0 .. %d (column %d holds %d); stored zeros are not allowed", MIG_MAX_L - 1, v, r.bad_val);
+        generic = generic || (r.mask >> 3) != 0;
+        // misc.jl:64-72 / :84-87: the distinct stored values, plus the zero when the column has an absence
+        levels[v] = (int32_t)__builtin_popcountll(r.mask) + (r.cnt_nz < n ? 1 : 0);
+        max_vals[v] = r.maxv;
+        cnt_nz[v] = r.cnt_nz;
+        cnt_hi[v] = r.cnt_hi;
+        maxv_all = std::max(maxv_all, (int)r.maxv);
+    }
+    ctx->levels = levels;
+    ctx->max_vals = max_vals;
+    ctx->mi_generic = false;
+    const MiCscDev src{d_colptr, d_rowval, d_nzval, nnz};
+    if (generic) return mig_finish(ctx, maxv_all, nullptr, nullptr, &src);
+    return mi_finish_planes(ctx, maxv_all, MiPlaneSrc{nullptr, nullptr, cnt_nz.data(), cnt_hi.data(), nullptr, &src});
+}
+
+// What follows levels / max_vals in the three-level form, for every build: the limits, the padded planes, the per-column records, the
 // tables and the thresholds.
 static int mi_finish_planes(fw_ctx *ctx, int maxv_all, const MiPlaneSrc &S)
 {
@@ -1635,7 +1810,14 @@ static int mi_finish_planes(fw_ctx *ctx, int maxv_all, const MiPlaneSrc &S)
     const size_t pb_alloc = sizeof(uint64_t) * ((size_t)((p + L0M_T - 1) / L0M_T * L0M_T) * W + L0M_WC);
     FW_HIP(ctx, hipMalloc((void **)&ctx->d_nzbits, pb_alloc));
     if (ctx->L > 2) FW_HIP(ctx, hipMalloc((void **)&ctx->d_hibits, pb_alloc));
-    if (S.d_src) {
+    if (S.csc) {
+        const int p_pad = (p + L0M_T - 1) / L0M_T * L0M_T;  // (+ one wavefront for the slack words)
+        hipLaunchKernelGGL(mi_csc_pack_kernel, dim3((unsigned)((p_pad + 1 + 3) / 4)), dim3(256), 0, ctx->stream, S.csc->colptr, S.csc->rowval, S.csc->nzval, p, p_pad, W,
+                           S.csc->nnz, (unsigned long long *)ctx->d_nzbits, (unsigned long long *)ctx->d_hibits);
+        FW_HIP(ctx, hipGetLastError());
+        FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->cnt.kernel_launches += 1;
+    } else if (S.d_src) {
         const unsigned long long words = pb_alloc / sizeof(uint64_t);
         hipLaunchKernelGGL(mi_dev_pack_kernel, dim3((unsigned)((words + 3) / 4)), dim3(256), 0, ctx->stream, S.d_src, n, p, W, words,
                            (unsigned long long *)ctx->d_nzbits, (unsigned long long *)ctx->d_hibits);

@@ -666,7 +666,9 @@ static __device__ __forceinline__ MiRes mi_test_core(const MiDev &P, const int X
 // scale problems): ~n / 64 LDS atomics per lane and test instead of a handful of popcounts.  tab: MIG_TAB32 32-bit words.
 // ------------------------------------------------------------------------------------------------
 #define MIG_MAX_L 62  // values 0 .. 61: the pair table L^2 + 1 of level 0 fits MIG_TAB32 words (r01-r04: 8)
-#define MIG_TAB32 3840  // words of one wavefront's table: L^k strata x (L^2 cells + the stratum total) must fit (host check)
+// (3 845 = 62^2 + 1: the level-0 kernel always counts in LDS, so the pair table of 62 levels must fit -- at 3 840 its last five words were the
+// next wavefront's first five, and level 0 of a table holding the value 61 changed from run to run)
+#define MIG_TAB32 3845  // words of one wavefront's table: L^k strata x (L^2 cells + the stratum total) must fit (host check)
 static __device__ __forceinline__ MiRes mi_test_core_gen(const MiDev &P, const int X_in, const int Y_in, const MiZs &zs_in, const int k_in,
                                                          unsigned *tab)
 {

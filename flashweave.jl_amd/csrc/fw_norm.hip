@@ -935,17 +935,31 @@ __global__ __launch_bounds__(256) void csc_adapt_scatter_kernel(const int64_t *_
 }
 
 // The input triple on the device and, per entry, its payload for the sort by row (Float64: the entry's index, its column in ecol).
+// cp / rv / nz are what the kernels read: the uploaded copies (stage) or, in the *_csc_dev forms, the caller's own device arrays (borrow).
 template <typename V> struct CscDev {
     FwDevArray<int64_t> colptr;
     FwDevArray<int32_t> rowval;
     FwDevArray<V> nzval;
+    const int64_t *cp = nullptr;
+    const int32_t *rv = nullptr;
+    const V *nz = nullptr;
     FwDevArray<typename CscPay<V>::T> pay;
     FwDevArray<uint32_t> ecol;
+    hipError_t stage(const int64_t *h_colptr, const int32_t *h_rowval, const V *h_nzval, int p, long long nnz)
+    {
+        hipError_t e = colptr.upload(h_colptr, (size_t)p + 1);
+        if (e == hipSuccess) e = rowval.upload(h_rowval, (size_t)nnz);
+        if (e == hipSuccess) e = nzval.upload(h_nzval, (size_t)nnz);
+        cp = colptr.get(), rv = rowval.get(), nz = nzval.get();
+        return e;
+    }
+    void borrow(const int64_t *d_colptr, const int32_t *d_rowval, const V *d_nzval) { cp = d_colptr, rv = d_rowval, nz = d_nzval; }
 };
 
 // The CSC filters.  Columns: structure and value check, var(data, dims=1) .> 0 (colq: input column -> its place in cols, or -1).  Row
 // totals: the CSR view (a stable sort of the entries by row; the payload: CscPay), then one thread per row over its run.
-template <typename V> int csc_filters(NormCall &c, int p, long long nnz, const int64_t *colptr, const int32_t *rowval, const V *nzval, CscDev<V> &D)
+// D holds the triple already, staged or borrowed.
+template <typename V> int csc_filters(NormCall &c, int p, long long nnz, CscDev<V> &D)
 {
     typedef typename CscPay<V>::T Pay;
     const int n = c.n;
@@ -959,13 +973,10 @@ template <typename V> int csc_filters(NormCall &c, int p, long long nnz, const i
     std::vector<V> MN((size_t)n);
     std::vector<float> s32(c.K.tss ? (size_t)n : 0);
     NormTotals T{std::vector<double>((size_t)n), std::vector<double>((size_t)n), std::vector<double>((size_t)n), std::vector<int64_t>((size_t)n)};
-    FW_HIP(nullptr, D.colptr.upload(colptr, (size_t)p + 1));
-    FW_HIP(nullptr, D.rowval.upload(rowval, (size_t)nnz));
-    FW_HIP(nullptr, D.nzval.upload(nzval, (size_t)nnz));
     FW_HIP(nullptr, d_colstat.alloc((size_t)p));
     FW_HIP(nullptr, D.pay.alloc((size_t)nnz));
     if (sizeof(Pay) == sizeof(uint32_t)) FW_HIP(nullptr, D.ecol.alloc((size_t)nnz));  // (Float64: the payload is the entry's index)
-    hipLaunchKernelGGL(csc_col_scan_kernel<V>, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), n, p, nnz, d_colstat.get(), D.pay.get(), D.ecol.get());
+    hipLaunchKernelGGL(csc_col_scan_kernel<V>, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, 0, D.cp, D.rv, D.nz, n, p, nnz, d_colstat.get(), D.pay.get(), D.ecol.get());
     FW_HIP(nullptr, hipGetLastError());
     FW_HIP(nullptr, d_colstat.download(colstat));
     for (int j = 0; j < p; ++j) {
@@ -983,16 +994,16 @@ template <typename V> int csc_filters(NormCall &c, int p, long long nnz, const i
     size_t tb = 0;
     FW_HIP(nullptr, d_krow.alloc((size_t)nnz));
     FW_HIP(nullptr, d_pay2.alloc((size_t)nnz));
-    FW_HIP(nullptr, (rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)D.rowval.get(), d_krow.get(), (const Pay *)D.pay.get(), d_pay2.get(), (size_t)nnz, 0u, (unsigned int)bits, (hipStream_t)0)));
+    FW_HIP(nullptr, (rocprim::radix_sort_pairs(nullptr, tb, (const uint32_t *)D.rv, d_krow.get(), (const Pay *)D.pay.get(), d_pay2.get(), (size_t)nnz, 0u, (unsigned int)bits, (hipStream_t)0)));
     FW_HIP(nullptr, d_tmp.alloc(tb ? tb : 1));
-    FW_HIP(nullptr, (rocprim::radix_sort_pairs((void *)d_tmp.get(), tb, (const uint32_t *)D.rowval.get(), d_krow.get(), (const Pay *)D.pay.get(), d_pay2.get(), (size_t)nnz, 0u, (unsigned int)bits, (hipStream_t)0)));
+    FW_HIP(nullptr, (rocprim::radix_sort_pairs((void *)d_tmp.get(), tb, (const uint32_t *)D.rv, d_krow.get(), (const Pay *)D.pay.get(), d_pay2.get(), (size_t)nnz, 0u, (unsigned int)bits, (hipStream_t)0)));
     FW_HIP(nullptr, d_colq.upload(colq));
     FW_HIP(nullptr, d_S.alloc((size_t)n));
     FW_HIP(nullptr, d_SL.alloc((size_t)n));
     FW_HIP(nullptr, d_cnt.alloc((size_t)n));
     FW_HIP(nullptr, d_mn.alloc((size_t)n));
     if (c.K.tss) FW_HIP(nullptr, c.d_s32.alloc((size_t)n));
-    hipLaunchKernelGGL(csc_row_stats_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow.get(), d_pay2.get(), D.nzval.get(), D.ecol.get(), nnz, n, d_colq.get(),
+    hipLaunchKernelGGL(csc_row_stats_kernel<V>, dim3((n + 255) / 256), dim3(256), 0, 0, d_krow.get(), d_pay2.get(), D.nz, D.ecol.get(), nnz, n, d_colq.get(),
                        pk, d_S.get(), d_SL.get(), d_cnt.get(), d_mn.get(), c.d_s32.get());
     FW_HIP(nullptr, hipGetLastError());
     FW_HIP(nullptr, d_S.download(T.S));
@@ -1009,6 +1020,7 @@ template <typename V> int csc_filters(NormCall &c, int p, long long nnz, const i
 
 // CSC output.  FW_FZ (clr_adapt): the dense matrix, pseudo-count cells first, the stored entries over them.  The sparse kinds: the
 // kind's own column filter, then the output triple (every entry of a kept column lies in a kept row: a column keeps its length).
+// The outputs are host buffers the result is downloaded into, or (c.dev_out) device buffers of the caller that the kernels write.
 template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *colptr, const CscDev<V> &D, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, int64_t *nnz_out)
 {
     const int nk = (int)c.R.rows.size(), pk = (int)c.cols.size();
@@ -1023,11 +1035,13 @@ template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *
     FW_HIP(nullptr, d_g.upload(c.R.g));
     if (c.kind == FW_FZ) {
         FW_HIP(nullptr, d_pseudo.upload(c.R.pseudo));
-        FW_HIP(nullptr, d_of.alloc((size_t)nk * pk));
-        hipLaunchKernelGGL(csc_adapt_fill_kernel, norm_out_grid(nk, pk), dim3(256), 0, 0, nk, pk, d_pseudo.get(), d_g.get(), d_of.get());
-        hipLaunchKernelGGL(csc_adapt_scatter_kernel<V>, dim3((unsigned)((pk + 3) / 4)), dim3(256), 0, 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), c.d_cols.get(), pk, d_rownew.get(), nk, d_g.get(), d_of.get());
+        if (!c.dev_out) FW_HIP(nullptr, d_of.alloc((size_t)nk * pk));
+        float *of = c.dev_out ? out_f32 : d_of.get();
+        hipLaunchKernelGGL(csc_adapt_fill_kernel, norm_out_grid(nk, pk), dim3(256), 0, 0, nk, pk, d_pseudo.get(), d_g.get(), of);
+        hipLaunchKernelGGL(csc_adapt_scatter_kernel<V>, dim3((unsigned)((pk + 3) / 4)), dim3(256), 0, 0, D.cp, D.rv, D.nz, c.d_cols.get(), pk, d_rownew.get(), nk, d_g.get(), of);
         FW_HIP(nullptr, hipGetLastError());
-        FW_HIP(nullptr, d_of.download(out_f32, (size_t)nk * pk));
+        if (c.dev_out) FW_HIP(nullptr, hipStreamSynchronize(0));  // (the caller reads its buffer at once)
+        if (!c.dev_out) FW_HIP(nullptr, d_of.download(out_f32, (size_t)nk * pk));
         *nnz_out = (int64_t)nk * pk;
         return FW_OK;
     }
@@ -1040,7 +1054,7 @@ template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *
         if (int rc = norm_bin_shape((const void *)binned, mmax, pk, false, B)) return rc;
         FW_HIP(nullptr, d_bins.alloc((size_t)nnz));
         FW_HIP(nullptr, d_two.alloc((size_t)pk));
-        hipLaunchKernelGGL(binned, dim3(B.grid), dim3(B.threads), B.lds(), 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), c.d_cols.get(), pk, d_rownew.get(),
+        hipLaunchKernelGGL(binned, dim3(B.grid), dim3(B.threads), B.lds(), 0, D.cp, D.rv, D.nz, c.d_cols.get(), pk, d_rownew.get(),
                            d_g.get(), c.d_s32.get(), d_bins.get(), d_two.get(), B.M, B.keys.get(), c.O.b, (int)c.O.dense, (int)c.O.mean);
         FW_HIP(nullptr, hipGetLastError());
         FW_HIP(nullptr, d_two.download(two));
@@ -1052,11 +1066,21 @@ template <typename V> int csc_output(NormCall &c, long long nnz, const int64_t *
     const std::vector<int64_t> ocolptr = norm_out_colptr(colptr, c.cols);
     const size_t onnz = (size_t)ocolptr[pf];
     FW_HIP(nullptr, hipMemcpy(c.d_cols.get(), c.cols.data(), sizeof(int32_t) * (size_t)pf, hipMemcpyHostToDevice));
+    if (c.dev_out) {  // the caller's device buffers take the output triple where the kernel writes it (onnz <= nnz, pf <= p)
+        FW_HIP(nullptr, hipMemcpy(out_colptr, ocolptr.data(), sizeof(int64_t) * ((size_t)pf + 1), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(csc_emit_kernel<V>, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, D.cp, D.rv, D.nz, c.d_cols.get(), pf,
+                           (const int64_t *)out_colptr, d_rownew.get(), d_g.get(), c.d_s32.get(), d_bins.get(), c.K.emit_mode, out_rowval, c.K.i32 ? out_i32 : nullptr,
+                           c.K.i32 ? nullptr : out_f32);
+        FW_HIP(nullptr, hipGetLastError());
+        FW_HIP(nullptr, hipStreamSynchronize(0));
+        *nnz_out = (int64_t)onnz;
+        return FW_OK;
+    }
     FW_HIP(nullptr, d_ocolptr.upload(ocolptr));
     FW_HIP(nullptr, d_orow.alloc(onnz));
     if (c.K.i32) FW_HIP(nullptr, d_oi.alloc(onnz));
     if (!c.K.i32) FW_HIP(nullptr, d_of.alloc(onnz));
-    hipLaunchKernelGGL(csc_emit_kernel<V>, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, D.colptr.get(), D.rowval.get(), D.nzval.get(), c.d_cols.get(), pf,
+    hipLaunchKernelGGL(csc_emit_kernel<V>, dim3((unsigned)((pf + 3) / 4)), dim3(256), 0, 0, D.cp, D.rv, D.nz, c.d_cols.get(), pf,
                        d_ocolptr.get(), d_rownew.get(), d_g.get(), c.d_s32.get(), d_bins.get(), c.K.emit_mode, d_orow.get(), d_oi.get(), d_of.get());
     FW_HIP(nullptr, hipGetLastError());
     FW_HIP(nullptr, d_orow.download(out_rowval, onnz));
@@ -1084,8 +1108,41 @@ int norm_csc(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p,
     if (nnz == 0) return norm_all_constant(fn);
     CscDev<V> D;
     FW_HIP(nullptr, hipSetDevice(device));
-    if (int rc = csc_filters(c, p, nnz, colptr, rowval, nzval, D)) return rc;
+    FW_HIP(nullptr, D.stage(colptr, rowval, nzval, p, nnz));
+    if (int rc = csc_filters(c, p, nnz, D)) return rc;
     if (int rc = csc_output(c, nnz, colptr, D, out_colptr, out_rowval, out_i32, out_f32, nnz_out)) return rc;
+    *n_out = (int32_t)c.R.rows.size();
+    *p_out = (int32_t)c.cols.size();
+    return FW_OK;
+}
+
+// The *_csc_dev forms: the triple and the output buffers in device memory of `device` (include/flashweave_amd.h).  Every pointer is
+// asked of the runtime first; then the p + 1 column pointers are downloaded and must run monotonically from 0 to nnz before any kernel
+// reads rowval or nzval (the kernels' own column check stays).  The triple is borrowed, the output written in place; the stages and
+// their kernels are those of norm_csc, so the bits are.
+template <typename V>
+int norm_csc_dev(const char *fn, int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *d_colptr, const int32_t *d_rowval, const V *d_nzval,
+                 int64_t nnz, int64_t *out_colptr, int32_t *out_rowval, int32_t *out_i32, float *out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out,
+                 int32_t *p_out, int64_t *nnz_out, const fw_norm_opts *opts)
+{
+    if (!row_mask || !col_mask || !n_out || !p_out || !nnz_out || n <= 0 || p <= 0) return fw_fail(nullptr, FW_ERR_ARG, "%s: invalid argument", fn);
+    NormCall c{fn, kind, norm_kind(kind), n, row_mask, col_mask};
+    if (int rc = norm_call_check(c, opts)) return rc;
+    c.dev_out = true;
+    if (int rc = fwi_csc_dev_ptrs(nullptr, fn, device, d_colptr, d_rowval, d_nzval, nnz)) return rc;
+    const void *value_out = c.K.i32 ? (const void *)out_i32 : (const void *)out_f32;
+    if (!value_out || (kind != FW_FZ && (!out_colptr || !out_rowval))) return fw_fail(nullptr, FW_ERR_ARG, "%s: missing output buffer", fn);
+    if (!fw_is_dev_ptr(value_out, device) || (kind != FW_FZ && (!fw_is_dev_ptr(out_colptr, device) || !fw_is_dev_ptr(out_rowval, device))))
+        return fw_fail(nullptr, FW_ERR_ARG, "%s: the output buffer is not device memory of device %d", fn, device);
+    if (nnz > 0x7fffffffll) return fw_fail(nullptr, FW_ERR_LIMIT, "%s: %lld stored entries exceed the 32-bit entry index", fn, (long long)nnz);
+    FW_HIP(nullptr, hipSetDevice(device));
+    std::vector<int64_t> colptr;
+    if (int rc = fwi_csc_dev_colptr(nullptr, fn, d_colptr, p, nnz, colptr)) return rc;
+    if (nnz == 0) return norm_all_constant(fn);
+    CscDev<V> D;
+    D.borrow(d_colptr, d_rowval, d_nzval);
+    if (int rc = csc_filters(c, p, nnz, D)) return rc;
+    if (int rc = csc_output(c, nnz, colptr.data(), D, out_colptr, out_rowval, out_i32, out_f32, nnz_out)) return rc;
     *n_out = (int32_t)c.R.rows.size();
     *p_out = (int32_t)c.cols.size();
     return FW_OK;
@@ -1123,4 +1180,23 @@ extern "C" int fw_normalize_abund_csc(int32_t device, int32_t kind, int32_t n, i
                                       uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out)
 {
     return fw_normalize_abund_csc_opts(device, kind, n, p, colptr, rowval, nzval, out_colptr, out_rowval, out_i32, out_f32, row_mask, col_mask, n_out, p_out, nnz_out, nullptr);
+}
+
+// The *_csc_dev forms: the triple and the output buffers in device memory (include/flashweave_amd.h); opts == NULL means the defaults.
+extern "C" int fw_normalize_counts_csc_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *d_colptr, const int32_t *d_rowval,
+                                           const int32_t *d_nzval, int64_t nnz, int64_t *d_out_colptr, int32_t *d_out_rowval, int32_t *d_out_i32,
+                                           float *d_out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                                           const fw_norm_opts *opts)
+{
+    return norm_csc_dev<int32_t>("fw_normalize_counts_csc_dev", device, kind, n, p, d_colptr, d_rowval, d_nzval, nnz, d_out_colptr, d_out_rowval, d_out_i32, d_out_f32,
+                                 row_mask, col_mask, n_out, p_out, nnz_out, opts);
+}
+
+extern "C" int fw_normalize_abund_csc_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *d_colptr, const int32_t *d_rowval,
+                                          const double *d_nzval, int64_t nnz, int64_t *d_out_colptr, int32_t *d_out_rowval, int32_t *d_out_i32,
+                                          float *d_out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                                          const fw_norm_opts *opts)
+{
+    return norm_csc_dev<double>("fw_normalize_abund_csc_dev", device, kind, n, p, d_colptr, d_rowval, d_nzval, nnz, d_out_colptr, d_out_rowval, d_out_i32, d_out_f32,
+                                row_mask, col_mask, n_out, p_out, nnz_out, opts);
 }

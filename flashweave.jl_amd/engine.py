@@ -176,6 +176,12 @@ def load_library():
         L.fw_set_data_dense_f32_dev.argtypes = [vp, vp]
         L.fw_normalize_counts_dev.argtypes = L.fw_normalize_counts.argtypes + [C.POINTER(_NormOpts)]
         L.fw_normalize_abund_dev.argtypes = L.fw_normalize_counts_dev.argtypes
+    if hasattr(L, "fw_set_data_csc_i32_dev"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        for name in ("fw_set_data_csc_i32_dev", "fw_set_data_csc_f32_dev", "fw_set_data_csc_f32_resident_dev"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
+        L.fw_normalize_counts_csc_dev.argtypes = ([C.c_int32] * 4 + [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                                     C.POINTER(C.c_int64), C.POINTER(_NormOpts)])
+        L.fw_normalize_abund_csc_dev.argtypes = L.fw_normalize_counts_csc_dev.argtypes
     if hasattr(L, "fw_set_data_csc_f32_resident"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
         L.fw_set_data_csc_f32_resident.argtypes = [vp, vp, vp, vp]
         L.fw_data_resident_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -237,6 +243,44 @@ def is_device_tensor(who, data):
     return True
 
 
+def is_sparse_csc_tensor(data):
+    """True for a torch.Tensor with layout torch.sparse_csc, on any device: the one sparse tensor form that is served (in GPU memory)."""
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(data, torch.Tensor) and data.layout == torch.sparse_csc
+
+
+def _dev_csc(who, t, device, dtype=None, numeric="biuf"):
+    """A 2-D sparse CSC tensor in GPU memory taken apart into the three plain device tensors the *_csc_*_dev entry points borrow:
+    -> (colptr int64 [p + 1], rowval int32 [nnz], nzval [nnz] of `dtype` (None: as it came), (n, p)), 0-based and contiguous; the
+    conversions run on the device (rows that come as int64 cost a 4 B / entry int32 copy) and the producer's stream is drained.  Shape,
+    numeric dtype and device index are checked as _dev_table checks them, and -- with torch ops, before any library call -- that the
+    column pointers start at 0, end at the length of both other arrays and never step down: every column's range then lies inside
+    the two arrays.  Nothing is made canonical: rows out of order, duplicates and stored zeros are the library's to refuse.
+    Keep the three tensors alive over the call."""
+    import torch
+    if t.dim() != 2 or _tensor_np_kind(t) not in numeric:
+        raise ValueError("%s: a device tensor must be a 2-D samples x variables table of a numeric dtype (got %d dimensions, %s)"
+                         % (who, t.dim(), t.dtype))
+    if t.device.index != device:
+        raise ValueError("%s: the tensor lives on %s while device=%d: pass the device the table is on (or tensor.cpu())" % (who, t.device, device))
+    t = t.detach()
+    n, p = (int(v) for v in t.shape)
+    ccol, rows, vals = t.ccol_indices(), t.row_indices(), t.values()
+    if vals.dim() != 1 or n >= 2**31 or p >= 2**31:
+        raise ValueError("%s: a sparse CSC tensor must hold one scalar per stored entry and fit the 32-bit row / column index" % who)
+    if rows.dtype != torch.int32 and rows.numel() and not (0 <= int(rows.min()) and int(rows.max()) < 2**31):
+        raise ValueError("%s: the sparse CSC tensor is not canonical: a row index lies outside 0 .. 2^31 - 1" % who)
+    colptr, rowval = ccol.to(torch.int64).contiguous(), rows.to(torch.int32).contiguous()
+    nzval = (vals if dtype is None else vals.to(dtype)).contiguous()
+    nnz = int(rowval.numel())
+    if (colptr.numel() != p + 1 or nzval.numel() != nnz or int(colptr[0]) != 0 or int(colptr[-1]) != nnz
+            or bool((colptr[1:] < colptr[:-1]).any())):
+        raise ValueError("%s: the sparse CSC tensor is not canonical: ccol_indices must run from 0 to the number of stored entries (%d) "
+                         "without stepping down, over %d columns" % (who, nnz, p))
+    torch.cuda.current_stream(t.device).synchronize()
+    return colptr, rowval, nzval, (n, p)
+
+
 def _dev_table(who, t, device, dtype, numeric="biuf"):
     """A 2-D GPU tensor as the *_dev entry points borrow it: `dtype`, column-major (strides (1, n): taken as it is, anything else
     through t.t().contiguous()), on GPU `device`; the conversions run on the device and the producer's stream is drained before the
@@ -244,7 +288,8 @@ def _dev_table(who, t, device, dtype, numeric="biuf"):
     import torch
     if t.layout != torch.strided:
         raise ValueError("%s: a sparse torch tensor is not supported: scipy.sparse is the sparse interface, pass tensor.to_dense() "
-                         "or a scipy matrix built from tensor.cpu()" % who)
+                         "or a scipy matrix built from tensor.cpu() (of the sparse layouts only tensor.to_sparse_csc() is taken where "
+                         "a sparse table is)" % who)
     kind = "b" if t.dtype == torch.bool else "f" if t.dtype.is_floating_point else "c" if t.dtype.is_complex else "i"
     if t.dim() != 2 or kind not in numeric:
         raise ValueError("%s: a device tensor must be a 2-D samples x variables table of a numeric dtype (got %d dimensions, %s)"
@@ -403,12 +448,20 @@ def normalize_counts(counts, test_name, device=0, norm=None, n_bins=3, rank_meth
     A 2-D torch.Tensor in GPU memory (device.type "cuda", on GPU `device`) is borrowed where it is (fw_normalize_counts_dev): the
     checks above run as torch ops on the device, and data comes back as a tensor on that device -- an (n_out, p_out) view with
     strides (1, n_out) of the output buffer, the bits the numpy table gives; the masks are numpy.  normalize_abundances likewise
-    (fw_normalize_abund_dev).  A CPU tensor is an array; any other device type raises ValueError."""
+    (fw_normalize_abund_dev).  A CPU tensor is an array; any other device type raises ValueError.
+    A 2-D sparse CSC tensor in GPU memory (layout torch.sparse_csc; torch.sparse_csc_tensor over a canonical scipy triple is one) is
+    the sparse table of that path: its three arrays are borrowed (fw_normalize_counts_csc_dev / fw_normalize_abund_csc_dev), the value
+    checks run on values(), and data comes back as a sparse CSC tensor over views of the output buffers (Int32 / Float32; a dense
+    tensor for "fz"), the bits of the scipy call.  The tensor must be canonical already -- rows ascending in every column, no
+    duplicates, no stored zeros: nothing is summed, dropped or sorted on the device, a defect is refused (FlashWeaveError naming the
+    column).  Every other sparse layout (COO, CSR, BSR, BSC) raises ValueError."""
     if norm is not None:
         _front_end_kind("normalize_counts", test_name, norm)  # (an unknown or misplaced norm is refused before anything is loaded)
     bins_check("normalize_counts", test_name, n_bins, rank_method, disc_method)
     bins = bins_kw(n_bins, rank_method, disc_method)
     if is_device_tensor("normalize_counts", counts):
+        if is_sparse_csc_tensor(counts):
+            return _normalize_counts_csc_dev(counts, test_name, device, norm, bins)
         return _normalize_counts_dev(counts, test_name, device, norm, bins)
     L = load_library()
     if is_sparse(counts) or isinstance(counts, CSC):  # (any other tuple is a dense table, as before)
@@ -437,6 +490,54 @@ def _normalize_counts_dev(counts, test_name, device, norm, bins):
     if x.numel() and (float(x.min()) < 0 or float(x.max()) > np.iinfo(np.int32).max):
         raise ValueError("normalize_counts: counts must lie in [0, 2^31 - 1]")
     return _normalize_dense_dev("fw_normalize_counts_dev", who, _dev_table(who, x, device, torch.int32), test_name, device, norm, bins)
+
+
+def _normalize_counts_csc_dev(counts, test_name, device, norm, bins):
+    """normalize_counts for a sparse CSC tensor in GPU memory: the value checks of the dense device path on values(), in torch ops, then
+    fw_normalize_counts_csc_dev on the borrowed triple"""
+    import torch
+    who = "normalize_counts"
+    colptr, rowval, v, shape = _dev_csc(who, counts, device)  # (the refusals of shape, dtype, device and column pointers first)
+    if _tensor_np_kind(v) == "f":  # a silent cast would truncate relative abundances / floats to zero
+        if not bool(torch.isfinite(v).all()) or bool((v != torch.floor(v)).any()):
+            raise TypeError("normalize_counts: the device front-end takes integer counts (got non-integral %s values)" % v.dtype)
+    if v.numel() and (float(v.min()) < 0 or float(v.max()) > np.iinfo(np.int32).max):
+        raise ValueError("normalize_counts: counts must lie in [0, 2^31 - 1]")
+    return _normalize_csc_dev("fw_normalize_counts_csc_dev", who, (colptr, rowval, v.to(torch.int32), shape), test_name, device, norm, bins)
+
+
+def _normalize_csc_dev(name, who, triple, test_name, device, norm, bins):
+    """fw_normalize_counts_csc_dev / fw_normalize_abund_csc_dev on the three device tensors of _dev_csc -> (data, row_mask, col_mask):
+    data a dense (n_out, p_out) view with strides (1, n_out) of the output buffer for "fz", else a sparse CSC tensor over views of the
+    three output buffers (Int32 levels, Float32 values; no copy, no invariant check: the library wrote a canonical triple); the masks
+    numpy"""
+    import torch
+    L = load_library()
+    if not hasattr(L, name):
+        raise FlashWeaveError(-2, "%s: the loaded library has no %s (an older build)" % (who, name))
+    colptr, rowval, nzval, (n, p) = triple
+    if n <= 0 or p <= 0:
+        raise ValueError("%s: counts must be a samples x OTUs matrix" % who)
+    kind = _front_end_kind(who, test_name, norm)
+    nnz, dev = int(rowval.numel()), colptr.device
+    rm, cm = np.zeros(n, np.uint8), np.zeros(p, np.uint8)
+    no, po, nz = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    ocp, orow = torch.empty(p + 1, dtype=torch.int64, device=dev), torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    out = torch.empty(n * p if kind == FW_FZ else max(nnz, 1), dtype=torch.float32 if NORM_OUT_DTYPE[kind] is np.float32 else torch.int32,
+                      device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    of, oi = (vp(out), None) if out.dtype == torch.float32 else (None, vp(out))
+    opts = C.byref(_NormOpts(int(bins.get("n_bins", 3)), FW_RANK[bins.get("rank_method", "tied")], FW_DISC[bins.get("disc_method", "median")])) if bins else None
+    rc = getattr(L, name)(device, kind, n, p, vp(colptr), vp(rowval), vp(nzval), nnz, vp(ocp), vp(orow), oi, of, _ptr(rm), _ptr(cm),
+                          C.byref(no), C.byref(po), C.byref(nz), opts)
+    if rc != 0:
+        raise FlashWeaveError(rc, L.fw_last_error(None).decode())
+    if kind == FW_FZ:
+        data = out[:no.value * po.value].view(po.value, no.value).t()
+    else:
+        data = torch.sparse_csc_tensor(ocp[:po.value + 1], orow[:nz.value], out[:nz.value], size=(no.value, po.value), check_invariants=False)
+    return data, rm.astype(bool), cm.astype(bool)
 
 
 def _normalize_dense_dev(name, who, x, test_name, device, norm, bins):
@@ -513,7 +614,12 @@ def normalize_abundances(table, test_name, device=0, norm=None, n_bins=3, rank_m
     bins = bins_kw(n_bins, rank_method, disc_method)
     sparse = is_sparse(table) or isinstance(table, CSC)
     on_gpu = is_device_tensor(who, table)
-    if on_gpu:
+    dev_csc = on_gpu and is_sparse_csc_tensor(table)
+    if dev_csc:  # (the checks below then run on values(), in torch ops)
+        import torch
+        dev_triple = _dev_csc(who, table, device, torch.float64)
+        values = dev_triple[2]
+    elif on_gpu:
         import torch
         values = _dev_table(who, table, device, torch.float64)
     elif sparse:
@@ -530,6 +636,8 @@ def normalize_abundances(table, test_name, device=0, norm=None, n_bins=3, rank_m
     defect = tss_range_defect(values) if norm is not None else None
     if defect:
         raise ValueError("%s: norm=%r: the table holds %s" % (who, norm, defect))
+    if dev_csc:
+        return _normalize_csc_dev("fw_normalize_abund_csc_dev", who, dev_triple, test_name, device, norm, bins)
     if on_gpu:
         return _normalize_dense_dev("fw_normalize_abund_dev", who, values, test_name, device, norm, bins)
     L = load_library()
@@ -606,8 +714,16 @@ class Engine:
         A 2-D torch.Tensor in GPU memory (device.type "cuda", on this engine's device) never leaves the device: it is converted
         there (float32 for fz / fz_nz, int32 for mi / mi_nz; column-major) and the resident layout is built from it on the device
         (fw_set_data_dense_f32_dev / fw_set_data_dense_i32_dev), the same bits as the upload of tensor.cpu().numpy().  Not served,
-        ValueError: csc_resident=True, prec=64, a sparse tensor, a tensor of another GPU.  A CPU tensor goes through np.asarray."""
+        ValueError: csc_resident=True, prec=64, a sparse tensor, a tensor of another GPU.  A CPU tensor goes through np.asarray.
+        A 2-D sparse CSC tensor in GPU memory (layout torch.sparse_csc) is the sparse form of that path, for mi / mi_nz / fz_nz, and
+        with csc_resident=True for fz_nz: its three arrays are borrowed where they lie (fw_set_data_csc_i32_dev,
+        fw_set_data_csc_f32_dev, fw_set_data_csc_f32_resident_dev) and leave the resident bytes of the scipy upload.  It must be
+        canonical already (nothing is summed, dropped or sorted on the device): unsorted, duplicate or out-of-range rows, a stored
+        zero or a value above 61 in a level table raise FlashWeaveError with the host form's code, naming the column; for fz_nz a
+        stored 0.0 is an absence.  "fz", prec=64 and a tensor of another GPU: ValueError.  Any other sparse layout: ValueError."""
         if is_device_tensor("Engine.set_data", data):
+            if is_sparse_csc_tensor(data):
+                return self._set_data_csc_dev(data, csc_resident)
             return self._set_data_dev(data, csc_resident)
         if csc_resident:
             if self.test_name != "fz_nz":
@@ -657,6 +773,31 @@ class Engine:
         d = _dev_table(who, t, self.device, torch.float32 if continuous else torch.int32)
         assert tuple(d.shape) == (self.n, self.p)
         self._ck((self.L.fw_set_data_dense_f32_dev if continuous else self.L.fw_set_data_dense_i32_dev)(self.h, C.c_void_p(d.data_ptr())))
+
+    def _set_data_csc_dev(self, t, csc_resident):
+        import torch
+        who = "Engine.set_data"
+        if self.prec == 64:
+            raise ValueError("Engine.set_data: prec=64 is not served for a device tensor (Float64 mode uploads from the host): pass tensor.cpu()")
+        if self.test_name == "fz":
+            raise ValueError("Engine.set_data: the plain \"fz\" test takes a dense matrix (sparse input is served for mi, mi_nz and fz_nz)")
+        if csc_resident and self.test_name != "fz_nz":
+            raise ValueError("Engine.set_data: csc_resident=True is served for test_name \"fz_nz\" only (got %r)" % (self.test_name,))
+        continuous = self.test_name == "fz_nz"
+        name = ("fw_set_data_csc_f32_resident_dev" if csc_resident else "fw_set_data_csc_f32_dev") if continuous else "fw_set_data_csc_i32_dev"
+        self._need(name, "a sparse CSC device tensor")
+        colptr, rowval, v, shape = _dev_csc(who, t, self.device, torch.float32 if continuous else None)
+        if not continuous:  # (what as_csc asks of a level table, in torch ops: a cast must not wrap or truncate)
+            if _tensor_np_kind(v) == "f" and not (bool(torch.isfinite(v).all()) and bool((v == torch.floor(v)).all())):
+                raise ValueError("Engine.set_data: non-integral values where integer levels are expected")
+            if v.numel() and (float(v.min()) < 0 or float(v.max()) > np.iinfo(np.int32).max):
+                raise ValueError("Engine.set_data: levels must lie in 0 .. 2^31 - 1")
+            if v.dtype != torch.int32:  # (queued on torch's stream after _dev_csc drained it: the library reads on a stream of its own)
+                v = v.to(torch.int32)
+                torch.cuda.current_stream(v.device).synchronize()
+        assert shape == (self.n, self.p)
+        self._ck(getattr(self.L, name)(self.h, C.c_void_p(colptr.data_ptr()), C.c_void_p(rowval.data_ptr()), C.c_void_p(v.data_ptr()),
+                                       int(rowval.numel())))
 
     def data_resident_bytes(self):
         """fz_nz: bytes of device memory the context holds for the data (fw_data_resident_bytes) -- 4 n p + 8 p W dense-resident,

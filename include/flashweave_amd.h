@@ -188,7 +188,7 @@ int fw_data_resident_bytes(const fw_ctx *ctx, int64_t *bytes);
  * colptr has p+1 entries; rowval is 0-based and sorted within each column; values are 1..61, stored
  * zeros are not allowed.  Values 1..2 everywhere (presence / absence, the two bins of binned_nz_clr): two bit planes per variable, the
  * fast kernels.  A value above 2 anywhere (meta variables with make_onehot = false, src/preprocessing.jl:42-117): the GENERIC form -- one
- * byte per value, tables of L x L x L^k cells as src/types.jl:98-117 sizes them, L = maximum + 1 <= 62; a test's table of L^max_k (L^2 + 1) words sits in LDS up to 3840
+ * byte per value, tables of L x L x L^k cells as src/types.jl:98-117 sizes them, L = maximum + 1 <= 62; a test's table of L^max_k (L^2 + 1) words sits in LDS up to 3845
  * words and in device memory up to 64 M words (r05), else FW_ERR_LIMIT; same entry points and results, HITON-PC through the host job pool.
  * Also computes levels / max_vals (src/misc.jl:64-97). */
 int fw_set_data_csc_i32(fw_ctx *ctx, const int64_t *colptr, const int32_t *rowval, const int32_t *nzval);
@@ -212,6 +212,31 @@ int fw_set_data_dense_i32(fw_ctx *ctx, const int32_t *data);
  * Either leaves the context in the state its host sibling leaves for the same table, to the bit. */
 int fw_set_data_dense_i32_dev(fw_ctx *ctx, const int32_t *d_data);
 int fw_set_data_dense_f32_dev(fw_ctx *ctx, const float *d_data);
+
+/* Sparse tables that already live in device memory (the three arrays of a sparse CSC torch tensor, of a CuSparseMatrixCSC-like ROCm
+ * array): d_colptr[p + 1] Int64, d_rowval[nnz] Int32, 0-based, and d_nzval[nnz], on the context's device, borrowed for the call only
+ * (the streams' rule is that of the dense _dev forms).  nnz is passed: the size of the two arrays.  Every pointer is asked of the
+ * runtime before anything reads it (NULL, a host pointer, memory of another device: FW_ERR_ARG without a dereference; d_rowval and
+ * d_nzval may be NULL when nnz == 0).  Then the p + 1 column pointers are downloaded, and FW_ERR_ARG is returned unless they run
+ * monotonically from 0 to nnz -- before any kernel reads d_rowval or d_nzval, so no kernel ever indexes outside the two arrays.  Nothing
+ * else of the triple crosses to the host, and the triple is not copied in device memory: what the uploads stage there is small and
+ * per column (the p column flags and the total in the FW_FZ_NZ forms, the p scan records in the discrete form).  The triple must be
+ * canonical (rows strictly ascending within a column, no duplicates): it is checked, not repaired.
+ * fw_set_data_csc_f32_dev / fw_set_data_csc_f32_resident_dev (FW_FZ_NZ): the kernels of fw_set_data_csc_f32 /
+ * fw_set_data_csc_f32_resident on the borrowed triple -- the same resident bytes, state rules, refusals and limits (a stored 0.0f or
+ * -0.0f is an absence; a refused triple leaves the context without data / as it was; recursive_pcor = 0 on the resident layout is
+ * FW_ERR_LIMIT).
+ * fw_set_data_csc_i32_dev (FW_MI / FW_MI_NZ): the resident layouts of fw_set_data_csc_i32 in the two passes of
+ * fw_set_data_dense_i32_dev.  Scan, one wavefront per column: the column's range, then one pass over its rows and stored values; p small records reach the
+ * host (value mask, counts, maximum, first defect), which picks the form, fills levels / max_vals (the distinct stored values, plus one
+ * when the column has fewer than n entries) and refuses with the code fw_set_data_csc_i32 gives the same defect, naming the column:
+ * rows unsorted or out of range FW_ERR_ARG, a stored zero or a value outside 1 .. 61 FW_ERR_LIMIT.  Pack, three-level form: every lane
+ * owns one plane word, finds its entries in the column's sorted run by binary search and writes the two words whole (no atomics, no
+ * clearing; pad columns and slack words come out zero).  Generic form: the byte matrix is cleared and scattered, one wavefront per
+ * column.  A refused triple leaves the context as it was. */
+int fw_set_data_csc_i32_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const int32_t *d_nzval, int64_t nnz);
+int fw_set_data_csc_f32_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, int64_t nnz);
+int fw_set_data_csc_f32_resident_dev(fw_ctx *ctx, const int64_t *d_colptr, const int32_t *d_rowval, const float *d_nzval, int64_t nnz);
 
 int fw_get_levels(const fw_ctx *ctx, int32_t *levels, int32_t *max_vals); /* p entries each */
 
@@ -497,6 +522,25 @@ int fw_normalize_counts_dev(int32_t device, int32_t kind, int32_t n, int32_t p, 
 int fw_normalize_abund_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const double *d_values, float *d_out_f32,
                            int32_t *d_out_i32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out,
                            const fw_norm_opts *opts);
+
+/* The CSC front-ends on a triple that already lives in device memory: the arguments of the *_csc_opts entry points, except that
+ * d_colptr (Int64, p + 1), d_rowval (Int32, nnz) and d_nzval (Int32 | Float64, nnz) are device pointers on `device`, borrowed and not
+ * uploaded; nnz is passed; and the outputs d_out_colptr (p + 1 entries), d_out_rowval (nnz), d_out_i32 | d_out_f32 (nnz; FW_FZ: n p
+ * floats, d_out_colptr / d_out_rowval unused) are device buffers of the caller that the output kernels write in place, nothing is
+ * downloaded.  row_mask, col_mask, n_out, p_out, nnz_out and opts (NULL: the defaults) stay on the host.  Every pointer is asked of
+ * the runtime before anything reads it (FW_ERR_ARG for NULL, a host pointer, memory of another device); then the column pointers are
+ * downloaded and FW_ERR_ARG is returned unless they run monotonically from 0 to nnz, before any kernel reads d_rowval or d_nzval.  The
+ * same kernels run in the same order as in the host forms, so the same bits come out and the same defects are refused with the same
+ * words; the per-column and per-row records go through the host as they do there.  The outputs must not overlap the inputs.  The
+ * call synchronises before it returns. */
+int fw_normalize_counts_csc_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *d_colptr, const int32_t *d_rowval,
+                                const int32_t *d_nzval, int64_t nnz, int64_t *d_out_colptr, int32_t *d_out_rowval, int32_t *d_out_i32,
+                                float *d_out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                                const fw_norm_opts *opts);
+int fw_normalize_abund_csc_dev(int32_t device, int32_t kind, int32_t n, int32_t p, const int64_t *d_colptr, const int32_t *d_rowval,
+                               const double *d_nzval, int64_t nnz, int64_t *d_out_colptr, int32_t *d_out_rowval, int32_t *d_out_i32,
+                               float *d_out_f32, uint8_t *row_mask, uint8_t *col_mask, int32_t *n_out, int32_t *p_out, int64_t *nnz_out,
+                               const fw_norm_opts *opts);
 
 /* Device self-test of hand-written arithmetic sequences that replace a compiler-generated IEEE sequence and must return the
  * same bits.  which = FW_SELFTEST_DIV: the unscaled Float64 division of the NaN-free partial-correlation path (statfuns.jl:44-62
