@@ -115,6 +115,7 @@ _REPORTED = ("sensitive", "heterogeneous", "max_k", "alpha", "feed_forward", "te
              "fast_elim", "no_red_tests", "track_rejections", "prec", "csc_resident")
 _ENGINE_KEYS = ("max_k", "alpha", "hps", "n_obs_min", "max_tests", "FDR", "device", "recursive_pcor", "dense_cor", "prec")
 _LGL_KEYS = ("feed_forward", "round_size", "fast_elim", "no_red_tests", "track_rejections")
+_NEIGHBORS_KEYS = ("fast_elim", "no_red_tests", "track_rejections")  # Engine.neighbors (learn_neighbors: no schedule to choose)
 
 
 def _is_path(x):
@@ -131,25 +132,25 @@ def _default_header(cols, start=0):
     return ["X%d" % (start + j + 1) for j in range(cols)]
 
 
-def _path_form(data, meta_data_path, transposed, header, meta_data, meta_header, meta_mask, extra_data):
+def _path_form(data, meta_data_path, transposed, header, meta_data, meta_header, meta_mask, extra_data, who="learn_network"):
     """learn_network(data_path | all_data_paths, meta_data_path) (learning.jl:354-401) -> (data, header, meta_data, meta_header,
     extra_data) as arrays: the first path is the main table, the others become extra_data with their file headers, ahead of the
     caller's; only the main table has meta data.  io.load_data decides what is readable.  Arrays pass through as they are."""
     paths = [data] if _is_path(data) else list(data) if (isinstance(data, (list, tuple)) and len(data) and all(_is_path(q) for q in data)) else None
     if paths is None:
         if meta_data_path is not None:
-            raise ValueError("learn_network: meta_data_path goes with a data path (learn_network(data_path, meta_data_path)); with an "
-                             "array pass meta_data")
+            raise ValueError("%s: meta_data_path goes with a data path (%s(data_path, meta_data_path)); with an "
+                             "array pass meta_data" % (who, who))
         if transposed:
-            raise ValueError("learn_network: transposed=True is served for the path form; pass the transposed array")
+            raise ValueError("%s: transposed=True is served for the path form; pass the transposed array" % who)
         return data, header, meta_data, meta_header, extra_data
     if not (meta_data_path is None or _is_path(meta_data_path)):
-        raise TypeError("learn_network: meta_data_path must be a path, got %s (options are keywords)" % type(meta_data_path).__name__)
+        raise TypeError("%s: meta_data_path must be a path, got %s (options are keywords)" % (who, type(meta_data_path).__name__))
     if header is not None or meta_data is not None or meta_header is not None:
-        raise ValueError("learn_network: header, meta_data and meta_header come from the files in the path form")
+        raise ValueError("%s: header, meta_data and meta_header come from the files in the path form" % who)
     if meta_mask is not None:
-        raise ValueError("learn_network: meta_mask goes with an array or a sparse matrix; in the path form the meta variables come "
-                         "from meta_data_path")
+        raise ValueError("%s: meta_mask goes with an array or a sparse matrix; in the path form the meta variables come "
+                         "from meta_data_path" % who)
     meta_path = None if meta_data_path is None else os.fspath(meta_data_path)
     data, header, meta_data, meta_header = fio.load_data(os.fspath(paths[0]), meta_path, transposed=transposed)
     from_files = [fio.load_data(os.fspath(q), None, transposed=transposed)[:2] for q in paths[1:]]
@@ -440,30 +441,30 @@ def _prepare_tables(who, data, header, meta_data, meta_header, make_onehot, extr
     return _Tables(data, header, meta_data, meta_header, make_onehot, extra, mask, sparse, 0 if mask is None else int(mask.sum()))
 
 
-def _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense_cor):
+def _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense_cor, who="learn_network", stacklevel=3):
     """The engine options of learn_network against the test kind and the table as the caller gave it: what the CSC-resident layout
     and the Float64 path do not serve is refused, and dense_cor / recursive_pcor become what will run (with the warning, attributed
-    to learn_network's caller).  -> (csc_resident, recursive_pcor, dense_cor)"""
+    to the caller `stacklevel` frames up: that of the entry point `who`).  -> (csc_resident, recursive_pcor, dense_cor)"""
     csc_resident = bool(csc_resident)
     if csc_resident:  # what the CSC-resident layout does not serve is refused by name, never densified
         if test_name != "fz_nz":
-            raise ValueError("learn_network: csc_resident=True is served for sensitive=True, heterogeneous=True (fz_nz) only; the discrete "
-                             "kinds are bit-packed already and the plain fz test needs the dense matrix")
-        if not (is_sparse(data) or (is_sparse_csc_tensor(data) and is_device_tensor("learn_network", data))):
-            raise ValueError("learn_network: csc_resident=True needs sparse data (a scipy.sparse matrix); a dense table is not "
-                             "converted silently")
+            raise ValueError("%s: csc_resident=True is served for sensitive=True, heterogeneous=True (fz_nz) only; the discrete "
+                             "kinds are bit-packed already and the plain fz test needs the dense matrix" % who)
+        if not (is_sparse(data) or (is_sparse_csc_tensor(data) and is_device_tensor(who, data))):
+            raise ValueError("%s: csc_resident=True needs sparse data (a scipy.sparse matrix); a dense table is not "
+                             "converted silently" % who)
         if not recursive_pcor:
-            raise ValueError("learn_network: csc_resident=True with recursive_pcor=False is not supported: those conditional tests "
-                             "stream whole dense columns")
+            raise ValueError("%s: csc_resident=True with recursive_pcor=False is not supported: those conditional tests "
+                             "stream whole dense columns" % who)
     if eng_prec == 64 and not (recursive_pcor and dense_cor):
-        raise ValueError("learn_network: prec=64 with %s is not supported: the Float64 path conditions on the resident Float64 "
+        raise ValueError("%s: prec=64 with %s is not supported: the Float64 path conditions on the resident Float64 "
                          "Pearson matrix (recursive_pcor=True, dense_cor=True)"
-                         % ("recursive_pcor=False" if not recursive_pcor else "dense_cor=False"))
+                         % (who, "recursive_pcor=False" if not recursive_pcor else "dense_cor=False"))
     if test_name != "fz":
         dense_cor = True  # (learning.jl:42: only the plain fz test ever builds a matrix; the engine takes the flag for fz alone)
     elif not dense_cor and recursive_pcor:
-        warnings.warn("learn_network: dense_cor=False leaves no correlation matrix for recursive partial correlations; "
-                      "running with recursive_pcor=False (conditional tests from the data)", stacklevel=3)
+        warnings.warn("%s: dense_cor=False leaves no correlation matrix for recursive partial correlations; "
+                      "running with recursive_pcor=False (conditional tests from the data)" % who, stacklevel=stacklevel)
         recursive_pcor = False
     return csc_resident, recursive_pcor, dense_cor
 
@@ -507,10 +508,10 @@ def _sharded_lgl(eng, test_name, lgl, dist, rank, world, device):
     return net, gathered
 
 
-def _run_engine(mat, n, p, run, dist, rank, world):
+def _run_engine(mat, n, p, run, dist, rank, world, targets=None):
     """One engine for one run: the matrix goes up, the Pearson matrix is computed where the mode has one, lgl runs single or
-    sharded (world > 1), the counters are read; the engine is closed whatever happens.  run: learn_network's keywords with the
-    resolved values.  -> (net, counters)"""
+    sharded (world > 1) -- or, for learn_neighbors, Engine.neighbors for `targets` (variable ids; one rank) -- the counters are
+    read; the engine is closed whatever happens.  run: the entry point's keywords with the resolved values.  -> (net, counters)"""
     test_name = run["test_name"]
     eng = Engine(test_name, n, p, **{k: run[k] for k in _ENGINE_KEYS})
     try:
@@ -519,7 +520,9 @@ def _run_engine(mat, n, p, run, dist, rank, world):
         if test_name == "fz" and run["dense_cor"]:
             eng.compute_cor()  # (replicated in a distributed run: row-block sharding stays an Engine-level tool, dist.sharded_cor)
         lgl, gathered = {k: run[k] for k in _LGL_KEYS}, None
-        if world > 1:
+        if targets is not None:  # (no feed-forward: each neighbourhood on its own; round_size 0 = one batch)
+            net = eng.neighbors(targets, edge_dict=True, **{k: run[k] for k in _NEIGHBORS_KEYS})
+        elif world > 1:
             net, gathered = _sharded_lgl(eng, test_name, lgl, dist, rank, world, run["device"])
         else:
             net = eng.lgl(**lgl)
@@ -623,6 +626,101 @@ def normalize_data(data, extra_data=None, test_name=None, header=None, meta_data
         _tss_range_refusals(who, norm_mode, t.data, t.extra)
     return _normalize_tables(t.data, list(t.header), t.extra, test_name, t.meta_data, t.meta_header, t.make_onehot, prec, device_normalize,
                              device, bool(abundances), tss=tss, bins=pre.bins_kw(n_bins, rank_method, disc_method))[0]
+
+
+def _targets_form(who, targets):
+    """learn_neighbors' targets as the caller wrote them: a non-empty list (tuple, 1-D array) that is all names (str) or all integers
+    (0-based columns of the main table; booleans are neither) -> "names" or "columns".  Looks at the list alone."""
+    if isinstance(targets, (str, bytes)) or not hasattr(targets, "__len__") or getattr(targets, "ndim", 1) != 1:
+        raise ValueError("%s: targets must be a list of variable names or of 0-based column indices, got %s" % (who, type(targets).__name__))
+    targets = list(targets)
+    if not targets:
+        raise ValueError("%s: targets is empty: name at least one variable" % who)
+    names = [isinstance(v, str) for v in targets]
+    columns = [isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in targets]
+    if not (all(names) or all(columns)):
+        bad = [v for v, a, b in zip(targets, names, columns) if not (a or b)]
+        raise ValueError("%s: targets is %s: pass all names (str) or all 0-based column indices (int)"
+                         % (who, "a mixed list of names and indices" if not bad else "not a list of names or indices (%r)" % (bad[0],)))
+    return "names" if all(names) else "columns"
+
+
+def _targets_names(who, targets, cols, header):
+    """targets -> names: a name stays, a column index of the main table as passed (cols columns) becomes its name under the header in
+    effect -- the caller's, or X1 .. -- so that it can be followed through normalisation, which drops and reorders columns."""
+    if _targets_form(who, targets) == "names":
+        return list(targets)
+    header = _default_header(cols) if header is None else [str(h) for h in header]
+    bad = [int(v) for v in targets if not 0 <= int(v) < cols]
+    if bad:
+        raise ValueError("%s: targets holds the column index %d, which is out of range for the %d columns of data (0-based)" % (who, bad[0], cols))
+    unnamed = [int(v) for v in targets if int(v) >= len(header)]
+    if unnamed:
+        raise ValueError("%s: targets holds the column index %d, which the header of %d names does not name" % (who, unnamed[0], len(header)))
+    return [header[int(v)] for v in targets]
+
+
+def resolve_targets(who, names, variable_ids, given=()):
+    """learn_neighbors' targets, as names, against the final variable_ids -> their indices there, in the caller's order.  given: the
+    names the tables came with (main header, extra headers, meta header): a target among them that variable_ids lacks was dropped by
+    normalisation, any other missing one matches nothing.  ValueError naming targets for a name that matches nothing or more than one
+    column, two entries that resolve to one variable, and -- all of them listed -- variables normalisation did not keep."""
+    where = {}
+    for j, h in enumerate(variable_ids):
+        where.setdefault(str(h), []).append(j)
+    known = set(str(h) for h in given)
+    unknown = [v for v in names if v not in where and v not in known]
+    if unknown:
+        raise ValueError("%s: targets names %r, which matches no variable" % (who, unknown[0]))
+    dropped = [v for v in names if v not in where]
+    if dropped:
+        raise ValueError("%s: targets names %s, which %s not among the variables normalisation kept (a column without enough "
+                         "variation is filtered out; normalize_data shows what stays)"
+                         % (who, ", ".join(repr(v) for v in dict.fromkeys(dropped)), "is" if len(set(dropped)) == 1 else "are"))
+    twice = [v for v in names if len(where[v]) > 1]
+    if twice:
+        raise ValueError("%s: targets names %r, which matches %d columns (%s): variable names must be unique to be targets"
+                         % (who, twice[0], len(where[twice[0]]), ", ".join(map(str, where[twice[0]]))))
+    ids = [where[v][0] for v in names]
+    if len(set(ids)) != len(ids):
+        again = next(v for i, v in enumerate(names) if v in names[:i])
+        raise ValueError("%s: targets lists the variable %r twice: every target once" % (who, again))
+    return ids
+
+
+def learn_neighbors(data, targets, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, normalize=True,
+                    header=None, hps=5, FDR=True, n_obs_min=-1, max_tests=10_000_000, prec=32, device=0, meta_data=None, meta_header=None,
+                    make_onehot=True, recursive_pcor=True, dense_cor=True, device_normalize=True, fast_elim=True, no_red_tests=True,
+                    track_rejections=False, csc_resident=False, extra_data=None, transposed=False, meta_mask=None, abundances=False,
+                    **unsupported):
+    """si_HITON_PC(T, data; test_name, ...) (src/hiton.jl:402-409) for a list of targets: the direct neighbourhoods of chosen
+    variables without learning the whole network.  Level 0 runs over all pairs with Benjamini-Hochberg as in learn_network; HITON-PC
+    then runs for the listed targets only, each on its own (no feed-forward: the reference passes an empty whitelist).
+    data, meta_data_path and every keyword mean what they mean for learn_network, with the same table forms (numpy, scipy.sparse,
+    dense and sparse CSC tensors in GPU memory, extra_data, meta_data / meta_mask, the path form, abundances, csc_resident, prec=64)
+    and the same refusals, under this function's name.  feed_forward, round_size and distributed are not taken: there is no schedule
+    to choose and no sharded form; they raise TypeError like any unknown keyword.
+    targets: a non-empty list, all names or all integers.  Names (str) are looked up in the final variable_ids.  Integers are 0-based
+    columns of the main `data` as passed; they are translated through the header in effect (the caller's, or X1 ..) and then looked
+    up the same way, so that a column normalisation dropped in front of a target does not shift it.  ValueError naming targets,
+    before any engine is created: an empty or a mixed list, a name that matches nothing or more than one column, an index out of
+    range, two entries that resolve to one variable, and variables normalisation did not keep (all of them are listed).
+    -> FWResult with learn_network's keys and
+        targets      the resolved indices into variable_ids, in the caller's order
+        neighbors    {target index: {neighbour index: (weight, pval)}}: HITON-PC's result for the target, in PC order
+    A target's neighbours are those of its row in learn_network(..., feed_forward=False), weight and p to the bit.  edges is
+    make_symmetric_graph of the targets' rows alone: an edge between two targets is merged as always, an edge to another variable
+    has the target's direction only.  rejections (track_rejections=True) holds the targets' records.  parameters["targets"] is their
+    number and parameters["schedule"] says that every neighbourhood ran on its own.  save and save_rejections work unchanged."""
+    if unsupported:
+        raise TypeError("learn_neighbors: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
+    _targets_form("learn_neighbors", targets)
+    return _learn("learn_neighbors", list(targets), data, meta_data_path, transposed, False, dict(
+        sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=False, normalize=normalize,
+        hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec, round_size=0, make_onehot=make_onehot,
+        recursive_pcor=recursive_pcor, dense_cor=dense_cor, device_normalize=device_normalize, fast_elim=fast_elim,
+        no_red_tests=no_red_tests, track_rejections=track_rejections, csc_resident=csc_resident, abundances=abundances),
+        dict(header=header, meta_data=meta_data, meta_header=meta_header, extra_data=extra_data, meta_mask=meta_mask), device)
 
 
 def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=False, max_k=3, alpha=0.01, feed_forward=True, normalize=True,
@@ -744,53 +842,79 @@ def learn_network(data, meta_data_path=None, *, sensitive=True, heterogeneous=Fa
     array raise ValueError."""
     if unsupported:
         raise TypeError("learn_network: unsupported options %s (see DESIGN.md section 7)" % sorted(unsupported))
+    return _learn("learn_network", None, data, meta_data_path, transposed, distributed, dict(
+        sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=feed_forward, normalize=normalize,
+        hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec, round_size=round_size, make_onehot=make_onehot,
+        recursive_pcor=recursive_pcor, dense_cor=dense_cor, device_normalize=device_normalize, fast_elim=fast_elim,
+        no_red_tests=no_red_tests, track_rejections=track_rejections, csc_resident=csc_resident, abundances=abundances),
+        dict(header=header, meta_data=meta_data, meta_header=meta_header, extra_data=extra_data, meta_mask=meta_mask), device)
+
+
+def _learn(who, targets, data, meta_data_path, transposed, distributed, mode, tables, device):
+    """The body learn_network and learn_neighbors share, one frame below either: mode holds the mode keywords as the caller passed
+    them (what the ranks of a distributed run compare), tables the arguments that describe the tables (header, meta_data, meta_header,
+    extra_data, meta_mask).  targets is None for learn_network; for learn_neighbors it is the caller's list, already checked for its
+    form (_targets_form), and is resolved against the final variable_ids before an engine exists (resolve_targets)."""
+    header, meta_data, meta_header, extra_data, meta_mask = (tables[k] for k in ("header", "meta_data", "meta_header", "extra_data", "meta_mask"))
+    normalize, prec, device_normalize, csc_resident = mode["normalize"], mode["prec"], mode["device_normalize"], mode["csc_resident"]
     if prec not in (32, 64):
-        raise ValueError("learn_network: prec=%r is not supported (32 or 64; the reference's 16 and 128 are not served)" % (prec,))
-    abundances = bool(abundances)  # (before the digest: ranks passing 1 and True make the same run)
-    on_gpu = is_device_tensor("learn_network", data)
+        raise ValueError("%s: prec=%r is not supported (32 or 64; the reference's 16 and 128 are not served)" % (who, prec))
+    abundances = mode["abundances"] = bool(mode["abundances"])  # (before the digest: ranks passing 1 and True make the same run)
+    on_gpu = is_device_tensor(who, data)
     if on_gpu:  # a table in GPU memory: what would need its bytes on the host is refused by name, before any library call
         if abundances and not normalize:
-            raise ValueError("learn_network: abundances=True with normalize=False is not supported: the option chooses the front-end of a "
-                             "table that is normalised here, and a prepared matrix has nothing left to normalise")
-        _tensor_refusals("learn_network", data, device, normalize, abundances, meta_data=meta_data, meta_mask=meta_mask, extra_data=extra_data,
+            raise ValueError("%s: abundances=True with normalize=False is not supported: the option chooses the front-end of a "
+                             "table that is normalised here, and a prepared matrix has nothing left to normalise" % who)
+        _tensor_refusals(who, data, device, normalize, abundances, meta_data=meta_data, meta_mask=meta_mask, extra_data=extra_data,
                          prec=prec, device_normalize=device_normalize, distributed=distributed, csc_resident=csc_resident)
-    # the mode keywords as the caller passed them, before any is resolved: what the ranks of a distributed run compare
-    caller = dict(sensitive=sensitive, heterogeneous=heterogeneous, max_k=max_k, alpha=alpha, feed_forward=feed_forward, normalize=normalize,
-                  hps=hps, FDR=FDR, n_obs_min=n_obs_min, max_tests=max_tests, prec=prec, round_size=round_size, make_onehot=make_onehot,
-                  recursive_pcor=recursive_pcor, dense_cor=dense_cor, device_normalize=device_normalize, fast_elim=fast_elim,
-                  no_red_tests=no_red_tests, track_rejections=track_rejections, csc_resident=csc_resident, abundances=abundances)
+    caller = mode  # the mode keywords as the caller passed them, before any is resolved
     data, header, meta_data, meta_header, extra_data = _path_form(data, meta_data_path, transposed, header, meta_data, meta_header, meta_mask,
-                                                                  extra_data)
-    test_name = ("fz" if sensitive else "mi") + ("_nz" if heterogeneous else "")  # src/learning.jl:480-483
+                                                                  extra_data, who=who)
+    test_name = ("fz" if mode["sensitive"] else "mi") + ("_nz" if mode["heterogeneous"] else "")  # src/learning.jl:480-483
     eng_prec = 64 if (prec == 64 and test_name == "fz") else 32  # the element type of the device pipeline
     dist, rank, world = _distributed_world() if distributed else (None, 0, 0)
     if world > 1:  # a sharded run (a world of one rank takes the ordinary path): its refusals first, the same on every rank
         _distributed_input_check(dist, rank, world, eng_prec, device, (data, meta_data, meta_header, header, meta_mask, extra_data), caller)
-    csc_resident, recursive_pcor, dense_cor = _resolve_mode(test_name, eng_prec, data, csc_resident, recursive_pcor, dense_cor)
-    # this entry point's rules of the table stage: an engine.CSC tuple is no sparse table here, and without a mask a header of
+    # (the warning of _resolve_mode goes to the caller of the entry point: this frame, the entry point's, then theirs)
+    csc_resident, recursive_pcor, dense_cor = _resolve_mode(test_name, eng_prec, data, csc_resident, mode["recursive_pcor"], mode["dense_cor"],
+                                                            who=who, stacklevel=4)
+    # the entry points' rules of the table stage: an engine.CSC tuple is no sparse table here, and without a mask a header of
     # another length than the table passes (zip truncates)
     if abundances and not normalize:
-        raise ValueError("learn_network: abundances=True with normalize=False is not supported: the option chooses the front-end of a "
-                         "table that is normalised here, and a prepared matrix has nothing left to normalise")
-    t = _prepare_tables("learn_network", data, header, meta_data, meta_header, make_onehot, extra_data, meta_mask, test_name, prec,
+        raise ValueError("%s: abundances=True with normalize=False is not supported: the option chooses the front-end of a "
+                         "table that is normalised here, and a prepared matrix has nothing left to normalise" % who)
+    if targets is not None:  # the names of the main table's columns as passed: what an integer target is translated through
+        cols = _shape(data if (_any_sparse(data) or is_device_tensor(who, data)) else np.asarray(data))
+        named = _targets_names(who, targets, cols[1] if len(cols) == 2 else 0, header)
+    t = _prepare_tables(who, data, header, meta_data, meta_header, mode["make_onehot"], extra_data, meta_mask, test_name, prec,
                         device_normalize, normalize=normalize, csc_tuple_is_sparse=False, strict_header=False, abundances=abundances)
     if meta_data is not None and not normalize:
         # the reference appends the meta columns as they are and keeps their mask (learning.jl:500-520); here an already
         # normalised matrix must already hold them -- silently dropping the argument would lose the mask
-        raise ValueError("learn_network: meta_data with normalize=False is not supported: append the prepared meta columns to "
-                         "`data` yourself (preprocess.normalize_with_meta) and mark them with meta_mask, or pass normalize=True")
+        raise ValueError("%s: meta_data with normalize=False is not supported: append the prepared meta columns to "
+                         "`data` yourself (preprocess.normalize_with_meta) and mark them with meta_mask, or pass normalize=True" % who)
     mat, header, meta_mask, on_device, t_norm = _matrix(t, test_name, normalize, prec, device_normalize, device, abundances)
     n, p = t.data[3] if isinstance(mat, tuple) else mat.shape
+    ids = None
+    if targets is not None:  # before an engine exists: a bad list costs no device call beyond the front-end's
+        given = list(t.header) + [h for _, hdr in t.extra for h in hdr] + [str(h) for h in (t.meta_header if t.meta_header is not None else [])]
+        ids = resolve_targets(who, named, header, given)
     run = dict(caller, device=device, test_name=test_name, prec=eng_prec, csc_resident=csc_resident, recursive_pcor=recursive_pcor,
-               dense_cor=dense_cor, round_size=default_round_size(p) if round_size is None else round_size)
-    net, counters = _run_engine(mat, n, p, run, dist, rank, world)
+               dense_cor=dense_cor, round_size=default_round_size(p) if mode["round_size"] is None else mode["round_size"])
+    net, counters = _run_engine(mat, n, p, run, dist, rank, world, targets=ids)
     counters.update(t_normalize_s=t_norm, normalized_on_device=on_device, sparse_input=t.sparse, n_tables=1 + len(t.extra),
                     csc_resident=csc_resident)
     parameters = {k: bool(run[k]) if k in ("fast_elim", "no_red_tests", "track_rejections") else run[k] for k in _REPORTED}
-    parameters.update(extra_data=len(t.extra), meta_mask=t.n_marked, distributed=world, schedule=_schedule(run["round_size"], feed_forward, p))
+    parameters.update(extra_data=len(t.extra), meta_mask=t.n_marked, distributed=world, schedule=_schedule(run["round_size"], mode["feed_forward"], p))
     if abundances:
         parameters["abundances"] = True
     if on_gpu:  # (the table never left the device: front-end and upload borrowed it there)
         counters["table_on_device"] = parameters["table_on_device"] = True
-    return FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header), parameters=parameters,
-                    counters=counters, rejections=net["rejections"])
+    res = FWResult(edges=net["edges"], variable_ids=header, meta_variable_mask=meta_mask or [False] * len(header), parameters=parameters,
+                   counters=counters, rejections=net["rejections"])
+    if targets is not None:
+        off, idx, w, pv = net["pc_off"], net["pc_idx"].tolist(), net["pc_weight"].tolist(), net["pc_pval"].tolist()
+        parameters.update(targets=len(ids), schedule="targets (no feed-forward: each neighbourhood on its own)")
+        res["targets"] = list(ids)
+        res["neighbors"] = {v: {idx[q]: (w[q], pv[q]) for q in range(int(off[v]), int(off[v + 1]))} for v in ids}
+    return res

@@ -213,12 +213,18 @@ struct PathChoice {
 // fwi_devhiton_fz_schedule: fz under the same conditions, when EVERY round of the schedule would take the device rounds), else the
 // rounds are asked one by one (`why` then says what kept the schedule off): order[r0 .. r1), n_my of them this rank's.
 // Knobs are read per call: the tests and bench.py switch them inside a live process.
-PathChoice choose_path(fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, const int32_t *order, int nt, const int *round, size_t n_my)
+// subset: fw_learn_neighbors -- order holds the listed targets alone.  Every count below (nt, the rounds, n_my) is then a count of listed
+// targets, and the degrees are read through order[], so the tests hold as they stand; one condition is the subset's own.
+PathChoice choose_path(fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, const int32_t *order, int nt, const int *round, size_t n_my, bool subset)
 {
     auto host = [](const char *why) { return PathChoice{PATH_HOST_POOL, false, why}; };
     const int kind = c->P.kind;
     const bool discrete = kind == FW_MI || kind == FW_MI_NZ;
     if (fw_host_hiton()) return host("FW_HOST_HITON=1");
+    // (the persistent kernel runs four tests per wavefront, the job pool one: another summation order of the same terms, DESIGN.md
+    // section 2.  Which of the two a run takes depends on the number of targets -- a target's row would change in its last bits with
+    // the length of the list it was named in)
+    if (subset && discrete) return host("fw_learn_neighbors, discrete kind: a neighbourhood must not depend on how many targets are listed");
     if (c->f64) return host("Float64 matrix (fw_fz64.hip): the general-form segment kernel serves the host pool");
     if (!discrete && !c->P.recursive_pcor) return host("streamed columns (recursive_pcor = 0): fw_fzs.hip serves the host pool");
     if (!discrete && c->P.n < c->n_obs_min_eff) return host("no power: fewer observations than n_obs_min, no device work at all");
@@ -272,7 +278,7 @@ PathChoice choose_path(fw_ctx *c, const fw_learn_opts &opt, bool has_exchange, c
     return PathChoice{PATH_DEV_ROUNDS, c->d_cand != nullptr, c->d_cand ? "candidate order from the device" : "candidate order built on the host"};
 }
 
-// What the stages of one fw_learn_network call share.
+// What the stages of one fw_learn_network / fw_learn_neighbors call share.
 struct Learn {
     fw_ctx *c;
     fw_learn_opts opt;
@@ -282,7 +288,8 @@ struct Learn {
     size_t rej_n = 0;
     double t0 = 0.0;             // start of the conditional stage
     std::vector<int32_t> order;  // learning.jl:97-98
-    int nt = 0;                  // targets of the schedule (fw_learn_opts.max_targets)
+    int nt = 0;                  // targets of the schedule (fw_learn_opts.max_targets; fw_learn_neighbors: the listed ones)
+    bool subset = false;         // fw_learn_neighbors: order holds the listed targets alone, nt of them
     FwDirected all;              // directed results of every target; all ranks hold all of them after each round's exchange
 };
 
@@ -599,7 +606,7 @@ int run_rounds(Learn &L)
         const std::vector<int32_t> owner = fw_deal_round(l0, L.order.data(), r0, r1, L.opt.world_size, c->P.max_k);
         const size_t n_my = (size_t)std::count(owner.begin(), owner.end(), L.opt.rank);
         const int round[2] = {r0, r1};
-        const PathChoice path = choose_path(c, L.opt, L.allgather != nullptr, L.order.data(), L.nt, round, n_my);
+        const PathChoice path = choose_path(c, L.opt, L.allgather != nullptr, L.order.data(), L.nt, round, n_my, L.subset);
         if (fw_trace_host()) fprintf(stderr, "[fw] round of targets %d..%d (%zu here): %s (%s)\n", r0, r1, n_my, path_name[path.path], path.why);
         std::vector<Target> tg;
         tg.reserve(n_my);
@@ -613,13 +620,16 @@ int run_rounds(Learn &L)
     return FW_OK;
 }
 
-// learning.jl:171-172 (max_k = 0): the level-0 lists are the network
-int level0_as_directed(fw_ctx *c, FwDirected &all)
+// learning.jl:171-172 (max_k = 0): the level-0 lists are the network.  targets == nullptr: every variable, ascending; else the rows of
+// targets[0 .. nt) alone (fw_learn_neighbors; the CSR over targets of fw_graph.h does not depend on the order of the rows)
+int level0_as_directed(fw_ctx *c, const int32_t *targets, int nt, FwDirected &all)
 {
     if (int rc = fwi_nb_host_ensure(c)) return rc;
     const FwLevel0 l0 = level0_view(c);
-    for (int v = 0; v < l0.p; ++v)
+    for (int i = 0; i < (targets ? nt : l0.p); ++i) {
+        const int v = targets ? targets[i] : i;
         for (int64_t q = l0.off[v]; q < l0.off[v + 1]; ++q) all.push(v, l0.idx[q], l0.stat[q], l0.pval[q]);
+    }
     return FW_OK;
 }
 
@@ -627,8 +637,8 @@ int level0_as_directed(fw_ctx *c, FwDirected &all)
 int conditional_stage(Learn &L)
 {
     fw_ctx *c = L.c;
-    if (c->P.max_k == 0) return level0_as_directed(c, L.all);
-    const PathChoice whole = choose_path(c, L.opt, L.allgather != nullptr, L.order.data(), L.nt, nullptr, 0);
+    if (c->P.max_k == 0) return level0_as_directed(c, L.subset ? L.order.data() : nullptr, L.nt, L.all);
+    const PathChoice whole = choose_path(c, L.opt, L.allgather != nullptr, L.order.data(), L.nt, nullptr, 0, L.subset);
     if (whole.path != PATH_DEV_SCHEDULE) {
         if (fw_trace_host()) fprintf(stderr, "[fw] no %s\n", whole.why);
         return run_rounds(L);
@@ -747,6 +757,53 @@ void fwi_host_workers_free(fw_ctx *c)
     c->host_workers = nullptr;
 }
 
+namespace {
+
+// The body fw_learn_network and fw_learn_neighbors share, behind their argument checks: level 0 (if not yet run), the schedule, the
+// conditional stage, the rejection log, the graph.  targets == nullptr: every variable in schedule order, the first
+// fw_learn_opts.max_targets of them; else the listed variables alone, in the order the schedule gives them -- every consumer of
+// order / nt below reads that list only, and what is sized per variable (round_of, the whitelist counts, the level-0 offsets the
+// targets' lists sit at, the rejection slots) stays sized for all p.
+int learn_body(Learn &L, const int32_t *targets, int32_t n_targets, int64_t *n_edges_out)
+{
+    fw_ctx *c = L.c;
+    const fw_learn_opts &opt = L.opt;
+    if (!c->have_level0)
+        if (int rc = fw_level0(c, nullptr)) return rc;
+    ViewGuard view_guard{c, c->mi_view};
+    c->mi_view = 1;
+    ElimGuard elim_guard{c};
+    c->elim_mode = opt.elim_mode;
+    RejGuard rej_guard{c};
+    if (int rc = rej_begin(c, &L.rej_n)) return rc;
+    c->rej_rank = opt.rank;
+    c->rej_world = opt.world_size;
+    L.t0 = fwi_now_s();
+    L.order = fw_target_order(level0_view(c));
+    L.nt = opt.max_targets > 0 && opt.max_targets < c->P.p ? opt.max_targets : c->P.p;
+    if (targets) {
+        std::vector<uint8_t> listed((size_t)c->P.p, 0);
+        for (int32_t i = 0; i < n_targets; ++i) listed[(size_t)targets[i]] = 1;
+        L.order.erase(std::remove_if(L.order.begin(), L.order.end(), [&](int32_t v) { return !listed[(size_t)v]; }), L.order.end());
+        L.nt = (int)L.order.size();
+        L.subset = true;
+    }
+
+    if (int rc = conditional_stage(L)) return rc;
+    if (int rc = rej_finish(c, L.rej_n)) return rc;
+    c->cnt.t_cond_s += fwi_now_s() - L.t0;
+    if (fw_trace_host()) fprintf(stderr, "[fw] conditional stage: %.2f ms\n", 1e3 * (fwi_now_s() - L.t0));
+
+    if (int rc = graph_stage(c, L.all, L.discrete)) return rc;
+#ifdef FW_FZ_FASTDBG
+    fwi_fz_fastdbg_print();
+#endif
+    if (n_edges_out) *n_edges_out = (int64_t)c->net.e_src.size();
+    return FW_OK;
+}
+
+}  // namespace
+
 extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allgather_fn allgather, void *user, int64_t *n_edges_out)
 {
     if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
@@ -761,31 +818,36 @@ extern "C" int fw_learn_network(fw_ctx *c, const fw_learn_opts *opts_in, fw_allg
     if (opt.rank < 0 || opt.rank >= opt.world_size) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: rank %d outside world of %d", opt.rank, opt.world_size);
     if (opt.world_size > 1 && !allgather) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: world_size > 1 needs an allgather callback");
     if (opt.elim_mode < 0 || opt.elim_mode > 2) return fw_fail(c, FW_ERR_ARG, "fw_learn_network: elim_mode %d is not 0, 1 or 2", opt.elim_mode);
-    if (!c->have_level0)
-        if (int rc = fw_level0(c, nullptr)) return rc;
-    ViewGuard view_guard{c, c->mi_view};
-    c->mi_view = 1;
-    ElimGuard elim_guard{c};
-    c->elim_mode = opt.elim_mode;
-    RejGuard rej_guard{c};
-    if (int rc = rej_begin(c, &L.rej_n)) return rc;
-    c->rej_rank = opt.rank;
-    c->rej_world = opt.world_size;
-    L.t0 = fwi_now_s();
-    L.order = fw_target_order(level0_view(c));
-    L.nt = opt.max_targets > 0 && opt.max_targets < c->P.p ? opt.max_targets : c->P.p;
+    return learn_body(L, nullptr, 0, n_edges_out);
+}
 
-    if (int rc = conditional_stage(L)) return rc;
-    if (int rc = rej_finish(c, L.rej_n)) return rc;
-    c->cnt.t_cond_s += fwi_now_s() - L.t0;
-    if (fw_trace_host()) fprintf(stderr, "[fw] conditional stage: %.2f ms\n", 1e3 * (fwi_now_s() - L.t0));
-
-    if (int rc = graph_stage(c, L.all, L.discrete)) return rc;
-#ifdef FW_FZ_FASTDBG
-    fwi_fz_fastdbg_print();
-#endif
-    if (n_edges_out) *n_edges_out = (int64_t)c->net.e_src.size();
-    return FW_OK;
+// si_HITON_PC(T, data; ...) (hiton.jl:402-409) for a list of targets: every refusal before anything runs, then the shared body
+extern "C" int fw_learn_neighbors(fw_ctx *c, const fw_learn_opts *opts_in, const int32_t *targets, int32_t n_targets, int64_t *n_edges_out)
+{
+    if (!c) return fw_fail(nullptr, FW_ERR_ARG, "NULL context");
+    if (!targets) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: targets is NULL");
+    if (n_targets < 1) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: n_targets %d: at least one target", n_targets);
+    Learn L{c, fw_learn_opts{}, nullptr, nullptr, c->P.kind == FW_MI || c->P.kind == FW_MI_NZ};
+    fw_learn_opts &opt = L.opt;  // (all zero: no feed-forward, one round, fast_elim)
+    if (opts_in) opt = *opts_in;
+    if (opt.feed_forward != 0)
+        return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: feed_forward %d: every neighbourhood is learned on its own, pass 0", opt.feed_forward);
+    if (opt.world_size > 1) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: world_size %d: sharded runs are not served", opt.world_size);
+    if (opt.rank != 0) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: rank %d: sharded runs are not served", opt.rank);
+    if (opt.max_targets != 0) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: max_targets %d: the list names the targets, pass 0", opt.max_targets);
+    if (opt.elim_mode < 0 || opt.elim_mode > 2) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: elim_mode %d is not 0, 1 or 2", opt.elim_mode);
+    opt.world_size = 1;
+    {
+        std::vector<uint8_t> seen((size_t)c->P.p, 0);
+        for (int32_t i = 0; i < n_targets; ++i) {
+            const int32_t v = targets[i];
+            if (v < 0 || v >= c->P.p) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: targets[%d] = %d is outside 0 .. %d", i, v, c->P.p - 1);
+            if (seen[(size_t)v]) return fw_fail(c, FW_ERR_ARG, "fw_learn_neighbors: targets[%d] = %d is a duplicate", i, v);
+            seen[(size_t)v] = 1;
+        }
+    }
+    (void)hipSetDevice(c->P.device);
+    return learn_body(L, targets, n_targets, n_edges_out);
 }
 
 extern "C" int fw_learn_network_dev(fw_ctx *c, const fw_learn_opts *opts_in, const fw_dev_exchange *x, int64_t *n_edges_out)

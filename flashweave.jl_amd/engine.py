@@ -194,6 +194,8 @@ def load_library():
     L.fw_test_subsets_batch.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp]
     L.fw_learn_network.argtypes = [vp, C.POINTER(_LearnOpts), vp, vp, C.POINTER(C.c_int64)]
     L.fw_learn_network_dev.argtypes = [vp, C.POINTER(_LearnOpts), C.POINTER(_DevExchange), C.POINTER(C.c_int64)]
+    if hasattr(L, "fw_learn_neighbors"):  # (absent from older builds loaded through FW_LIB_PATH for A/B profiling)
+        L.fw_learn_neighbors.argtypes = [vp, C.POINTER(_LearnOpts), vp, C.c_int32, C.POINTER(C.c_int64)]
     L.fw_network_get.argtypes = [vp, vp, vp, vp]
     L.fw_network_get_directed.argtypes = [vp, vp, vp, vp, vp]
     L.fw_get_counters.argtypes = [vp, C.POINTER(_Counters)]
@@ -1003,6 +1005,27 @@ class Engine:
             self._ck(self.L.fw_learn_network_dev(self.h, C.byref(opts), C.byref(x), C.byref(ne)))
         else:
             self._ck(self.L.fw_learn_network(self.h, C.byref(opts), C.cast(cb, C.c_void_p) if cb else None, None, C.byref(ne)))
+        return self._network(ne.value, edge_dict, track_rejections)
+
+    def neighbors(self, targets, round_size=0, edge_dict=True, fast_elim=True, no_red_tests=True, track_rejections=False):
+        """fw_learn_neighbors: si_HITON_PC(T, data; ...) (src/hiton.jl:402-409) for a list of targets -- level 0 over all pairs (if it
+        has not run), then HITON-PC for the listed variables only, each on its own (no feed-forward).  targets: distinct variable ids
+        in 0 .. p-1, in any order.  Returns what lgl returns: a listed target's directed row is its row of lgl(feed_forward=False), to
+        the bit, the rows of the other variables are empty, and the edges are make_symmetric_graph of those rows alone (an edge to an
+        unlisted variable has one direction only); with track_rejections the log holds the listed targets' records.  round_size only
+        batches the work.  The context keeps level 0 and the Pearson matrix: it can be asked again, and lgl can follow."""
+        self._need("fw_learn_neighbors", "neighbors()")
+        t = np.asarray(targets)
+        t = t.astype(np.int32) if (t.ndim == 1 and t.size == 0) else t  # (an empty list: the library refuses it by name)
+        if t.ndim != 1 or t.dtype.kind not in "iu":
+            raise ValueError("neighbors: targets must be a list of variable ids (integers), got %s" % (t.dtype if t.ndim == 1 else "%d dimensions" % t.ndim))
+        if t.size and (t.min() < -2**31 or t.max() >= 2**31):
+            raise ValueError("neighbors: targets holds an id outside the Int32 range")
+        t = np.ascontiguousarray(t, dtype=np.int32)
+        self._set_track(track_rejections)
+        opts = _LearnOpts(0, int(round_size), 0, 1, 0, elim_mode(fast_elim, no_red_tests))
+        ne = C.c_int64(0)
+        self._ck(self.L.fw_learn_neighbors(self.h, C.byref(opts), _ptr(t), int(t.size), C.byref(ne)))
         return self._network(ne.value, edge_dict, track_rejections)
 
     def _set_track(self, on):

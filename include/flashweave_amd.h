@@ -359,6 +359,20 @@ int fw_learn_network(fw_ctx *ctx, const fw_learn_opts *opts, fw_allgather_fn all
  * send buffer, all-gathered by the caller's collective and unpacked from the gathered buffer -- the host language only runs the
  * collective (r02's callback packed and unpacked in numpy: ~0.9 ms per round of a cfg3 pass). */
 int fw_learn_network_dev(fw_ctx *ctx, const fw_learn_opts *opts, const fw_dev_exchange *exchange, int64_t *n_edges_out);
+/* replaces: si_HITON_PC(T, data; ...) (src/hiton.jl:402-409) for a list of targets: level 0 over all pairs (if not yet run), then
+ * HITON-PC for the n_targets variables targets[0 .. n_targets) only, each on its own (no feed-forward: the reference's convenience
+ * function passes an empty whitelist), then make_weights + make_symmetric_graph over those rows alone.  A listed target's directed row
+ * is its row of fw_learn_network with feed_forward = 0, to the bit; the rows of the other variables are empty, so an edge to an
+ * unlisted variable has one direction only.  The rejection log holds the listed targets' records.  max_k = 0: the targets' level-0
+ * rows.  The targets run in the order of the schedule (ascending level-0 degree, stable), whatever the order of the list; nothing
+ * is launched or counted for an unlisted variable.  Afterwards fw_network_get, fw_network_get_directed and the fw_rejections_*
+ * getters work as after fw_learn_network; a later fw_learn_network or fw_learn_neighbors replaces the result and reuses level 0 and
+ * the Pearson matrix.
+ * opts: NULL means feed_forward = 0, round_size = 0, elim_mode = 0.  round_size only batches the work and does not change a bit.
+ * FW_ERR_ARG, the message naming the field or the entry: a NULL context, NULL targets, n_targets < 1, an id outside 0 .. p-1, a
+ * duplicate id, feed_forward != 0, world_size > 1, rank != 0, max_targets != 0, elim_mode outside 0 .. 2.  One rank only: there is no
+ * sharded or communicator form. */
+int fw_learn_neighbors(fw_ctx *ctx, const fw_learn_opts *opts, const int32_t *targets, int32_t n_targets, int64_t *n_edges_out);
 /* ---- library-side collectives (ABI 5): the same exchanges on a communicator the LIBRARY owns ------------------------------------
  * replaces: the master <-> worker message loop of src/interleaved.jl:112-183 for one process per GPU.  RCCL (librccl.so.1, reached
  * through dlopen: single-GPU users never load it) on the context's stream; the host language only carries the 128-byte rendezvous
